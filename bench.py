@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the MS-GAT graph-attention hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pemsd7|pemsd4|stress]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pemsd7|pemsd4|stress] [--dump-outputs DIR]
 
 One JSON line (rank 0 prints it; see the repo prompt for the contract).  `value` means the SAME thing at every N
 (`value_kind` = "hot_path"), so any two lines of a scaling curve compare like for like:
@@ -107,6 +107,7 @@ class HotPath:
     def step(self, allreduce=False):
         # the order of a training step of the model that holds these layers (msgat.py:143-150: the two MEAMs of a TPC
         # in sequence): forward of the first depth, forward of the second, then backward second depth first
+        self.last_zs = None   # the previous step's outputs go before this step allocates, as a caller's would
         for m, x in zip(self.layers, self.xs):
             x.grad = None
             for p in m.parameters():
@@ -117,12 +118,40 @@ class HotPath:
         # created last).  Two calls cost a second start of the autograd engine (~150 us of host time each at this
         # size, tools/host_overhead.py), which a launch-bound step (PEMSD4) would be charged for.
         torch.autograd.backward(zs, self.dzs)
+        # what a caller of the step receives besides the gradients (--dump-outputs); detached: a z that held its autograd
+        # graph would keep the parameters' AccumulateGrad nodes alive into the HIP-graph captures that follow
+        self.last_zs = [z.detach() for z in zs]
         if allreduce:  # one flat bucket: the payload is KBs, the collective is latency-bound
             self.sync(weight=float(self.wl["B"]))
 
     def forward_only(self):
         with torch.no_grad():
             return [m(x, self.graph) for m, x in zip(self.layers, self.xs)]
+
+
+DUMP_SAMPLE = 1 << 21   # entries --dump-outputs keeps of a larger array: a fixed, seeded sample (8 MB in fp32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(hp, out_dir):
+    """--dump-outputs DIR: what the last step of `hp` computed -- per GACN depth the output z and the gradients of the
+    input and of the three parameters -- as DIR/depth<d>_<name>.npy in float32.  An array of more than DUMP_SAMPLE
+    entries is written as the 1-D gather of DUMP_SAMPLE flat positions drawn by np.random.default_rng(0) (sorted), the
+    same positions in every run of the same workload, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for d, (m, x, z) in enumerate(zip(hp.layers, hp.xs, hp.last_zs)):
+        for name, t in (("z", z), ("dx", x.grad), ("dWg", m.Wg.grad), ("dalpha", m.alpha.grad), ("dW", m.W.grad)):
+            t = t.detach()
+            if t.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            a = t.to(torch.float32).cpu().numpy()
+            total += a.nbytes
+            assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB"
+            np.save(os.path.join(out_dir, f"depth{d}_{name}.npy"), a)
+    print(f"[bench] --dump-outputs: {total / 2**20:.1f} MB written to {out_dir}", file=sys.stderr, flush=True)
 
 
 SETTLE_MS = 60.0   # see settle()
@@ -810,6 +839,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="pemsd7", choices=sorted(WORKLOADS))
     ap.add_argument("--no-baselines", action="store_true", help="skip the CPU / eager baselines and the secondary objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ     # under torch.distributed.run
@@ -865,6 +896,9 @@ def main():
     hot_wall, hot_steps = timed_steps(lambda: hp.step(allreduce=multi), args.steps, args.warmup, dev, barrier)
     hot_wall = max_over_ranks(hot_wall)
     hot_allreduce_us = collective_us(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hp, args.dump_outputs)
+    hp.last_zs = None
     workload = (f"{args.workload}: N={wl['N']} nodes, {wl['E']} undirected edges (+self loops, sym-normalised), "
                 f"T={wl['T']}, B={wl['B']}/GPU, R={wl['R']} relations, GACN {wl['Cin']}->{wl['Co']} and "
                 f"{wl['hidden']}->{wl['Co']} (msgat72 widths), forward+backward of the hot path"
