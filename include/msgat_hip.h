@@ -47,14 +47,16 @@
 extern "C" {
 #endif
 
-/* 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
+/* 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
+ * + msgat_graph_edge_values.
+ * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
  * 7 (round 6): + msgat_dense_scratch_bytes; msgat_fwd_t.dense_scratch (new last field); msgat_stage_scores and
  * msgat_stage_dense_column_pass take a dense_scratch pointer in front of the stream.  The one process-wide environment switch,
  * MSGAT_DENSE_SPLIT = 0 | 1, forces the arithmetic of the dense passes for A/B runs and tests (read once).
  * 6 (round 5): + msgat_contract_form_name, msgat_causal_conv{,_fused,_grad_weight}, msgat_layernorm_head_backward
  * {,_partial_floats}, msgat_head_forward_ln, msgat_gate_sum{,_backward}, msgat_layernorm_{forward,backward}_pooled, msgat_layernorm_pool_partial_floats,
  * msgat_contract_mix_partial_floats; no existing signature or structure changed since 5. */
-#define MSGAT_ABI_VERSION 8
+#define MSGAT_ABI_VERSION 9
 
 enum {
   MSGAT_OK = 0,
@@ -122,6 +124,10 @@ typedef struct msgat_graph {
                                    edge coefficients in CSC order too, so backward starts without a re-ordering pass */
   msgat_sell_t sell_rows; /* SELL of the CSR (forward aggregate, SDDMM); optional     */
   msgat_sell_t sell_cols; /* SELL of the CSC (transposed aggregate of backward); opt. */
+  int32_t val_sets;       /* value sets behind `val`: 0 or 1 = one [nnz] set shared by every group; Bg or R*Bg = a
+                             per-sample graph (adjacency [V,N,N], attention.py:22): `val` is [val_sets, nnz] and group g
+                             reads set g % val_sets (g % Bg is the sample of the relation-major layout).  The structure
+                             is the union of the samples' patterns; a sample without an edge of it carries 0 there */
 } msgat_graph_t;
 
 typedef struct msgat_shape {
@@ -213,6 +219,13 @@ int msgat_graph_sell_count(const int32_t* ptr, int32_t n, int32_t* n_slices_out,
 int msgat_graph_sell_build(const int32_t* ptr, const int32_t* idx, const int32_t* perm, int32_t n,
                            int32_t nnz, int32_t n_slices, int32_t n_pos, int32_t* slice_off,
                            int32_t* lane_row, uint16_t* sidx, int32_t* ssrc, int32_t* spos);
+
+/* Values of a batched adjacency on a shared structure (device pointers): vals[v, e] = dense[v, erow_e, col_e] for the
+ * n_sets contiguous [N,N] fp32 matrices of `dense` and the CSR (rowptr, col) of `graph`; the non-zeros of `dense` that
+ * lie outside the structure (`!(x == 0)`: NaN counts) are ADDED to *outside (device int32).  One pass over the dense
+ * tensor, nothing read back: capturable in a HIP graph.  vals holds n_sets * nnz floats. */
+int msgat_graph_edge_values(const msgat_graph_t* graph, const float* dense, int32_t n_sets, float* vals,
+                            int32_t* outside, void* stream);
 
 /* ---- device: fused entry points --------------------------------------------------
  * msgat_gacn_forward replaces attention.py:33-36 (+ msgat.py:27-28 when Co > 0).

@@ -18,7 +18,7 @@ from . import ops
 
 
 class GraphAttention(nn.Module):
-    """signals [B,C,N,T], adjacency [N,N] -> [B,C,N,T]   (attention.py:21-23)."""
+    """signals [B,C,N,T], adjacency [N,N] or per sample [B,N,N] -> [B,C,N,T]   (attention.py:21-23)."""
 
     def __init__(self, n_channels: int, n_timesteps: int):
         super().__init__()
@@ -59,7 +59,8 @@ class GACN(nn.Module):
 class StackedGACN(nn.Module):
     """R independent GACNs over one adjacency, evaluated together.
 
-    signals [R,B,C,N,T] -> [R,B,Co,N,T].  `from_modules` stacks the parameters of
+    signals [R,B,C,N,T] -> [R,B,Co,N,T]; adjacency [N,N], [B,N,N] (one graph per sample, shared by the R relations) or
+    [R*B,N,N].  `from_modules` stacks the parameters of
     R ordinary `GACN`s (whose keys are the reference's checkpoint names).
     """
 

@@ -32,6 +32,9 @@ int check_graph(const msgat_shape_t* sh, const msgat_graph_t* gr) {
     if (gr->nnz > 0 && (!j->idx || !j->src)) return MSGAT_ERR_NULL;
   }
   if (gr->sell_rows.n_slices != 0 && gr->nnz > 0 && !gr->sell_rows.pos) return MSGAT_ERR_NULL;
+  // one value set, or one per sample (Bg: shared by the R relations; R*Bg: one per group)
+  if (gr->val_sets > 1 && gr->val_sets != sh->Bg && (int64_t)gr->val_sets != (int64_t)sh->R * sh->Bg) return MSGAT_ERR_SHAPE;
+  if (gr->val_sets < 0) return MSGAT_ERR_SHAPE;
   return MSGAT_OK;
 }
 
@@ -110,6 +113,15 @@ extern "C" const char* msgat_status_string(int status) {
 extern "C" int msgat_gacn_mode(int32_t C, int32_t Co) {
   if (Co <= 0) return MSGAT_MODE_PLAIN;
   return (C > Co) ? MSGAT_MODE_PROJ_FIRST : MSGAT_MODE_AGG_FIRST;
+}
+
+extern "C" int msgat_graph_edge_values(const msgat_graph_t* gr, const float* dense, int32_t n_sets, float* vals,
+                                       int32_t* outside, void* stream) {
+  if (!gr || !dense || !outside) return MSGAT_ERR_NULL;
+  if (gr->n_nodes <= 0 || gr->nnz < 0 || n_sets <= 0) return MSGAT_ERR_SHAPE;
+  if (!gr->rowptr || (gr->nnz > 0 && (!gr->col || !vals))) return MSGAT_ERR_NULL;
+  if ((int64_t)n_sets * gr->n_nodes * 64 >= ((int64_t)1 << 32)) return MSGAT_ERR_UNSUPPORTED;   // one wave per row: the grid's threads
+  return launch_edge_values(dense, gr->rowptr, gr->col, vals, outside, n_sets, gr->n_nodes, gr->nnz, (hipStream_t)stream);
 }
 
 // ---- stages -------------------------------------------------------------------------------------

@@ -264,6 +264,9 @@ int contract_form_name(int Ca, int Cb, int b_ones, int P, int with_mix, char* bu
 // also finishes the layer for its rows, y = E x (to apY[G,C,N,T] when not NULL) and z = W y (to apZ[G,apCo,N,T]) -- no
 // k_agg_proj launch.
 bool scores_take_x(int C, bool with_tail);
+// edge_values.hip: vals[v, e] = adj[v, erow_e, col_e]; non-zeros outside the structure added to *outside
+int launch_edge_values(const float* adj, const int* rowptr, const int* col, float* vals, int* outside, int V, int N,
+                       int nnz, hipStream_t s);
 int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse,
                   float* pq, float* E, float* Ec, int G, int Bg, int N, int T, hipStream_t s,
                   const float* x = nullptr, const float* alpha = nullptr, int C = 0, float* qout = nullptr,

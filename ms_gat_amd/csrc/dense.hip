@@ -236,7 +236,7 @@ static size_t balance_pad_bytes(int nblocks, size_t static_lds) {
 // kept for grids that leave CUs empty (PEMSD4's single relation: 192 blocks, two waves per SIMD), where the matrix pipe is idle
 // most of the time anyway and the conversion of the payload planes with its third barrier per chunk is pure latency
 // (0.2168 -> 0.2205 ms per hot-path step with the fp16 form there, same box).
-template <int T, bool WITH_PQ, int XC = 0, bool F16P = true>
+template <int T, bool WITH_PQ, int XC = 0, bool F16P = true, bool VS = false>
 __global__ __launch_bounds__(kDBlock) void k_scores(
     const float* __restrict__ q, const float* __restrict__ Wg, const int* __restrict__ rowptr,
     const int* __restrict__ col, const float* __restrict__ val, const int* __restrict__ erow,
@@ -244,7 +244,8 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
     const int* __restrict__ cpos, float* __restrict__ Ec, int Bg, int N, int nnz,
     const float* __restrict__ alpha, float* __restrict__ qout,   // XC > 0: `q` is x[G,XC,N,T], the q rows go to qout
     const float* __restrict__ apW, int apCo, float* __restrict__ apY, float* __restrict__ apZ,   // XC > 0 and apZ: the aggregate + projection tail
-    float one) {   // 1.0f, opaque to the compiler (split2_f16)
+    float one,     // 1.0f, opaque to the compiler (split2_f16)
+    int val_sets) {   // VS: group g reads the value set val + (g % val_sets) nnz (a per-sample graph); unused otherwise
   constexpr int T4 = T / 4;
   __shared__ float4 qs4[kDMC * kPS / 4];  // staged columns: [column][q(T) | zeros]
   __shared__ uint4 pl4[WITH_PQ && F16P ? kPlaneU4 : 1];   // their payload planes (fp16 terms, see build_payload_planes)
@@ -441,6 +442,8 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
 
   // edge coefficients of this block's rows: one lane per CSR edge, coalesced over e.  The VALU
   // chain below is the MFMA's k order starting from 0, exactly what k_bwd_dense_col re-creates.
+  // the adjacency weights this group multiplies by: its sample's own value set when the graph is per sample (VS)
+  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
   const int e0 = rowptr[n0];
   const int e1 = rowptr[min(n0 + kDRows, N)];
   __shared__ int tl_rp[XC > 0 ? kDRows + 1 : 1];
@@ -461,7 +464,7 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
       a = fmaf(v.z, kw2s[nl][4 * t4 + 2], a);
       a = fmaf(v.w, kw2s[nl][4 * t4 + 3], a);
     }
-    const float ev = fast_exp2(a - lse2s[nl]) * val[e];
+    const float ev = fast_exp2(a - lse2s[nl]) * vals[e];
     E[(size_t)g * nnz + e] = ev;
     // the same coefficient at its CSC position: the transposed passes of backward (du = E^T dv on the CSC) then
     // start without a re-ordering launch
@@ -495,14 +498,15 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
 constexpr int kHOwners = 7;
 constexpr int kHRows = 16 * kHOwners;
 
-template <int T, bool WITH_PQ, int XC = 0>
+template <int T, bool WITH_PQ, int XC = 0, bool VS = false>
 __global__ __launch_bounds__(kDBlock) void k_scores7(
     const float* __restrict__ q, const float* __restrict__ Wg, const int* __restrict__ rowptr,
     const int* __restrict__ col, const float* __restrict__ val, const int* __restrict__ erow,
     float* __restrict__ kW, float* __restrict__ lse, float* __restrict__ pq, float* __restrict__ E,
     const int* __restrict__ cpos, float* __restrict__ Ec, int Bg, int N, int nnz, int Ca,
     const float* __restrict__ alpha, float* __restrict__ qout,
-    const float* __restrict__ apW, int apCo, float* __restrict__ apY, float* __restrict__ apZ, float one) {
+    const float* __restrict__ apW, int apCo, float* __restrict__ apY, float* __restrict__ apZ, float one,
+    int val_sets) {   // see k_scores
   constexpr int T4 = T / 4;
   constexpr bool ONES = WITH_PQ && T < 16;
   constexpr float kPOff = WITH_PQ ? kPOffF : 0.f;               // see k_scores
@@ -756,6 +760,7 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
   MSGAT_STAMP(4);
 
   // edge coefficients of this block's rows (see k_scores)
+  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
   const int e0 = rowptr[min(n0, N)];
   const int e1 = rowptr[min(n0 + kHRows, N)];
   // the tail's row extents / edge list / coefficients take over the staging buffers (dead behind the barrier above): with
@@ -779,7 +784,7 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
       a = fmaf(v.z, kw2s[nl][4 * t4 + 2], a);
       a = fmaf(v.w, kw2s[nl][4 * t4 + 3], a);
     }
-    const float ev = fast_exp2(a - lse2s[nl]) * val[e];
+    const float ev = fast_exp2(a - lse2s[nl]) * vals[e];
     E[(size_t)g * nnz + e] = ev;
     if (Ec != nullptr) Ec[(size_t)g * nnz + cpos[e]] = ev;
     if (tail_cached) { tl_col[e - e0] = (int)ce; tl_E[e - e0] = ev; }
@@ -817,11 +822,13 @@ static int scores7_owner_columns(int N, int G) {
   return (Tn - Th) * 16;
 }
 
-// XC > 0: `q` is read-only x[G,XC,N,T] and the q rows are WRITTEN to qout (see QRows); XC = 0: `q` is the q array
-template <int T, int XC>
+// XC > 0: `q` is read-only x[G,XC,N,T] and the q rows are WRITTEN to qout (see QRows); XC = 0: `q` is the q array.
+// VS: the graph carries one value set per sample (gr.val_sets > 1); the kernels of a shared graph are those of VS = false.
+template <int T, int XC, bool VS>
 static int launch_scores_x(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse, float* pq,
                            float* E, float* Ec, int G, int Bg, int N, hipStream_t s, const float* alpha, float* qout,
                            const float* apW = nullptr, int apCo = 0, float* apY = nullptr, float* apZ = nullptr) {
+  const int vsets = gr.val_sets > 1 ? gr.val_sets : 1;
 #ifndef MSGAT_NO_SCORES7
   if (const int Ca = scores7_owner_columns(N, G)) {
     dim3 grid7(cdiv(N, kHRows), G);
@@ -829,11 +836,11 @@ static int launch_scores_x(const msgat_graph_t& gr, const float* q, const float*
                         (pq != nullptr ? 2 * sizeof(uint4) * kPlaneU4 : 2 * sizeof(uint4));   // + the payload planes (the tail re-uses the staging buffers)
     const size_t pad7 = balance_pad_bytes((int)(grid7.x * grid7.y), lds7);
     if (pq != nullptr)
-      hipLaunchKernelGGL((k_scores7<T, true, XC>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f);
+      hipLaunchKernelGGL((k_scores7<T, true, XC, VS>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
+                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
     else
-      hipLaunchKernelGGL((k_scores7<T, false, XC>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f);
+      hipLaunchKernelGGL((k_scores7<T, false, XC, VS>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
+                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
     MSGAT_CHECK_LAUNCH();
     return MSGAT_OK;
   }
@@ -844,25 +851,34 @@ static int launch_scores_x(const msgat_graph_t& gr, const float* q, const float*
                             (XC > 0 ? sizeof(int) * (kDRows + 1 + 2 * kTailEdges) : 0);
   const size_t pad = balance_pad_bytes((int)(grid.x * grid.y), static_lds);
   if (pq != nullptr && (int)(grid.x * grid.y) <= device_cu_count())   // a grid that leaves CUs empty: the fp32 payload product
-    hipLaunchKernelGGL((k_scores<T, true, XC, false>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f);
+    hipLaunchKernelGGL((k_scores<T, true, XC, false, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
+                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
   else if (pq != nullptr)
-    hipLaunchKernelGGL((k_scores<T, true, XC>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f);
+    hipLaunchKernelGGL((k_scores<T, true, XC, true, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
+                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
   else
-    hipLaunchKernelGGL((k_scores<T, false, XC>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f);
+    hipLaunchKernelGGL((k_scores<T, false, XC, true, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
+                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
+}
+
+template <int T, bool VS>
+static int launch_scores_v(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse, float* pq,
+                           float* E, float* Ec, int G, int Bg, int N, hipStream_t s, const float* x, const float* alpha,
+                           int C, float* qout, const float* apW, int apCo, float* apY, float* apZ) {
+  if (x != nullptr && C == 1) return launch_scores_x<T, 1, VS>(gr, x, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, alpha, qout, apW, apCo, apY, apZ);
+  if (x != nullptr && C == 3) return launch_scores_x<T, 3, VS>(gr, x, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, alpha, qout, apW, apCo, apY, apZ);
+  return launch_scores_x<T, 0, VS>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, nullptr, nullptr);
 }
 
 template <int T>
 static int launch_scores_t(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse, float* pq,
                            float* E, float* Ec, int G, int Bg, int N, hipStream_t s, const float* x, const float* alpha,
                            int C, float* qout, const float* apW, int apCo, float* apY, float* apZ) {
-  if (x != nullptr && C == 1) return launch_scores_x<T, 1>(gr, x, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, alpha, qout, apW, apCo, apY, apZ);
-  if (x != nullptr && C == 3) return launch_scores_x<T, 3>(gr, x, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, alpha, qout, apW, apCo, apY, apZ);
-  return launch_scores_x<T, 0>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, nullptr, nullptr);
+  if (gr.val_sets > 1)
+    return launch_scores_v<T, true>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
+  return launch_scores_v<T, false>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
 }
 
 // q inside the score kernel: with ONE input channel always (PEMSD7 / PEMSD8 / PEMSD3: -4.9 us per hot-path step); with three

@@ -267,13 +267,14 @@ constexpr float kBDefer = 8.f;
 // Wave w owns rows n0 + 16w .. +15; all columns stream through LDS in chunks of kChunkTiles records, two LDS buffers,
 // the next chunk in flight (LDS-DMA) while this one is multiplied; one barrier per chunk.
 // Score tile D[i = column][j = row]: lane (row j, quad) holds columns 4 quad + r.  Payload tile D2[i = s][j = row].
-template <bool WITH_PQ>
+template <bool WITH_PQ, bool VS = false>
 __global__ __launch_bounds__(kBBlock) void k_scores_b(
     const float* __restrict__ q, const float* __restrict__ Wg, const uint4* __restrict__ img,
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
     const int* __restrict__ erow, float* __restrict__ kW, float* __restrict__ lse, float* __restrict__ pq,
     float* __restrict__ E, const int* __restrict__ cpos, float* __restrict__ Ec, const float2* __restrict__ scales, float one,
-    int G, int Bg, int N, int nnz, int NTp, int nb) {
+    int G, int Bg, int N, int nnz, int NTp, int nb,
+    int val_sets) {   // VS: group g reads the value set val + (g % val_sets) nnz (a per-sample graph); unused otherwise
   constexpr int T = kBT, T4 = T / 4;
   constexpr int kRecU = kRecA / 16;                    // uint4 per record
   constexpr int kChunkU = kChunkTiles * kRecU;         // 832
@@ -422,6 +423,7 @@ __global__ __launch_bounds__(kBBlock) void k_scores_b(
   // step on the A side (their columns' fragments gathered from the image in memory), the wave's rows on the B side, and edge
   // i's score is D[i][row of edge i] -- held by the lane of that row.
   const int nw = n0 + 16 * wave;
+  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
   const int e0 = rowptr[min(nw, N)], e1 = rowptr[min(nw + 16, N)];
   for (int et = e0; et < e1; et += 16) {
     const int ea = min(et + j, e1 - 1);
@@ -436,7 +438,7 @@ __global__ __launch_bounds__(kBBlock) void k_scores_b(
     for (int rr = 0; rr < 4; ++rr) {
       ee[rr] = min(et + 4 * quad + rr, e1 - 1);
       er[rr] = erow[ee[rr]];
-      ev[rr] = val[ee[rr]];
+      ev[rr] = vals[ee[rr]];
     }
     f32x4 S = {0.f, 0.f, 0.f, 0.f};
     S = mfma_bf(a_hm, fb.hh, S); S = mfma_bf(a_hm, fb.mm, S); S = mfma_bf(a_hl, fb.lh, S);
@@ -604,12 +606,19 @@ int launch_scores_b(const msgat_graph_t& gr, const float* q, const float* Wg, fl
   const int nb = cdiv(N, kBRows);
   const dim3 grid(8 * nb * cdiv(G, 8));
   const size_t lds = 2 * (size_t)kChunkTiles * kRecA;
-  if (pq != nullptr)
+  const int vsets = gr.val_sets > 1 ? gr.val_sets : 1;
+  if (pq != nullptr && vsets > 1)
+    hipLaunchKernelGGL((k_scores_b<true, true>), grid, dim3(kBBlock), lds, s, q, Wg, img, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse,
+                       pq, E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb, vsets);
+  else if (pq != nullptr)
     hipLaunchKernelGGL(k_scores_b<true>, grid, dim3(kBBlock), lds, s, q, Wg, img, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse, pq,
-                       E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb);
+                       E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb, vsets);
+  else if (vsets > 1)
+    hipLaunchKernelGGL((k_scores_b<false, true>), grid, dim3(kBBlock), lds, s, q, Wg, img, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse,
+                       pq, E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb, vsets);
   else
     hipLaunchKernelGGL(k_scores_b<false>, grid, dim3(kBBlock), lds, s, q, Wg, img, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse,
-                       pq, E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb);
+                       pq, E, gr.cpos, Ec, scales, 1.0f, G, Bg, N, gr.nnz, NTp, nb, vsets);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }

@@ -1,5 +1,5 @@
 """Sensor-graph adjacency: the sym-normalised dense matrix the reference uses and the
-CSR/CSC form the HIP kernels walk.
+CSR/CSC form the HIP kernels walk; `BatchedGraph` is a per-sample adjacency [V,N,N] on one shared structure.
 
 Reference: /root/reference/src/data_loader.py:49-66 builds `D^-1/2 (A + I) D^-1/2` from a
 csv edge list; src/models/msgat.py:190 keeps it as a frozen parameter `adj`;
@@ -79,8 +79,9 @@ class SparseGraph:
             # everything here: the CSR / CSC / SELL structures are built per graph, not per sample
             raise ValueError(
                 f"adjacency must be one [n_nodes, n_nodes] matrix, got {tuple(adjacency.shape)}: the batched form "
-                "`[..., n_nodes, n_nodes]` that the reference's attention.py:22 documents is not supported -- call the "
-                "op once per adjacency (one SparseGraph each)")
+                "`[..., n_nodes, n_nodes]` that the reference's attention.py:22 documents is not supported by "
+                "SparseGraph -- a [B, n_nodes, n_nodes] adjacency goes through BatchedGraph / batched_graph_of "
+                "(the ops and modules accept it directly)")
         if adjacency.dim() != 2 or adjacency.size(0) != adjacency.size(1):
             raise ValueError(f"adjacency must be [N,N], got {tuple(adjacency.shape)}")
         a = adjacency.detach().to(device="cpu", dtype=torch.float32).contiguous()
@@ -214,4 +215,218 @@ def graph_of(adjacency: torch.Tensor) -> SparseGraph:
     _CACHE.move_to_end(key)
     while len(_CACHE) > _CACHE_MAX:
         _CACHE.popitem(last=False)
+    return g
+
+
+_SQ_CACHE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
+
+
+def _squeezed_graph_of(adjacency: torch.Tensor) -> SparseGraph:
+    """`graph_of(adjacency[0])` for a [1,N,N] tensor, cached on the 3-D tensor itself: its [N,N] view is a new object
+    at every call, which graph_of could only confirm by comparing contents (a read-back, impossible under capture)."""
+    key = (adjacency.data_ptr(), tuple(adjacency.shape), str(adjacency.device), adjacency._version)
+    hit = _SQ_CACHE.get(key)
+    if hit is not None and hit[1]() is adjacency:
+        _SQ_CACHE.move_to_end(key)
+        return hit[0]
+    g = graph_of(adjacency[0])
+    _SQ_CACHE[key] = (g, weakref.ref(adjacency))
+    while len(_SQ_CACHE) > _CACHE_MAX:
+        _SQ_CACHE.popitem(last=False)
+    return g
+
+
+# ---- per-sample adjacency [V,N,N] ------------------------------------------------------------------------------------
+# The reference's `softmax(k Wg q^T) * adjacency` (attention.py:36) broadcasts over the batch, so [B,N,N] gives every
+# sample its own graph.  The kernels read adjacency values in one place only (the edge tail of the score kernels), so a
+# batched adjacency is ONE structure -- the union of the samples' patterns, shared by every object with that pattern --
+# and one value set per sample, val [V,nnz], with explicit zeros where a sample lacks a union edge (E = 0 there).
+
+_PATTERNS: "collections.OrderedDict[tuple, SparseGraph]" = collections.OrderedDict()   # (N, sell, packed mask) -> structure
+_LAST_PATTERN = {}   # (N, sell) -> the structure used last: what a miss tries first
+_PATTERNS_MAX = 8
+
+
+def _union_structure(mask: torch.Tensor, sell: str) -> SparseGraph:
+    """The shared CSR / CSC (/ SELL) of a host [N,N] bool mask (values 1 at the edges; BatchedGraph brings its own)."""
+    m = mask.to(device="cpu", dtype=torch.bool).contiguous()
+    n = m.shape[0]
+    key = (n, sell, np.packbits(m.numpy()).tobytes())
+    g = _PATTERNS.get(key)
+    if g is None:
+        g = _PATTERNS[key] = SparseGraph(m.to(torch.float32), sell=sell)
+        while len(_PATTERNS) > _PATTERNS_MAX:
+            _PATTERNS.popitem(last=False)
+    _PATTERNS.move_to_end(key)
+    _LAST_PATTERN[(n, sell)] = g
+    return g
+
+
+def _check_batched(adjacency: torch.Tensor):
+    if adjacency.dim() != 3 or adjacency.shape[1] != adjacency.shape[2] or adjacency.shape[0] < 1:
+        raise ValueError(f"a batched adjacency must be [V, N, N], got {tuple(adjacency.shape)}")
+
+
+class BatchedGraph:
+    """A per-sample adjacency [V,N,N]: one shared sparse structure (the union of the samples' non-zero patterns, built
+    by `SparseGraph` from the [N,N] mask `(adj != 0).any(0)`) and this object's own values val [V,nnz].
+
+    Exposes what the ops use of a `SparseGraph` (`n_nodes`, `nnz`, `on(device)`, a `__dict__` for the per-shape plans)
+    plus `n_sets` = V; `on()` hands the library the structure's device arrays with `val` pointing at this object's values
+    and `val_sets = V`.  Group g of a call reads value set g % V: V = B for a [B,...] batch (shared by R stacked
+    relations), V = R*B for one set per group.
+
+    `update_(adj)` refills the values in place from a device tensor with the `msgat_graph_edge_values` kernel, which also
+    adds the non-zeros it finds outside the structure to a device counter; nothing is read back, so it may sit inside a
+    HIP-graph capture.  `check()` reads the counter and raises if any sample had an edge the structure lacks (those edges
+    would be silently dropped).  A CPU tensor is gathered on the host by indexing (no GPU needed)."""
+
+    def __init__(self, adjacency: torch.Tensor, sell: str = "auto", structure: SparseGraph = None):
+        _check_batched(adjacency)
+        V, N = int(adjacency.shape[0]), int(adjacency.shape[1])
+        if structure is None:
+            structure = _union_structure((adjacency.detach() != 0).any(0), sell)
+        elif structure.n_nodes != N:
+            raise ValueError(f"structure has {structure.n_nodes} nodes, the adjacency {N}")
+        self.structure = structure
+        self.n_nodes, self.nnz, self.n_sets = N, structure.nnz, V
+        self.device = adjacency.device
+        self.val = torch.zeros((V, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
+        self._outside = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._dev = {}
+        self.update_(adjacency)
+
+    @property
+    def has_sell(self) -> bool:
+        return self.structure.has_sell
+
+    def update_(self, adjacency: torch.Tensor) -> "BatchedGraph":
+        """Refill the values from `adjacency` [V,N,N] (same V, N and device); non-zeros outside the structure are added
+        to the counter that `check()` reads."""
+        _check_batched(adjacency)
+        if tuple(adjacency.shape) != (self.n_sets, self.n_nodes, self.n_nodes):
+            raise ValueError(f"adjacency {tuple(adjacency.shape)} does not match this graph's "
+                             f"[{self.n_sets}, {self.n_nodes}, {self.n_nodes}]")
+        if adjacency.device != self.device:
+            raise ValueError(f"adjacency is on {adjacency.device}, this graph's values on {self.device}")
+        a = adjacency.detach()
+        if a.dtype != torch.float32:
+            a = a.float()
+        if not a.is_contiguous():        # an expanded [N,N] too: the kernel streams contiguous rows
+            a = a.contiguous()
+        s = self.structure
+        if not a.is_cuda:
+            if self.nnz:
+                self.val[:, : self.nnz] = a[:, s.erow[: self.nnz].long(), s.col[: self.nnz].long()]
+            inside = int((self.val[:, : self.nnz] != 0).sum())
+            self._outside += int((a != 0).sum()) - inside
+            return self
+        gstruct, _ = s.on(a.device)
+        _lib.check(_lib.lib().msgat_graph_edge_values(C.byref(gstruct), a.data_ptr(), self.n_sets, self.val.data_ptr(),
+                                                      self._outside.data_ptr(), _current_stream(a.device)),
+                   "msgat_graph_edge_values")
+        return self
+
+    def outside(self) -> int:
+        """Non-zeros found outside the structure by every refresh so far (a read-back)."""
+        return int(self._outside.item())
+
+    def check(self) -> "BatchedGraph":
+        n = self.outside()
+        if n:
+            raise _lib.MsgatError(f"{n} non-zero adjacency entries lie outside this BatchedGraph's pattern: build a "
+                                  "new one for this adjacency (batched_graph_of does so)")
+        return self
+
+    def on(self, device: torch.device):
+        """(ctypes struct of device pointers, tensors kept alive) for `device`: the shared structure, this object's
+        values."""
+        key = str(device)
+        if key not in self._dev:
+            _, tensors = self.structure.on(device)
+            val = self.val if self.val.device == torch.device(device) else self.val.to(device)
+            g = self.structure._struct(tensors)
+            g.val, g.val_sets = val.data_ptr(), self.n_sets
+            self._dev[key] = (g, (tensors, val))
+        return self._dev[key]
+
+    def dense(self) -> torch.Tensor:
+        """[V,N,N] of the values on the structure (host)."""
+        s = self.structure
+        a = torch.zeros(self.n_sets, self.n_nodes, self.n_nodes)
+        if self.nnz:
+            a[:, s.erow[: self.nnz].long(), s.col[: self.nnz].long()] = self.val[:, : self.nnz].cpu()
+        return a
+
+
+def _current_stream(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+_BCACHE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
+
+
+def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGraph:
+    """Cached `BatchedGraph` of a dense [V,N,N] adjacency, keyed on (storage address, shape, device, version).
+
+    A hit on the very same tensor object is free, except under a HIP-graph capture, where it enqueues the refresh: a
+    captured static input keeps its identity while its contents change at every replay.  A miss reuses the pattern used
+    last for this N when there is one: the values are filled by the kernel and the 4-byte outside count is read back;
+    a non-zero count rebuilds the union pattern (N^2 mask bytes to the host) and fills again.  Under capture nothing is
+    read back: the known pattern is used and the count only accumulates (`check()` reads it later); with no known
+    pattern it raises, as graph_of does."""
+    _check_batched(adjacency)
+    capturing = adjacency.is_cuda and torch.cuda.is_current_stream_capturing()
+    key = (adjacency.data_ptr(), tuple(adjacency.shape), str(adjacency.device), adjacency._version, sell)
+    hit = _BCACHE.get(key)
+    if hit is not None and hit[1]() is adjacency:
+        _BCACHE.move_to_end(key)
+        if capturing:
+            hit[0].update_(adjacency)
+        return hit[0]
+    known = hit[0].structure if hit is not None else _LAST_PATTERN.get((int(adjacency.shape[1]), sell))
+    if not adjacency.is_cuda:
+        g = BatchedGraph(adjacency, sell)
+    elif known is not None:
+        g = BatchedGraph(adjacency, sell, structure=known)
+        if not capturing and g.outside() != 0:
+            g = BatchedGraph(adjacency, sell)
+    elif capturing:
+        raise _lib.MsgatError("the pattern of this batched adjacency is not known yet: run one forward outside the "
+                              "HIP-graph capture first (engine.Trainer does this in its warm-up)")
+    else:
+        g = BatchedGraph(adjacency, sell)
+    if not capturing:
+        _LAST_PATTERN[(g.n_nodes, sell)] = g.structure
+    _BCACHE[key] = (g, weakref.ref(adjacency))
+    _BCACHE.move_to_end(key)
+    while len(_BCACHE) > _CACHE_MAX:
+        _BCACHE.popitem(last=False)
+    return g
+
+
+def graph_for(adjacency, groups: int, relations: int):
+    """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N]
+    through graph_of; [1,N,N] as [N,N]; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one
+    per group) through batched_graph_of.  A batched adjacency gets no gradient: one that requires grad while autograd
+    records is refused."""
+    if isinstance(adjacency, (SparseGraph, BatchedGraph)):
+        g = adjacency
+    elif not isinstance(adjacency, torch.Tensor):
+        raise TypeError(f"adjacency must be a tensor, a SparseGraph or a BatchedGraph, got {type(adjacency).__name__}")
+    elif adjacency.dim() == 3:
+        V = adjacency.shape[0]
+        Bg = groups // relations
+        if V != 1 and V != Bg and V != groups:
+            allowed = sorted({1, Bg, groups})
+            raise ValueError(f"a batched adjacency {tuple(adjacency.shape)} needs a leading size in {allowed} for signals of "
+                             f"{groups} groups ({relations} relation(s) x {Bg} samples)")
+        if V != 1 and adjacency.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"the batched adjacency {tuple(adjacency.shape)} requires grad: it gets no gradient (the "
+                             "reference's adjacency is a frozen parameter); pass adjacency.detach()")
+        g = _squeezed_graph_of(adjacency) if V == 1 else batched_graph_of(adjacency)
+    else:
+        g = graph_of(adjacency)
+    if isinstance(g, BatchedGraph) and g.n_sets not in (1, groups // relations, groups):
+        raise ValueError(f"BatchedGraph with {g.n_sets} value sets for signals of {groups} groups ({relations} relation(s))")
     return g

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .graph import SparseGraph, graph_of
+from .graph import graph_for
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -101,7 +101,7 @@ class _GACNFunction(torch.autograd.Function):
     """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg."""
 
     @staticmethod
-    def forward(ctx, x, alpha, Wg, W, graph: SparseGraph, recording: bool = True):
+    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True):   # graph: SparseGraph or BatchedGraph
         L = _lib.lib()
         dev = x.device
         G, Cin, N, T = x.shape
@@ -183,7 +183,9 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
     """Graph attention (+ channel projection when `W` is given) over R stacked relations.
 
     x [R*Bg, C, N, T] (relation-major), alpha [R,C], Wg [R,T,T], W [R,Co,C] or None,
-    adjacency: dense [N,N] tensor or a prebuilt `SparseGraph`.  Returns [R*Bg, Co|C, N, T].
+    adjacency: dense [N,N] tensor or a prebuilt `SparseGraph`; or a per-sample adjacency -- dense [Bg,N,N] (one graph per
+    sample, shared by the R relations), [R*Bg,N,N] (one per group) or a prebuilt `BatchedGraph` of either ([1,N,N] is
+    [N,N]; `graph.graph_for`).  Returns [R*Bg, Co|C, N, T].
     One relation may come without the leading axis -- alpha [C], Wg [T,T], W [Co,C], the reference's own parameter
     shapes (attention.py:29-30, msgat.py:23): the module classes call it that way, so that no view nodes sit between
     the parameters and the op (three `unsqueeze` forward and three more nodes backward were a sixth of a call's host time).
@@ -209,7 +211,7 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
             raise ValueError(f"Wg must be [{R},{T},{T}], got {tuple(Wg.shape)}")
         if W is not None and (W.dim() != 3 or W.shape[0] != R or W.shape[2] != Cin):
             raise ValueError(f"W must be [{R},Co,{Cin}], got {tuple(W.shape)}")
-    graph = adjacency if isinstance(adjacency, SparseGraph) else graph_of(adjacency)
+    graph = graph_for(adjacency, G, alpha.shape[0] if alpha.dim() == 2 else 1)
     if graph.n_nodes != N:
         raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
     return _GACNFunction.apply(x, alpha, Wg, W, graph, torch.is_grad_enabled())
@@ -1093,7 +1095,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
     msgat_attention_backward)."""
 
     @staticmethod
-    def forward(ctx, u, q, Wg, graph: SparseGraph, recording: bool = True):
+    def forward(ctx, u, q, Wg, graph, recording: bool = True):   # graph: SparseGraph or BatchedGraph
         L = _lib.lib()
         u, q, Wg = u.contiguous(), q.contiguous(), Wg.contiguous()
         G, Cu, N, T = u.shape
@@ -1147,7 +1149,7 @@ def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency
     G, Cu, N, T = u.shape
     if tuple(q.shape) != (G, N, T) or Wg.dim() != 3 or tuple(Wg.shape[1:]) != (T, T) or G % Wg.shape[0]:
         raise ValueError(f"attention_core: u {tuple(u.shape)}, q {tuple(q.shape)}, Wg {tuple(Wg.shape)}")
-    graph = adjacency if isinstance(adjacency, SparseGraph) else graph_of(adjacency)
+    graph = graph_for(adjacency, G, Wg.shape[0])
     if graph.n_nodes != N:
         raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
     return _AttentionCoreFunction.apply(u, q, Wg, graph, torch.is_grad_enabled())
