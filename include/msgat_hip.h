@@ -47,7 +47,8 @@
 extern "C" {
 #endif
 
-/* 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
+/* 10: + msgat_adjacency_grad{,_workspace_bytes} (the gradient of a dense adjacency that requires grad); nothing else changed.
+ * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
  * 7 (round 6): + msgat_dense_scratch_bytes; msgat_fwd_t.dense_scratch (new last field); msgat_stage_scores and
@@ -56,7 +57,7 @@ extern "C" {
  * 6 (round 5): + msgat_contract_form_name, msgat_causal_conv{,_fused,_grad_weight}, msgat_layernorm_head_backward
  * {,_partial_floats}, msgat_head_forward_ln, msgat_gate_sum{,_backward}, msgat_layernorm_{forward,backward}_pooled, msgat_layernorm_pool_partial_floats,
  * msgat_contract_mix_partial_floats; no existing signature or structure changed since 5. */
-#define MSGAT_ABI_VERSION 9
+#define MSGAT_ABI_VERSION 10
 
 enum {
   MSGAT_OK = 0,
@@ -229,8 +230,8 @@ int msgat_graph_edge_values(const msgat_graph_t* graph, const float* dense, int3
 
 /* ---- device: fused entry points --------------------------------------------------
  * msgat_gacn_forward replaces attention.py:33-36 (+ msgat.py:27-28 when Co > 0).
- * msgat_gacn_backward replaces the autograd of those lines (adj gets no gradient,
- * msgat.py:190). */
+ * msgat_gacn_backward replaces the autograd of those lines for x, alpha, Wg and W; the adjacency's own gradient, when it
+ * requires one, is msgat_adjacency_grad (below), enqueued after it. */
 size_t msgat_edge_scratch_floats(const msgat_shape_t* shape, const msgat_graph_t* graph);
 /* Scratch of the two dense passes over all N columns of a row (the softmax denominator of attention.py:34 and its
  * backward).  From N = 1536 nodes (T = 12) they run on the bf16 / fp16 matrix core with every fp32 operand split into
@@ -245,6 +246,23 @@ size_t msgat_bwd_workspace_bytes(const msgat_shape_t* shape, const msgat_graph_t
 int msgat_bwd_accepts_strided_dz(const msgat_shape_t* shape, const msgat_graph_t* graph);
 int msgat_gacn_backward(const msgat_shape_t* shape, const msgat_graph_t* graph,
                         const msgat_bwd_t* io, void* stream);
+
+/* ---- device: gradient of the adjacency (attention.py:36 with an adjacency that requires grad) ----
+ *   dadj[v,n,m] = sum_{g : g % n_sets == v} P_g[n,m] H_g[n,m],   H_g[n,m] = sum_{c < Cu, t} dv[g,c,n,t] feat[g,c,m,t]
+ *   P_g = 2^(S_g[n,m] log2 e - lse_g[n]),  S_g = kW_g q_g^T:  the softmax over ALL N columns, before the mask.
+ * P does not depend on the adjacency, so dadj is DENSE: written for every (n, m), edge or not (no graph argument).
+ * q, kW, lse [G,N,T] / [G,N] are what the forward saved.  dv / feat / Cu by path: PLAIN dz / x / C; PROJ_FIRST dz / u = W x
+ * / Co; AGG_FIRST W^T dz (msgat_stage_mix) / x / C; the attention core dv / u / Cu.  dv_group_channels: 0 (contiguous) or the
+ * channel count of the wider tensor dv is a channel slice of, as msgat_bwd_t.dz_group_channels.  n_sets: 1 (one [N,N]
+ * adjacency, summed over all G groups), Bg ([Bg,N,N]: sample b shared by its R relations) or R*Bg (one per group) --
+ * the convention of msgat_graph_t.val_sets; dadj is [n_sets,N,N].  shape->C / Co are those of the call (only checked).
+ * Deterministic (a fixed order of additions, no atomics); nothing is read back, so it may be captured in a HIP graph.
+ * workspace: msgat_adjacency_grad_workspace_bytes() bytes, 256-byte aligned (the per-split partial sums; may be 0).
+ * T in {4,8,12,16} and Cu <= 256, else MSGAT_ERR_UNSUPPORTED; a bad n_sets or Cu <= 0 is MSGAT_ERR_SHAPE. */
+size_t msgat_adjacency_grad_workspace_bytes(const msgat_shape_t* shape, int32_t Cu, int32_t n_sets);
+int msgat_adjacency_grad(const msgat_shape_t* shape, int32_t Cu, const float* dv, int32_t dv_group_channels,
+                         const float* feat, const float* q, const float* kW, const float* lse, int32_t n_sets, float* dadj,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- device: the individual stages (exposed for tests, profiling and bench.py) ----
  * Each is what the fused entry points enqueue, in order. */

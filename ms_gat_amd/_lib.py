@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libmsgat_hip.so")
 
 MSGAT_OK = 0
-ABI_VERSION = 9  # MSGAT_ABI_VERSION of include/msgat_hip.h
+ABI_VERSION = 10  # MSGAT_ABI_VERSION of include/msgat_hip.h
 MODE_PLAIN, MODE_AGG_FIRST, MODE_PROJ_FIRST = 0, 1, 2
 
 c_float_p = C.POINTER(C.c_float)
@@ -71,6 +71,10 @@ _PROTOTYPES = {
     "msgat_graph_sell_count": (C.c_int, [C.c_void_p, C.c_int32, c_int_p, c_int_p, c_int_p]),
     "msgat_graph_sell_build": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 5),
     "msgat_graph_edge_values": (C.c_int, [C.POINTER(Graph), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "msgat_adjacency_grad_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.c_int32, C.c_int32]),
+    "msgat_adjacency_grad": (C.c_int, [C.POINTER(Shape), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     "msgat_edge_scratch_floats": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),
     "msgat_gacn_forward": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.POINTER(Fwd), C.c_void_p]),
     "msgat_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),

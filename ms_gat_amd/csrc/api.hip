@@ -124,6 +124,38 @@ extern "C" int msgat_graph_edge_values(const msgat_graph_t* gr, const float* den
   return launch_edge_values(dense, gr->rowptr, gr->col, vals, outside, n_sets, gr->n_nodes, gr->nnz, (hipStream_t)stream);
 }
 
+// ---- gradient of the adjacency ------------------------------------------------------------------
+static int check_adjacency_grad(const msgat_shape_t* sh, int32_t Cu, int32_t n_sets) {
+  int st = check_shape(sh);
+  if (st) return st;
+  const int64_t G = (int64_t)sh->R * sh->Bg;
+  if (Cu <= 0 || (n_sets != 1 && n_sets != sh->Bg && n_sets != G)) return MSGAT_ERR_SHAPE;
+  if (Cu > kMaxC) return MSGAT_ERR_UNSUPPORTED;
+  if ((int64_t)sh->N * sh->N >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;   // the final reduction indexes [N*N] with int
+  if ((int64_t)Cu * sh->N * sh->T >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;
+  return MSGAT_OK;
+}
+
+extern "C" size_t msgat_adjacency_grad_workspace_bytes(const msgat_shape_t* sh, int32_t Cu, int32_t n_sets) {
+  if (check_adjacency_grad(sh, Cu, n_sets) != MSGAT_OK) return 0;
+  return adjacency_grad_workspace_bytes(sh->N, sh->R * sh->Bg, n_sets);
+}
+
+extern "C" int msgat_adjacency_grad(const msgat_shape_t* sh, int32_t Cu, const float* dv, int32_t dv_group_channels,
+                                    const float* feat, const float* q, const float* kW, const float* lse, int32_t n_sets,
+                                    float* dadj, void* workspace, size_t workspace_bytes, void* stream) {
+  int st = check_adjacency_grad(sh, Cu, n_sets);
+  if (st) return st;
+  if (dv_group_channels < 0 || (dv_group_channels > 0 && dv_group_channels < Cu)) return MSGAT_ERR_SHAPE;
+  if (!dv || !feat || !q || !kW || !lse || !dadj) return MSGAT_ERR_NULL;
+  const int G = sh->R * sh->Bg;
+  const size_t need = adjacency_grad_workspace_bytes(sh->N, G, n_sets);
+  if (need > 0 && !workspace) return MSGAT_ERR_NULL;
+  if (workspace_bytes < need) return MSGAT_ERR_WORKSPACE;
+  return launch_adjacency_grad(dv, dv_group_channels, feat, q, kW, lse, dadj, static_cast<float*>(workspace), G, n_sets,
+                               Cu, sh->N, sh->T, (hipStream_t)stream);
+}
+
 // ---- stages -------------------------------------------------------------------------------------
 extern "C" int msgat_stage_project(const msgat_shape_t* sh, const float* x, const float* alpha,
                                    const float* W, float* q, float* u, void* stream) {

@@ -267,6 +267,11 @@ bool scores_take_x(int C, bool with_tail);
 // edge_values.hip: vals[v, e] = adj[v, erow_e, col_e]; non-zeros outside the structure added to *outside
 int launch_edge_values(const float* adj, const int* rowptr, const int* col, float* vals, int* outside, int V, int N,
                        int nnz, hipStream_t s);
+// adjacency_grad.hip: dadj[v,n,m] = sum_{g % V == v} P_g[n,m] sum_{c,t} dv[g,c,n,t] feat[g,c,m,t] (dense, deterministic);
+// ws: adjacency_grad_workspace_bytes(N, G, V) bytes (the per-split partial sums; 0 when the groups are not split)
+size_t adjacency_grad_workspace_bytes(int N, int G, int V);
+int launch_adjacency_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
+                          const float* lse, float* dadj, float* ws, int G, int V, int Cu, int N, int T, hipStream_t s);
 int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse,
                   float* pq, float* E, float* Ec, int G, int Bg, int N, int T, hipStream_t s,
                   const float* x = nullptr, const float* alpha = nullptr, int C = 0, float* qout = nullptr,

@@ -408,8 +408,9 @@ def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGrap
 def graph_for(adjacency, groups: int, relations: int):
     """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N]
     through graph_of; [1,N,N] as [N,N]; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one
-    per group) through batched_graph_of.  A batched adjacency gets no gradient: one that requires grad while autograd
-    records is refused."""
+    per group) through batched_graph_of.  The graph carries no gradient: a batched adjacency that requires grad while
+    autograd records is refused here.  The ops (`ops.gacn`, `graph_attention`, `attention_core`, and the modules on
+    them) accept one -- they hand this function a detached alias and route the gradient themselves."""
     if isinstance(adjacency, (SparseGraph, BatchedGraph)):
         g = adjacency
     elif not isinstance(adjacency, torch.Tensor):
@@ -422,8 +423,9 @@ def graph_for(adjacency, groups: int, relations: int):
             raise ValueError(f"a batched adjacency {tuple(adjacency.shape)} needs a leading size in {allowed} for signals of "
                              f"{groups} groups ({relations} relation(s) x {Bg} samples)")
         if V != 1 and adjacency.requires_grad and torch.is_grad_enabled():
-            raise ValueError(f"the batched adjacency {tuple(adjacency.shape)} requires grad: it gets no gradient (the "
-                             "reference's adjacency is a frozen parameter); pass adjacency.detach()")
+            raise ValueError(f"the batched adjacency {tuple(adjacency.shape)} requires grad: graph_for builds a graph without "
+                             "one; call ops.gacn / graph_attention / attention_core (or a module) with it, which give it its "
+                             "gradient, or pass adjacency.detach()")
         g = _squeezed_graph_of(adjacency) if V == 1 else batched_graph_of(adjacency)
     else:
         g = graph_of(adjacency)

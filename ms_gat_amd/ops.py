@@ -9,6 +9,7 @@ arithmetic step runs in libmsgat_hip.so through the C ABI of include/msgat_hip.h
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Optional
 
 import torch
@@ -97,11 +98,59 @@ def _gacn_plan(graph, dev, R, Bg, Cin, Co, N, T, need_bwd, own_q=True) -> _GacnP
     return plan
 
 
+# ---- an adjacency that requires grad ----------------------------------------------------------------------------------
+# The graph is built from a detached alias of the adjacency, and the tensor itself rides into the autograd Function as a
+# last input, so that its gradient (msgat_adjacency_grad) has somewhere to go.  The alias is ONE object per adjacency:
+# graph_of / batched_graph_of hit their caches by identity (a fresh `detach()` per call would be confirmed by a content
+# read-back every time, which a HIP-graph capture cannot contain).  It shares the version counter, so an in-place update
+# of the adjacency still rebuilds the graph.
+_DETACHED = {}   # id(adjacency) -> (weakref to it, its detached alias); an entry leaves with its tensor
+
+
+def _detached(adjacency: torch.Tensor) -> torch.Tensor:
+    key = id(adjacency)
+    hit = _DETACHED.get(key)
+    if hit is not None and hit[0]() is adjacency:
+        return hit[1]
+    alias = adjacency.detach()
+    _DETACHED[key] = (weakref.ref(adjacency, lambda _r, k=key: _DETACHED.pop(k, None)), alias)
+    return alias
+
+
+def _adjacency_operand(adjacency, recording: bool):
+    """(what graph_for gets, the adjacency tensor that receives a gradient or None).  A frozen adjacency -- every
+    caller of the reference's models -- costs this one `requires_grad` check; a prebuilt SparseGraph / BatchedGraph is
+    not a tensor and gets no gradient."""
+    if recording and getattr(adjacency, "requires_grad", False):
+        return _detached(adjacency), adjacency
+    return adjacency, None
+
+
+def _adjacency_sets(adj: torch.Tensor) -> int:
+    """n_sets of msgat_adjacency_grad for a dense [N,N] / [V,N,N] adjacency (graph_for has checked V already)."""
+    return 1 if adj.dim() == 2 else int(adj.shape[0])
+
+
+def _adjacency_grad(shape, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int, n_sets: int,
+                    adj_shape, dev, stream) -> torch.Tensor:
+    """dadj in the adjacency's own shape, enqueued on `stream` after the backward of the other inputs."""
+    L = _lib.lib()
+    N = shape.N
+    dadj = torch.empty((n_sets, N, N), device=dev, dtype=torch.float32)
+    nbytes = int(L.msgat_adjacency_grad_workspace_bytes(C.byref(shape), Cu, n_sets))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    st = L.msgat_adjacency_grad(C.byref(shape), Cu, _ptr(dv), dv_gs, feat, q, kW, lse, n_sets, _ptr(dadj), _ptr(ws),
+                                nbytes, stream)
+    _lib.check(st, "msgat_adjacency_grad")
+    return dadj.view(adj_shape)
+
+
 class _GACNFunction(torch.autograd.Function):
-    """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg."""
+    """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg.  `adj`: the dense adjacency
+    tensor when it requires grad (the graph was built from its detached alias), else None."""
 
     @staticmethod
-    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True):   # graph: SparseGraph or BatchedGraph
+    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj=None):   # graph: SparseGraph or BatchedGraph
         L = _lib.lib()
         dev = x.device
         G, Cin, N, T = x.shape
@@ -137,6 +186,7 @@ class _GACNFunction(torch.autograd.Function):
 
         if need_bwd:
             ctx.plan, ctx.has_W = plan, W is not None
+            ctx.adj_grad = None if adj is None else (_adjacency_sets(adj), tuple(adj.shape))
             if W is not None:
                 ctx.save_for_backward(x, alpha, Wg, buf, W)
             else:
@@ -149,8 +199,10 @@ class _GACNFunction(torch.autograd.Function):
         # separate work.  PROJ_FIRST: dW, dalpha AND dx leave ONE launch that reads du, dq and x once
         # (msgat_stage_project_backward); AGG_FIRST: dW rides in the pass that forms dy, dalpha in the transposed aggregate
         # that forms dx; dWg is a [T,T] partial of the row pass that every other gradient needs.  The only input that
-        # is ever frozen in the reference's models is none of these (adj, msgat.py:190, gets no gradient here at all), and
-        # x always requires one (it is a LayerNorm output with learnable weights, msgat.py:122).
+        # is ever frozen in the reference's models is none of these (adj, msgat.py:190), and x always requires one (it is
+        # a LayerNorm output with learnable weights, msgat.py:122).  An adjacency that requires grad gets it from one more
+        # launch after that backward, msgat_adjacency_grad, which re-creates the dense softmax from q, kW and lse:
+        # dv / feat are dz / x (plain), dz / u = W x (project-first), W^T dz / x (aggregate-first, one more mix).
         L = _lib.lib()
         saved = ctx.saved_tensors
         x, alpha, Wg, buf = saved[:4]
@@ -173,8 +225,23 @@ class _GACNFunction(torch.autograd.Function):
         ws = torch.empty(plan.bwd_bytes, device=dev, dtype=torch.uint8)
         io = _lib.Bwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), q, kW, lse, pq, E, u, _ptr(dz), _ptr(dx), _ptr(dalpha),
                       _ptr(dWg), _ptr(dW), _ptr(ws), ws.numel(), dz_gs, Ec)
-        st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), _stream_handle(dev))
+        stream = _stream_handle(dev)
+        st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
         _lib.check(st, "msgat_gacn_backward")
+        if ctx.adj_grad is not None:   # (the adjacency is an input of this node only when it requires grad)
+            n_sets, adj_shape = ctx.adj_grad
+            Cin = x.shape[1]
+            if plan.mode == _lib.MODE_AGG_FIRST:
+                dy = torch.empty_like(x)
+                dzc = dz if dz_gs == 0 else dz.contiguous()
+                _lib.check(L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy),
+                                             stream), "msgat_stage_mix")
+                dadj = _adjacency_grad(shape, Cin, dy, 0, _ptr(x), q, kW, lse, n_sets, adj_shape, dev, stream)
+            elif plan.mode == _lib.MODE_PROJ_FIRST:
+                dadj = _adjacency_grad(shape, shape.Co, dz, dz_gs, u, q, kW, lse, n_sets, adj_shape, dev, stream)
+            else:
+                dadj = _adjacency_grad(shape, Cin, dz, dz_gs, _ptr(x), q, kW, lse, n_sets, adj_shape, dev, stream)
+            return dx, dalpha, dWg, dW, None, None, dadj
         return dx, dalpha, dWg, dW, None, None
 
 
@@ -186,6 +253,8 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
     adjacency: dense [N,N] tensor or a prebuilt `SparseGraph`; or a per-sample adjacency -- dense [Bg,N,N] (one graph per
     sample, shared by the R relations), [R*Bg,N,N] (one per group) or a prebuilt `BatchedGraph` of either ([1,N,N] is
     [N,N]; `graph.graph_for`).  Returns [R*Bg, Co|C, N, T].
+    A dense adjacency tensor that requires grad gets its gradient, in its own shape: dense, non-zero off the edges too,
+    since softmax(k Wg q^T) does not depend on it.  A prebuilt SparseGraph / BatchedGraph is not a tensor and gets none.
     One relation may come without the leading axis -- alpha [C], Wg [T,T], W [Co,C], the reference's own parameter
     shapes (attention.py:29-30, msgat.py:23): the module classes call it that way, so that no view nodes sit between
     the parameters and the op (three `unsqueeze` forward and three more nodes backward were a sixth of a call's host time).
@@ -211,10 +280,14 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
             raise ValueError(f"Wg must be [{R},{T},{T}], got {tuple(Wg.shape)}")
         if W is not None and (W.dim() != 3 or W.shape[0] != R or W.shape[2] != Cin):
             raise ValueError(f"W must be [{R},Co,{Cin}], got {tuple(W.shape)}")
+    recording = torch.is_grad_enabled()
+    adjacency, adj = _adjacency_operand(adjacency, recording)
     graph = graph_for(adjacency, G, alpha.shape[0] if alpha.dim() == 2 else 1)
     if graph.n_nodes != N:
         raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
-    return _GACNFunction.apply(x, alpha, Wg, W, graph, torch.is_grad_enabled())
+    if adj is None:
+        return _GACNFunction.apply(x, alpha, Wg, W, graph, recording)
+    return _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj)
 
 
 def graph_attention(x, alpha, Wg, adjacency):
@@ -1095,7 +1168,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
     msgat_attention_backward)."""
 
     @staticmethod
-    def forward(ctx, u, q, Wg, graph, recording: bool = True):   # graph: SparseGraph or BatchedGraph
+    def forward(ctx, u, q, Wg, graph, recording: bool = True, adj=None):   # graph / adj: see _GACNFunction
         L = _lib.lib()
         u, q, Wg = u.contiguous(), q.contiguous(), Wg.contiguous()
         G, Cu, N, T = u.shape
@@ -1119,6 +1192,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
                    "msgat_stage_aggregate")
         if need_bwd:
             ctx.plan = plan
+            ctx.adj_grad = None if adj is None else (_adjacency_sets(adj), tuple(adj.shape))
             ctx.save_for_backward(u, q, Wg, buf)
         return z
 
@@ -1135,24 +1209,35 @@ class _AttentionCoreFunction(torch.autograd.Function):
         if plan.bwd_bytes is None:
             plan.bwd_bytes = max(int(L.msgat_attention_bwd_workspace_bytes(shape, gstruct)), 256)
         ws = torch.empty(plan.bwd_bytes, device=u.device, dtype=torch.uint8)
+        stream = _stream_handle(u.device)
         st = L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
-                                        _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), _stream_handle(u.device))
+                                        _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
         _lib.check(st, "msgat_attention_backward")
+        if ctx.adj_grad is not None:
+            n_sets, adj_shape = ctx.adj_grad
+            dadj = _adjacency_grad(plan.shape, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, n_sets, adj_shape,
+                                   u.device, stream)
+            return du, dq, dWg, None, None, dadj
         return du, dq, dWg, None, None
 
 
 def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency) -> torch.Tensor:
-    """Graph attention on already projected features `u` [G,Cu,N,T] with pooled signals `q` [G,N,T]."""
+    """Graph attention on already projected features `u` [G,Cu,N,T] with pooled signals `q` [G,N,T].  `adjacency` as in
+    `gacn`, its gradient included."""
     _require_device_tensor("features", u)
     _require_device_tensor("pooled signals", q, u.device)
     _require_device_tensor("Wg", Wg, u.device)
     G, Cu, N, T = u.shape
     if tuple(q.shape) != (G, N, T) or Wg.dim() != 3 or tuple(Wg.shape[1:]) != (T, T) or G % Wg.shape[0]:
         raise ValueError(f"attention_core: u {tuple(u.shape)}, q {tuple(q.shape)}, Wg {tuple(Wg.shape)}")
+    recording = torch.is_grad_enabled()
+    adjacency, adj = _adjacency_operand(adjacency, recording)
     graph = graph_for(adjacency, G, Wg.shape[0])
     if graph.n_nodes != N:
         raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
-    return _AttentionCoreFunction.apply(u, q, Wg, graph, torch.is_grad_enabled())
+    if adj is None:
+        return _AttentionCoreFunction.apply(u, q, Wg, graph, recording)
+    return _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj)
 
 
 # ---- the tiny attention matrices of a MEAM block, one launch each way ----------------------------------------------
