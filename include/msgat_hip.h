@@ -48,6 +48,9 @@ extern "C" {
 #endif
 
 /* 10: + msgat_adjacency_grad{,_workspace_bytes} (the gradient of a dense adjacency that requires grad); nothing else changed.
+ *     Later, still 10 (new functions only; no structure, signature or status code changed): + msgat_graph_build_indices
+ *     (a structure from CSR index arrays) and msgat_edge_weight_grad{,_workspace_bytes} (the gradient of the stored
+ *     values of a sparse adjacency).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -208,6 +211,15 @@ int msgat_graph_count(const float* adj, int32_t n, int64_t ld, int32_t* nnz_out)
 int msgat_graph_build(const float* adj, int32_t n, int64_t ld, int32_t nnz,
                       int32_t* rowptr, int32_t* col, float* val, int32_t* erow,
                       int32_t* colptr, int32_t* crow, int32_t* cperm, int32_t* cpos);
+/* The same structure from the CSR index arrays of a sparse [n,n] adjacency (HOST pointers): in_rowptr [n+1], in_col
+ * [nnz], columns in any order inside a row.  Every stored index is an edge, whatever its value.  The output arrays are
+ * those of msgat_graph_build() except `val`, which the caller points at its values in library order: order [nnz] maps
+ * the library's CSR edge k (columns ascending inside a row) to its position in the input, order[k] = input index.
+ * Never touches [n,n].  A decreasing in_rowptr, in_rowptr[0] != 0 or in_rowptr[n] != nnz, a column outside [0,n) or a
+ * column stored twice in a row is MSGAT_ERR_GRAPH; n <= 0 or nnz < 0 is MSGAT_ERR_SHAPE. */
+int msgat_graph_build_indices(const int32_t* in_rowptr, const int32_t* in_col, int32_t n, int32_t nnz,
+                              int32_t* rowptr, int32_t* col, int32_t* erow, int32_t* colptr, int32_t* crow,
+                              int32_t* cperm, int32_t* cpos, int32_t* order);
 /* Host-side structural check of a (host-resident) graph (its SELL forms too, when present). */
 int msgat_graph_validate(const msgat_graph_t* host_graph);
 /* SELL form of a CSR (ptr = rowptr, idx = col, perm = NULL) or CSC (ptr = colptr, idx = crow,
@@ -263,6 +275,20 @@ size_t msgat_adjacency_grad_workspace_bytes(const msgat_shape_t* shape, int32_t 
 int msgat_adjacency_grad(const msgat_shape_t* shape, int32_t Cu, const float* dv, int32_t dv_group_channels,
                          const float* feat, const float* q, const float* kW, const float* lse, int32_t n_sets, float* dadj,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device: gradient of the stored values of a sparse adjacency (a learned weight per existing edge) ----
+ *   dval[e] = sum_g P_g[n_e,m_e] H_g[n_e,m_e]   for the CSR edges e of `graph` (erow, col), in CSR order
+ * the dense gradient of msgat_adjacency_grad restricted to the structure's edges (one value set: the adjacency is one
+ * [N,N] matrix, summed over all G groups).  Nothing [N,N] is read or written: P is re-created at each edge from q, kW and
+ * lse.  dv / dv_group_channels / feat / Cu exactly as for msgat_adjacency_grad.  The graph's `val` is not read.
+ * Deterministic (a fixed order of additions, no atomics); nothing is read back, so it may be captured in a HIP graph.
+ * workspace: msgat_edge_weight_grad_workspace_bytes() bytes, 256-byte aligned (the per-split partial sums; may be 0).
+ * T in {4,8,12,16} and Cu <= 256, else MSGAT_ERR_UNSUPPORTED; Cu <= 0 or graph->n_nodes != N is MSGAT_ERR_SHAPE.
+ * A graph without edges launches nothing. */
+size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu);
+int msgat_edge_weight_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu, const float* dv,
+                           int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
+                           const float* lse, float* dval, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- device: the individual stages (exposed for tests, profiling and bench.py) ----
  * Each is what the fused entry points enqueue, in order. */

@@ -75,6 +75,10 @@ _PROTOTYPES = {
     "msgat_adjacency_grad": (C.c_int, [C.POINTER(Shape), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "msgat_graph_build_indices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "msgat_edge_weight_grad_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32]),
+    "msgat_edge_weight_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32, C.c_void_p, C.c_int32]
+                               + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     "msgat_edge_scratch_floats": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),
     "msgat_gacn_forward": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.POINTER(Fwd), C.c_void_p]),
     "msgat_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),

@@ -156,6 +156,39 @@ extern "C" int msgat_adjacency_grad(const msgat_shape_t* sh, int32_t Cu, const f
                                Cu, sh->N, sh->T, (hipStream_t)stream);
 }
 
+// ---- gradient of a sparse adjacency's values -----------------------------------------------------
+static int check_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu) {
+  int st = check_shape(sh);
+  if (st) return st;
+  if (!gr) return MSGAT_ERR_NULL;
+  if (Cu <= 0 || gr->n_nodes != sh->N || gr->nnz < 0) return MSGAT_ERR_SHAPE;
+  if (Cu > kMaxC) return MSGAT_ERR_UNSUPPORTED;
+  if ((int64_t)Cu * sh->N * sh->T >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;
+  return MSGAT_OK;
+}
+
+extern "C" size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu) {
+  if (check_edge_weight_grad(sh, gr, Cu) != MSGAT_OK) return 0;
+  return edge_weight_grad_workspace_bytes(gr->nnz, sh->R * sh->Bg);
+}
+
+extern "C" int msgat_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, const float* dv,
+                                      int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
+                                      const float* lse, float* dval, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  int st = check_edge_weight_grad(sh, gr, Cu);
+  if (st) return st;
+  if (dv_group_channels < 0 || (dv_group_channels > 0 && dv_group_channels < Cu)) return MSGAT_ERR_SHAPE;
+  if (!dv || !feat || !q || !kW || !lse) return MSGAT_ERR_NULL;
+  if (gr->nnz > 0 && (!dval || !gr->erow || !gr->col)) return MSGAT_ERR_NULL;
+  const int G = sh->R * sh->Bg;
+  const size_t need = edge_weight_grad_workspace_bytes(gr->nnz, G);
+  if (need > 0 && !workspace) return MSGAT_ERR_NULL;
+  if (workspace_bytes < need) return MSGAT_ERR_WORKSPACE;
+  return launch_edge_weight_grad(dv, dv_group_channels, feat, q, kW, lse, gr->erow, gr->col, dval,
+                                 static_cast<float*>(workspace), G, Cu, sh->N, gr->nnz, sh->T, (hipStream_t)stream);
+}
+
 // ---- stages -------------------------------------------------------------------------------------
 extern "C" int msgat_stage_project(const msgat_shape_t* sh, const float* x, const float* alpha,
                                    const float* W, float* q, float* u, void* stream) {

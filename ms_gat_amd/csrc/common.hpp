@@ -272,6 +272,12 @@ int launch_edge_values(const float* adj, const int* rowptr, const int* col, floa
 size_t adjacency_grad_workspace_bytes(int N, int G, int V);
 int launch_adjacency_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
                           const float* lse, float* dadj, float* ws, int G, int V, int Cu, int N, int T, hipStream_t s);
+// edge_weight_grad.hip: dval[e] = sum_g P_g[n_e,m_e] sum_{c,t} dv[g,c,n_e,t] feat[g,c,m_e,t] at the CSR edges (erow, col),
+// deterministic; ws: edge_weight_grad_workspace_bytes(nnz, G) bytes (the per-split partial sums; 0 when not split)
+size_t edge_weight_grad_workspace_bytes(int nnz, int G);
+int launch_edge_weight_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
+                            const float* lse, const int* erow, const int* col, float* dval, float* ws, int G, int Cu,
+                            int N, int nnz, int T, hipStream_t s);
 int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse,
                   float* pq, float* E, float* Ec, int G, int Bg, int N, int T, hipStream_t s,
                   const float* x = nullptr, const float* alpha = nullptr, int C = 0, float* qout = nullptr,

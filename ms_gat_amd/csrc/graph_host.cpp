@@ -67,6 +67,55 @@ extern "C" int msgat_graph_build(const float* adj, int32_t n, int64_t ld, int32_
   return MSGAT_OK;
 }
 
+// CSC (+ both permutations) of a finished CSR: counting sort over the edges, rows ascending inside a column
+static void build_csc(int32_t n, int32_t nnz, const int32_t* col, const int32_t* erow, int32_t* colptr, int32_t* crow,
+                      int32_t* cperm, int32_t* cpos) {
+  colptr[0] = 0;
+  for (int32_t j = 0; j <= n; ++j) colptr[j] = 0;
+  for (int32_t k = 0; k < nnz; ++k) colptr[col[k] + 1]++;
+  for (int32_t j = 0; j < n; ++j) colptr[j + 1] += colptr[j];
+  std::vector<int32_t> cursor(colptr, colptr + n);
+  for (int32_t k = 0; k < nnz; ++k) {
+    const int32_t pos = cursor[col[k]]++;
+    crow[pos] = erow[k];
+    cperm[pos] = k;
+    cpos[k] = pos;
+  }
+}
+
+// A sparse adjacency brings its pattern as indices: every stored index is an edge, an explicit 0 included (its value
+// is a weight that may become non-zero later), and [n,n] is never formed (n = 200 000 is 160 GB of floats).
+extern "C" int msgat_graph_build_indices(const int32_t* in_rowptr, const int32_t* in_col, int32_t n, int32_t nnz,
+                                         int32_t* rowptr, int32_t* col, int32_t* erow, int32_t* colptr, int32_t* crow,
+                                         int32_t* cperm, int32_t* cpos, int32_t* order) {
+  if (!in_rowptr || !rowptr || !colptr) return MSGAT_ERR_NULL;
+  if (nnz > 0 && (!in_col || !col || !erow || !crow || !cperm || !cpos || !order)) return MSGAT_ERR_NULL;
+  if (n <= 0 || nnz < 0) return MSGAT_ERR_SHAPE;
+  if (in_rowptr[0] != 0 || in_rowptr[n] != nnz) return MSGAT_ERR_GRAPH;
+  for (int32_t i = 0; i < n; ++i)
+    if (in_rowptr[i + 1] < in_rowptr[i]) return MSGAT_ERR_GRAPH;
+  std::vector<std::pair<int32_t, int32_t>> row;   // (column, input index) of one row
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t b = in_rowptr[i], e = in_rowptr[i + 1];
+    rowptr[i] = b;
+    row.clear();
+    for (int32_t k = b; k < e; ++k) {
+      if (in_col[k] < 0 || in_col[k] >= n) return MSGAT_ERR_GRAPH;
+      row.emplace_back(in_col[k], k);
+    }
+    std::sort(row.begin(), row.end());
+    for (size_t k = 0; k < row.size(); ++k) {
+      if (k > 0 && row[k].first == row[k - 1].first) return MSGAT_ERR_GRAPH;   // a column stored twice
+      col[b + k] = row[k].first;
+      order[b + k] = row[k].second;
+      erow[b + k] = i;
+    }
+  }
+  rowptr[n] = nnz;
+  build_csc(n, nnz, col, erow, colptr, crow, cperm, cpos);
+  return MSGAT_OK;
+}
+
 extern "C" int msgat_graph_validate(const msgat_graph_t* g) {
   if (!g || !g->rowptr || !g->colptr) return MSGAT_ERR_NULL;
   const int32_t n = g->n_nodes, nnz = g->nnz;

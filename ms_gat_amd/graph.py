@@ -102,11 +102,42 @@ class SparseGraph:
         _lib.check(L.msgat_graph_build(a.data_ptr(), n, n, self.nnz, self.rowptr.data_ptr(), self.col.data_ptr(),
                                        self.val.data_ptr(), self.erow.data_ptr(), self.colptr.data_ptr(),
                                        self.crow.data_ptr(), self.cperm.data_ptr(), self.cpos.data_ptr()), "msgat_graph_build")
+        self._finish(sell)
+
+    @classmethod
+    def from_indices(cls, rowptr: torch.Tensor, col: torch.Tensor, n_nodes: int, sell: str = "auto") -> "SparseGraph":
+        """The structure of a sparse [N,N] adjacency from its CSR index arrays (`msgat_graph_build_indices`): every stored
+        index is an edge, an explicit 0 included, columns in any order inside a row, and [N,N] is never formed.  `val`
+        is left at 0 (the caller's values are pointed at on the device); `order` [nnz] maps the library's edge k to
+        its input position."""
+        self = cls.__new__(cls)
+        rp = rowptr.detach().to(device="cpu", dtype=torch.int32).contiguous()
+        ci = col.detach().to(device="cpu", dtype=torch.int32).contiguous()
+        n = int(n_nodes)
+        if rp.dim() != 1 or rp.numel() != n + 1 or ci.dim() != 1:
+            raise ValueError(f"rowptr must be [{n + 1}] and col 1-D, got {tuple(rp.shape)} and {tuple(ci.shape)}")
+        self.n_nodes, self.nnz = n, int(ci.numel())
+        m = max(self.nnz, 1)
+        self.rowptr = torch.zeros(n + 1, dtype=torch.int32)
+        self.colptr = torch.zeros(n + 1, dtype=torch.int32)
+        self.col, self.erow = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
+        self.crow, self.cperm = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
+        self.cpos, self.order = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
+        self.val = torch.zeros(m, dtype=torch.float32)
+        _lib.check(_lib.lib().msgat_graph_build_indices(
+            rp.data_ptr(), ci.data_ptr(), n, self.nnz, self.rowptr.data_ptr(), self.col.data_ptr(), self.erow.data_ptr(),
+            self.colptr.data_ptr(), self.crow.data_ptr(), self.cperm.data_ptr(), self.cpos.data_ptr(),
+            self.order.data_ptr()), "msgat_graph_build_indices")
+        self._finish(sell)
+        return self
+
+    def _finish(self, sell: str) -> None:
         self._dev = {}
         if sell not in ("auto", "always", "never"):
             raise ValueError(f"sell must be 'auto', 'always' or 'never', got {sell!r}")
         self.sell_prefer = sell == "always"
         self._sell = {}
+        n = self.n_nodes
         if sell != "never" and self.nnz > 0 and n <= _SELL_MAX_NODES and (self.sell_prefer or n >= _SELL_AUTO_MIN):
             self._sell["sell_rows"] = self._build_sell(self.rowptr, self.col, None, with_pos=True)
             self._sell["sell_cols"] = self._build_sell(self.colptr, self.crow, self.cperm, with_pos=False)
@@ -405,14 +436,170 @@ def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGrap
     return g
 
 
+# ---- a sparse adjacency [N,N] (torch COO / CSR): a learned weight per stored edge --------------------------------------
+# The pattern is the set of stored indices; the values stay on the device and the library reads them where they are
+# (msgat_graph_t.val, val_sets = 1): the edge tail of the score kernels is their only reader.  The structure is built once
+# per pattern -- keyed on the index tensors' storage (kept alive by the cache, so an address is never reused under it) and
+# version, confirmed by content on first sight -- and after that a call reads nothing back and may be captured.
+
+def is_sparse_adjacency(adjacency) -> bool:
+    return isinstance(adjacency, torch.Tensor) and adjacency.layout in (torch.sparse_coo, torch.sparse_csr)
+
+
+class EdgeWeightGraph:
+    """What the ops hand the library for a sparse adjacency: the pattern's structure with `val` at `values_ptr` (device
+    values in library order, one set).  One per (pattern, values address): the per-shape plans live on it."""
+
+    def __init__(self, pattern: "SparsePattern", values_ptr: int):
+        self.pattern, self.structure = pattern, pattern.structure
+        self.n_nodes, self.nnz, self.n_sets = self.structure.n_nodes, self.structure.nnz, 1
+        self._ptr = values_ptr
+        self._dev = {}
+
+    @property
+    def has_sell(self) -> bool:
+        return self.structure.has_sell
+
+    def on(self, device: torch.device):
+        key = str(device)
+        if key not in self._dev:
+            _, tensors = self.structure.on(device)
+            g = self.structure._struct(tensors)
+            g.val, g.val_sets = self._ptr, 1
+            self._dev[key] = (g, tensors)
+        return self._dev[key]
+
+
+class SparsePattern:
+    """The structure of one sparse pattern (`SparseGraph.from_indices`) plus, when the caller's order inside a row is
+    not the library's, the device permutations between them (computed once): values are gathered into a buffer of
+    this pattern's, and the gradient is gathered back."""
+
+    _VIEWS_MAX = 8
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, n_nodes: int, sell: str = "auto"):
+        self.structure = SparseGraph.from_indices(crow, col, n_nodes, sell=sell)
+        nnz = self.structure.nnz
+        order = self.structure.order[:nnz].long()
+        self.identity = bool(torch.equal(order, torch.arange(nnz)))
+        self._order = order
+        self._inverse = torch.empty_like(order)
+        self._inverse[order] = torch.arange(nnz)
+        self._dev = {}
+        self._views: "collections.OrderedDict[tuple, EdgeWeightGraph]" = collections.OrderedDict()
+
+    def _perm(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (self._order.to(device), self._inverse.to(device),
+                              torch.empty(max(self.structure.nnz, 1), dtype=torch.float32, device=device))
+        return self._dev[key]
+
+    def graph(self, values: torch.Tensor) -> EdgeWeightGraph:
+        """The graph whose `val` holds `values` (input order, on the device) in library order.  Values in another order,
+        or not contiguous (a strided view), are copied into this pattern's own buffer: the library keeps only a pointer,
+        so it must point at memory that outlives the call (a temporary copy would be freed before the score kernels
+        read it) and that a captured step re-reads at every replay."""
+        if not self.identity or not values.is_contiguous():
+            order, _, buf = self._perm(values.device)
+            dst = buf[: self.structure.nnz]
+            if self.identity:
+                dst.copy_(values)
+            else:
+                torch.index_select(values, 0, order, out=dst)
+            values = buf
+        key = (values.data_ptr(), str(values.device))
+        g = self._views.get(key)
+        if g is None:
+            g = self._views[key] = EdgeWeightGraph(self, values.data_ptr())
+            while len(self._views) > self._VIEWS_MAX:
+                self._views.popitem(last=False)
+        self._views.move_to_end(key)
+        return g
+
+    def to_input_order(self, dval: torch.Tensor) -> torch.Tensor:
+        """A gradient in library order -> the caller's order of the values."""
+        if self.identity:
+            return dval
+        return dval.index_select(0, self._perm(dval.device)[1])
+
+
+_SPARSE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()    # index storages -> (pattern, indices)
+_SPARSE_PATTERNS: "collections.OrderedDict[tuple, SparsePattern]" = collections.OrderedDict()   # by content
+
+
+def sparse_parts(adjacency: torch.Tensor):
+    """(layout, index tensors, values) of a sparse [N,N] adjacency; an uncoalesced COO tensor must be coalesced first."""
+    if adjacency.layout == torch.sparse_csr:
+        return "csr", (adjacency.crow_indices(), adjacency.col_indices()), adjacency.values()
+    return "coo", (adjacency._indices(),), adjacency._values()
+
+
+def check_sparse_adjacency(adjacency: torch.Tensor) -> None:
+    if adjacency.dim() != 2 or adjacency.shape[0] != adjacency.shape[1]:
+        raise ValueError(f"a sparse adjacency must be one [n_nodes, n_nodes] matrix, got {tuple(adjacency.shape)}: "
+                         "batched sparse adjacencies [B, n_nodes, n_nodes] are not supported (pass a dense [B,N,N] "
+                         "or a BatchedGraph)")
+    if adjacency.layout == torch.sparse_coo and adjacency.sparse_dim() != 2:
+        raise ValueError("a sparse COO adjacency must have two sparse dimensions and no dense ones")
+    if adjacency.dtype != torch.float32:
+        raise TypeError(f"a sparse adjacency must be float32 (the reference arithmetic type), got {adjacency.dtype}")
+
+
+def sparse_pattern_of(adjacency: torch.Tensor, sell: str = "auto") -> SparsePattern:
+    """Cached `SparsePattern` of a (coalesced, if COO) sparse [N,N] adjacency.  A hit is keyed on the index tensors'
+    storage address, size and version; the first sight of a key reads the indices back, and a pattern with the same
+    content is shared.  The first sight inside a HIP-graph capture raises, as graph_of does."""
+    check_sparse_adjacency(adjacency)
+    layout, idx, _ = sparse_parts(adjacency)
+    n = int(adjacency.shape[0])
+    key = (layout, n, sell, str(adjacency.device)) + tuple((t.data_ptr(), t.numel(), t._version) for t in idx)
+    hit = _SPARSE.get(key)
+    if hit is not None:
+        _SPARSE.move_to_end(key)
+        return hit[0]
+    if adjacency.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise _lib.MsgatError("the structure of this sparse adjacency is not cached yet: run one forward outside the "
+                              "HIP-graph capture first (engine.Trainer does this in its warm-up)")
+    if layout == "csr":
+        crow, col = (t.detach().to(device="cpu", dtype=torch.int64) for t in idx)
+    else:
+        ij = idx[0].detach().to(device="cpu", dtype=torch.int64)
+        crow = torch.zeros(n + 1, dtype=torch.int64)
+        crow[1:] = torch.bincount(ij[0], minlength=n).cumsum(0)
+        col = ij[1]
+    if crow.numel() != n + 1 or int(crow[-1]) != col.numel():
+        raise ValueError("malformed sparse adjacency indices")
+    ckey = (n, sell, crow.numpy().tobytes(), col.numpy().tobytes())
+    pattern = _SPARSE_PATTERNS.get(ckey)
+    if pattern is None:
+        pattern = _SPARSE_PATTERNS[ckey] = SparsePattern(crow, col, n, sell)
+        while len(_SPARSE_PATTERNS) > _PATTERNS_MAX:
+            _SPARSE_PATTERNS.popitem(last=False)
+    _SPARSE_PATTERNS.move_to_end(ckey)
+    _SPARSE[key] = (pattern, idx)     # the index tensors stay alive with the entry: their addresses cannot be reused
+    while len(_SPARSE) > _CACHE_MAX:
+        _SPARSE.popitem(last=False)
+    return pattern
+
+
+def sparse_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> EdgeWeightGraph:
+    """The graph of a sparse [N,N] adjacency: its cached pattern with `val` at its values on the device."""
+    pattern = sparse_pattern_of(adjacency, sell)
+    _, _, values = sparse_parts(adjacency)
+    return pattern.graph(values.detach())
+
+
 def graph_for(adjacency, groups: int, relations: int):
     """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N]
     through graph_of; [1,N,N] as [N,N]; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one
     per group) through batched_graph_of.  The graph carries no gradient: a batched adjacency that requires grad while
     autograd records is refused here.  The ops (`ops.gacn`, `graph_attention`, `attention_core`, and the modules on
     them) accept one -- they hand this function a detached alias and route the gradient themselves."""
-    if isinstance(adjacency, (SparseGraph, BatchedGraph)):
+    if isinstance(adjacency, (SparseGraph, BatchedGraph, EdgeWeightGraph)):
         g = adjacency
+    elif is_sparse_adjacency(adjacency):
+        g = sparse_graph_of(adjacency)
     elif not isinstance(adjacency, torch.Tensor):
         raise TypeError(f"adjacency must be a tensor, a SparseGraph or a BatchedGraph, got {type(adjacency).__name__}")
     elif adjacency.dim() == 3:

@@ -308,10 +308,15 @@ class MSGAT(nn.Module):
 
     `use_te=False` uses the learned static gate `W [R,N,T_out]` that the reference declares
     (msgat.py:189) but cannot reach (its forward reads `self.te` unconditionally, msgat.py:203).
+
+    `learn_edge_weights=True` learns one weight per existing edge of the road graph: the pattern of `adj != 0` is kept as
+    the index buffers `edge_crow` / `edge_col` and the weights, initialised from `adj`, as the parameter `edge_weight`
+    [nnz].  The forward hands every block the sparse CSR adjacency built from them, whose gradient is computed at the
+    edges only (msgat_edge_weight_grad).  `adj` stays as the frozen dense parameter of the reference's layout.
     """
 
     def __init__(self, components: Sequence[Dict], in_timesteps: int, out_timesteps: int, use_te: bool,
-                 adj: torch.Tensor):
+                 adj: torch.Tensor, learn_edge_weights: bool = False):
         super().__init__()
         n_nodes = len(adj)
         if use_te:
@@ -324,16 +329,33 @@ class MSGAT(nn.Module):
             TPC(channels=c["channels"], n_nodes=n_nodes, in_timesteps=in_timesteps, out_timesteps=out_timesteps,
                 dilations=c["dilations"]) for c in components)
         self.stack_components = True   # False: evaluate the components one by one, as the reference does
+        self.learn_edge_weights = bool(learn_edge_weights)
+        if self.learn_edge_weights:
+            pattern = self.adj.detach().cpu().to_sparse_csr()
+            self.register_buffer("edge_crow", pattern.crow_indices().clone())
+            self.register_buffer("edge_col", pattern.col_indices().clone())
+            self.edge_weight = nn.Parameter(pattern.values().clone())
         self.reset_parameters()
+        if self.learn_edge_weights:
+            # after reset_parameters, which re-initialises every 1-D trainable tensor
+            with torch.no_grad():
+                self.edge_weight.copy_(self.adj.detach().cpu().to_sparse_csr().values())
+
+    def adjacency(self):
+        """What the blocks get: the frozen dense `adj`, or the sparse CSR adjacency of the learned edge weights."""
+        if not self.learn_edge_weights:
+            return self.adj
+        return ops.edge_adjacency(self.edge_crow, self.edge_col, self.edge_weight)
 
     def forward(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
         if self.stack_components and stacked.can_stack(self):
             # all components in each kernel launch (stacked.py) instead of the reference's loop (msgat.py:204)
             return stacked.forward(self, X, H, D)
         gates = self.te(H, D).unbind(1) if self.te is not None else self.W.unbind(0)
+        adjacency = self.adjacency()
         out = None
         for tpc, x, gate in zip(self.tpcs, X.unbind(1), gates):
-            term = tpc(x, self.adj) * gate
+            term = tpc(x, adjacency) * gate
             out = term if out is None else out + term
         return out
 

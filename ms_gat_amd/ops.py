@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .graph import graph_for
+from .graph import check_sparse_adjacency, graph_for, is_sparse_adjacency
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -117,10 +117,33 @@ def _detached(adjacency: torch.Tensor) -> torch.Tensor:
     return alias
 
 
+# A sparse adjacency of learned edge weights, `edge_adjacency(crow, col, weight)`: a CSR tensor on weight.detach() (the
+# same storage: the library reads the current weights), remembered here with the weight itself.  The ops hand the
+# weight to their autograd Function, and its gradient arrives as a dense [nnz] tensor: torch's own backward of
+# `sparse_csr_tensor` densifies the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync, which a
+# captured step cannot contain), and adding the sparse gradients of several layers needs the pattern on the host too.
+_EDGE_WEIGHTS = {}   # id(sparse adjacency) -> (weakref to it, the weight that receives its gradient)
+
+
+def edge_adjacency(crow: torch.Tensor, col: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """The sparse CSR adjacency [N,N] (N = crow.numel() - 1) with a learned weight per stored edge: `weight` [nnz] in
+    the order of (crow, col), columns ascending inside a row.  Every op and module accepts it like any sparse adjacency;
+    `weight` gets its gradient at the stored edges, dense [nnz], and a step that uses it can be captured in a HIP graph."""
+    n = crow.numel() - 1
+    adj = torch.sparse_csr_tensor(crow, col, weight.detach(), (n, n))
+    key = id(adj)
+    _EDGE_WEIGHTS[key] = (weakref.ref(adj, lambda _r, k=key: _EDGE_WEIGHTS.pop(k, None)), weight)
+    return adj
+
+
 def _adjacency_operand(adjacency, recording: bool):
     """(what graph_for gets, the adjacency tensor that receives a gradient or None).  A frozen adjacency -- every
     caller of the reference's models -- costs this one `requires_grad` check; a prebuilt SparseGraph / BatchedGraph is
-    not a tensor and gets no gradient."""
+    not a tensor and gets no gradient.  For an `edge_adjacency` the tensor that receives the gradient is its weight."""
+    if recording and _EDGE_WEIGHTS:
+        hit = _EDGE_WEIGHTS.get(id(adjacency))
+        if hit is not None and hit[0]() is adjacency:
+            return adjacency, (hit[1] if hit[1].requires_grad else None)
     if recording and getattr(adjacency, "requires_grad", False):
         return _detached(adjacency), adjacency
     return adjacency, None
@@ -129,6 +152,63 @@ def _adjacency_operand(adjacency, recording: bool):
 def _adjacency_sets(adj: torch.Tensor) -> int:
     """n_sets of msgat_adjacency_grad for a dense [N,N] / [V,N,N] adjacency (graph_for has checked V already)."""
     return 1 if adj.dim() == 2 else int(adj.shape[0])
+
+
+def _sparse_operand(adjacency, device):
+    """A sparse [N,N] adjacency checked for the ops: one matrix, float32, on the signals' device; an uncoalesced COO
+    tensor is coalesced (duplicates add, as in torch.sparse) -- by an autograd op, so its gradient still reaches the
+    caller's values.  Anything else is returned as it is."""
+    if not is_sparse_adjacency(adjacency):
+        return adjacency
+    check_sparse_adjacency(adjacency)
+    if adjacency.device != device:
+        raise ValueError(f"the sparse adjacency is on {adjacency.device}, the signals on {device}")
+    if adjacency.layout == torch.sparse_coo and not adjacency.is_coalesced():
+        adjacency = adjacency.coalesce()
+    return adjacency
+
+
+def _adjacency_grad_state(adj, graph):
+    """What backward needs to give `adj` its gradient, None without: ("dense", n_sets, shape) for a dense adjacency
+    (msgat_adjacency_grad); for a sparse one (msgat_edge_weight_grad at the stored edges) ("sparse", graph, layout, index
+    tensors, shape), or ("weight", graph) for the weight of an edge_adjacency."""
+    if adj is None:
+        return None
+    if is_sparse_adjacency(adj):
+        idx = (adj.crow_indices(), adj.col_indices()) if adj.layout == torch.sparse_csr else (adj._indices(),)
+        return ("sparse", graph, adj.layout, tuple(t.detach() for t in idx), tuple(adj.shape))
+    if adj.dim() == 1:
+        return ("weight", graph)
+    return ("dense", _adjacency_sets(adj), tuple(adj.shape))
+
+
+def _adjacency_gradient(state, shape, gstruct, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int,
+                        lse: int, dev, stream) -> torch.Tensor:
+    """The gradient of the adjacency that `state` (_adjacency_grad_state) describes, in its own shape and layout."""
+    if state[0] == "dense":
+        return _adjacency_grad(shape, Cu, dv, dv_gs, feat, q, kW, lse, state[1], state[2], dev, stream)
+    graph = state[1]
+    dval = _edge_weight_grad(shape, gstruct, Cu, dv, dv_gs, feat, q, kW, lse, graph.nnz, dev, stream)
+    dval = graph.pattern.to_input_order(dval)
+    if state[0] == "weight":
+        return dval
+    _, _, layout, idx, adj_shape = state
+    if layout == torch.sparse_csr:
+        return torch.sparse_csr_tensor(idx[0], idx[1], dval, adj_shape)
+    return torch.sparse_coo_tensor(idx[0], dval, adj_shape, is_coalesced=True)
+
+
+def _edge_weight_grad(shape, gstruct, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
+                      nnz: int, dev, stream) -> torch.Tensor:
+    """dval [nnz] in the library's CSR order, enqueued on `stream` after the backward of the other inputs."""
+    L = _lib.lib()
+    dval = torch.empty(nnz, device=dev, dtype=torch.float32)
+    nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(C.byref(shape), C.byref(gstruct), Cu))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    st = L.msgat_edge_weight_grad(C.byref(shape), C.byref(gstruct), Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dval),
+                                  _ptr(ws), nbytes, stream)
+    _lib.check(st, "msgat_edge_weight_grad")
+    return dval
 
 
 def _adjacency_grad(shape, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int, n_sets: int,
@@ -186,7 +266,7 @@ class _GACNFunction(torch.autograd.Function):
 
         if need_bwd:
             ctx.plan, ctx.has_W = plan, W is not None
-            ctx.adj_grad = None if adj is None else (_adjacency_sets(adj), tuple(adj.shape))
+            ctx.adj_grad = _adjacency_grad_state(adj, graph)
             if W is not None:
                 ctx.save_for_backward(x, alpha, Wg, buf, W)
             else:
@@ -229,18 +309,18 @@ class _GACNFunction(torch.autograd.Function):
         st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
         _lib.check(st, "msgat_gacn_backward")
         if ctx.adj_grad is not None:   # (the adjacency is an input of this node only when it requires grad)
-            n_sets, adj_shape = ctx.adj_grad
+            state = ctx.adj_grad
             Cin = x.shape[1]
             if plan.mode == _lib.MODE_AGG_FIRST:
                 dy = torch.empty_like(x)
                 dzc = dz if dz_gs == 0 else dz.contiguous()
                 _lib.check(L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy),
                                              stream), "msgat_stage_mix")
-                dadj = _adjacency_grad(shape, Cin, dy, 0, _ptr(x), q, kW, lse, n_sets, adj_shape, dev, stream)
+                dadj = _adjacency_gradient(state, shape, gstruct, Cin, dy, 0, _ptr(x), q, kW, lse, dev, stream)
             elif plan.mode == _lib.MODE_PROJ_FIRST:
-                dadj = _adjacency_grad(shape, shape.Co, dz, dz_gs, u, q, kW, lse, n_sets, adj_shape, dev, stream)
+                dadj = _adjacency_gradient(state, shape, gstruct, shape.Co, dz, dz_gs, u, q, kW, lse, dev, stream)
             else:
-                dadj = _adjacency_grad(shape, Cin, dz, dz_gs, _ptr(x), q, kW, lse, n_sets, adj_shape, dev, stream)
+                dadj = _adjacency_gradient(state, shape, gstruct, Cin, dz, dz_gs, _ptr(x), q, kW, lse, dev, stream)
             return dx, dalpha, dWg, dW, None, None, dadj
         return dx, dalpha, dWg, dW, None, None
 
@@ -255,6 +335,12 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
     [N,N]; `graph.graph_for`).  Returns [R*Bg, Co|C, N, T].
     A dense adjacency tensor that requires grad gets its gradient, in its own shape: dense, non-zero off the edges too,
     since softmax(k Wg q^T) does not depend on it.  A prebuilt SparseGraph / BatchedGraph is not a tensor and gets none.
+    A torch sparse COO / CSR [N,N] adjacency is its stored indices (explicit zeros included) with its values; one that
+    requires grad gets the gradient at those indices only (msgat_edge_weight_grad), sparse with the same layout.  From
+    there torch's own backward of the sparse constructor carries it to the values tensor, and that backward densifies
+    the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync): fine for small graphs in eager mode,
+    but it cannot be captured in a HIP graph and costs N^2.  For learned edge weights at scale or under capture use
+    `edge_adjacency(crow, col, weight)`, whose gradient reaches `weight` directly, dense [nnz].
     One relation may come without the leading axis -- alpha [C], Wg [T,T], W [Co,C], the reference's own parameter
     shapes (attention.py:29-30, msgat.py:23): the module classes call it that way, so that no view nodes sit between
     the parameters and the op (three `unsqueeze` forward and three more nodes backward were a sixth of a call's host time).
@@ -281,6 +367,7 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
         if W is not None and (W.dim() != 3 or W.shape[0] != R or W.shape[2] != Cin):
             raise ValueError(f"W must be [{R},Co,{Cin}], got {tuple(W.shape)}")
     recording = torch.is_grad_enabled()
+    adjacency = _sparse_operand(adjacency, x.device)
     adjacency, adj = _adjacency_operand(adjacency, recording)
     graph = graph_for(adjacency, G, alpha.shape[0] if alpha.dim() == 2 else 1)
     if graph.n_nodes != N:
@@ -1192,7 +1279,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
                    "msgat_stage_aggregate")
         if need_bwd:
             ctx.plan = plan
-            ctx.adj_grad = None if adj is None else (_adjacency_sets(adj), tuple(adj.shape))
+            ctx.adj_grad = _adjacency_grad_state(adj, graph)
             ctx.save_for_backward(u, q, Wg, buf)
         return z
 
@@ -1214,9 +1301,8 @@ class _AttentionCoreFunction(torch.autograd.Function):
                                         _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
         _lib.check(st, "msgat_attention_backward")
         if ctx.adj_grad is not None:
-            n_sets, adj_shape = ctx.adj_grad
-            dadj = _adjacency_grad(plan.shape, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, n_sets, adj_shape,
-                                   u.device, stream)
+            dadj = _adjacency_gradient(ctx.adj_grad, plan.shape, plan.gstruct, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW,
+                                       lse, u.device, stream)
             return du, dq, dWg, None, None, dadj
         return du, dq, dWg, None, None
 
@@ -1231,6 +1317,7 @@ def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency
     if tuple(q.shape) != (G, N, T) or Wg.dim() != 3 or tuple(Wg.shape[1:]) != (T, T) or G % Wg.shape[0]:
         raise ValueError(f"attention_core: u {tuple(u.shape)}, q {tuple(q.shape)}, Wg {tuple(Wg.shape)}")
     recording = torch.is_grad_enabled()
+    adjacency = _sparse_operand(adjacency, u.device)
     adjacency, adj = _adjacency_operand(adjacency, recording)
     graph = graph_for(adjacency, G, Wg.shape[0])
     if graph.n_nodes != N:
