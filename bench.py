@@ -2,24 +2,28 @@
 """Throughput of the MS-GAT graph-attention hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pemsd7|pemsd4|stress] [--dump-outputs DIR]
+                    [--full [--no-baselines]]
 
-One JSON line (rank 0 prints it; see the repo prompt for the contract).  `value` means the SAME thing at every N
-(`value_kind` = "hot_path"), so any two lines of a scaling curve compare like for like:
+One JSON line (rank 0 prints it).  `value` means the SAME thing at every N (`value_kind` = "hot_path"), so any two lines
+of a scaling curve compare like for like.  A plain run measures the headline figure and nothing else: set-up, W warm-up
+steps, K timed steps, the outputs (--dump-outputs) and the line.  `--full` adds every other object below (the training
+steps, rooflines, baselines and the other workloads), with `--no-baselines` only the two roofline objects.
 
 * one *step* = forward + backward of the hot path over one synthetic batch -- BASELINE.json's headline configuration,
   configs[2]: both GACN depths of every MS-GAT component (reference msgat.py:25-28 called from msgat.py:127, twice
   per TPC), i.e. for msgat72 on PEMSD7 GACN(1->24) and GACN(72->24), R = 3 relations stacked into one launch
   sequence, B = 32 samples PER GPU (weak scaling); with several ranks the step ends with the flat all-reduce of the
   hot path's parameter gradients (one bucket).  `value` = B * N / t_step.
-* `full_step_cfg4` (every N, both launch modes) -- configs[3]: one whole msgat72 TRAINING step through
+* `full_step_cfg4` (--full; every N, both launch modes) -- configs[3]: one whole msgat72 TRAINING step through
   `engine.Trainer`: forward of all R = 5 components, Huber loss + metrics, backward, ONE flat RCCL all-reduce of every
   gradient (1.96 M parameters, 7.8 MB) and Adam, B = 32 per GPU; `full_step_cfg4.value` is ITS samples/s over all ranks,
   timed with the same barrier + MAX-over-ranks clock.  It replaces the reference's `nn.DataParallel` loop
   (main.py:52-55, engine.py:49-63).
-* rank 0 adds `roofline` (attention-aggregate kernel, HIP-event timed on the launch stream), `roofline_dense` (the
-  score / column passes against the fp32 matrix-core peak) and -- single GPU only -- `cpu_baseline`
-  (oracle/dense_torch.py, the reference's op sequence, on the host cores), the eager PyTorch-ROCm baselines,
-  `full_step_cfg3`, `pemsd4` (configs[1]: N = 307, B = 64, one relation, against eager) and `stress` (configs[4]: N = 8192).
+* with --full rank 0 adds `roofline` (attention-aggregate kernel, HIP-event timed on the launch stream),
+  `roofline_dense` (the score / column passes against the fp32 matrix-core peak) and -- single GPU only --
+  `cpu_baseline` (oracle/dense_torch.py, the reference's op sequence, on the host cores), the eager PyTorch-ROCm
+  baselines, `full_step_cfg3`, `pemsd4` (configs[1]: N = 307, B = 64, one relation, against eager) and `stress`
+  (configs[4]: N = 8192).
 
 Launch: `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` by itself
 when N > 1 and no process group environment is present (before anything touches the GPU) and exits with its code;
@@ -832,16 +836,24 @@ def small_graph_object(name, dev, steps=100):
     }
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="pemsd7", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-baselines", action="store_true", help="skip the CPU / eager baselines and the secondary objects")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure the training steps, rooflines, baselines and the other "
+                         "workloads (off: the line carries the headline figure alone)")
+    ap.add_argument("--no-baselines", action="store_true",
+                    help="with --full: skip the CPU / eager baselines and the secondary objects (the rooflines stay)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ     # under torch.distributed.run
     if not launched and args.gpus > 1:
@@ -927,7 +939,7 @@ def main():
                        "ms_per_step_median_hip_events": out["ms_per_step_median_hip_events"]}
 
     sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
-    with_secondary = not args.no_baselines
+    with_secondary = args.full and not args.no_baselines
     if with_secondary:
         # configs[3]: the whole training step, B = 32 per GPU, all gradients in one flat all-reduce.  Every rank runs
         # it (the collective needs them all); timed like `value`: barrier on both sides, MAX over ranks.
@@ -970,7 +982,7 @@ def main():
             except RuntimeError as e:
                 out["full_step_cfg4"] = {"error": str(e).splitlines()[0][:160]}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"] = roofline_object(hp)
         out["roofline_dense"] = time_dense_kernels(hp)
     if rank == 0 and not multi and with_secondary:

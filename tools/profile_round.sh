@@ -2,9 +2,9 @@
 # Collects the profiles a round commits under profiles/rNN/.  Runs ON THE GPU BOX:
 #     gpurun --timeout 1200 -- 'bash tools/profile_round.sh r03 [parts]'
 # parts (default "hot full stress pmc"; "pemsd4" on request):
-#   pemsd4  kernel trace of `bench.py --workload pemsd4 --no-baselines` (configs[1]): per-kernel totals per step and one
-#           step in launch order with the gaps between launches (the eager step is host-bound there)
-#   hot     rocprofv3 kernel trace of `bench.py --no-baselines` (the hot-path step): per-kernel totals per step,
+#   pemsd4  kernel trace of `bench.py --workload pemsd4 --full --no-baselines` (configs[1]): per-kernel totals per step
+#           and one step in launch order with the gaps between launches (the eager step is host-bound there)
+#   hot     rocprofv3 kernel trace of `bench.py --full --no-baselines` (the hot-path step): per-kernel totals per step,
 #           one step in launch order, the attention-aggregate kernel by phase (cold loop / in step / cached loop)
 #   full    kernel traces of whole training steps (tools/full_model_profile.py, R = 3 and R = 5) + unprofiled wall times
 #   stress  kernel trace of the N = 8192 stress kernels (tools/stress_kernels.py)
@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; RND=${1:-r03}; PARTS=${2:-"hot full stress pmc"}; O=$R/gpurun_out/$RND; mkdir -p $O
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has hot; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_kt -- python3 $R/bench.py --no-baselines --steps 20 --warmup 5 > $O/bench_hot_under_rocprof.json 2>/dev/null
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_kt -- python3 $R/bench.py --full --no-baselines --steps 20 --warmup 5 > $O/bench_hot_under_rocprof.json 2>/dev/null
   KT=$(ls $O/bench_kt/*/*kernel_trace.csv | head -1)
   # (anchor: a kernel launched once per step -- k_project_mfma, the second depth's projection; k_qonly and k_agg_proj are
   # gone from this workload since round 4: the first depth's forward is one launch)
@@ -27,7 +27,7 @@ if has hot; then
   rm -rf $O/bench_kt
 fi
 if has pemsd4; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p4_kt -- python3 $R/bench.py --workload pemsd4 --no-baselines --steps 50 --warmup 10 > $O/pemsd4_bench_under_rocprof.json 2>/dev/null
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p4_kt -- python3 $R/bench.py --workload pemsd4 --full --no-baselines --steps 50 --warmup 10 > $O/pemsd4_bench_under_rocprof.json 2>/dev/null
   KT=$(ls $O/p4_kt/*/*kernel_trace.csv | head -1)
   python3 $R/tools/trace_summary.py $KT k_project_mfma 1 30 40 > $O/pemsd4_per_step.txt
   python3 $R/tools/trace_one_step.py $O/p4_kt --anchor k_project_mfma > $O/pemsd4_launches.txt 2>&1

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Separates the launches of the attention-aggregate kernel in a rocprofv3 kernel trace of `bench.py --no-baselines`:
-the launches inside the timed steps, the roofline loop on four operand sets (cold operands: the figure `roofline.frac`
-is computed from) and the loop on one operand set (cache-resident operands).
+"""Separates the launches of the attention-aggregate kernel in a rocprofv3 kernel trace of
+`bench.py --full --no-baselines`: the launches inside the timed steps, the roofline loop on four operand sets (cold
+operands: the figure `roofline.frac` is computed from) and the loop on one operand set (cache-resident operands).
 
 usage: roofline_trace_table.py <kernel_trace.csv> [kernel-substring=k_agg_ring] [loop-launches=44]
 
