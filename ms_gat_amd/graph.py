@@ -89,19 +89,8 @@ class SparseGraph:
         L = _lib.lib()
         nnz = C.c_int32(0)
         _lib.check(L.msgat_graph_count(a.data_ptr(), n, n, C.byref(nnz)), "msgat_graph_count")
-        self.n_nodes, self.nnz = n, int(nnz.value)
-        m = max(self.nnz, 1)
-        self.rowptr = torch.zeros(n + 1, dtype=torch.int32)
-        self.colptr = torch.zeros(n + 1, dtype=torch.int32)
-        self.col = torch.zeros(m, dtype=torch.int32)
-        self.val = torch.zeros(m, dtype=torch.float32)
-        self.erow = torch.zeros(m, dtype=torch.int32)
-        self.crow = torch.zeros(m, dtype=torch.int32)
-        self.cperm = torch.zeros(m, dtype=torch.int32)
-        self.cpos = torch.zeros(m, dtype=torch.int32)
-        _lib.check(L.msgat_graph_build(a.data_ptr(), n, n, self.nnz, self.rowptr.data_ptr(), self.col.data_ptr(),
-                                       self.val.data_ptr(), self.erow.data_ptr(), self.colptr.data_ptr(),
-                                       self.crow.data_ptr(), self.cperm.data_ptr(), self.cpos.data_ptr()), "msgat_graph_build")
+        self._alloc(n, int(nnz.value))
+        _lib.check(L.msgat_graph_build(a.data_ptr(), n, n, self.nnz, *self._ptrs(self._FIELDS)), "msgat_graph_build")
         self._finish(sell)
 
     @classmethod
@@ -116,20 +105,23 @@ class SparseGraph:
         n = int(n_nodes)
         if rp.dim() != 1 or rp.numel() != n + 1 or ci.dim() != 1:
             raise ValueError(f"rowptr must be [{n + 1}] and col 1-D, got {tuple(rp.shape)} and {tuple(ci.shape)}")
-        self.n_nodes, self.nnz = n, int(ci.numel())
-        m = max(self.nnz, 1)
-        self.rowptr = torch.zeros(n + 1, dtype=torch.int32)
-        self.colptr = torch.zeros(n + 1, dtype=torch.int32)
-        self.col, self.erow = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
-        self.crow, self.cperm = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
-        self.cpos, self.order = torch.zeros(m, dtype=torch.int32), torch.zeros(m, dtype=torch.int32)
-        self.val = torch.zeros(m, dtype=torch.float32)
+        self._alloc(n, int(ci.numel()))
+        self.order = torch.zeros(max(self.nnz, 1), dtype=torch.int32)
         _lib.check(_lib.lib().msgat_graph_build_indices(
-            rp.data_ptr(), ci.data_ptr(), n, self.nnz, self.rowptr.data_ptr(), self.col.data_ptr(), self.erow.data_ptr(),
-            self.colptr.data_ptr(), self.crow.data_ptr(), self.cperm.data_ptr(), self.cpos.data_ptr(),
-            self.order.data_ptr()), "msgat_graph_build_indices")
+            rp.data_ptr(), ci.data_ptr(), n, self.nnz,
+            *self._ptrs(("rowptr", "col", "erow", "colptr", "crow", "cperm", "cpos", "order"))), "msgat_graph_build_indices")
         self._finish(sell)
         return self
+
+    def _alloc(self, n: int, nnz: int) -> None:
+        """Zeroed host arrays for `nnz` edges on `n` nodes (one entry at least per edge array)."""
+        self.n_nodes, self.nnz = n, nnz
+        for name in self._FIELDS:
+            size = n + 1 if name in ("rowptr", "colptr") else max(nnz, 1)
+            setattr(self, name, torch.zeros(size, dtype=torch.float32 if name == "val" else torch.int32))
+
+    def _ptrs(self, names):
+        return [getattr(self, name).data_ptr() for name in names]
 
     def _finish(self, sell: str) -> None:
         self._dev = {}
@@ -204,67 +196,139 @@ class SparseGraph:
         return self._dev[key]
 
     def dense(self) -> torch.Tensor:
-        a = torch.zeros(self.n_nodes, self.n_nodes)
-        if self.nnz:
-            a[self.erow[: self.nnz].long(), self.col[: self.nnz].long()] = self.val[: self.nnz]
-        return a
+        return _dense(self, self.val)
 
 
-# The adjacency is a frozen parameter (msgat.py:190): one CSR build per tensor version.
-_CACHE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
+def _dense(structure: SparseGraph, val: torch.Tensor) -> torch.Tensor:
+    """[..., N, N] (host) of the values val [..., >= nnz] on the edges of `structure`."""
+    n, nnz = structure.n_nodes, structure.nnz
+    a = torch.zeros(tuple(val.shape[:-1]) + (n, n))
+    if nnz:
+        a[..., structure.erow[:nnz].long(), structure.col[:nnz].long()] = val[..., :nnz].cpu()
+    return a
+
+
+class ValuedGraph:
+    """Values on a shared structure: what the ops hand the library for a per-sample adjacency (`BatchedGraph`) and for a
+    sparse one.  `structure` is a `SparseGraph` shared by every graph with its pattern; `val` holds this graph's values
+    in the structure's edge order, a tensor [n_sets, nnz] or the address of values on the device (a sparse adjacency's
+    own, read where they are); group g of a call reads value set g % n_sets.
+
+    Exposes what the ops use of a `SparseGraph` (`n_nodes`, `nnz`, `has_sell`, `on(device)`, a `__dict__` for the
+    per-shape plans) plus `n_sets`; `on()` hands the library the structure's device arrays with `val` pointing at this
+    graph's values and `val_sets = n_sets`."""
+
+    def __init__(self, structure: SparseGraph, val, n_sets: int):
+        self.structure, self.val, self.n_sets = structure, val, n_sets
+        self.n_nodes, self.nnz = structure.n_nodes, structure.nnz
+        self._dev = {}
+
+    @property
+    def has_sell(self) -> bool:
+        return self.structure.has_sell
+
+    def on(self, device: torch.device):
+        """(ctypes struct of device pointers, what it keeps alive) for `device`: the shared structure, this graph's
+        values."""
+        key = str(device)
+        if key not in self._dev:
+            _, tensors = self.structure.on(device)
+            val = self.val
+            if isinstance(val, torch.Tensor) and val.device != torch.device(device):
+                val = val.to(device)
+            g = self.structure._struct(tensors)
+            g.val, g.val_sets = val if isinstance(val, int) else val.data_ptr(), self.n_sets
+            self._dev[key] = (g, (tensors, val))
+        return self._dev[key]
+
+    def dense(self) -> torch.Tensor:
+        """[n_sets,N,N] of the values on the structure (host; `val` a tensor)."""
+        return _dense(self.structure, self.val)
+
+
+# ---- caches ----------------------------------------------------------------------------------------------------------
+
+class _Lru(collections.OrderedDict):
+    """A table that keeps the `bound` entries used last."""
+
+    def __init__(self, bound: int):
+        super().__init__()
+        self.bound = bound
+
+    def hit(self, key):
+        value = self.get(key)
+        if value is not None:
+            self.move_to_end(key)
+        return value
+
+    def put(self, key, value):
+        self[key] = value
+        self.move_to_end(key)
+        while len(self) > self.bound:
+            self.popitem(last=False)
+        return value
+
+
+def _tensor_key(t: torch.Tensor) -> tuple:
+    return (t.data_ptr(), tuple(t.shape), str(t.device), t._version)
+
+
+class _TensorCache(_Lru):
+    """An LRU keyed on tensors' `_tensor_key` (storage address, shape, device, version).  Another tensor object can have
+    the key of an entry -- a view, or a new tensor the allocator placed at a recycled address -- so each entry holds the
+    object it was made for by weakref, and `lookup` tells a hit on that very object apart."""
+
+    def lookup(self, key, obj):
+        """(the value cached under `key` or None, whether it was cached for `obj` itself)."""
+        entry = self.hit(key)
+        if entry is None:
+            return None, False
+        return entry[0], entry[1]() is obj
+
+    def remember(self, key, obj, value):
+        self.put(key, (value, weakref.ref(obj)))
+        return value
+
+
 _CACHE_MAX = 16
+_GRAPHS = _TensorCache(_CACHE_MAX)     # dense [N,N] / [1,N,N] -> (SparseGraph, a copy of the contents)
+_BATCHED = _TensorCache(_CACHE_MAX)    # dense [V,N,N], sell -> BatchedGraph
+_SPARSE = _TensorCache(_CACHE_MAX)     # index tensors of a sparse adjacency, layout, N, sell -> (SparsePattern, indices)
+_PATTERNS = _Lru(8)                    # CSR content (N, sell, rowptr, col) -> SparsePattern
+
+
+def _capturing(t: torch.Tensor) -> bool:
+    return t.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
+def _not_cached(what: str) -> _lib.MsgatError:
+    # a first build reads the adjacency (or its indices) back to the host, which a stream capture cannot contain
+    return _lib.MsgatError(f"{what}: run one forward outside the HIP-graph capture first (engine.Trainer does this in "
+                           "its warm-up)")
 
 
 def graph_of(adjacency: torch.Tensor) -> SparseGraph:
-    """Cached `SparseGraph` of a dense adjacency tensor.
+    """Cached `SparseGraph` of a dense adjacency tensor [N,N] (or [1,N,N], its one matrix).
 
-    Keyed on (storage address, shape, device, version).  A hit on the very same tensor
-    object is free; a hit through a different object (a view, or a new tensor the allocator
-    placed at a recycled address) is confirmed by comparing contents before it is trusted.
+    The adjacency is a frozen parameter (msgat.py:190): one CSR build per tensor version.  Keyed on (storage address,
+    shape, device, version).  A hit on the very same tensor object is free; a hit through a different object (a view,
+    or a new tensor the allocator placed at a recycled address) is confirmed by comparing contents before it is trusted.
     """
-    key = (adjacency.data_ptr(), tuple(adjacency.shape), str(adjacency.device), adjacency._version)
-    hit = _CACHE.get(key)
-    if hit is not None:
-        g, ref, snapshot = hit
-        if ref() is adjacency:
-            _CACHE.move_to_end(key)
-            return g
-        # another tensor object at a cached address: compare contents ONCE (a device read-back, which a HIP-graph capture
-        # cannot contain) and remember the new object, so that its later calls -- the captured one included -- hit by
-        # identity.  (A model built where a freed model's adjacency lived used to compare on every call, and its first
-        # capture failed with "operation not permitted when stream is capturing".)
-        if not (adjacency.is_cuda and torch.cuda.is_current_stream_capturing()) and torch.equal(snapshot, adjacency.detach()):
-            _CACHE[key] = (g, weakref.ref(adjacency), snapshot)
-            _CACHE.move_to_end(key)
-            return g
-    if adjacency.is_cuda and torch.cuda.is_current_stream_capturing():
-        # building the CSR reads the adjacency back to the host, which a stream capture cannot contain
-        raise _lib.MsgatError("the CSR of this adjacency is not cached yet: run one forward outside the HIP-graph "
-                              "capture first (engine.Trainer does this in its warm-up)")
-    g = SparseGraph(adjacency)
-    _CACHE[key] = (g, weakref.ref(adjacency), adjacency.detach().clone())
-    _CACHE.move_to_end(key)
-    while len(_CACHE) > _CACHE_MAX:
-        _CACHE.popitem(last=False)
-    return g
-
-
-_SQ_CACHE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
-
-
-def _squeezed_graph_of(adjacency: torch.Tensor) -> SparseGraph:
-    """`graph_of(adjacency[0])` for a [1,N,N] tensor, cached on the 3-D tensor itself: its [N,N] view is a new object
-    at every call, which graph_of could only confirm by comparing contents (a read-back, impossible under capture)."""
-    key = (adjacency.data_ptr(), tuple(adjacency.shape), str(adjacency.device), adjacency._version)
-    hit = _SQ_CACHE.get(key)
-    if hit is not None and hit[1]() is adjacency:
-        _SQ_CACHE.move_to_end(key)
+    key = _tensor_key(adjacency)
+    hit, same = _GRAPHS.lookup(key, adjacency)
+    if same:
         return hit[0]
-    g = graph_of(adjacency[0])
-    _SQ_CACHE[key] = (g, weakref.ref(adjacency))
-    while len(_SQ_CACHE) > _CACHE_MAX:
-        _SQ_CACHE.popitem(last=False)
-    return g
+    capturing = _capturing(adjacency)
+    # another tensor object at a cached address: compare contents ONCE (a device read-back, which a HIP-graph capture
+    # cannot contain) and remember the new object, so that its later calls -- the captured one included -- hit by
+    # identity.  (A model built where a freed model's adjacency lived used to compare on every call, and its first
+    # capture failed with "operation not permitted when stream is capturing".)
+    if hit is not None and not capturing and torch.equal(hit[1], adjacency.detach()):
+        return _GRAPHS.remember(key, adjacency, hit)[0]
+    if capturing:
+        raise _not_cached("the CSR of this adjacency is not cached yet")
+    g = SparseGraph(adjacency[0] if adjacency.dim() == 3 and adjacency.shape[0] == 1 else adjacency)
+    return _GRAPHS.remember(key, adjacency, (g, adjacency.detach().clone()))[0]
 
 
 # ---- per-sample adjacency [V,N,N] ------------------------------------------------------------------------------------
@@ -273,24 +337,11 @@ def _squeezed_graph_of(adjacency: torch.Tensor) -> SparseGraph:
 # batched adjacency is ONE structure -- the union of the samples' patterns, shared by every object with that pattern --
 # and one value set per sample, val [V,nnz], with explicit zeros where a sample lacks a union edge (E = 0 there).
 
-_PATTERNS: "collections.OrderedDict[tuple, SparseGraph]" = collections.OrderedDict()   # (N, sell, packed mask) -> structure
-_LAST_PATTERN = {}   # (N, sell) -> the structure used last: what a miss tries first
-_PATTERNS_MAX = 8
-
-
-def _union_structure(mask: torch.Tensor, sell: str) -> SparseGraph:
-    """The shared CSR / CSC (/ SELL) of a host [N,N] bool mask (values 1 at the edges; BatchedGraph brings its own)."""
-    m = mask.to(device="cpu", dtype=torch.bool).contiguous()
-    n = m.shape[0]
-    key = (n, sell, np.packbits(m.numpy()).tobytes())
-    g = _PATTERNS.get(key)
-    if g is None:
-        g = _PATTERNS[key] = SparseGraph(m.to(torch.float32), sell=sell)
-        while len(_PATTERNS) > _PATTERNS_MAX:
-            _PATTERNS.popitem(last=False)
-    _PATTERNS.move_to_end(key)
-    _LAST_PATTERN[(n, sell)] = g
-    return g
+def _row_pointers(rows: torch.Tensor, n: int) -> torch.Tensor:
+    """CSR row pointers [n+1] of the row indices of edges in row-major order."""
+    crow = torch.zeros(n + 1, dtype=torch.int64)
+    crow[1:] = torch.bincount(rows, minlength=n).cumsum(0)
+    return crow
 
 
 def _check_batched(adjacency: torch.Tensor):
@@ -298,14 +349,11 @@ def _check_batched(adjacency: torch.Tensor):
         raise ValueError(f"a batched adjacency must be [V, N, N], got {tuple(adjacency.shape)}")
 
 
-class BatchedGraph:
-    """A per-sample adjacency [V,N,N]: one shared sparse structure (the union of the samples' non-zero patterns, built
-    by `SparseGraph` from the [N,N] mask `(adj != 0).any(0)`) and this object's own values val [V,nnz].
-
-    Exposes what the ops use of a `SparseGraph` (`n_nodes`, `nnz`, `on(device)`, a `__dict__` for the per-shape plans)
-    plus `n_sets` = V; `on()` hands the library the structure's device arrays with `val` pointing at this object's values
-    and `val_sets = V`.  Group g of a call reads value set g % V: V = B for a [B,...] batch (shared by R stacked
-    relations), V = R*B for one set per group.
+class BatchedGraph(ValuedGraph):
+    """A per-sample adjacency [V,N,N]: one shared sparse structure (the union of the samples' non-zero patterns, the
+    `SparseGraph` of the [N,N] mask `(adj != 0).any(0)`) and this object's own values val [V,nnz], n_sets = V.  Group g
+    of a call reads value set g % V: V = B for a [B,...] batch (shared by R stacked relations), V = R*B for one set per
+    group.
 
     `update_(adj)` refills the values in place from a device tensor with the `msgat_graph_edge_values` kernel, which also
     adds the non-zeros it finds outside the structure to a device counter; nothing is read back, so it may sit inside a
@@ -315,21 +363,15 @@ class BatchedGraph:
     def __init__(self, adjacency: torch.Tensor, sell: str = "auto", structure: SparseGraph = None):
         _check_batched(adjacency)
         V, N = int(adjacency.shape[0]), int(adjacency.shape[1])
-        if structure is None:
-            structure = _union_structure((adjacency.detach() != 0).any(0), sell)
+        if structure is None:            # the shared CSR / CSC (/ SELL) of the union mask
+            rows, cols = (adjacency.detach() != 0).any(0).cpu().nonzero(as_tuple=True)
+            structure = _pattern(_row_pointers(rows, N), cols, N, sell).structure
         elif structure.n_nodes != N:
             raise ValueError(f"structure has {structure.n_nodes} nodes, the adjacency {N}")
-        self.structure = structure
-        self.n_nodes, self.nnz, self.n_sets = N, structure.nnz, V
         self.device = adjacency.device
-        self.val = torch.zeros((V, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
+        super().__init__(structure, torch.zeros((V, max(structure.nnz, 1)), dtype=torch.float32, device=self.device), V)
         self._outside = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._dev = {}
         self.update_(adjacency)
-
-    @property
-    def has_sell(self) -> bool:
-        return self.structure.has_sell
 
     def update_(self, adjacency: torch.Tensor) -> "BatchedGraph":
         """Refill the values from `adjacency` [V,N,N] (same V, N and device); non-zeros outside the structure are added
@@ -354,7 +396,7 @@ class BatchedGraph:
             return self
         gstruct, _ = s.on(a.device)
         _lib.check(_lib.lib().msgat_graph_edge_values(C.byref(gstruct), a.data_ptr(), self.n_sets, self.val.data_ptr(),
-                                                      self._outside.data_ptr(), _current_stream(a.device)),
+                                                      self._outside.data_ptr(), _lib.stream_handle(a.device)),
                    "msgat_graph_edge_values")
         return self
 
@@ -369,33 +411,6 @@ class BatchedGraph:
                                   "new one for this adjacency (batched_graph_of does so)")
         return self
 
-    def on(self, device: torch.device):
-        """(ctypes struct of device pointers, tensors kept alive) for `device`: the shared structure, this object's
-        values."""
-        key = str(device)
-        if key not in self._dev:
-            _, tensors = self.structure.on(device)
-            val = self.val if self.val.device == torch.device(device) else self.val.to(device)
-            g = self.structure._struct(tensors)
-            g.val, g.val_sets = val.data_ptr(), self.n_sets
-            self._dev[key] = (g, (tensors, val))
-        return self._dev[key]
-
-    def dense(self) -> torch.Tensor:
-        """[V,N,N] of the values on the structure (host)."""
-        s = self.structure
-        a = torch.zeros(self.n_sets, self.n_nodes, self.n_nodes)
-        if self.nnz:
-            a[:, s.erow[: self.nnz].long(), s.col[: self.nnz].long()] = self.val[:, : self.nnz].cpu()
-        return a
-
-
-def _current_stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-_BCACHE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()
-
 
 def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGraph:
     """Cached `BatchedGraph` of a dense [V,N,N] adjacency, keyed on (storage address, shape, device, version).
@@ -407,15 +422,16 @@ def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGrap
     read back: the known pattern is used and the count only accumulates (`check()` reads it later); with no known
     pattern it raises, as graph_of does."""
     _check_batched(adjacency)
-    capturing = adjacency.is_cuda and torch.cuda.is_current_stream_capturing()
-    key = (adjacency.data_ptr(), tuple(adjacency.shape), str(adjacency.device), adjacency._version, sell)
-    hit = _BCACHE.get(key)
-    if hit is not None and hit[1]() is adjacency:
-        _BCACHE.move_to_end(key)
-        if capturing:
-            hit[0].update_(adjacency)
-        return hit[0]
-    known = hit[0].structure if hit is not None else _LAST_PATTERN.get((int(adjacency.shape[1]), sell))
+    capturing = _capturing(adjacency)
+    key = _tensor_key(adjacency) + (sell,)
+    hit, same = _BATCHED.lookup(key, adjacency)
+    if same:
+        return hit.update_(adjacency) if capturing else hit
+    if hit is not None:
+        known = hit.structure
+    else:                                # the pattern on N nodes used last: the latest entry of _PATTERNS with (N, sell)
+        n_sell = (int(adjacency.shape[1]), sell)
+        known = next((p.structure for key, p in reversed(_PATTERNS.items()) if key[:2] == n_sell), None)
     if not adjacency.is_cuda:
         g = BatchedGraph(adjacency, sell)
     elif known is not None:
@@ -423,17 +439,10 @@ def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGrap
         if not capturing and g.outside() != 0:
             g = BatchedGraph(adjacency, sell)
     elif capturing:
-        raise _lib.MsgatError("the pattern of this batched adjacency is not known yet: run one forward outside the "
-                              "HIP-graph capture first (engine.Trainer does this in its warm-up)")
+        raise _not_cached("the pattern of this batched adjacency is not known yet")
     else:
         g = BatchedGraph(adjacency, sell)
-    if not capturing:
-        _LAST_PATTERN[(g.n_nodes, sell)] = g.structure
-    _BCACHE[key] = (g, weakref.ref(adjacency))
-    _BCACHE.move_to_end(key)
-    while len(_BCACHE) > _CACHE_MAX:
-        _BCACHE.popitem(last=False)
-    return g
+    return _BATCHED.remember(key, adjacency, g)
 
 
 # ---- a sparse adjacency [N,N] (torch COO / CSR): a learned weight per stored edge --------------------------------------
@@ -446,36 +455,10 @@ def is_sparse_adjacency(adjacency) -> bool:
     return isinstance(adjacency, torch.Tensor) and adjacency.layout in (torch.sparse_coo, torch.sparse_csr)
 
 
-class EdgeWeightGraph:
-    """What the ops hand the library for a sparse adjacency: the pattern's structure with `val` at `values_ptr` (device
-    values in library order, one set).  One per (pattern, values address): the per-shape plans live on it."""
-
-    def __init__(self, pattern: "SparsePattern", values_ptr: int):
-        self.pattern, self.structure = pattern, pattern.structure
-        self.n_nodes, self.nnz, self.n_sets = self.structure.n_nodes, self.structure.nnz, 1
-        self._ptr = values_ptr
-        self._dev = {}
-
-    @property
-    def has_sell(self) -> bool:
-        return self.structure.has_sell
-
-    def on(self, device: torch.device):
-        key = str(device)
-        if key not in self._dev:
-            _, tensors = self.structure.on(device)
-            g = self.structure._struct(tensors)
-            g.val, g.val_sets = self._ptr, 1
-            self._dev[key] = (g, tensors)
-        return self._dev[key]
-
-
 class SparsePattern:
     """The structure of one sparse pattern (`SparseGraph.from_indices`) plus, when the caller's order inside a row is
     not the library's, the device permutations between them (computed once): values are gathered into a buffer of
     this pattern's, and the gradient is gathered back."""
-
-    _VIEWS_MAX = 8
 
     def __init__(self, crow: torch.Tensor, col: torch.Tensor, n_nodes: int, sell: str = "auto"):
         self.structure = SparseGraph.from_indices(crow, col, n_nodes, sell=sell)
@@ -486,7 +469,7 @@ class SparsePattern:
         self._inverse = torch.empty_like(order)
         self._inverse[order] = torch.arange(nnz)
         self._dev = {}
-        self._views: "collections.OrderedDict[tuple, EdgeWeightGraph]" = collections.OrderedDict()
+        self._views = _Lru(8)     # (values address, device) -> ValuedGraph: its per-shape plans live on it
 
     def _perm(self, device):
         key = str(device)
@@ -495,7 +478,7 @@ class SparsePattern:
                               torch.empty(max(self.structure.nnz, 1), dtype=torch.float32, device=device))
         return self._dev[key]
 
-    def graph(self, values: torch.Tensor) -> EdgeWeightGraph:
+    def graph(self, values: torch.Tensor) -> ValuedGraph:
         """The graph whose `val` holds `values` (input order, on the device) in library order.  Values in another order,
         or not contiguous (a strided view), are copied into this pattern's own buffer: the library keeps only a pointer,
         so it must point at memory that outlives the call (a temporary copy would be freed before the score kernels
@@ -509,13 +492,8 @@ class SparsePattern:
                 torch.index_select(values, 0, order, out=dst)
             values = buf
         key = (values.data_ptr(), str(values.device))
-        g = self._views.get(key)
-        if g is None:
-            g = self._views[key] = EdgeWeightGraph(self, values.data_ptr())
-            while len(self._views) > self._VIEWS_MAX:
-                self._views.popitem(last=False)
-        self._views.move_to_end(key)
-        return g
+        g = self._views.hit(key)
+        return g if g is not None else self._views.put(key, ValuedGraph(self.structure, values.data_ptr(), 1))
 
     def to_input_order(self, dval: torch.Tensor) -> torch.Tensor:
         """A gradient in library order -> the caller's order of the values."""
@@ -524,8 +502,11 @@ class SparsePattern:
         return dval.index_select(0, self._perm(dval.device)[1])
 
 
-_SPARSE: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()    # index storages -> (pattern, indices)
-_SPARSE_PATTERNS: "collections.OrderedDict[tuple, SparsePattern]" = collections.OrderedDict()   # by content
+def _pattern(crow: torch.Tensor, col: torch.Tensor, n: int, sell: str) -> SparsePattern:
+    """The `SparsePattern` of host CSR indices (int64), shared by every caller with the same content."""
+    key = (n, sell, crow.numpy().tobytes(), col.numpy().tobytes())
+    pattern = _PATTERNS.hit(key)
+    return pattern if pattern is not None else _PATTERNS.put(key, SparsePattern(crow, col, n, sell))
 
 
 def sparse_parts(adjacency: torch.Tensor):
@@ -547,75 +528,62 @@ def check_sparse_adjacency(adjacency: torch.Tensor) -> None:
 
 
 def sparse_pattern_of(adjacency: torch.Tensor, sell: str = "auto") -> SparsePattern:
-    """Cached `SparsePattern` of a (coalesced, if COO) sparse [N,N] adjacency.  A hit is keyed on the index tensors'
-    storage address, size and version; the first sight of a key reads the indices back, and a pattern with the same
-    content is shared.  The first sight inside a HIP-graph capture raises, as graph_of does."""
+    """Cached `SparsePattern` of a (coalesced, if COO) sparse [N,N] adjacency, after `check_sparse_adjacency`.  A hit is
+    keyed on the index tensors' storage address, shape and version; the first sight of a key reads the indices back,
+    and a pattern with the same content is shared.  The first sight inside a HIP-graph capture raises, as graph_of
+    does."""
     check_sparse_adjacency(adjacency)
     layout, idx, _ = sparse_parts(adjacency)
     n = int(adjacency.shape[0])
-    key = (layout, n, sell, str(adjacency.device)) + tuple((t.data_ptr(), t.numel(), t._version) for t in idx)
-    hit = _SPARSE.get(key)
+    key = (layout, n, sell) + tuple(_tensor_key(t) for t in idx)
+    hit, _ = _SPARSE.lookup(key, adjacency)
     if hit is not None:
-        _SPARSE.move_to_end(key)
         return hit[0]
-    if adjacency.is_cuda and torch.cuda.is_current_stream_capturing():
-        raise _lib.MsgatError("the structure of this sparse adjacency is not cached yet: run one forward outside the "
-                              "HIP-graph capture first (engine.Trainer does this in its warm-up)")
+    if _capturing(adjacency):
+        raise _not_cached("the structure of this sparse adjacency is not cached yet")
     if layout == "csr":
         crow, col = (t.detach().to(device="cpu", dtype=torch.int64) for t in idx)
     else:
         ij = idx[0].detach().to(device="cpu", dtype=torch.int64)
-        crow = torch.zeros(n + 1, dtype=torch.int64)
-        crow[1:] = torch.bincount(ij[0], minlength=n).cumsum(0)
-        col = ij[1]
+        crow, col = _row_pointers(ij[0], n), ij[1]
     if crow.numel() != n + 1 or int(crow[-1]) != col.numel():
         raise ValueError("malformed sparse adjacency indices")
-    ckey = (n, sell, crow.numpy().tobytes(), col.numpy().tobytes())
-    pattern = _SPARSE_PATTERNS.get(ckey)
-    if pattern is None:
-        pattern = _SPARSE_PATTERNS[ckey] = SparsePattern(crow, col, n, sell)
-        while len(_SPARSE_PATTERNS) > _PATTERNS_MAX:
-            _SPARSE_PATTERNS.popitem(last=False)
-    _SPARSE_PATTERNS.move_to_end(ckey)
-    _SPARSE[key] = (pattern, idx)     # the index tensors stay alive with the entry: their addresses cannot be reused
-    while len(_SPARSE) > _CACHE_MAX:
-        _SPARSE.popitem(last=False)
-    return pattern
-
-
-def sparse_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> EdgeWeightGraph:
-    """The graph of a sparse [N,N] adjacency: its cached pattern with `val` at its values on the device."""
-    pattern = sparse_pattern_of(adjacency, sell)
-    _, _, values = sparse_parts(adjacency)
-    return pattern.graph(values.detach())
+    # the index tensors stay alive with the entry: their addresses cannot be reused under it
+    return _SPARSE.remember(key, adjacency, (_pattern(crow, col, n, sell), idx))[0]
 
 
 def graph_for(adjacency, groups: int, relations: int):
-    """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N]
-    through graph_of; [1,N,N] as [N,N]; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one
-    per group) through batched_graph_of.  The graph carries no gradient: a batched adjacency that requires grad while
-    autograd records is refused here.  The ops (`ops.gacn`, `graph_attention`, `attention_core`, and the modules on
-    them) accept one -- they hand this function a detached alias and route the gradient themselves."""
-    if isinstance(adjacency, (SparseGraph, BatchedGraph, EdgeWeightGraph)):
+    """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N] or
+    [1,N,N] through graph_of; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one per group)
+    through batched_graph_of; a sparse [N,N] as its cached pattern with `val` at its values on the device.  The graph
+    carries no gradient: a batched adjacency that requires grad while autograd records is refused here.  The ops
+    (`ops.gacn`, `graph_attention`, `attention_core`, and the modules on them) accept one -- they route its gradient
+    themselves."""
+    if is_sparse_adjacency(adjacency):
+        return sparse_pattern_of(adjacency).graph(sparse_parts(adjacency)[2].detach())
+    return _dense_graph_for(adjacency, groups, relations, refuse_grad=True)
+
+
+def _dense_graph_for(adjacency, groups: int, relations: int, refuse_grad: bool):
+    """graph_for of anything but a sparse tensor; `refuse_grad=False` for a caller that routes the gradient itself."""
+    if isinstance(adjacency, (SparseGraph, ValuedGraph)):
         g = adjacency
-    elif is_sparse_adjacency(adjacency):
-        g = sparse_graph_of(adjacency)
     elif not isinstance(adjacency, torch.Tensor):
         raise TypeError(f"adjacency must be a tensor, a SparseGraph or a BatchedGraph, got {type(adjacency).__name__}")
-    elif adjacency.dim() == 3:
+    elif adjacency.dim() == 3 and adjacency.shape[0] != 1:
         V = adjacency.shape[0]
         Bg = groups // relations
-        if V != 1 and V != Bg and V != groups:
+        if V != Bg and V != groups:
             allowed = sorted({1, Bg, groups})
             raise ValueError(f"a batched adjacency {tuple(adjacency.shape)} needs a leading size in {allowed} for signals of "
                              f"{groups} groups ({relations} relation(s) x {Bg} samples)")
-        if V != 1 and adjacency.requires_grad and torch.is_grad_enabled():
+        if refuse_grad and adjacency.requires_grad and torch.is_grad_enabled():
             raise ValueError(f"the batched adjacency {tuple(adjacency.shape)} requires grad: graph_for builds a graph without "
                              "one; call ops.gacn / graph_attention / attention_core (or a module) with it, which give it its "
                              "gradient, or pass adjacency.detach()")
-        g = _squeezed_graph_of(adjacency) if V == 1 else batched_graph_of(adjacency)
+        g = batched_graph_of(adjacency)
     else:
         g = graph_of(adjacency)
-    if isinstance(g, BatchedGraph) and g.n_sets not in (1, groups // relations, groups):
+    if isinstance(g, ValuedGraph) and g.n_sets not in (1, groups // relations, groups):
         raise ValueError(f"BatchedGraph with {g.n_sets} value sets for signals of {groups} groups ({relations} relation(s))")
     return g

@@ -9,13 +9,13 @@ arithmetic step runs in libmsgat_hip.so through the C ABI of include/msgat_hip.h
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 from typing import Optional
 
 import torch
 
 from . import _lib
-from .graph import check_sparse_adjacency, graph_for, is_sparse_adjacency
+from ._lib import stream_handle as _stream_handle
+from .graph import _dense_graph_for, is_sparse_adjacency, sparse_parts, sparse_pattern_of
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -33,17 +33,6 @@ def _require_device_tensor(name: str, t: torch.Tensor, device=None):
         raise TypeError(f"{name} must be float32 (the reference arithmetic type), got {t.dtype}")
     if device is not None and t.device != device:
         raise ValueError(f"{name} is on {t.device}, expected {device}")
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream_handle(device) -> int:
-    """The current HIP stream of `device` as an integer handle.  (`torch.cuda.current_stream(...).cuda_stream` builds a
-    Stream object per call, ~5 us -- a tenth of the host time of a PEMSD4-sized forward.)"""
-    if _raw_stream is not None:
-        return _raw_stream(device.index if device.index is not None else torch.cuda.current_device())
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class _GacnPlan:
@@ -82,6 +71,11 @@ class _GacnPlan:
         self.bwd_bytes = None                # asked for by the first backward
         self.z_channels = Co if Co else Cin
 
+    def pointers(self, buf: torch.Tensor):
+        """(q, kW, lse, pq, E, Ec, u): the device addresses of the pieces of the saved buffer `buf` (None: absent)."""
+        base = buf.data_ptr()
+        return tuple(None if o < 0 else base + 4 * o for o in self.offs)
+
 
 def _gacn_plan(graph, dev, R, Bg, Cin, Co, N, T, need_bwd, own_q=True) -> _GacnPlan:
     # the plans live ON the graph object and die with it (a module-level table keyed by id(graph) kept every graph a
@@ -99,138 +93,100 @@ def _gacn_plan(graph, dev, R, Bg, Cin, Co, N, T, need_bwd, own_q=True) -> _GacnP
 
 
 # ---- an adjacency that requires grad ----------------------------------------------------------------------------------
-# The graph is built from a detached alias of the adjacency, and the tensor itself rides into the autograd Function as a
-# last input, so that its gradient (msgat_adjacency_grad) has somewhere to go.  The alias is ONE object per adjacency:
-# graph_of / batched_graph_of hit their caches by identity (a fresh `detach()` per call would be confirmed by a content
-# read-back every time, which a HIP-graph capture cannot contain).  It shares the version counter, so an in-place update
-# of the adjacency still rebuilds the graph.
-_DETACHED = {}   # id(adjacency) -> (weakref to it, its detached alias); an entry leaves with its tensor
-
-
-def _detached(adjacency: torch.Tensor) -> torch.Tensor:
-    key = id(adjacency)
-    hit = _DETACHED.get(key)
-    if hit is not None and hit[0]() is adjacency:
-        return hit[1]
-    alias = adjacency.detach()
-    _DETACHED[key] = (weakref.ref(adjacency, lambda _r, k=key: _DETACHED.pop(k, None)), alias)
-    return alias
-
-
-# A sparse adjacency of learned edge weights, `edge_adjacency(crow, col, weight)`: a CSR tensor on weight.detach() (the
-# same storage: the library reads the current weights), remembered here with the weight itself.  The ops hand the
-# weight to their autograd Function, and its gradient arrives as a dense [nnz] tensor: torch's own backward of
-# `sparse_csr_tensor` densifies the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync, which a
-# captured step cannot contain), and adding the sparse gradients of several layers needs the pattern on the host too.
-_EDGE_WEIGHTS = {}   # id(sparse adjacency) -> (weakref to it, the weight that receives its gradient)
-
+# The adjacency tensor rides into the autograd Function as a last input, so that its gradient has somewhere to go; the
+# graph is built from the tensor itself (the caches hit it by identity, inside a HIP-graph capture too, and an in-place
+# update bumps its version and rebuilds the graph).  A frozen adjacency -- every caller of the reference's models -- costs
+# one `requires_grad` check; a prebuilt SparseGraph / BatchedGraph is not a tensor and gets no gradient.
 
 def edge_adjacency(crow: torch.Tensor, col: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """The sparse CSR adjacency [N,N] (N = crow.numel() - 1) with a learned weight per stored edge: `weight` [nnz] in
     the order of (crow, col), columns ascending inside a row.  Every op and module accepts it like any sparse adjacency;
-    `weight` gets its gradient at the stored edges, dense [nnz], and a step that uses it can be captured in a HIP graph."""
+    `weight` gets its gradient at the stored edges, dense [nnz], and a step that uses it can be captured in a HIP graph.
+
+    It is a CSR tensor on weight.detach() (the same storage: the library reads the current weights) that carries the
+    weight itself as an attribute.  The ops hand the weight to their autograd Function: torch's own backward of
+    `sparse_csr_tensor` densifies the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync, which a
+    captured step cannot contain), and adding the sparse gradients of several layers needs the pattern on the host too."""
     n = crow.numel() - 1
     adj = torch.sparse_csr_tensor(crow, col, weight.detach(), (n, n))
-    key = id(adj)
-    _EDGE_WEIGHTS[key] = (weakref.ref(adj, lambda _r, k=key: _EDGE_WEIGHTS.pop(k, None)), weight)
+    adj._msgat_edge_weight = weight
     return adj
 
 
-def _adjacency_operand(adjacency, recording: bool):
-    """(what graph_for gets, the adjacency tensor that receives a gradient or None).  A frozen adjacency -- every
-    caller of the reference's models -- costs this one `requires_grad` check; a prebuilt SparseGraph / BatchedGraph is
-    not a tensor and gets no gradient.  For an `edge_adjacency` the tensor that receives the gradient is its weight."""
-    if recording and _EDGE_WEIGHTS:
-        hit = _EDGE_WEIGHTS.get(id(adjacency))
-        if hit is not None and hit[0]() is adjacency:
-            return adjacency, (hit[1] if hit[1].requires_grad else None)
-    if recording and getattr(adjacency, "requires_grad", False):
-        return _detached(adjacency), adjacency
-    return adjacency, None
+class _AdjacencyGrad:
+    """The gradient route of an adjacency that requires grad, built by `_resolve_adjacency`.  Called by backward with
+    `(dv, feat, Cu)` and the saved q, kW, lse, it returns the gradient in the caller's own shape and layout: dense [N,N] /
+    [V,N,N] from msgat_adjacency_grad (n_sets = V, the convention of `val_sets`), or from msgat_edge_weight_grad at the
+    stored edges of a sparse adjacency -- dense [nnz] in input order for an `edge_adjacency` weight, else a sparse tensor
+    with the caller's layout and indices.  Either is enqueued on `stream` after the backward of the other inputs."""
+
+    def __init__(self, target: torch.Tensor, pattern=None, parts=None):
+        self.shape, self.pattern, self.parts = tuple(target.shape), pattern, parts
+        self.n_sets = 1 if target.dim() == 2 else self.shape[0]
+
+    def __call__(self, plan: _GacnPlan, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
+                 stream) -> torch.Tensor:
+        L = _lib.lib()
+        shape, dev = C.byref(plan.shape), dv.device
+        if self.pattern is None:
+            dadj = torch.empty((self.n_sets, plan.shape.N, plan.shape.N), device=dev, dtype=torch.float32)
+            nbytes = int(L.msgat_adjacency_grad_workspace_bytes(shape, Cu, self.n_sets))
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+            _lib.check(L.msgat_adjacency_grad(shape, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, self.n_sets, _ptr(dadj), _ptr(ws),
+                                              nbytes, stream), "msgat_adjacency_grad")
+            return dadj.view(self.shape)
+        gstruct = C.byref(plan.gstruct)
+        dval = torch.empty(self.pattern.structure.nnz, device=dev, dtype=torch.float32)
+        nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(shape, gstruct, Cu))
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+        _lib.check(L.msgat_edge_weight_grad(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dval), _ptr(ws),
+                                            nbytes, stream), "msgat_edge_weight_grad")
+        dval = self.pattern.to_input_order(dval)
+        if self.parts is None:                            # the weight of an edge_adjacency
+            return dval
+        layout, idx = self.parts
+        if layout == "csr":
+            return torch.sparse_csr_tensor(idx[0], idx[1], dval, self.shape)
+        return torch.sparse_coo_tensor(idx[0], dval, self.shape, is_coalesced=True)
 
 
-def _adjacency_sets(adj: torch.Tensor) -> int:
-    """n_sets of msgat_adjacency_grad for a dense [N,N] / [V,N,N] adjacency (graph_for has checked V already)."""
-    return 1 if adj.dim() == 2 else int(adj.shape[0])
-
-
-def _sparse_operand(adjacency, device):
-    """A sparse [N,N] adjacency checked for the ops: one matrix, float32, on the signals' device; an uncoalesced COO
-    tensor is coalesced (duplicates add, as in torch.sparse) -- by an autograd op, so its gradient still reaches the
-    caller's values.  Anything else is returned as it is."""
-    if not is_sparse_adjacency(adjacency):
-        return adjacency
-    check_sparse_adjacency(adjacency)
-    if adjacency.device != device:
-        raise ValueError(f"the sparse adjacency is on {adjacency.device}, the signals on {device}")
-    if adjacency.layout == torch.sparse_coo and not adjacency.is_coalesced():
-        adjacency = adjacency.coalesce()
-    return adjacency
-
-
-def _adjacency_grad_state(adj, graph):
-    """What backward needs to give `adj` its gradient, None without: ("dense", n_sets, shape) for a dense adjacency
-    (msgat_adjacency_grad); for a sparse one (msgat_edge_weight_grad at the stored edges) ("sparse", graph, layout, index
-    tensors, shape), or ("weight", graph) for the weight of an edge_adjacency."""
-    if adj is None:
-        return None
-    if is_sparse_adjacency(adj):
-        idx = (adj.crow_indices(), adj.col_indices()) if adj.layout == torch.sparse_csr else (adj._indices(),)
-        return ("sparse", graph, adj.layout, tuple(t.detach() for t in idx), tuple(adj.shape))
-    if adj.dim() == 1:
-        return ("weight", graph)
-    return ("dense", _adjacency_sets(adj), tuple(adj.shape))
-
-
-def _adjacency_gradient(state, shape, gstruct, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int,
-                        lse: int, dev, stream) -> torch.Tensor:
-    """The gradient of the adjacency that `state` (_adjacency_grad_state) describes, in its own shape and layout."""
-    if state[0] == "dense":
-        return _adjacency_grad(shape, Cu, dv, dv_gs, feat, q, kW, lse, state[1], state[2], dev, stream)
-    graph = state[1]
-    dval = _edge_weight_grad(shape, gstruct, Cu, dv, dv_gs, feat, q, kW, lse, graph.nnz, dev, stream)
-    dval = graph.pattern.to_input_order(dval)
-    if state[0] == "weight":
-        return dval
-    _, _, layout, idx, adj_shape = state
-    if layout == torch.sparse_csr:
-        return torch.sparse_csr_tensor(idx[0], idx[1], dval, adj_shape)
-    return torch.sparse_coo_tensor(idx[0], dval, adj_shape, is_coalesced=True)
-
-
-def _edge_weight_grad(shape, gstruct, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
-                      nnz: int, dev, stream) -> torch.Tensor:
-    """dval [nnz] in the library's CSR order, enqueued on `stream` after the backward of the other inputs."""
-    L = _lib.lib()
-    dval = torch.empty(nnz, device=dev, dtype=torch.float32)
-    nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(C.byref(shape), C.byref(gstruct), Cu))
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-    st = L.msgat_edge_weight_grad(C.byref(shape), C.byref(gstruct), Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dval),
-                                  _ptr(ws), nbytes, stream)
-    _lib.check(st, "msgat_edge_weight_grad")
-    return dval
-
-
-def _adjacency_grad(shape, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int, n_sets: int,
-                    adj_shape, dev, stream) -> torch.Tensor:
-    """dadj in the adjacency's own shape, enqueued on `stream` after the backward of the other inputs."""
-    L = _lib.lib()
-    N = shape.N
-    dadj = torch.empty((n_sets, N, N), device=dev, dtype=torch.float32)
-    nbytes = int(L.msgat_adjacency_grad_workspace_bytes(C.byref(shape), Cu, n_sets))
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-    st = L.msgat_adjacency_grad(C.byref(shape), Cu, _ptr(dv), dv_gs, feat, q, kW, lse, n_sets, _ptr(dadj), _ptr(ws),
-                                nbytes, stream)
-    _lib.check(st, "msgat_adjacency_grad")
-    return dadj.view(adj_shape)
+def _resolve_adjacency(adjacency, device, groups: int, relations: int, n_nodes: int, recording: bool):
+    """(graph, the tensor that receives the adjacency's gradient or None, its `_AdjacencyGrad` or None) for an op on
+    signals of `groups` groups on `device`.  A sparse [N,N] adjacency must be one float32 matrix on the signals' device
+    (`graph.sparse_pattern_of` checks it); an uncoalesced COO tensor is coalesced (duplicates add, as in torch.sparse) --
+    by an autograd op, so its gradient still reaches the caller's values.  For an `edge_adjacency` the tensor that
+    receives the gradient is its weight.  Anything else goes through `graph.graph_for`."""
+    target = route = None
+    if is_sparse_adjacency(adjacency):
+        if adjacency.device != device:
+            raise ValueError(f"the sparse adjacency is on {adjacency.device}, the signals on {device}")
+        if adjacency.layout == torch.sparse_coo and not adjacency.is_coalesced():
+            adjacency = adjacency.coalesce()
+        pattern = sparse_pattern_of(adjacency)
+        layout, idx, values = sparse_parts(adjacency)
+        graph = pattern.graph(values.detach())
+        if recording:
+            target = adjacency.__dict__.get("_msgat_edge_weight", adjacency)
+            if target.requires_grad:
+                parts = None if target.dim() == 1 else (layout, tuple(t.detach() for t in idx))   # dim 1: a weight
+                route = _AdjacencyGrad(target, pattern, parts)
+            else:
+                target = None
+    else:
+        graph = _dense_graph_for(adjacency, groups, relations, refuse_grad=False)
+        if recording and getattr(adjacency, "requires_grad", False):
+            target, route = adjacency, _AdjacencyGrad(adjacency)
+    if graph.n_nodes != n_nodes:
+        raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {n_nodes}")
+    return graph, target, route
 
 
 class _GACNFunction(torch.autograd.Function):
-    """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg.  `adj`: the dense adjacency
-    tensor when it requires grad (the graph was built from its detached alias), else None."""
+    """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg.  `adj`: the tensor that
+    receives the adjacency's gradient and `adj_grad` its route (`_resolve_adjacency`), or None both."""
 
     @staticmethod
-    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj=None):   # graph: SparseGraph or BatchedGraph
+    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj_grad=None, adj=None):   # graph: see graph_for
         L = _lib.lib()
         dev = x.device
         G, Cin, N, T = x.shape
@@ -254,8 +210,7 @@ class _GACNFunction(torch.autograd.Function):
         # per forward were a quarter of its host time, which is what a PEMSD4-sized step is bound by.
         z = torch.empty((G, plan.z_channels, N, T), device=dev, dtype=torch.float32)
         buf = torch.empty(plan.total, device=dev, dtype=torch.float32)
-        base = buf.data_ptr()
-        q, kW, lse, pq, E, Ec, u = (None if o < 0 else base + 4 * o for o in plan.offs)
+        q, kW, lse, pq, E, Ec, u = plan.pointers(buf)
         scratch_t = torch.empty(plan.nscratch, device=dev, dtype=torch.float32) if plan.nscratch else None
         scratch = _ptr(scratch_t)
         dense_t = torch.empty(plan.ndense, device=dev, dtype=torch.uint8) if plan.ndense else None
@@ -265,8 +220,7 @@ class _GACNFunction(torch.autograd.Function):
         _lib.check(st, "msgat_gacn_forward")
 
         if need_bwd:
-            ctx.plan, ctx.has_W = plan, W is not None
-            ctx.adj_grad = _adjacency_grad_state(adj, graph)
+            ctx.plan, ctx.has_W, ctx.adj_grad = plan, W is not None, adj_grad
             if W is not None:
                 ctx.save_for_backward(x, alpha, Wg, buf, W)
             else:
@@ -281,15 +235,14 @@ class _GACNFunction(torch.autograd.Function):
         # that forms dx; dWg is a [T,T] partial of the row pass that every other gradient needs.  The only input that
         # is ever frozen in the reference's models is none of these (adj, msgat.py:190), and x always requires one (it is
         # a LayerNorm output with learnable weights, msgat.py:122).  An adjacency that requires grad gets it from one more
-        # launch after that backward, msgat_adjacency_grad, which re-creates the dense softmax from q, kW and lse:
+        # launch after that backward (its `_AdjacencyGrad`), which re-creates the softmax from q, kW and lse:
         # dv / feat are dz / x (plain), dz / u = W x (project-first), W^T dz / x (aggregate-first, one more mix).
         L = _lib.lib()
         saved = ctx.saved_tensors
         x, alpha, Wg, buf = saved[:4]
         W = saved[4] if ctx.has_W else None
-        base = buf.data_ptr()
         plan = ctx.plan
-        q, kW, lse, pq, E, Ec, u = (None if o < 0 else base + 4 * o for o in plan.offs)
+        q, kW, lse, pq, E, Ec, u = plan.pointers(buf)
         dev = x.device
         shape, gstruct = plan.shape, plan.gstruct
         # a gradient that arrives as a channel slice dout[:, a:b] of a wider tensor is read in place where the library
@@ -308,21 +261,20 @@ class _GACNFunction(torch.autograd.Function):
         stream = _stream_handle(dev)
         st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
         _lib.check(st, "msgat_gacn_backward")
-        if ctx.adj_grad is not None:   # (the adjacency is an input of this node only when it requires grad)
-            state = ctx.adj_grad
-            Cin = x.shape[1]
-            if plan.mode == _lib.MODE_AGG_FIRST:
-                dy = torch.empty_like(x)
-                dzc = dz if dz_gs == 0 else dz.contiguous()
-                _lib.check(L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy),
-                                             stream), "msgat_stage_mix")
-                dadj = _adjacency_gradient(state, shape, gstruct, Cin, dy, 0, _ptr(x), q, kW, lse, dev, stream)
-            elif plan.mode == _lib.MODE_PROJ_FIRST:
-                dadj = _adjacency_gradient(state, shape, gstruct, shape.Co, dz, dz_gs, u, q, kW, lse, dev, stream)
-            else:
-                dadj = _adjacency_gradient(state, shape, gstruct, Cin, dz, dz_gs, _ptr(x), q, kW, lse, dev, stream)
-            return dx, dalpha, dWg, dW, None, None, dadj
-        return dx, dalpha, dWg, dW, None, None
+        if ctx.adj_grad is None:
+            return dx, dalpha, dWg, dW, None, None, None, None
+        Cin = x.shape[1]
+        if plan.mode == _lib.MODE_AGG_FIRST:
+            dy = torch.empty_like(x)
+            dzc = dz if dz_gs == 0 else dz.contiguous()
+            _lib.check(L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy), stream),
+                       "msgat_stage_mix")
+            Cu, dv, dv_gs, feat = Cin, dy, 0, _ptr(x)
+        elif plan.mode == _lib.MODE_PROJ_FIRST:
+            Cu, dv, dv_gs, feat = shape.Co, dz, dz_gs, u
+        else:
+            Cu, dv, dv_gs, feat = Cin, dz, dz_gs, _ptr(x)
+        return dx, dalpha, dWg, dW, None, None, None, ctx.adj_grad(plan, Cu, dv, dv_gs, feat, q, kW, lse, stream)
 
 
 def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[torch.Tensor],
@@ -367,14 +319,8 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
         if W is not None and (W.dim() != 3 or W.shape[0] != R or W.shape[2] != Cin):
             raise ValueError(f"W must be [{R},Co,{Cin}], got {tuple(W.shape)}")
     recording = torch.is_grad_enabled()
-    adjacency = _sparse_operand(adjacency, x.device)
-    adjacency, adj = _adjacency_operand(adjacency, recording)
-    graph = graph_for(adjacency, G, alpha.shape[0] if alpha.dim() == 2 else 1)
-    if graph.n_nodes != N:
-        raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
-    if adj is None:
-        return _GACNFunction.apply(x, alpha, Wg, W, graph, recording)
-    return _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj)
+    graph, adj, adj_grad = _resolve_adjacency(adjacency, x.device, G, alpha.shape[0] if alpha.dim() == 2 else 1, N, recording)
+    return _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj_grad, adj)
 
 
 def graph_attention(x, alpha, Wg, adjacency):
@@ -1255,7 +1201,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
     msgat_attention_backward)."""
 
     @staticmethod
-    def forward(ctx, u, q, Wg, graph, recording: bool = True, adj=None):   # graph / adj: see _GACNFunction
+    def forward(ctx, u, q, Wg, graph, recording: bool = True, adj_grad=None, adj=None):   # see _GACNFunction
         L = _lib.lib()
         u, q, Wg = u.contiguous(), q.contiguous(), Wg.contiguous()
         G, Cu, N, T = u.shape
@@ -1267,8 +1213,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
         plan = _gacn_plan(graph, dev, R, G // R, Cu, 0, N, T, need_bwd, own_q=False)
         z = torch.empty_like(u)
         buf = torch.empty(plan.total, device=dev, dtype=torch.float32)
-        base = buf.data_ptr()
-        _, kW, lse, pq, E, Ec, _ = (None if o < 0 else base + 4 * o for o in plan.offs)
+        _, kW, lse, pq, E, Ec, _ = plan.pointers(buf)
         dense_t = torch.empty(plan.ndense, device=dev, dtype=torch.uint8) if plan.ndense else None
         scratch = _new(u, plan.nscratch) if plan.nscratch else None
         stream = _stream_handle(dev)
@@ -1278,8 +1223,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
         _lib.check(L.msgat_stage_aggregate(shape, gstruct, Cu, _ptr(u), E, _ptr(z), _ptr(scratch), stream),
                    "msgat_stage_aggregate")
         if need_bwd:
-            ctx.plan = plan
-            ctx.adj_grad = _adjacency_grad_state(adj, graph)
+            ctx.plan, ctx.adj_grad = plan, adj_grad
             ctx.save_for_backward(u, q, Wg, buf)
         return z
 
@@ -1288,8 +1232,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
         L = _lib.lib()
         u, q, Wg, buf = ctx.saved_tensors
         plan = ctx.plan
-        base = buf.data_ptr()
-        _, kW, lse, pq, E, Ec, _ = (None if o < 0 else base + 4 * o for o in plan.offs)
+        _, kW, lse, pq, E, Ec, _ = plan.pointers(buf)
         shape, gstruct = C.byref(plan.shape), C.byref(plan.gstruct)
         dz, dz_gs = _sliced_grad(dz, lambda: L.msgat_attention_bwd_accepts_strided_dv(shape, gstruct))
         du, dq, dWg = torch.empty_like(u), torch.empty_like(q), torch.empty_like(Wg)
@@ -1300,11 +1243,8 @@ class _AttentionCoreFunction(torch.autograd.Function):
         st = L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
                                         _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
         _lib.check(st, "msgat_attention_backward")
-        if ctx.adj_grad is not None:
-            dadj = _adjacency_gradient(ctx.adj_grad, plan.shape, plan.gstruct, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW,
-                                       lse, u.device, stream)
-            return du, dq, dWg, None, None, dadj
-        return du, dq, dWg, None, None
+        dadj = None if ctx.adj_grad is None else ctx.adj_grad(plan, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, stream)
+        return du, dq, dWg, None, None, None, dadj
 
 
 def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency) -> torch.Tensor:
@@ -1317,14 +1257,8 @@ def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency
     if tuple(q.shape) != (G, N, T) or Wg.dim() != 3 or tuple(Wg.shape[1:]) != (T, T) or G % Wg.shape[0]:
         raise ValueError(f"attention_core: u {tuple(u.shape)}, q {tuple(q.shape)}, Wg {tuple(Wg.shape)}")
     recording = torch.is_grad_enabled()
-    adjacency = _sparse_operand(adjacency, u.device)
-    adjacency, adj = _adjacency_operand(adjacency, recording)
-    graph = graph_for(adjacency, G, Wg.shape[0])
-    if graph.n_nodes != N:
-        raise ValueError(f"adjacency has {graph.n_nodes} nodes, signals have {N}")
-    if adj is None:
-        return _AttentionCoreFunction.apply(u, q, Wg, graph, recording)
-    return _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj)
+    graph, adj, adj_grad = _resolve_adjacency(adjacency, u.device, G, Wg.shape[0], N, recording)
+    return _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj_grad, adj)
 
 
 # ---- the tiny attention matrices of a MEAM block, one launch each way ----------------------------------------------
