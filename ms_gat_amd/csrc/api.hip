@@ -102,7 +102,7 @@ extern "C" const char* msgat_status_string(int status) {
     case MSGAT_OK: return "ok";
     case MSGAT_ERR_NULL: return "required pointer is NULL";
     case MSGAT_ERR_SHAPE: return "bad or inconsistent dimension";
-    case MSGAT_ERR_UNSUPPORTED: return "unsupported size (T must be 4/8/12/16, channels <= 256)";
+    case MSGAT_ERR_UNSUPPORTED: return "unsupported size (T must be 4/8/12/16, channels <= 256, T_out <= 64)";
     case MSGAT_ERR_WORKSPACE: return "workspace too small";
     case MSGAT_ERR_GRAPH: return "malformed CSR/CSC graph";
   }
@@ -671,7 +671,7 @@ extern "C" int msgat_stage_dense_column_pass(const msgat_shape_t* sh, const msga
 // ---- prediction head ----------------------------------------------------------------------------------
 static int check_head(int32_t B, int32_t C, int32_t N, int32_t T, int32_t To) {
   if (B <= 0 || B > 65535 || C <= 0 || C > 65535 || N <= 0 || To <= 0) return MSGAT_ERR_SHAPE;
-  if (!t_supported(T) || To > 16) return MSGAT_ERR_UNSUPPORTED;
+  if (!t_supported(T) || To > 64) return MSGAT_ERR_UNSUPPORTED;
   return MSGAT_OK;
 }
 

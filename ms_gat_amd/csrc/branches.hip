@@ -361,14 +361,21 @@ constexpr int kHeadTo = 16;  // T_out <= 16
 constexpr int kHeadFwdCC = 32;   // channels of W staged in LDS at a time (24 KB at T = 12: six blocks per CU)
 constexpr int kHeadFwdUn = 8;    // channels whose loads are in flight together
 
-// Wp[r][c][t][o < 16] = W[r][o][t][0][c] (0 for o >= To): the convolution's weights in the order the kernels stage them.
+// T_out > 16 (up to 64) runs as OT = ceil(T_out / 16) output tiles of 16: the kernels below take OT as a template argument,
+// OT = 1 being the T_out <= 16 form.  The channels staged at a time shrink with OT so that the forward's LDS stays at
+// 32 x T x 16 floats (24 KB at T = 12) per block.
+template <int OT> constexpr int head_fwd_cc() { return OT == 1 ? kHeadFwdCC : OT == 2 ? 16 : 8; }
+
+// Wp[r][c][t][o < 16 OT] = W[r][o][t][0][c] (0 for o >= To): the convolution's weights in the order the kernels stage them.
 // Staged straight from the convolution layout, every block gathered its 3 x 6144 weights as 4-byte loads at a
 // stride of T*C floats; from Wp a chunk is one contiguous 24 KB copy.
+template <int OT = 1>
 __global__ __launch_bounds__(kBlock) void k_head_wperm(const float* __restrict__ W, float* __restrict__ Wp, int C, int T,
                                                        int To, int total) {
+  constexpr int OW = kHeadTo * OT;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= total) return;
-  const int o = i % kHeadTo, t = (i / kHeadTo) % T, c = (i / (kHeadTo * T)) % C, r = i / (kHeadTo * T * C);
+  const int o = i % OW, t = (i / OW) % T, c = (i / (OW * T)) % C, r = i / (OW * T * C);
   Wp[i] = (o < To) ? W[(((size_t)r * To + o) * T + t) * C + c] : 0.f;
 }
 
@@ -453,11 +460,105 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd(const float* __restrict__ x
   }
 }
 
+// T_out > 16: k_head_fwd with OT output tiles, every loaded x float4 feeding all of them (4 OT MFMAs per channel)
+template <int T, bool LN, int OT>
+__global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restrict__ x, const float* __restrict__ W,
+                                                     const float* __restrict__ bias, float* __restrict__ out,
+                                                     int C, int N, int To, int Bg, const float* __restrict__ lnw,
+                                                     const float* __restrict__ lnb, float eps, float* __restrict__ xn) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  constexpr int T4 = T / 4, OW = kHeadTo * OT, CC = head_fwd_cc<OT>();
+  __shared__ float Wl[CC * T * OW];
+  const int b = blockIdx.y;
+  W += (size_t)(b / Bg) * C * T * OW;   // pre-laid-out weights Wp [R,C,T,16 OT] (k_head_wperm), bias [R,To]
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int m = lane & 15, kq = lane >> 4;
+  const int n0 = (blockIdx.x * (kBlock / kWave) + wave) * 16;
+  const int nrow = min(n0 + m, N - 1);  // clamped: rows past N are computed from row N-1 and never stored
+  f32x4 acc[OT];   // one 16-output tile each, all fed from the same loaded x
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < C; c0 += CC) {
+    const int cn = min(CC, C - c0);
+    __syncthreads();  // the previous chunk's weights are no longer read
+    for (int i = threadIdx.x; i < CC * T * OW; i += kBlock)   // one contiguous copy (Wp is zero past To)
+      Wl[i] = (i < cn * T * OW) ? W[(size_t)c0 * T * OW + i] : 0.f;
+    __syncthreads();
+    const int kqc = min(kq, T4 - 1);
+    const float kmask = kq < T4 ? 1.f : 0.f;
+    const float4* src = reinterpret_cast<const float4*>(x + (((size_t)b * C + c0) * N + nrow) * T) + kqc;
+    float4 lw4 = make_float4(1.f, 1.f, 1.f, 1.f), lb4 = f4zero();
+    if (LN) {
+      const int rel = b / Bg;
+      if (lnw) lw4 = make_float4(lnw[rel * T + 4 * kqc], lnw[rel * T + 4 * kqc + 1], lnw[rel * T + 4 * kqc + 2], lnw[rel * T + 4 * kqc + 3]);
+      if (lnb) lb4 = make_float4(lnb[rel * T + 4 * kqc], lnb[rel * T + 4 * kqc + 1], lnb[rel * T + 4 * kqc + 2], lnb[rel * T + 4 * kqc + 3]);
+    }
+    for (int cc = 0; cc < cn; cc += kHeadFwdUn) {
+      float4 av[kHeadFwdUn];
+#pragma unroll
+      for (int u = 0; u < kHeadFwdUn; ++u) av[u] = src[(size_t)min(cc + u, cn - 1) * N * T4];
+      if (LN) {   // normalise the row: its T values are this lane's float4 and those of the lanes 16 and 32 away
+#pragma unroll
+        for (int u = 0; u < kHeadFwdUn; ++u) {
+          float4 v = av[u];
+          float s1 = ((v.x + v.y) + (v.z + v.w)) * kmask;
+          s1 += __shfl_xor(s1, 16);
+          s1 += __shfl_xor(s1, 32);
+          const float mean = s1 * (1.0f / T);
+          v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
+          float s2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w))) * kmask;
+          s2 += __shfl_xor(s2, 16);
+          s2 += __shfl_xor(s2, 32);
+          const float rstd = rsqrtf(s2 * (1.0f / T) + eps);
+          av[u] = make_float4(fmaf(v.x * rstd, lw4.x, lb4.x), fmaf(v.y * rstd, lw4.y, lb4.y), fmaf(v.z * rstd, lw4.z, lb4.z),
+                              fmaf(v.w * rstd, lw4.w, lb4.w));
+        }
+        if (xn != nullptr && kq < T4 && n0 + m < N) {   // training: the weight gradient reads the normalised rows
+          float4* dst = reinterpret_cast<float4*>(xn + (((size_t)b * C + c0) * N + n0 + m) * T) + kq;
+#pragma unroll
+          for (int u = 0; u < kHeadFwdUn; ++u)
+            if (cc + u < cn) dst[(size_t)(cc + u) * N * T4] = av[u];
+        }
+      }
+      // K slots kq >= T/4 hold a clamped duplicate row: zero it once here (4 multiplies per channel) rather than the
+      // weight of every MFMA (4 OT: the T_out <= 16 form's v_mul per MFMA)
+#pragma unroll
+      for (int u = 0; u < kHeadFwdUn; ++u)
+        av[u] = make_float4(av[u].x * kmask, av[u].y * kmask, av[u].z * kmask, av[u].w * kmask);
+#pragma unroll
+      for (int u = 0; u < kHeadFwdUn; ++u)
+        if (cc + u < cn) {  // wave-uniform; no loads inside
+          const float* wl = Wl + ((cc + u) * T + 4 * kqc) * OW + m;
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].x, wl[0 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].y, wl[1 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].z, wl[2 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].w, wl[3 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+        }
+    }
+  }
+  // D[node = 4 * (lane >> 4) + reg][o = 16 ot + (lane & 15)]
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot) {
+    const int o = kHeadTo * ot + m;
+    const float bo = (bias != nullptr && o < To) ? bias[(size_t)(b / Bg) * To + o] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int n = n0 + 4 * kq + reg;
+      if (n < N && o < To) out[((size_t)b * N + n) * To + o] = acc[ot][reg] + bo;
+    }
+  }
+}
+
 // dx[b,c,n,t] = sum_o W[o,t,c] dout[b,n,o]
-template <int T>
+template <int T, int OT = 1>
 __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ dout, const float* __restrict__ W,
                                                     float* __restrict__ dx, int C, int N, int To, int Bg) {
-  __shared__ float Wl[kHeadCC][T][kHeadTo];
+  constexpr int OW = kHeadTo * OT;   // OT tiles of 16 outputs: d and a weight row hold all of them
+  __shared__ float Wl[kHeadCC][T][OW];
   __shared__ float4 tiles[kBlock / kWave][RowTile<T>::kFloat4s];
   const int b = blockIdx.z, ck = blockIdx.y;
   W += (size_t)(b / Bg) * To * T * C;
@@ -465,27 +566,27 @@ __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ do
   // weights of this channel chunk and the lane's dout row: every load unconditional (clamped index, masked value) and
   // issued together -- as loops with a load and its use per trip hipcc emitted load, s_waitcnt vmcnt(0), use: 6 + 12
   // dependent round trips in front of every block's first store (110 us for a 293 MB write)
-  constexpr int kWn = (kHeadCC * kHeadTo * T + kBlock - 1) / kBlock;
+  constexpr int kWn = (kHeadCC * OW * T + kBlock - 1) / kBlock;
   float wv[kWn];
 #pragma unroll
   for (int k = 0; k < kWn; ++k) {
-    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * kHeadTo * T - 1);
-    const int c = i / (kHeadTo * T), t = (i / kHeadTo) % T, o = i % kHeadTo;
+    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * OW * T - 1);
+    const int c = i / (OW * T), t = (i / OW) % T, o = i % OW;
     const float w = W[((size_t)min(o, To - 1) * T + t) * C + c0 + min(c, cn - 1)];
     wv[k] = (c < cn && o < To) ? w : 0.f;
   }
   const int n = blockIdx.x * kBlock + threadIdx.x;
   const float* src = dout + ((size_t)b * N + min(n, N - 1)) * To;
-  float d[kHeadTo];
+  float d[OW];
 #pragma unroll
-  for (int o = 0; o < kHeadTo; ++o) {
+  for (int o = 0; o < OW; ++o) {
     const float v = src[min(o, To - 1)];
     d[o] = o < To ? v : 0.f;
   }
 #pragma unroll
   for (int k = 0; k < kWn; ++k) {
     const int i = threadIdx.x + k * kBlock;
-    if (i < kHeadCC * kHeadTo * T) (&Wl[0][0][0])[i] = wv[k];
+    if (i < kHeadCC * OW * T) (&Wl[0][0][0])[i] = wv[k];
   }
   __syncthreads();
   // a wave's 64 nodes are 64 consecutive rows of every channel: stored in flat order (rowtile.hpp)
@@ -499,7 +600,7 @@ __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ do
     for (int t = 0; t < T; ++t) {
       v[t] = 0.f;
 #pragma unroll
-      for (int o = 0; o < kHeadTo; ++o) v[t] = fmaf(Wl[c][t][o], d[o], v[t]);
+      for (int o = 0; o < OW; ++o) v[t] = fmaf(Wl[c][t][o], d[o], v[t]);
     }
     rt.store(dx + (((size_t)b * C + c0 + c) * N + n0) * T, nf, v);
   }
@@ -523,23 +624,24 @@ __device__ __forceinline__ float lnh_centre_row(float (&x)[T], float eps) {   //
   return rsqrtf(v * (1.0f / T) + eps);
 }
 
-template <int T>
+template <int T, int OT = 1>
 __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__ dout, const float* __restrict__ W,
                                                        const float* __restrict__ x, const float* __restrict__ lnw,
                                                        float* __restrict__ dx, float* __restrict__ part, int C, int N,
                                                        int To, int Bg, float eps, int relu_mask) {
-  __shared__ __attribute__((aligned(16))) float Wl[kHeadCC][T][kHeadTo];
+  constexpr int OW = kHeadTo * OT;   // OT tiles of 16 outputs, as in k_head_dx
+  __shared__ __attribute__((aligned(16))) float Wl[kHeadCC][T][OW];
   __shared__ float4 tiles[kBlock / kWave][RowTile<T>::kFloat4s];
   __shared__ float red[kBlock / kWave][2 * T];
   const int b = blockIdx.z, ck = blockIdx.y, rel = b / Bg;
   W += (size_t)rel * To * T * C;
   const int c0 = ck * kHeadCC, cn = min(kHeadCC, C - c0);
-  constexpr int kWn = (kHeadCC * kHeadTo * T + kBlock - 1) / kBlock;
+  constexpr int kWn = (kHeadCC * OW * T + kBlock - 1) / kBlock;
   float wv[kWn];
 #pragma unroll
   for (int k = 0; k < kWn; ++k) {   // unconditional, clamped: see k_head_dx
-    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * kHeadTo * T - 1);
-    const int c = i / (kHeadTo * T), t = (i / kHeadTo) % T, o = i % kHeadTo;
+    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * OW * T - 1);
+    const int c = i / (OW * T), t = (i / OW) % T, o = i % OW;
     const float w = W[((size_t)min(o, To - 1) * T + t) * C + c0 + min(c, cn - 1)];
     wv[k] = (c < cn && o < To) ? w : 0.f;
   }
@@ -547,16 +649,16 @@ __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__
   const int nc = min(n, N - 1);
   const bool live = n < N;
   const float* src = dout + ((size_t)b * N + nc) * To;
-  float d[kHeadTo];
+  float d[OW];
 #pragma unroll
-  for (int o = 0; o < kHeadTo; ++o) {
+  for (int o = 0; o < OW; ++o) {
     const float v = src[min(o, To - 1)];
     d[o] = (o < To && live) ? v : 0.f;     // lanes past N: a zero gradient row
   }
 #pragma unroll
   for (int k = 0; k < kWn; ++k) {
     const int i = threadIdx.x + k * kBlock;
-    if (i < kHeadCC * kHeadTo * T) (&Wl[0][0][0])[i] = wv[k];
+    if (i < kHeadCC * OW * T) (&Wl[0][0][0])[i] = wv[k];
   }
   float gw[T], dwa[T], dba[T];
 #pragma unroll
@@ -587,7 +689,7 @@ __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__
     for (int t = 0; t < T; ++t) {   // the weights four at a time (one ds_read_b128 per four FMAs; same order of the sum)
       gv[t] = 0.f;
 #pragma unroll
-      for (int o4 = 0; o4 < kHeadTo / 4; ++o4) {
+      for (int o4 = 0; o4 < OW / 4; ++o4) {
         const float4 w4 = *reinterpret_cast<const float4*>(&Wl[c][t][4 * o4]);
         gv[t] = fmaf(w4.x, d[4 * o4 + 0], gv[t]);
         gv[t] = fmaf(w4.y, d[4 * o4 + 1], gv[t]);
@@ -685,10 +787,75 @@ __global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ do
   }
 }
 
-// the buffer holds the pre-laid-out weights [R,C,T,16] (R <= B, T <= 16); never smaller than the channel-chunk partials
+
+// T_out > 16: k_head_dW with OT tiles of 16 outputs, each x float loaded once for all of them (one MFMA per tile and k-step).
+template <int T, int OT>
+__global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restrict__ dout, const float* __restrict__ x,
+                                                    float* __restrict__ part, int B, int C, int N, int To) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  __shared__ float red[kBlock / kWave][256 * OT];
+  const int c = blockIdx.y, j = blockIdx.x, rel = blockIdx.z;   // B = samples per relation
+  const int b0 = rel * B + (int)((long long)B * j / gridDim.x), b1 = rel * B + (int)((long long)B * (j + 1) / gridDim.x);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int m = lane & 15, kq = lane >> 4;
+  const int mt = min(m, T - 1);
+  const float tmask = m < T ? 1.f : 0.f;
+  int mo[OT];
+  float omask[OT];
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot) {
+    mo[ot] = min(kHeadTo * ot + m, To - 1);
+    omask[ot] = kHeadTo * ot + m < To ? 1.f : 0.f;
+  }
+  constexpr int kWaves = kBlock / kWave;
+  f32x4 acc[OT];
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int b = b0; b < b1; ++b) {
+    // one base pointer per operand and 32-bit element offsets, all loads issued before any use: with a pointer per tile
+    // (and the masks applied inside the load loop) hipcc put an s_waitcnt vmcnt(0) behind every load at OT = 2, 3
+    // (598 us at T_out = 36 against 207 us at 64, where it did not)
+    const float* dsrc = dout + (size_t)b * N * To;
+    const float* xsrc = x + ((size_t)b * C + c) * N * T;
+    for (int s0 = 4 * wave * kTdaUnroll; s0 < N; s0 += 4 * kWaves * kTdaUnroll) {
+      float av[OT][kTdaUnroll], bv[kTdaUnroll];
+#pragma unroll
+      for (int u = 0; u < kTdaUnroll; ++u) {
+        const int nc = min(s0 + 4 * u + kq, N - 1);
+#pragma unroll
+        for (int ot = 0; ot < OT; ++ot) av[ot][u] = dsrc[nc * To + mo[ot]];
+        bv[u] = xsrc[nc * T + mt];
+      }
+#pragma unroll
+      for (int u = 0; u < kTdaUnroll; ++u) {
+        const float keep = s0 + 4 * u + kq < N ? 1.f : 0.f;
+        bv[u] *= keep * tmask;   // a zero x row (or timestep) clears the products of every tile
+#pragma unroll
+        for (int ot = 0; ot < OT; ++ot) av[ot][u] *= omask[ot];
+      }
+#pragma unroll
+      for (int u = 0; u < kTdaUnroll; ++u)
+#pragma unroll
+        for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ot][u], bv[u], acc[ot], 0, 0, 0);
+    }
+  }
+  // D[o = 16 ot + 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order
+#pragma unroll
+  for (int ot = 0; ot < OT; ++ot)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) red[wave][256 * ot + (4 * kq + reg) * 16 + m] = acc[ot][reg];
+  __syncthreads();
+  for (int i = threadIdx.x; i < To * T; i += kBlock) {
+    const int o = i / T, t = i - o * T;
+    const int e = o * 16 + t;   // = 256 (o / 16) + 16 (o % 16) + t
+    part[((((size_t)rel * gridDim.y + c) * gridDim.x + j) * To * T) + i] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+  }
+}
+
+// the buffer holds the pre-laid-out weights [R,C,T,16 OT] (R <= B, T <= 16); never smaller than the channel-chunk partials
 // of the VALU form it was first sized for
 size_t head_fwd_partial_floats(int B, int C, int N, int To) {
-  const size_t old = (size_t)B * cdiv(C, kHeadCC) * N * To, wp = (size_t)B * C * 16 * kHeadTo;
+  const size_t old = (size_t)B * cdiv(C, kHeadCC) * N * To, wp = (size_t)B * C * 16 * kHeadTo * cdiv(To, kHeadTo);
   return old > wp ? old : wp;
 }
 size_t head_dw_partial_floats(int C, int T, int To, int R) { return (size_t)R * C * kHeadChunks * To * T; }
@@ -702,8 +869,69 @@ size_t head_dw_partial_floats(int C, int T, int To, int R) { return (size_t)R * 
     default: return MSGAT_ERR_UNSUPPORTED;      \
   }
 
+// T_out in (16, 64]: OT = ceil(T_out / 16) output tiles; the launchers below keep their T_out <= 16 launches as they were
+// and hand the wider heads to these, which launch the same grids with the OT-tile kernels.
+#define MSGAT_OT_DISPATCH(To, FN, ...)                      \
+  switch (cdiv(To, kHeadTo)) {                              \
+    case 2: return FN<2>(__VA_ARGS__);                      \
+    case 3: return FN<3>(__VA_ARGS__);                      \
+    case 4: return FN<4>(__VA_ARGS__);                      \
+    default: return MSGAT_ERR_UNSUPPORTED;                  \
+  }
+
+template <int OT>
+static int launch_head_fwd_tiles(const float* x, const float* W, const float* bias, float* out, float* part, int B, int C,
+                                 int N, int T, int To, int R, hipStream_t s, int ln, const float* lnw, const float* lnb,
+                                 float eps, float* xn) {
+  const int Bg = B / R;
+  const int total = R * C * T * kHeadTo * OT;
+  if ((size_t)total > head_fwd_partial_floats(B, C, N, To)) return MSGAT_ERR_WORKSPACE;
+  hipLaunchKernelGGL(k_head_wperm<OT>, dim3(cdiv(total, kBlock)), dim3(kBlock), 0, s, W, part, C, T, To, total);
+  MSGAT_CHECK_LAUNCH();
+  dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
+  if (ln) {
+    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd_tiles<TT, true, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, xn));
+  } else {
+    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd_tiles<TT, false, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, nullptr));
+  }
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+template <int OT>
+static int launch_head_dx_tiles(const float* dout, const float* W, float* dx, int B, int C, int N, int T, int To, int R,
+                                hipStream_t s) {
+  const int Bg = B / R;
+  dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
+  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_dx<TT, OT>), grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg));
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+template <int OT>
+static int launch_lnhead_bwd_tiles(const float* dout, const float* W, const float* x, const float* lnw, float* dx,
+                                   float* dlnw, float* dlnb, float* part, int B, int C, int N, int T, int To, int R,
+                                   float eps, int relu_mask, hipStream_t s) {
+  const int Bg = B / R;
+  dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);   // the grid of the T_out <= 16 form: the partials keep their size
+  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_lnhead_bwd<TT, OT>), grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To,
+                                       Bg, eps, relu_mask));
+  MSGAT_CHECK_LAUNCH();
+  return launch_reduce_split(part, R, Bg * (int)grid.y * (int)grid.x, 2 * T, dlnw, T, dlnb, T, s);
+}
+
+template <int OT>
+static int launch_head_dW_tiles(const float* dout, const float* x, float* dWc, float* part, int B, int C, int N, int T,
+                                int To, int R, hipStream_t s) {
+  dim3 grid(kHeadChunks, C, R);
+  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_dW_tiles<TT, OT>), grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To));
+  MSGAT_CHECK_LAUNCH();
+  return launch_reduce_groups(part, R * C, kHeadChunks, To * T, dWc, s);
+}
+
 int launch_head_fwd(const float* x, const float* W, const float* bias, float* out, float* part, int B, int C, int N,
                     int T, int To, int R, hipStream_t s, int ln, const float* lnw, const float* lnb, float eps, float* xn) {
+  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_fwd_tiles, x, W, bias, out, part, B, C, N, T, To, R, s, ln, lnw, lnb, eps, xn);
   // the matrix-core form needs no channel-chunk partials; the buffer holds the weights in staging order
   const int Bg = B / R;
   const int total = R * C * T * kHeadTo;
@@ -722,6 +950,7 @@ int launch_head_fwd(const float* x, const float* W, const float* bias, float* ou
 
 int launch_head_dx(const float* dout, const float* W, float* dx, int B, int C, int N, int T, int To, int R,
                    hipStream_t s) {
+  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dx_tiles, dout, W, dx, B, C, N, T, To, R, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
   MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_head_dx<TT>, grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg));
@@ -737,6 +966,8 @@ size_t lnhead_partial_floats(int B, int C, int N, int T) {
 int launch_lnhead_bwd(const float* dout, const float* W, const float* x, const float* lnw, float* dx, float* dlnw,
                       float* dlnb, float* part, int B, int C, int N, int T, int To, int R, float eps, int relu_mask,
                       hipStream_t s) {
+  if (To > kHeadTo)
+    MSGAT_OT_DISPATCH(To, launch_lnhead_bwd_tiles, dout, W, x, lnw, dx, dlnw, dlnb, part, B, C, N, T, To, R, eps, relu_mask, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
   MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_lnhead_bwd<TT>, grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To, Bg,
@@ -749,6 +980,7 @@ int launch_lnhead_bwd(const float* dout, const float* W, const float* x, const f
 // dWc[c][o][t] (the caller permutes to the convolution's [To][T][1][C] layout)
 int launch_head_dW(const float* dout, const float* x, float* dWc, float* part, int B, int C, int N, int T, int To,
                    int R, hipStream_t s) {
+  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dW_tiles, dout, x, dWc, part, B, C, N, T, To, R, s);
   dim3 grid(kHeadChunks, C, R);
   MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_head_dW<TT>, grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To));
   MSGAT_CHECK_LAUNCH();
