@@ -50,7 +50,8 @@ extern "C" {
 /* 10: + msgat_adjacency_grad{,_workspace_bytes} (the gradient of a dense adjacency that requires grad); nothing else changed.
  *     Later, still 10 (new functions only; no structure, signature or status code changed): + msgat_graph_build_indices
  *     (a structure from CSR index arrays) and msgat_edge_weight_grad{,_workspace_bytes} (the gradient of the stored
- *     values of a sparse adjacency).
+ *     values of a sparse adjacency); + msgat_attention_map, msgat_gacn_backward_edge_grad,
+ *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -289,6 +290,40 @@ size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* shape, const 
 int msgat_edge_weight_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu, const float* dv,
                            int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
                            const float* lse, float* dval, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device: reading the attention (attention.py:34 `att`, :36 `att * adjacency`) ----
+ * msgat_attention_map:  out[g,n,m] = P_g[n,m] = 2^(S_g[n,m] log2 e - lse_g[n]),  S_g = kW_g q_g^T, for every (n, m) of
+ *   every group g < R*Bg: the dense row softmax over all N columns, before the mask.  out [G,N,N] fp32, row-major,
+ *   4 G N^2 bytes (17 GB at G = 64, N = 8192: the caller sizes its batch).  q, kW [G,N,T] and lse [G,N] are what a
+ *   forward saved (msgat_fwd_t, or msgat_stage_scores with the caller's q).  S is the forward's k-ordered fp32 chain on
+ *   v_mfma_f32_16x16x4_f32 (k_adjacency_grad's); from N = 1536 the forward forms lse with split operands
+ *   (msgat_dense_scratch_bytes), whose scores agree with it to fp32 rounding: rows sum to 1 within fp32 accuracy either
+ *   way.  Deterministic; nothing is read back, so it may be captured in a HIP graph.  Needs N*N < 2^31.
+ * msgat_gacn_backward_edge_grad / msgat_attention_backward_edge_grad: msgat_gacn_backward / msgat_attention_backward with
+ *   an extra gradient dE_extra [G,nnz] (CSR order) arriving at E = softmax(S) (.) A itself -- a loss on the returned
+ *   weights.  It is added where g_e = E_e dE_e is formed, g_e = E_e (dE_e + dE_extra_e), and everything downstream (delta,
+ *   the dense column correction, dWg, dq, dx / du, dalpha, dW) follows from g as before.  dE_extra = NULL is exactly the
+ *   function without the suffix (the same launches).  Deterministic and capturable as those.
+ * msgat_edge_softmax_grad:  the adjacency's share of that extra gradient, ADDED to what msgat_adjacency_grad /
+ *   msgat_edge_weight_grad wrote (enqueue it after them on the same stream):
+ *     dadj[v, erow_e, col_e] += sum_{g % n_sets == v} P_g[e] dE_extra[g,e]     (dense [n_sets,N,N]; dval == NULL), or
+ *     dval[e]                += sum_g P_g[e] dE_extra[g,e]                     (sparse values [nnz], CSR order; n_sets 1)
+ *   for the CSR edges e of `graph`; exactly one of dadj / dval is given.  P_g[e] is re-created from q, kW and lse with the
+ *   score sum of msgat_edge_weight_grad (not as E / A, which fails at explicit zeros).  One lane per (edge, set) sums its
+ *   groups in ascending order: deterministic, no atomics, nothing read back.  n_sets as for msgat_adjacency_grad.
+ * T in {4,8,12,16}, else MSGAT_ERR_UNSUPPORTED. */
+int msgat_attention_map(const msgat_shape_t* shape, const float* q, const float* kW, const float* lse, float* out,
+                        void* stream);
+int msgat_gacn_backward_edge_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, const msgat_bwd_t* io,
+                                  const float* dE_extra, void* stream);
+int msgat_attention_backward_edge_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, const float* u,
+                                       const float* dv, int32_t dv_group_channels, const float* q, const float* kW,
+                                       const float* lse, const float* pq, const float* E, const float* Ec,
+                                       const float* Wg, float* du, float* dq, float* dWg, void* workspace,
+                                       size_t workspace_bytes, const float* dE_extra, void* stream);
+int msgat_edge_softmax_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, const float* q, const float* kW,
+                            const float* lse, const float* dE_extra, int32_t n_sets, float* dadj, float* dval,
+                            void* stream);
 
 /* ---- device: the individual stages (exposed for tests, profiling and bench.py) ----
  * Each is what the fused entry points enqueue, in order. */

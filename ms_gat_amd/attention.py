@@ -27,8 +27,10 @@ class GraphAttention(nn.Module):
         self.Wg = nn.Parameter(torch.empty(n_timesteps, n_timesteps))
         self.alpha = nn.Parameter(torch.empty(n_channels))
 
-    def forward(self, signals: torch.Tensor, adjacency: torch.Tensor) -> torch.Tensor:
-        return ops.gacn(signals, self.alpha, self.Wg, None, adjacency)
+    def forward(self, signals: torch.Tensor, adjacency: torch.Tensor, need_weights: bool = False, weights: str = "masked"):
+        """`need_weights=True`: `(output, weights)`, the attention [B,N,N] -- "masked" (`att * adjacency`, sparse COO,
+        differentiable) or "softmax" (`att`, dense, no gradient); see `ops.gacn`."""
+        return ops.gacn(signals, self.alpha, self.Wg, None, adjacency, need_weights=need_weights, weights=weights)
 
     def extra_repr(self) -> str:
         return f"n_channels={self.n_channels}, n_timesteps={self.n_timesteps}"
@@ -48,8 +50,10 @@ class GACN(nn.Module):
         self.gatt = GraphAttention(n_channels=in_channels, n_timesteps=n_timesteps)
         self.W = nn.Parameter(torch.empty(out_channels, in_channels))
 
-    def forward(self, signals: torch.Tensor, adjacency: torch.Tensor) -> torch.Tensor:
-        return ops.gacn(signals, self.gatt.alpha, self.gatt.Wg, self.W, adjacency)
+    def forward(self, signals: torch.Tensor, adjacency: torch.Tensor, need_weights: bool = False, weights: str = "masked"):
+        """`need_weights` / `weights` as in `GraphAttention.forward`."""
+        return ops.gacn(signals, self.gatt.alpha, self.gatt.Wg, self.W, adjacency, need_weights=need_weights,
+                        weights=weights)
 
     def extra_repr(self) -> str:
         return (f"in_channels={self.in_channels}, out_channels={self.out_channels}, "
@@ -83,10 +87,15 @@ class StackedGACN(nn.Module):
             m.W.copy_(torch.stack([g.W for g in gacns]))
         return m.to(g0.W.device)
 
-    def forward(self, signals: torch.Tensor, adjacency) -> torch.Tensor:
+    def forward(self, signals: torch.Tensor, adjacency, need_weights: bool = False, weights: str = "masked"):
+        """`need_weights=True`: `(output, weights)` with weights [R,B,N,N] (see `GraphAttention.forward`)."""
         R, B = signals.shape[:2]
-        z = ops.gacn(signals.reshape(R * B, *signals.shape[2:]), self.alpha, self.Wg, self.W, adjacency)
-        return z.view(R, B, *z.shape[1:])
+        x = signals.reshape(R * B, *signals.shape[2:])
+        if not need_weights:
+            z = ops.gacn(x, self.alpha, self.Wg, self.W, adjacency)
+            return z.view(R, B, *z.shape[1:])
+        z, w = ops.gacn(x, self.alpha, self.Wg, self.W, adjacency, need_weights=True, weights=weights, _lead=(R, B))
+        return z.view(R, B, *z.shape[1:]), w
 
     def extra_repr(self) -> str:
         return (f"n_relations={self.n_relations}, in_channels={self.in_channels}, "

@@ -605,7 +605,8 @@ extern "C" int msgat_attention_bwd_accepts_strided_dv(const msgat_shape_t* sh, c
 static int attention_core_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const BwdPlan& p, char* ws, bool fused,
                                    const float* u, const float* dv, int dv_gs, const float* q, const float* kW,
                                    const float* lse, const float* pq, const float* E, const float* Ec_in, const float* Wg,
-                                   float* du, float* dq, float* dWg, hipStream_t s, ReduceJobs* jobs) {
+                                   float* du, float* dq, float* dWg, hipStream_t s, ReduceJobs* jobs,
+                                   const float* dEx = nullptr) {
   const int G = p.G, Cu = p.Cu, N = sh->N, T = sh->T;
   float* dEp = (float*)(ws + p.off_dEp);
   float* gE = (float*)(ws + p.off_gE);
@@ -627,18 +628,17 @@ static int attention_core_backward(const msgat_shape_t* sh, const msgat_graph_t*
   }
   if (st) return st;
   st = launch_bwd_rows(*gr, dEp, p.nch, fused ? Ecsc : nullptr, direct_c, u, dv, E, q, pq, Wg, gE, delta,
-                       (float*)(ws + p.off_dkW), dq, (float*)(ws + p.off_dwg), dWg, G, sh->Bg, N, T, s, jobs);
+                       (float*)(ws + p.off_dkW), dq, (float*)(ws + p.off_dwg), dWg, G, sh->Bg, N, T, s, jobs, dEx);
   if (st) return st;
   st = launch_bwd_dense_col(*gr, q, kW, lse, delta, gE, dq, G, N, T, s, ws + p.off_dense);
   if (st || fused || du == nullptr) return st;
   return aggregate_cols(sh, gr, Cu, dv, E, Ec, nullptr, nullptr, du, s, nullptr, nullptr, nullptr, Ec_in);
 }
 
-extern "C" int msgat_attention_backward(const msgat_shape_t* shp, const msgat_graph_t* gr, const float* u,
-                                        const float* dv, int32_t dv_group_channels, const float* q, const float* kW,
-                                        const float* lse, const float* pq, const float* E, const float* Ec_in,
-                                        const float* Wg, float* du, float* dq, float* dWg, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
+static int attention_backward(const msgat_shape_t* shp, const msgat_graph_t* gr, const float* u, const float* dv,
+                              int32_t dv_group_channels, const float* q, const float* kW, const float* lse, const float* pq,
+                              const float* E, const float* Ec_in, const float* Wg, float* du, float* dq, float* dWg,
+                              void* workspace, size_t workspace_bytes, const float* dEx, void* stream) {
   int st = check_shape(shp);
   if (st) return st;
   const msgat_shape_t shv = plain_shape(shp);
@@ -651,8 +651,55 @@ extern "C" int msgat_attention_backward(const msgat_shape_t* shp, const msgat_gr
   if (p.total > 0 && (!workspace || workspace_bytes < p.total)) return MSGAT_ERR_WORKSPACE;
   const bool fused = agg_sddmm_fusable(*gr, sh->N, sh->T, sh->C);
   if (dv_group_channels != 0 && (dv_group_channels < sh->C || !fused)) return MSGAT_ERR_SHAPE;  // see ..._accepts_strided_dv
+  if (dEx != nullptr && gr->nnz == 0) dEx = nullptr;   // no edges: nothing for it to reach
   return attention_core_backward(sh, gr, p, (char*)workspace, fused, u, dv, dv_group_channels ? dv_group_channels : sh->C,
-                                 q, kW, lse, pq, E, Ec_in, Wg, du, dq, dWg, (hipStream_t)stream, nullptr);
+                                 q, kW, lse, pq, E, Ec_in, Wg, du, dq, dWg, (hipStream_t)stream, nullptr, dEx);
+}
+
+extern "C" int msgat_attention_backward(const msgat_shape_t* shp, const msgat_graph_t* gr, const float* u,
+                                        const float* dv, int32_t dv_group_channels, const float* q, const float* kW,
+                                        const float* lse, const float* pq, const float* E, const float* Ec_in,
+                                        const float* Wg, float* du, float* dq, float* dWg, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  return attention_backward(shp, gr, u, dv, dv_group_channels, q, kW, lse, pq, E, Ec_in, Wg, du, dq, dWg, workspace,
+                            workspace_bytes, nullptr, stream);
+}
+
+extern "C" int msgat_attention_backward_edge_grad(const msgat_shape_t* shp, const msgat_graph_t* gr, const float* u,
+                                                  const float* dv, int32_t dv_group_channels, const float* q,
+                                                  const float* kW, const float* lse, const float* pq, const float* E,
+                                                  const float* Ec_in, const float* Wg, float* du, float* dq, float* dWg,
+                                                  void* workspace, size_t workspace_bytes, const float* dE_extra,
+                                                  void* stream) {
+  return attention_backward(shp, gr, u, dv, dv_group_channels, q, kW, lse, pq, E, Ec_in, Wg, du, dq, dWg, workspace,
+                            workspace_bytes, dE_extra, stream);
+}
+
+// ---- reading the attention ----------------------------------------------------------------------
+extern "C" int msgat_attention_map(const msgat_shape_t* sh, const float* q, const float* kW, const float* lse, float* out,
+                                   void* stream) {
+  int st = check_shape(sh);
+  if (st) return st;
+  if (!q || !kW || !lse || !out) return MSGAT_ERR_NULL;
+  if ((int64_t)sh->N * sh->N >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;   // as msgat_adjacency_grad
+  return launch_attention_map(q, kW, lse, out, sh->R * sh->Bg, sh->N, sh->T, (hipStream_t)stream);
+}
+
+extern "C" int msgat_edge_softmax_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, const float* q, const float* kW,
+                                       const float* lse, const float* dE_extra, int32_t n_sets, float* dadj, float* dval,
+                                       void* stream) {
+  int st = check_shape(sh);
+  if (st) return st;
+  if (!gr) return MSGAT_ERR_NULL;
+  const int64_t G = (int64_t)sh->R * sh->Bg;
+  if (gr->n_nodes != sh->N || gr->nnz < 0) return MSGAT_ERR_SHAPE;
+  if ((dadj == nullptr) == (dval == nullptr)) return MSGAT_ERR_NULL;           // exactly one target
+  if (n_sets != 1 && n_sets != sh->Bg && n_sets != G) return MSGAT_ERR_SHAPE;
+  if (dval != nullptr && n_sets != 1) return MSGAT_ERR_SHAPE;
+  if (gr->nnz == 0) return MSGAT_OK;
+  if (!q || !kW || !lse || !dE_extra || !gr->erow || !gr->col) return MSGAT_ERR_NULL;
+  return launch_edge_softmax_grad(q, kW, lse, dE_extra, gr->erow, gr->col, dadj ? dadj : dval, dadj != nullptr, (int)G,
+                                  n_sets, sh->N, gr->nnz, sh->T, (hipStream_t)stream);
 }
 
 // The dense column pass of the backward alone (what msgat_attention_backward / msgat_gacn_backward enqueue after the
@@ -859,8 +906,8 @@ extern "C" int msgat_bwd_accepts_strided_dz(const msgat_shape_t* sh, const msgat
   return 0;
 }
 
-extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr,
-                                   const msgat_bwd_t* io, void* stream) {
+static int gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io, const float* dEx,
+                         void* stream) {
   int st = check_shape(sh);
   if (st) return st;
   st = check_graph(sh, gr);
@@ -918,8 +965,9 @@ extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t*
   const bool proj_first = p.mode == MSGAT_MODE_PROJ_FIRST;
   const bool fused = proj_first && agg_sddmm_fusable(*gr, N, T, p.Cu);
   if (strided && p.mode != MSGAT_MODE_AGG_FIRST && !fused) return MSGAT_ERR_SHAPE;  // see msgat_bwd_accepts_strided_dz
+  if (dEx != nullptr && gr->nnz == 0) dEx = nullptr;   // no edges: nothing for it to reach
   st = attention_core_backward(sh, gr, p, ws, fused, u, dv, dzgs, io->q, io->kW, io->lse, io->pq, io->E, io->Ec, io->Wg,
-                               proj_first ? dvb : nullptr, dq, io->dWg, s, &jobs);
+                               proj_first ? dvb : nullptr, dq, io->dWg, s, &jobs, dEx);
   if (st) return st;
 
   if (proj_first) {
@@ -940,6 +988,16 @@ extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t*
     st = launch_chanpair(nullptr, dq, io->x, dap, nullptr, 0, io->dalpha, C, G, Bg, 1, C, P, s, &jobs);
   if (st) return st;
   return launch_reduce_jobs(jobs, s);
+}
+
+extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io,
+                                   void* stream) {
+  return gacn_backward(sh, gr, io, nullptr, stream);
+}
+
+extern "C" int msgat_gacn_backward_edge_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io,
+                                             const float* dE_extra, void* stream) {
+  return gacn_backward(sh, gr, io, dE_extra, stream);
 }
 
 // ---- the gated sum over the components (msgat.py:203-205) --------------------------------------------------------

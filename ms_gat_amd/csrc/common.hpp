@@ -272,6 +272,12 @@ int launch_edge_values(const float* adj, const int* rowptr, const int* col, floa
 size_t adjacency_grad_workspace_bytes(int N, int G, int V);
 int launch_adjacency_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
                           const float* lse, float* dadj, float* ws, int G, int V, int Cu, int N, int T, hipStream_t s);
+// attention_map.hip: out[g,n,m] = 2^(S_g[n,m] log2 e - lse_g[n]) for every (n, m), the dense softmax of every group
+int launch_attention_map(const float* q, const float* kW, const float* lse, float* out, int G, int N, int T, hipStream_t s);
+// attention_map.hip: dst[v, e] (+)= sum_{g % V == v} P_g[e] dEx[g,e] at the CSR edges; dense: dst is [V,N,N] and edge e
+// lands at (erow[e], col[e]), else dst is [V,nnz]
+int launch_edge_softmax_grad(const float* q, const float* kW, const float* lse, const float* dEx, const int* erow,
+                             const int* col, float* dst, bool dense, int G, int V, int N, int nnz, int T, hipStream_t s);
 // edge_weight_grad.hip: dval[e] = sum_g P_g[n_e,m_e] sum_{c,t} dv[g,c,n_e,t] feat[g,c,m_e,t] at the CSR edges (erow, col),
 // deterministic; ws: edge_weight_grad_workspace_bytes(nnz, G) bytes (the per-split partial sums; 0 when not split)
 size_t edge_weight_grad_workspace_bytes(int nnz, int G);
@@ -346,7 +352,7 @@ int bwd_rows_direct_max_channels();
 int launch_bwd_rows(const msgat_graph_t& gr, const float* dEp, int nchunks, const float* Ecsc, int direct_c,
                     const float* u, const float* dv, const float* E, const float* q, const float* pq, const float* Wg,
                     float* gE, float* delta, float* dkW, float* dq, float* dwg_part, float* dWg, int G, int Bg, int N,
-                    int T, hipStream_t s, ReduceJobs* defer = nullptr);
+                    int T, hipStream_t s, ReduceJobs* defer = nullptr, const float* dEx = nullptr);
 // out[r,a,c] = sum_{g in r, p} A(g,a,p) B[g,c,p];  channel a == Ca-1 comes from Aextra[g,p] when given
 size_t chanpair_partial_floats(int G, int Bg, int Ca, int Cb);
 int launch_chanpair(const float* A, const float* Aextra, const float* B, float* part, float* dst0,

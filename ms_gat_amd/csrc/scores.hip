@@ -64,7 +64,56 @@ __global__ __launch_bounds__(kBlock) void k_edge_grad_csc(const float* __restric
   gE[(size_t)g * nnz + dst] = ec * (((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])));
 }
 
+// k_edge_grad / k_edge_grad_csc with a gradient that arrives at E itself (the caller's loss on the attention weights):
+// dEx [G,nnz] in CSR order joins the SDDMM's sum before the multiply, g_e = E_e (dE_e + dEx_e).  Separate kernels, so
+// that the plain ones keep their instruction streams.
+__global__ __launch_bounds__(kBlock) void k_edge_grad_x(const float* __restrict__ dEp, int nchunks,
+                                                        const float* __restrict__ E, const int* __restrict__ epos,
+                                                        int stride, float* __restrict__ gE, int nnz,
+                                                        const float* __restrict__ dEx) {
+  const int g = blockIdx.y;
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  if (e >= nnz) return;
+  const float* p = dEp + (size_t)g * nchunks * stride + (epos != nullptr ? epos[e] : e);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int k = 0;
+  for (; k + 4 <= nchunks; k += 4) {
+    a0 += p[(size_t)(k + 0) * stride];
+    a1 += p[(size_t)(k + 1) * stride];
+    a2 += p[(size_t)(k + 2) * stride];
+    a3 += p[(size_t)(k + 3) * stride];
+  }
+  for (; k < nchunks; ++k) a0 += p[(size_t)k * stride];
+  const size_t i = (size_t)g * nnz + e;
+  gE[i] = E[i] * (((a0 + a1) + (a2 + a3)) + dEx[i]);
+}
 
+// ... in CSC order: the extra gradient is read at the CSR edge cperm[k]
+__global__ __launch_bounds__(kBlock) void k_edge_grad_csc_x(const float* __restrict__ dEp, int nchunks,
+                                                            const float* __restrict__ Ec, const int* __restrict__ cperm,
+                                                            float* __restrict__ gE, int nnz, const float* __restrict__ dEx) {
+  const int g = blockIdx.y;
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nnz) return;
+  const float* p = dEp + (size_t)g * nchunks * nnz + k;
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const float ec = Ec[(size_t)g * nnz + k];
+  const int dst = cperm[k];
+  int c = 0;
+  for (; c + 8 <= nchunks; c += 8) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] += p[(size_t)(c + i) * nnz];
+  }
+  for (; c < nchunks; ++c) a[0] += p[(size_t)c * nnz];
+  const size_t i = (size_t)g * nnz + dst;
+  gE[i] = ec * ((((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]))) + dEx[i]);
+}
+
+
+// DC < 0: the direct form with -DC channels and an extra edge gradient -- a gradient that arrives at E itself (the
+// caller's loss on the attention weights), which the caller has copied into gE [G,nnz] beforehand: dE_e += gE_e before
+// the multiply by E, and g_e then overwrites it (a lane reads and writes only its own row's edges).  With DC = 0 the
+// extra gradient is inside gE already (k_edge_grad_x / k_edge_grad_csc_x).
 template <int T, int DC>
 __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ E,
@@ -73,7 +122,8 @@ __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
     float* gE, float* __restrict__ delta, float* __restrict__ dkW, float* __restrict__ dq,
     float* __restrict__ dwg_part, int Bg, int N, int nnz, int nblk) {
   constexpr int T4 = T / 4;
-  constexpr int DCn = DC > 0 ? DC : 1;
+  constexpr int DCa = DC < 0 ? -DC : DC;
+  constexpr int DCn = DCa > 0 ? DCa : 1;
   __shared__ float qs[kRowBlock * T];
   __shared__ float ds[kRowBlock * T];
   const int g = blockIdx.y;
@@ -90,28 +140,29 @@ __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
     pr[4 * t4 + 0] = v.x; pr[4 * t4 + 1] = v.y; pr[4 * t4 + 2] = v.z; pr[4 * t4 + 3] = v.w;
     dk[4 * t4 + 0] = 0.f; dk[4 * t4 + 1] = 0.f; dk[4 * t4 + 2] = 0.f; dk[4 * t4 + 3] = 0.f;
   }
-  float4 dvr[DCn][T4];  // DC > 0: this row of dv, all DC channels
-  if (DC > 0) {
+  float4 dvr[DCn][T4];  // DCa > 0: this row of dv, all DCa channels
+  if (DCa > 0) {
 #pragma unroll
     for (int c = 0; c < DCn; ++c)
 #pragma unroll
       for (int t4 = 0; t4 < T4; ++t4)
-        dvr[c][t4] = reinterpret_cast<const float4*>(dv + (((size_t)g * DC + c) * N + nc) * T)[t4];
+        dvr[c][t4] = reinterpret_cast<const float4*>(dv + (((size_t)g * DCa + c) * N + nc) * T)[t4];
   }
   // the gradient of one edge coefficient
   auto edge_grad = [&](int e, int ce) -> float {
     float dE;
-    if (DC > 0) {
+    if (DCa > 0) {
       dE = 0.f;
 #pragma unroll
       for (int c = 0; c < DCn; ++c) {
-        const float4* um = reinterpret_cast<const float4*>(u + (((size_t)g * DC + c) * N + ce) * T);
+        const float4* um = reinterpret_cast<const float4*>(u + (((size_t)g * DCa + c) * N + ce) * T);
 #pragma unroll
         for (int t4 = 0; t4 < T4; ++t4) dE = f4dot(dvr[c][t4], um[t4], dE);
       }
     } else {
       return gE[(size_t)g * nnz + e];  // left by k_edge_grad / k_edge_grad_csc
     }
+    if constexpr (DC < 0) dE += gE[(size_t)g * nnz + e];   // the extra edge gradient
     return E[(size_t)g * nnz + e] * dE;
   };
   // dkW[n] = sum_e g_e q[col_e] - delta_n pq[n] = sum_e g_e (q[col_e] - pq[n]): subtracting
@@ -135,7 +186,7 @@ __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
       const float raw = edge_grad(ee[i], cc[i]);
       gg[i] = (e + i < e1) ? raw : 0.f;
     }
-    if (DC > 0) {
+    if (DCa > 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (e + i < e1) gE[(size_t)g * nnz + ee[i]] = gg[i];
@@ -221,31 +272,48 @@ int bwd_rows_direct_max_channels() { return 4; }
 int launch_bwd_rows(const msgat_graph_t& gr, const float* dEp, int nchunks, const float* Ecsc, int direct_c,
                     const float* u, const float* dv, const float* E, const float* q, const float* pq, const float* Wg,
                     float* gE, float* delta, float* dkW, float* dq, float* dwg_part, float* dWg, int G, int Bg, int N,
-                    int T, hipStream_t s, ReduceJobs* defer) {
+                    int T, hipStream_t s, ReduceJobs* defer, const float* dEx) {
   const int nblk = cdiv(N, kRowBlock);
   dim3 grid(nblk, G);
   const bool partials_in_csc = Ecsc != nullptr;
   if (direct_c == 0 && gr.nnz > 0) {
     dim3 ge(cdiv(gr.nnz, kBlock), G);
     if (partials_in_csc) {   // k_agg_sddmm: partials in CSC order; E itself is read at cperm[k] (== Ec[k])
-      hipLaunchKernelGGL(k_edge_grad_csc, ge, dim3(kBlock), 0, s, dEp, nchunks, Ecsc, gr.cperm, gE, gr.nnz);
+      if (dEx != nullptr)
+        hipLaunchKernelGGL(k_edge_grad_csc_x, ge, dim3(kBlock), 0, s, dEp, nchunks, Ecsc, gr.cperm, gE, gr.nnz, dEx);
+      else
+        hipLaunchKernelGGL(k_edge_grad_csc, ge, dim3(kBlock), 0, s, dEp, nchunks, Ecsc, gr.cperm, gE, gr.nnz);
     } else {
       const bool sell = sell_usable(gr.sell_rows, gr.nnz, N, T);
-      hipLaunchKernelGGL(k_edge_grad, ge, dim3(kBlock), 0, s, dEp, nchunks, E, sell ? gr.sell_rows.pos : nullptr,
-                         sell ? gr.sell_rows.n_pos : gr.nnz, gE, gr.nnz);
+      if (dEx != nullptr)
+        hipLaunchKernelGGL(k_edge_grad_x, ge, dim3(kBlock), 0, s, dEp, nchunks, E, sell ? gr.sell_rows.pos : nullptr,
+                           sell ? gr.sell_rows.n_pos : gr.nnz, gE, gr.nnz, dEx);
+      else
+        hipLaunchKernelGGL(k_edge_grad, ge, dim3(kBlock), 0, s, dEp, nchunks, E, sell ? gr.sell_rows.pos : nullptr,
+                           sell ? gr.sell_rows.n_pos : gr.nnz, gE, gr.nnz);
     }
     MSGAT_CHECK_LAUNCH();
+  }
+  if (direct_c > 0 && dEx != nullptr && gr.nnz > 0) {
+    const hipError_t e = hipMemcpyAsync(gE, dEx, sizeof(float) * (size_t)G * gr.nnz, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return MSGAT_ERR_HIP_BASE - (int)e;
   }
 #define MSGAT_ROWS(TT, DC)                                                                                          \
   hipLaunchKernelGGL((k_bwd_rows<TT, DC>), grid, dim3(kRowBlock), 0, s, gr.rowptr, gr.col, E, u, dv, q, pq, Wg, gE,  \
                      delta, dkW, dq, dwg_part, Bg, N, gr.nnz, nblk)
+  // the direct form takes the extra edge gradient through gE (k_bwd_rows<T, -DC>); with DC = 0 it is inside gE already
+#define MSGAT_ROWS_DC(TT, DC)  \
+  if (dEx != nullptr)          \
+    MSGAT_ROWS(TT, -DC);       \
+  else                         \
+    MSGAT_ROWS(TT, DC)
 #define MSGAT_ROWS_T(TT)                        \
   switch (direct_c) {                           \
     case 0: MSGAT_ROWS(TT, 0); break;           \
-    case 1: MSGAT_ROWS(TT, 1); break;           \
-    case 2: MSGAT_ROWS(TT, 2); break;           \
-    case 3: MSGAT_ROWS(TT, 3); break;           \
-    case 4: MSGAT_ROWS(TT, 4); break;           \
+    case 1: MSGAT_ROWS_DC(TT, 1); break;        \
+    case 2: MSGAT_ROWS_DC(TT, 2); break;        \
+    case 3: MSGAT_ROWS_DC(TT, 3); break;        \
+    case 4: MSGAT_ROWS_DC(TT, 4); break;        \
     default: return MSGAT_ERR_UNSUPPORTED;      \
   }
   switch (T) {
@@ -256,6 +324,7 @@ int launch_bwd_rows(const msgat_graph_t& gr, const float* dEp, int nchunks, cons
     default: return MSGAT_ERR_UNSUPPORTED;
   }
 #undef MSGAT_ROWS_T
+#undef MSGAT_ROWS_DC
 #undef MSGAT_ROWS
   MSGAT_CHECK_LAUNCH();
   return launch_reduce_groups_defer(dwg_part, G / Bg, Bg * nblk, T * T, dWg, s, defer);

@@ -359,6 +359,30 @@ class MSGAT(nn.Module):
             out = term if out is None else out + term
         return out
 
+    def attention_maps(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor, weights: str = "masked") -> Dict[str, torch.Tensor]:
+        """The graph attention of every GACN for the inputs of `forward`, keyed by the reference's module names
+        (`tpcs.{r}.tgacns.{l}.gacn`), one [B,N,N] tensor each: "masked" = `att * adjacency` as a sparse COO tensor,
+        "softmax" = `att`, dense (`ops.gacn`'s need_weights).  Runs the forward under torch.no_grad(), on whichever path
+        `forward` takes (stacked or component by component), and returns no prediction."""
+        R, L = len(self.tpcs), len(self.tpcs[0].tgacns)
+        B = X.shape[0]
+        with torch.no_grad(), ops.collect_weights(weights) as seen:
+            stacked_path = self.stack_components and stacked.can_stack(self)
+            self.forward(X, H, D)
+        maps = {}
+        if stacked_path:     # one call per level with R * B groups, relation-major
+            for level, entry in enumerate(seen):
+                for r in range(R):
+                    maps[f"tpcs.{r}.tgacns.{level}.gacn"] = ops.weights_of(entry, weights, (B,), slice(r * B, (r + 1) * B))
+        else:                # one call per (component, level), in that order
+            it = iter(seen)
+            for r, tpc in enumerate(self.tpcs):
+                for level in range(len(tpc.tgacns)):
+                    maps[f"tpcs.{r}.tgacns.{level}.gacn"] = ops.weights_of(next(it), weights, (B,))
+        if len(maps) != sum(len(t.tgacns) for t in self.tpcs) or (stacked_path and len(seen) != L):
+            raise RuntimeError(f"attention_maps: {len(seen)} graph-attention calls for {R} components of {L} blocks")
+        return maps
+
     def reset_parameters(self) -> None:
         """xavier_normal_ for >= 2-D, U(-size0^-1/2, +size0^-1/2) for 1-D, every trainable tensor (msgat.py:206-217)."""
         with torch.no_grad():

@@ -9,6 +9,7 @@ arithmetic step runs in libmsgat_hip.so through the C ABI of include/msgat_hip.h
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Optional
 
 import torch
@@ -125,22 +126,30 @@ class _AdjacencyGrad:
         self.n_sets = 1 if target.dim() == 2 else self.shape[0]
 
     def __call__(self, plan: _GacnPlan, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
-                 stream) -> torch.Tensor:
+                 stream, dE: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`dE` [G,nnz]: the gradient at the returned attention weights (`need_weights`), or None; its share
+        sum_g P_g dE_g is added at the edges by msgat_edge_softmax_grad."""
         L = _lib.lib()
         shape, dev = C.byref(plan.shape), dv.device
+        gstruct = C.byref(plan.gstruct)
         if self.pattern is None:
             dadj = torch.empty((self.n_sets, plan.shape.N, plan.shape.N), device=dev, dtype=torch.float32)
             nbytes = int(L.msgat_adjacency_grad_workspace_bytes(shape, Cu, self.n_sets))
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
             _lib.check(L.msgat_adjacency_grad(shape, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, self.n_sets, _ptr(dadj), _ptr(ws),
                                               nbytes, stream), "msgat_adjacency_grad")
+            if dE is not None:
+                _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), self.n_sets, _ptr(dadj), None,
+                                                     stream), "msgat_edge_softmax_grad")
             return dadj.view(self.shape)
-        gstruct = C.byref(plan.gstruct)
         dval = torch.empty(self.pattern.structure.nnz, device=dev, dtype=torch.float32)
         nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(shape, gstruct, Cu))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
         _lib.check(L.msgat_edge_weight_grad(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dval), _ptr(ws),
                                             nbytes, stream), "msgat_edge_weight_grad")
+        if dE is not None:
+            _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), 1, None, _ptr(dval), stream),
+                       "msgat_edge_softmax_grad")
         dval = self.pattern.to_input_order(dval)
         if self.parts is None:                            # the weight of an edge_adjacency
             return dval
@@ -181,12 +190,81 @@ def _resolve_adjacency(adjacency, device, groups: int, relations: int, n_nodes: 
     return graph, target, route
 
 
+# ---- reading the attention (need_weights) -----------------------------------------------------------------------------
+# The forward keeps E = softmax(S) * A at the edges ([G,nnz], CSR order) and q, kW, lse, from which the dense softmax is
+# re-created (msgat_attention_map).  "masked" hands out a copy of E as a sparse COO tensor on the graph's structure,
+# differentiable (its gradient reaches the backward as an extra edge gradient); "softmax" the dense map, without one.
+
+_WEIGHT_FORMS = ("masked", "softmax")
+
+
+def _check_weights(weights: str) -> str:
+    if weights not in _WEIGHT_FORMS:
+        raise ValueError(f"weights must be 'masked' or 'softmax', got {weights!r}")
+    return weights
+
+
+def _refuse_softmax_grad(*inputs) -> None:
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs):
+        raise ValueError("weights='softmax' has no gradient (the dense map is not differentiable here): ask for "
+                         "weights='masked', whose values carry one, or run the call under torch.no_grad()")
+
+
+def _weight_indices(graph, device, lead) -> torch.Tensor:
+    """[len(lead) + 2, prod(lead) * nnz] int64: the coalesced COO indices of `lead` copies of the graph's edges in CSR
+    (= row-major) order, cached on the structure."""
+    structure = getattr(graph, "structure", graph)
+    cache = structure.__dict__.setdefault("_weight_indices", {})
+    key = (str(device), tuple(lead))
+    idx = cache.get(key)
+    if idx is None:
+        nnz = structure.nnz
+        edges = torch.stack([structure.erow[:nnz].long(), structure.col[:nnz].long()])          # [2,nnz], host
+        G = 1
+        for d in lead:
+            G *= d
+        groups = torch.arange(G).repeat_interleave(nnz)
+        lead_idx, rest = [], groups
+        for d in reversed(lead):
+            lead_idx.insert(0, rest % d)
+            rest = rest // d
+        idx = torch.cat([torch.stack(lead_idx), edges.repeat(1, G)]).to(device)
+        if len(cache) > 16:
+            cache.clear()
+        cache[key] = idx
+    return idx
+
+
+def _weights_out(w: torch.Tensor, graph, weights: str, lead) -> torch.Tensor:
+    """The tensor handed to the caller: the sparse COO [*lead,N,N] of the edge values w [G,nnz] ("masked"), or the dense
+    map w [G,N,N] viewed as [*lead,N,N] ("softmax")."""
+    N = graph.n_nodes
+    if weights == "softmax":
+        return w.view(*lead, N, N)
+    return torch.sparse_coo_tensor(_weight_indices(graph, w.device, lead), w.reshape(-1), (*lead, N, N),
+                                   is_coalesced=True)
+
+
+def _forward_weights(weights, plan: _GacnPlan, nnz: int, buf: torch.Tensor, q: int, kW: int, lse: int,
+                     stream) -> torch.Tensor:
+    """After a forward: E copied out of the saved buffer (an in-place edit by the caller must not reach backward), or the
+    dense softmax map from q, kW, lse."""
+    shape = plan.shape
+    G, N = shape.R * shape.Bg, shape.N
+    if weights == "masked":
+        return buf.narrow(0, plan.offs[4], G * nnz).view(G, nnz).clone()
+    out = torch.empty((G, N, N), device=buf.device, dtype=torch.float32)
+    _lib.check(_lib.lib().msgat_attention_map(C.byref(shape), q, kW, lse, _ptr(out), stream), "msgat_attention_map")
+    return out
+
+
 class _GACNFunction(torch.autograd.Function):
     """x[G,C,N,T], alpha[R,C], Wg[R,T,T], W[R,Co,C] or None -> z[G,Co|C,N,T];  G = R*Bg.  `adj`: the tensor that
     receives the adjacency's gradient and `adj_grad` its route (`_resolve_adjacency`), or None both."""
 
     @staticmethod
-    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj_grad=None, adj=None):   # graph: see graph_for
+    def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj_grad=None, adj=None, weights=None):
+        # graph: see graph_for.  weights: None, or "masked" / "softmax" -- then a second output (see _forward_weights)
         L = _lib.lib()
         dev = x.device
         G, Cin, N, T = x.shape
@@ -225,10 +303,16 @@ class _GACNFunction(torch.autograd.Function):
                 ctx.save_for_backward(x, alpha, Wg, buf, W)
             else:
                 ctx.save_for_backward(x, alpha, Wg, buf)
-        return z
+        if weights is None:
+            return z
+        ctx.set_materialize_grads(False)      # a weights output nobody differentiates arrives as None: the plain backward
+        w = _forward_weights(weights, plan, graph.nnz, buf, q, kW, lse, _stream_handle(dev))
+        if weights == "softmax":
+            ctx.mark_non_differentiable(w)
+        return z, w
 
     @staticmethod
-    def backward(ctx, dz):
+    def backward(ctx, dz, dE=None):
         # All four gradients are computed whatever `ctx.needs_input_grad` says: they are by-products of shared passes, not
         # separate work.  PROJ_FIRST: dW, dalpha AND dx leave ONE launch that reads du, dq and x once
         # (msgat_stage_project_backward); AGG_FIRST: dW rides in the pass that forms dy, dalpha in the transposed aggregate
@@ -245,6 +329,10 @@ class _GACNFunction(torch.autograd.Function):
         q, kW, lse, pq, E, Ec, u = plan.pointers(buf)
         dev = x.device
         shape, gstruct = plan.shape, plan.gstruct
+        if dz is None:                        # only the attention weights reached the loss
+            dz = torch.zeros((x.shape[0], plan.z_channels, shape.N, shape.T), device=dev, dtype=torch.float32)
+        if dE is not None:
+            dE = dE.contiguous()
         # a gradient that arrives as a channel slice dout[:, a:b] of a wider tensor is read in place where the library
         # can (one 98 MB copy less per GACN at PEMSD7 size), copied otherwise
         dz, dz_gs = _sliced_grad(dz, lambda: L.msgat_bwd_accepts_strided_dz(C.byref(shape), C.byref(gstruct)))
@@ -259,10 +347,13 @@ class _GACNFunction(torch.autograd.Function):
         io = _lib.Bwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), q, kW, lse, pq, E, u, _ptr(dz), _ptr(dx), _ptr(dalpha),
                       _ptr(dWg), _ptr(dW), _ptr(ws), ws.numel(), dz_gs, Ec)
         stream = _stream_handle(dev)
-        st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
+        if dE is None:
+            st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
+        else:
+            st = L.msgat_gacn_backward_edge_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dE), stream)
         _lib.check(st, "msgat_gacn_backward")
         if ctx.adj_grad is None:
-            return dx, dalpha, dWg, dW, None, None, None, None
+            return dx, dalpha, dWg, dW, None, None, None, None, None
         Cin = x.shape[1]
         if plan.mode == _lib.MODE_AGG_FIRST:
             dy = torch.empty_like(x)
@@ -274,11 +365,11 @@ class _GACNFunction(torch.autograd.Function):
             Cu, dv, dv_gs, feat = shape.Co, dz, dz_gs, u
         else:
             Cu, dv, dv_gs, feat = Cin, dz, dz_gs, _ptr(x)
-        return dx, dalpha, dWg, dW, None, None, None, ctx.adj_grad(plan, Cu, dv, dv_gs, feat, q, kW, lse, stream)
+        return dx, dalpha, dWg, dW, None, None, None, ctx.adj_grad(plan, Cu, dv, dv_gs, feat, q, kW, lse, stream, dE), None
 
 
 def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[torch.Tensor],
-         adjacency) -> torch.Tensor:
+         adjacency, need_weights: bool = False, weights: str = "masked", _lead=None):
     """Graph attention (+ channel projection when `W` is given) over R stacked relations.
 
     x [R*Bg, C, N, T] (relation-major), alpha [R,C], Wg [R,T,T], W [R,Co,C] or None,
@@ -293,10 +384,18 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
     the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync): fine for small graphs in eager mode,
     but it cannot be captured in a HIP graph and costs N^2.  For learned edge weights at scale or under capture use
     `edge_adjacency(crow, col, weight)`, whose gradient reaches `weight` directly, dense [nnz].
+    `need_weights=True` returns `(output, weights)` with the attention of every group, [R*Bg,N,N]:
+    weights="masked" is the reference's `att * adjacency` (attention.py:36) as a coalesced sparse COO tensor on the
+    graph's structure in row-major order (a dense adjacency's non-zeros, a sparse one's stored indices, a batched one's
+    union pattern with explicit zeros), differentiable -- a loss on it reaches x, alpha, Wg and the adjacency;
+    weights="softmax" is `att` (attention.py:34), the dense row softmax over all N columns before the mask, without a
+    gradient (a ValueError if grad mode is on and an input requires grad).  `output` is the same either way.
     One relation may come without the leading axis -- alpha [C], Wg [T,T], W [Co,C], the reference's own parameter
     shapes (attention.py:29-30, msgat.py:23): the module classes call it that way, so that no view nodes sit between
     the parameters and the op (three `unsqueeze` forward and three more nodes backward were a sixth of a call's host time).
     """
+    if need_weights and _check_weights(weights) == "softmax":
+        _refuse_softmax_grad(x, alpha, Wg, W, adjacency, getattr(adjacency, "_msgat_edge_weight", None))
     if x.dim() != 4:
         raise ValueError(f"signals must be [batch, channels, nodes, timesteps], got {tuple(x.shape)}")
     _require_device_tensor("signals", x)
@@ -318,14 +417,74 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
             raise ValueError(f"Wg must be [{R},{T},{T}], got {tuple(Wg.shape)}")
         if W is not None and (W.dim() != 3 or W.shape[0] != R or W.shape[2] != Cin):
             raise ValueError(f"W must be [{R},Co,{Cin}], got {tuple(W.shape)}")
+    return _gacn_checked(x, alpha, Wg, W, adjacency, need_weights, weights, _lead or (G,))
+
+
+def _gacn_checked(x, alpha, Wg, W, adjacency, need_weights: bool, weights: str, lead):
+    """gacn after its argument checks; `lead`: the leading shape of the weights ((G,), or (R, Bg) for StackedGACN)."""
+    G, N = x.shape[0], x.shape[2]
     recording = torch.is_grad_enabled()
     graph, adj, adj_grad = _resolve_adjacency(adjacency, x.device, G, alpha.shape[0] if alpha.dim() == 2 else 1, N, recording)
-    return _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj_grad, adj)
+    if not need_weights:
+        sink = _sink_slot.sink
+        if sink is None:
+            return _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj_grad, adj)
+        z, w = _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj_grad, adj, sink.form)
+        sink.append(w, graph)
+        return z
+    z, w = _GACNFunction.apply(x, alpha, Wg, W, graph, recording, adj_grad, adj, weights)
+    return z, _weights_out(w, graph, weights, lead)
 
 
-def graph_attention(x, alpha, Wg, adjacency):
+class _WeightSink(list):
+    """What `collect_weights` records: (weights [G,nnz] or [G,N,N], graph) of every graph-attention call, in order."""
+
+    def __init__(self, form: str):
+        super().__init__()
+        self.form = form
+
+    def append(self, w, graph):
+        super().append((w, graph))
+
+
+class _SinkSlot(threading.local):
+    sink: Optional[_WeightSink] = None
+
+
+_sink_slot = _SinkSlot()      # per thread: a collection in one thread changes no call of another
+
+
+class collect_weights:
+    """Within this context every `gacn` / `attention_core` call of the current thread also records its attention weights
+    (`weights` as for need_weights) in the list it yields, in call order, while returning only its output: how
+    `MSGAT.attention_maps` reads the attention of every block on either evaluation path.  Meanwhile those calls run their
+    autograd Function with the weights as a second output (its gradient None unless used): recorded "masked" weights
+    stay differentiable under grad mode, "softmax" ones never are.  `weights_of(entry, form, lead)` turns an entry into
+    the caller's tensor.  Not re-entrant; calls in other threads are not affected."""
+
+    def __init__(self, weights: str = "masked"):
+        self.form = _check_weights(weights)
+
+    def __enter__(self) -> _WeightSink:
+        if _sink_slot.sink is not None:
+            raise RuntimeError("collect_weights is not re-entrant")
+        _sink_slot.sink = _WeightSink(self.form)
+        return _sink_slot.sink
+
+    def __exit__(self, *exc):
+        _sink_slot.sink = None
+        return False
+
+
+def weights_of(entry, form: str, lead, groups: slice = slice(None)):
+    """The caller's weights tensor [*lead,N,N] of a `collect_weights` entry, restricted to `groups`."""
+    w, graph = entry
+    return _weights_out(w[groups], graph, form, lead)
+
+
+def graph_attention(x, alpha, Wg, adjacency, need_weights: bool = False, weights: str = "masked"):
     """`GraphAttention.forward` (attention.py:32-36) for R stacked relations."""
-    return gacn(x, alpha, Wg, None, adjacency)
+    return gacn(x, alpha, Wg, None, adjacency, need_weights=need_weights, weights=weights)
 
 
 class _LayerNormTFunction(torch.autograd.Function):
@@ -1201,7 +1360,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
     msgat_attention_backward)."""
 
     @staticmethod
-    def forward(ctx, u, q, Wg, graph, recording: bool = True, adj_grad=None, adj=None):   # see _GACNFunction
+    def forward(ctx, u, q, Wg, graph, recording: bool = True, adj_grad=None, adj=None, weights=None):   # see _GACNFunction
         L = _lib.lib()
         u, q, Wg = u.contiguous(), q.contiguous(), Wg.contiguous()
         G, Cu, N, T = u.shape
@@ -1225,31 +1384,50 @@ class _AttentionCoreFunction(torch.autograd.Function):
         if need_bwd:
             ctx.plan, ctx.adj_grad = plan, adj_grad
             ctx.save_for_backward(u, q, Wg, buf)
-        return z
+        if weights is None:
+            return z
+        ctx.set_materialize_grads(False)
+        w = _forward_weights(weights, plan, graph.nnz, buf, _ptr(q), kW, lse, stream)
+        if weights == "softmax":
+            ctx.mark_non_differentiable(w)
+        return z, w
 
     @staticmethod
-    def backward(ctx, dz):
+    def backward(ctx, dz, dE=None):
         L = _lib.lib()
         u, q, Wg, buf = ctx.saved_tensors
         plan = ctx.plan
         _, kW, lse, pq, E, Ec, _ = plan.pointers(buf)
         shape, gstruct = C.byref(plan.shape), C.byref(plan.gstruct)
+        if dz is None:                        # only the attention weights reached the loss
+            dz = torch.zeros_like(u)
+        if dE is not None:
+            dE = dE.contiguous()
         dz, dz_gs = _sliced_grad(dz, lambda: L.msgat_attention_bwd_accepts_strided_dv(shape, gstruct))
         du, dq, dWg = torch.empty_like(u), torch.empty_like(q), torch.empty_like(Wg)
         if plan.bwd_bytes is None:
             plan.bwd_bytes = max(int(L.msgat_attention_bwd_workspace_bytes(shape, gstruct)), 256)
         ws = torch.empty(plan.bwd_bytes, device=u.device, dtype=torch.uint8)
         stream = _stream_handle(u.device)
-        st = L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
-                                        _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
+        if dE is None:
+            st = L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
+                                            _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
+        else:
+            st = L.msgat_attention_backward_edge_grad(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec,
+                                                      _ptr(Wg), _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(),
+                                                      _ptr(dE), stream)
         _lib.check(st, "msgat_attention_backward")
-        dadj = None if ctx.adj_grad is None else ctx.adj_grad(plan, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, stream)
-        return du, dq, dWg, None, None, None, dadj
+        dadj = None if ctx.adj_grad is None else ctx.adj_grad(plan, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, stream,
+                                                              dE)
+        return du, dq, dWg, None, None, None, dadj, None
 
 
-def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency) -> torch.Tensor:
+def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency, need_weights: bool = False,
+                   weights: str = "masked"):
     """Graph attention on already projected features `u` [G,Cu,N,T] with pooled signals `q` [G,N,T].  `adjacency` as in
-    `gacn`, its gradient included."""
+    `gacn`, its gradient included; `need_weights` / `weights` as in `gacn`."""
+    if need_weights and _check_weights(weights) == "softmax":
+        _refuse_softmax_grad(u, q, Wg, adjacency, getattr(adjacency, "_msgat_edge_weight", None))
     _require_device_tensor("features", u)
     _require_device_tensor("pooled signals", q, u.device)
     _require_device_tensor("Wg", Wg, u.device)
@@ -1258,7 +1436,15 @@ def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency
         raise ValueError(f"attention_core: u {tuple(u.shape)}, q {tuple(q.shape)}, Wg {tuple(Wg.shape)}")
     recording = torch.is_grad_enabled()
     graph, adj, adj_grad = _resolve_adjacency(adjacency, u.device, G, Wg.shape[0], N, recording)
-    return _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj_grad, adj)
+    if not need_weights:
+        sink = _sink_slot.sink
+        if sink is None:
+            return _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj_grad, adj)
+        z, w = _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj_grad, adj, sink.form)
+        sink.append(w, graph)
+        return z
+    z, w = _AttentionCoreFunction.apply(u, q, Wg, graph, recording, adj_grad, adj, weights)
+    return z, _weights_out(w, graph, weights, (G,))
 
 
 # ---- the tiny attention matrices of a MEAM block, one launch each way ----------------------------------------------
