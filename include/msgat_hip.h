@@ -51,7 +51,8 @@ extern "C" {
  *     Later, still 10 (new functions only; no structure, signature or status code changed): + msgat_graph_build_indices
  *     (a structure from CSR index arrays) and msgat_edge_weight_grad{,_workspace_bytes} (the gradient of the stored
  *     values of a sparse adjacency); + msgat_attention_map, msgat_gacn_backward_edge_grad,
- *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights).
+ *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights);
+ *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -290,6 +291,25 @@ size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* shape, const 
 int msgat_edge_weight_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu, const float* dv,
                            int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
                            const float* lse, float* dval, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- device: gradient of the stored values of a per-sample sparse adjacency (one structure, n_sets value sets) ----
+ *   dval[v,e] = sum_{g : g % n_sets == v} P_g[n_e,m_e] (H_g[n_e,m_e] + dE_extra[g,e])   for the CSR edges e, in CSR order
+ * msgat_edge_weight_grad with the sum over the groups cut at the value sets of msgat_graph_t.val_sets: n_sets = Bg (sample
+ * b's values are shared by its R relations, whose gradients add in ascending g) or R*Bg (one set per group); n_sets = 1
+ * is msgat_edge_weight_grad followed by msgat_edge_softmax_grad.  dval is [n_sets,nnz].  dv / dv_group_channels / feat /
+ * Cu exactly as for msgat_edge_weight_grad.  dE_extra [G,nnz] (CSR order) or NULL: the gradient arriving at the returned
+ * attention weights (msgat_*_backward_edge_grad), whose share P_g dE_extra is added here, where P is formed anyway.  P is
+ * re-created with the forward's score sum, not as E / A (explicit zeros).  The graph's `val` is not read.
+ * Deterministic: every (v,e) has one owner that adds its groups in ascending order, no atomics; nothing is read back, so
+ * it may be captured in a HIP graph.  workspace: msgat_edge_weight_grad_sets_workspace_bytes() bytes, 256-byte aligned
+ * (0 unless n_sets = 1).  T in {4,8,12,16} and Cu <= 256, else MSGAT_ERR_UNSUPPORTED; n_sets not in {1, Bg, R*Bg}, Cu <= 0
+ * or graph->n_nodes != N is MSGAT_ERR_SHAPE.  A graph without edges launches nothing. */
+size_t msgat_edge_weight_grad_sets_workspace_bytes(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu,
+                                                   int32_t n_sets);
+int msgat_edge_weight_grad_sets(const msgat_shape_t* shape, const msgat_graph_t* graph, int32_t Cu, const float* dv,
+                                int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
+                                const float* lse, const float* dE_extra, int32_t n_sets, float* dval, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* ---- device: reading the attention (attention.py:34 `att`, :36 `att * adjacency`) ----
  * msgat_attention_map:  out[g,n,m] = P_g[n,m] = 2^(S_g[n,m] log2 e - lse_g[n]),  S_g = kW_g q_g^T, for every (n, m) of

@@ -81,6 +81,9 @@ _PROTOTYPES = {
     "msgat_edge_weight_grad_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32]),
     "msgat_edge_weight_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32, C.c_void_p, C.c_int32]
                                + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    "msgat_edge_weight_grad_sets_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32, C.c_int32]),
+    "msgat_edge_weight_grad_sets": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.c_int32, C.c_void_p, C.c_int32]
+                                    + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "msgat_attention_map": (C.c_int, [C.POINTER(Shape)] + [C.c_void_p] * 5),
     "msgat_gacn_backward_edge_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.POINTER(Bwd), C.c_void_p, C.c_void_p]),
     "msgat_attention_backward_edge_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_int32] +

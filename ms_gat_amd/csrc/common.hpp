@@ -284,6 +284,11 @@ size_t edge_weight_grad_workspace_bytes(int nnz, int G);
 int launch_edge_weight_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
                             const float* lse, const int* erow, const int* col, float* dval, float* ws, int G, int Cu,
                             int N, int nnz, int T, hipStream_t s);
+// edge_weight_grad_sets.hip: dval[v,e] = sum_{g % V == v} P_g[e] (H_g[e] + dEx[g,e]) at the CSR edges, V > 1 value sets
+// (dEx [G,nnz] or nullptr); one owner per (v,e), no workspace, deterministic
+int launch_edge_weight_grad_sets(const float* dv, int dv_group_channels, const float* feat, const float* q,
+                                 const float* kW, const float* lse, const float* dEx, const int* erow, const int* col,
+                                 float* dval, int G, int V, int Cu, int N, int nnz, int T, hipStream_t s);
 int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse,
                   float* pq, float* E, float* Ec, int G, int Bg, int N, int T, hipStream_t s,
                   const float* x = nullptr, const float* alpha = nullptr, int C = 0, float* qout = nullptr,

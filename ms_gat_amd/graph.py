@@ -1,5 +1,6 @@
 """Sensor-graph adjacency: the sym-normalised dense matrix the reference uses and the
-CSR/CSC form the HIP kernels walk; `BatchedGraph` is a per-sample adjacency [V,N,N] on one shared structure.
+CSR/CSC form the HIP kernels walk; `BatchedGraph` is a per-sample adjacency [V,N,N] on one shared structure, `SparseSets`
+the same for a sparse [V,N,N] tensor (a weight per stored edge and per sample).
 
 Reference: /root/reference/src/data_loader.py:49-66 builds `D^-1/2 (A + I) D^-1/2` from a
 csv edge list; src/models/msgat.py:190 keeps it as a frozen parameter `adj`;
@@ -293,7 +294,7 @@ class _TensorCache(_Lru):
 _CACHE_MAX = 16
 _GRAPHS = _TensorCache(_CACHE_MAX)     # dense [N,N] / [1,N,N] -> (SparseGraph, a copy of the contents)
 _BATCHED = _TensorCache(_CACHE_MAX)    # dense [V,N,N], sell -> BatchedGraph
-_SPARSE = _TensorCache(_CACHE_MAX)     # index tensors of a sparse adjacency, layout, N, sell -> (SparsePattern, indices)
+_SPARSE = _TensorCache(_CACHE_MAX)     # index tensors of a sparse adjacency, layout, N, sell -> (SparsePattern | SparseSets, indices)
 _PATTERNS = _Lru(8)                    # CSR content (N, sell, rowptr, col) -> SparsePattern
 
 
@@ -517,12 +518,13 @@ def sparse_parts(adjacency: torch.Tensor):
 
 
 def check_sparse_adjacency(adjacency: torch.Tensor) -> None:
-    if adjacency.dim() != 2 or adjacency.shape[0] != adjacency.shape[1]:
-        raise ValueError(f"a sparse adjacency must be one [n_nodes, n_nodes] matrix, got {tuple(adjacency.shape)}: "
-                         "batched sparse adjacencies [B, n_nodes, n_nodes] are not supported (pass a dense [B,N,N] "
-                         "or a BatchedGraph)")
-    if adjacency.layout == torch.sparse_coo and adjacency.sparse_dim() != 2:
-        raise ValueError("a sparse COO adjacency must have two sparse dimensions and no dense ones")
+    """One [N,N] matrix, or [V,N,N] (one value set per sample or per group: `sparse_sets_of`)."""
+    if adjacency.dim() not in (2, 3) or adjacency.shape[-2] != adjacency.shape[-1]:
+        raise ValueError(f"a sparse adjacency must be [n_nodes, n_nodes] or [V, n_nodes, n_nodes], got "
+                         f"{tuple(adjacency.shape)}")
+    if adjacency.layout == torch.sparse_coo and adjacency.sparse_dim() != adjacency.dim():
+        raise ValueError(f"a sparse COO adjacency {tuple(adjacency.shape)} must have {adjacency.dim()} sparse dimensions and "
+                         "no dense ones (hybrid tensors are not supported)")
     if adjacency.dtype != torch.float32:
         raise TypeError(f"a sparse adjacency must be float32 (the reference arithmetic type), got {adjacency.dtype}")
 
@@ -533,6 +535,9 @@ def sparse_pattern_of(adjacency: torch.Tensor, sell: str = "auto") -> SparsePatt
     and a pattern with the same content is shared.  The first sight inside a HIP-graph capture raises, as graph_of
     does."""
     check_sparse_adjacency(adjacency)
+    if adjacency.dim() != 2:
+        raise ValueError(f"sparse_pattern_of takes one [n_nodes, n_nodes] matrix, got {tuple(adjacency.shape)}: a sparse "
+                         "[V, n_nodes, n_nodes] adjacency goes through sparse_sets_of")
     layout, idx, _ = sparse_parts(adjacency)
     n = int(adjacency.shape[0])
     key = (layout, n, sell) + tuple(_tensor_key(t) for t in idx)
@@ -552,15 +557,161 @@ def sparse_pattern_of(adjacency: torch.Tensor, sell: str = "auto") -> SparsePatt
     return _SPARSE.remember(key, adjacency, (_pattern(crow, col, n, sell), idx))[0]
 
 
+# ---- a per-sample sparse adjacency [V,N,N]: a weight per stored edge and per sample ---------------------------------------
+# torch COO with three sparse dimensions, torch batched CSR, or `ops.edge_adjacency` with weights [V,nnz] on one shared
+# pattern.  The samples may store different patterns: the structure is the union of their stored indices (built from the
+# indices, never from an [N,N] mask) and a flat map sends stored entry k to v_k * nnz_union + (its position in the union's
+# CSR order).  Values are scattered through it into a [V,nnz_union] buffer (an edge a sample lacks stays an explicit 0,
+# E = 0 there) and the [V,nnz_union] gradient is gathered back through it -- torch ops on V * nnz floats.  When the map
+# is the identity (one shared pattern in the library's order) and the values are contiguous, they are read where they
+# are: no copy.  Built once per index tensors and cached like `sparse_pattern_of`.
+
+class SparseSets:
+    """The union structure (`pattern`, a `SparsePattern` shared by content), the number of value sets `n_sets` and
+    `flat` [entries] int64 (host), the position of every stored entry in the [n_sets, nnz_union] value buffer -- None
+    when it is the identity."""
+
+    def __init__(self, pattern: SparsePattern, n_sets: int, flat):
+        self.pattern, self.structure, self.n_sets, self.flat = pattern, pattern.structure, int(n_sets), flat
+        self._dev = {}
+        self._views = _Lru(8)     # (values address, device) -> ValuedGraph read in place
+
+    def _on(self, device):
+        """(flat map on the device, this object's value buffer [n_sets, nnz_union] with its ValuedGraph)"""
+        key = str(device)
+        if key not in self._dev:
+            buf = torch.zeros((self.n_sets, max(self.structure.nnz, 1)), dtype=torch.float32, device=device)
+            flat = None if self.flat is None else self.flat.to(device)
+            self._dev[key] = (flat, buf, ValuedGraph(self.structure, buf, self.n_sets))
+        return self._dev[key]
+
+    def graph(self, values: torch.Tensor) -> ValuedGraph:
+        """The graph whose `val` holds `values` (the stored entries in input order, on their device) as [n_sets,
+        nnz_union] in library order.  Read in place when they already are that, else scattered into this object's own
+        buffer, which outlives the call and is re-filled at every replay of a captured step; the entries nobody stores
+        were zeroed when it was made and are never written."""
+        nnz = self.structure.nnz
+        entries = self.n_sets * nnz if self.flat is None else self.flat.numel()
+        if values.numel() != entries:    # the library is handed a bare pointer: it must cover every entry it reads
+            raise ValueError(f"the sparse adjacency stores {values.numel()} values ({tuple(values.shape)}), its indices "
+                             f"{entries} entries ({self.n_sets} value set(s))")
+        if self.flat is None and values.is_contiguous():
+            key = (values.data_ptr(), str(values.device))
+            g = self._views.hit(key)
+            return g if g is not None else self._views.put(key, ValuedGraph(self.structure, values.data_ptr(), self.n_sets))
+        flat, buf, g = self._on(values.device)
+        if nnz:
+            if flat is None:
+                buf[:, :nnz].copy_(values.reshape(self.n_sets, nnz))
+            else:
+                buf.view(-1).index_copy_(0, flat, values.reshape(-1))
+        return g
+
+    def to_input_order(self, dval: torch.Tensor) -> torch.Tensor:
+        """A gradient [n_sets, nnz_union] in library order -> one per stored entry, in the caller's order (flat)."""
+        if self.flat is None:
+            return dval.reshape(-1)
+        return dval.reshape(-1).index_select(0, self._on(dval.device)[0])
+
+
+def sparse_sets_parts(adjacency: torch.Tensor):
+    """(layout, index tensors, values) of a sparse [V,N,N] adjacency: "edge" for an `ops.edge_adjacency` (its one shared
+    (crow, col) and the weight [V,nnz] itself), else as `sparse_parts`."""
+    edge = adjacency.__dict__.get("_msgat_edge_index")
+    if edge is not None:
+        return "edge", edge, adjacency.__dict__["_msgat_edge_weight"].detach()
+    return sparse_parts(adjacency)
+
+
+def _union_map(v: np.ndarray, i: np.ndarray, j: np.ndarray, V: int, n: int, sell: str):
+    """(SparsePattern of the union of the stored (i, j), flat map entry -> v * nnz_union + position) from host arrays"""
+    for name, a, hi in (("sample", v, V), ("row", i, n), ("column", j, n)):
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= hi):
+            raise ValueError(f"malformed sparse adjacency indices: a {name} index outside [0, {hi})")
+    edges, pos = np.unique(i * n + j, return_inverse=True)           # sorted: the union in row-major = CSR order
+    crow = _row_pointers(torch.from_numpy(edges // n), n)
+    pattern = _pattern(crow, torch.from_numpy(edges % n), n, sell)
+    if not pattern.identity:             # sorted unique (row, column) keys are CSR order
+        raise _lib.MsgatError("the union of a sparse adjacency's patterns did not come out in CSR order")
+    flat = v * max(len(edges), 1) + pos.reshape(-1)
+    if np.unique(flat).size != flat.size:
+        raise ValueError("malformed sparse adjacency indices: an entry is stored twice in one sample")
+    return pattern, flat
+
+
+def sparse_sets_of(adjacency: torch.Tensor, sell: str = "auto") -> SparseSets:
+    """Cached `SparseSets` of a (coalesced, if COO) sparse [V,N,N] adjacency, after `check_sparse_adjacency`.  Keyed on
+    the index tensors' storage address, shape and version; the first sight of a key reads the indices back and builds
+    the union and the flat map, and a union with the same content shares its structure.  The first sight inside a
+    HIP-graph capture raises, as graph_of does."""
+    check_sparse_adjacency(adjacency)
+    layout, idx, values = sparse_sets_parts(adjacency)
+    if adjacency.dim() != 3:
+        raise ValueError(f"sparse_sets_of takes a [V, n_nodes, n_nodes] adjacency, got {tuple(adjacency.shape)}")
+    V, n = int(adjacency.shape[0]), int(adjacency.shape[1])
+    key = ("sets", layout, V, n, sell) + tuple(_tensor_key(t) for t in idx)
+    hit, _ = _SPARSE.lookup(key, adjacency)
+    if hit is not None:
+        return hit[0]
+    if _capturing(adjacency):
+        raise _not_cached("the structure of this sparse adjacency is not cached yet")
+    host = [t.detach().to(device="cpu", dtype=torch.int64) for t in idx]
+    if layout == "edge":                 # one shared pattern; the order inside a row may not be the library's
+        crow, col = host
+        if crow.dim() != 1 or crow.numel() != n + 1 or col.dim() != 1 or int(crow[-1]) != col.numel():
+            raise ValueError("malformed sparse adjacency indices")
+        pattern = _pattern(crow, col, n, sell)
+        nnz = pattern.structure.nnz
+        flat = None if pattern.identity else \
+            (torch.arange(V)[:, None] * max(nnz, 1) + pattern._inverse[None, :]).reshape(-1)
+        sets = SparseSets(pattern, V, flat)
+    else:
+        if layout == "csr":
+            crow, col = (t.numpy() for t in host)
+            if crow.shape != (V, n + 1) or col.ndim != 2 or (crow[:, 0] != 0).any() or (crow[:, -1] != col.shape[1]).any() \
+                    or (np.diff(crow, axis=1) < 0).any():
+                raise ValueError("malformed sparse adjacency indices")
+            v = np.repeat(np.arange(V), col.shape[1])
+            i = np.repeat(np.tile(np.arange(n), V), np.diff(crow, axis=1).reshape(-1))
+            j = col.reshape(-1)
+        else:
+            v, i, j = host[0].numpy()
+        pattern, flat = _union_map(v, i, j, V, n, sell)
+        identity = flat.size == V * pattern.structure.nnz and bool((flat == np.arange(flat.size)).all())
+        sets = SparseSets(pattern, V, None if identity else torch.from_numpy(flat))
+    # the index tensors stay alive with the entry: their addresses cannot be reused under it
+    return _SPARSE.remember(key, adjacency, (sets, idx))[0]
+
+
+def _check_sets(adjacency, groups: int, relations: int) -> None:
+    V, Bg = int(adjacency.shape[0]), groups // relations
+    if V not in (1, Bg, groups):
+        raise ValueError(f"a batched sparse adjacency {tuple(adjacency.shape)} needs a leading size in {sorted({1, Bg, groups})} "
+                         f"for signals of {groups} groups ({relations} relation(s) x {Bg} samples)")
+
+
+def sparse_graph_for(adjacency: torch.Tensor, groups: int, relations: int):
+    """(graph, its `SparsePattern` or `SparseSets`) of a sparse adjacency (coalesced, if COO): [N,N] with `val` at its
+    values on the device, [V,N,N] with V in {1, groups / relations, groups} as its union structure and value sets."""
+    check_sparse_adjacency(adjacency)
+    if adjacency.dim() == 2:
+        pattern = sparse_pattern_of(adjacency)
+        return pattern.graph(sparse_parts(adjacency)[2].detach()), pattern
+    _check_sets(adjacency, groups, relations)
+    sets = sparse_sets_of(adjacency)
+    return sets.graph(sparse_sets_parts(adjacency)[2].detach()), sets
+
+
 def graph_for(adjacency, groups: int, relations: int):
     """What the ops hand the library for `adjacency`: a prebuilt SparseGraph / BatchedGraph as it is; a dense [N,N] or
     [1,N,N] through graph_of; [V,N,N] with V = groups / relations (one set per sample) or V = groups (one per group)
-    through batched_graph_of; a sparse [N,N] as its cached pattern with `val` at its values on the device.  The graph
+    through batched_graph_of; a sparse [N,N] as its cached pattern with `val` at its values on the device, a sparse
+    [V,N,N] as the union of its samples' patterns with V value sets (`sparse_sets_of`).  The graph
     carries no gradient: a batched adjacency that requires grad while autograd records is refused here.  The ops
     (`ops.gacn`, `graph_attention`, `attention_core`, and the modules on them) accept one -- they route its gradient
     themselves."""
     if is_sparse_adjacency(adjacency):
-        return sparse_pattern_of(adjacency).graph(sparse_parts(adjacency)[2].detach())
+        return sparse_graph_for(adjacency, groups, relations)[0]
     return _dense_graph_for(adjacency, groups, relations, refuse_grad=True)
 
 

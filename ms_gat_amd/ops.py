@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import stream_handle as _stream_handle
-from .graph import _dense_graph_for, is_sparse_adjacency, sparse_parts, sparse_pattern_of
+from .graph import _dense_graph_for, is_sparse_adjacency, sparse_graph_for, sparse_parts
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -103,13 +103,24 @@ def edge_adjacency(crow: torch.Tensor, col: torch.Tensor, weight: torch.Tensor) 
     """The sparse CSR adjacency [N,N] (N = crow.numel() - 1) with a learned weight per stored edge: `weight` [nnz] in
     the order of (crow, col), columns ascending inside a row.  Every op and module accepts it like any sparse adjacency;
     `weight` gets its gradient at the stored edges, dense [nnz], and a step that uses it can be captured in a HIP graph.
+    `weight` [V,nnz] is a weight per stored edge AND per sample on the one shared pattern, V = the batch size (shared
+    by stacked relations) or relations x batch size: a batched CSR adjacency [V,N,N] whose `to_dense()` is the
+    reference's `adjacency: [..., n_nodes, n_nodes]`; `weight` gets a dense [V,nnz] gradient in its own order
+    (msgat_edge_weight_grad_sets).  Contiguous weights in the library's order are read where they are.
 
     It is a CSR tensor on weight.detach() (the same storage: the library reads the current weights) that carries the
     weight itself as an attribute.  The ops hand the weight to their autograd Function: torch's own backward of
     `sparse_csr_tensor` densifies the gradient to [N,N] and reads the pattern back with `nonzero` (a host sync, which a
     captured step cannot contain), and adding the sparse gradients of several layers needs the pattern on the host too."""
     n = crow.numel() - 1
-    adj = torch.sparse_csr_tensor(crow, col, weight.detach(), (n, n))
+    if weight.dim() == 2:
+        V = weight.shape[0]
+        adj = torch.sparse_csr_tensor(crow.expand(V, -1), col.expand(V, -1), weight.detach(), (V, n, n))
+        adj._msgat_edge_index = (crow, col)       # the pattern is keyed on these, not on torch's expanded views
+    elif weight.dim() == 1:
+        adj = torch.sparse_csr_tensor(crow, col, weight.detach(), (n, n))
+    else:
+        raise ValueError(f"weight must be [nnz] or [V, nnz], got {tuple(weight.shape)}")
     adj._msgat_edge_weight = weight
     return adj
 
@@ -119,11 +130,13 @@ class _AdjacencyGrad:
     `(dv, feat, Cu)` and the saved q, kW, lse, it returns the gradient in the caller's own shape and layout: dense [N,N] /
     [V,N,N] from msgat_adjacency_grad (n_sets = V, the convention of `val_sets`), or from msgat_edge_weight_grad at the
     stored edges of a sparse adjacency -- dense [nnz] in input order for an `edge_adjacency` weight, else a sparse tensor
-    with the caller's layout and indices.  Either is enqueued on `stream` after the backward of the other inputs."""
+    with the caller's layout and indices; a sparse [V,N,N] adjacency (`pattern` a `graph.SparseSets`) from
+    msgat_edge_weight_grad_sets at every sample's stored entries, [V,nnz] for an `edge_adjacency` weight.  Either is
+    enqueued on `stream` after the backward of the other inputs."""
 
-    def __init__(self, target: torch.Tensor, pattern=None, parts=None):
-        self.shape, self.pattern, self.parts = tuple(target.shape), pattern, parts
-        self.n_sets = 1 if target.dim() == 2 else self.shape[0]
+    def __init__(self, target: torch.Tensor, pattern=None, parts=None, sets: bool = False):
+        self.shape, self.pattern, self.parts, self.sets = tuple(target.shape), pattern, parts, sets
+        self.n_sets = pattern.n_sets if sets else (1 if target.dim() == 2 else self.shape[0])
 
     def __call__(self, plan: _GacnPlan, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
                  stream, dE: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -142,6 +155,8 @@ class _AdjacencyGrad:
                 _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), self.n_sets, _ptr(dadj), None,
                                                      stream), "msgat_edge_softmax_grad")
             return dadj.view(self.shape)
+        if self.sets:
+            return self._sets(plan, Cu, dv, dv_gs, feat, q, kW, lse, stream, dE)
         dval = torch.empty(self.pattern.structure.nnz, device=dev, dtype=torch.float32)
         nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(shape, gstruct, Cu))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
@@ -158,11 +173,29 @@ class _AdjacencyGrad:
             return torch.sparse_csr_tensor(idx[0], idx[1], dval, self.shape)
         return torch.sparse_coo_tensor(idx[0], dval, self.shape, is_coalesced=True)
 
+    def _sets(self, plan, Cu, dv, dv_gs, feat, q, kW, lse, stream, dE):
+        """One value set per sample or per group: one launch for dval [n_sets, nnz_union] (the share of `dE` folded in),
+        gathered back to the stored entries."""
+        L = _lib.lib()
+        shape, gstruct, dev = C.byref(plan.shape), C.byref(plan.gstruct), dv.device
+        dval = torch.empty((self.n_sets, max(self.pattern.structure.nnz, 1)), device=dev, dtype=torch.float32)
+        nbytes = int(L.msgat_edge_weight_grad_sets_workspace_bytes(shape, gstruct, Cu, self.n_sets))
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+        _lib.check(L.msgat_edge_weight_grad_sets(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dE), self.n_sets,
+                                                 _ptr(dval), _ptr(ws), nbytes, stream), "msgat_edge_weight_grad_sets")
+        dval = self.pattern.to_input_order(dval[:, : self.pattern.structure.nnz])
+        if self.parts is None:                            # the weight [V,nnz] of an edge_adjacency
+            return dval.view(self.shape)
+        layout, idx = self.parts
+        if layout == "csr":
+            return torch.sparse_csr_tensor(idx[0], idx[1], dval.view(idx[1].shape), self.shape)
+        return torch.sparse_coo_tensor(idx[0], dval, self.shape, is_coalesced=True)
+
 
 def _resolve_adjacency(adjacency, device, groups: int, relations: int, n_nodes: int, recording: bool):
     """(graph, the tensor that receives the adjacency's gradient or None, its `_AdjacencyGrad` or None) for an op on
-    signals of `groups` groups on `device`.  A sparse [N,N] adjacency must be one float32 matrix on the signals' device
-    (`graph.sparse_pattern_of` checks it); an uncoalesced COO tensor is coalesced (duplicates add, as in torch.sparse) --
+    signals of `groups` groups on `device`.  A sparse adjacency must be float32, [N,N] or [V,N,N], on the signals' device
+    (`graph.sparse_graph_for` checks it); an uncoalesced COO tensor is coalesced (duplicates add, as in torch.sparse) --
     by an autograd op, so its gradient still reaches the caller's values.  For an `edge_adjacency` the tensor that
     receives the gradient is its weight.  Anything else goes through `graph.graph_for`."""
     target = route = None
@@ -171,14 +204,14 @@ def _resolve_adjacency(adjacency, device, groups: int, relations: int, n_nodes: 
             raise ValueError(f"the sparse adjacency is on {adjacency.device}, the signals on {device}")
         if adjacency.layout == torch.sparse_coo and not adjacency.is_coalesced():
             adjacency = adjacency.coalesce()
-        pattern = sparse_pattern_of(adjacency)
-        layout, idx, values = sparse_parts(adjacency)
-        graph = pattern.graph(values.detach())
+        graph, pattern = sparse_graph_for(adjacency, groups, relations)
         if recording:
-            target = adjacency.__dict__.get("_msgat_edge_weight", adjacency)
+            weight = adjacency.__dict__.get("_msgat_edge_weight")
+            target = adjacency if weight is None else weight
             if target.requires_grad:
-                parts = None if target.dim() == 1 else (layout, tuple(t.detach() for t in idx))   # dim 1: a weight
-                route = _AdjacencyGrad(target, pattern, parts)
+                layout, idx, _ = sparse_parts(adjacency)
+                parts = None if weight is not None else (layout, tuple(t.detach() for t in idx))
+                route = _AdjacencyGrad(target, pattern, parts, sets=adjacency.dim() == 3)
             else:
                 target = None
     else:
