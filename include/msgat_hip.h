@@ -52,7 +52,8 @@ extern "C" {
  *     (a structure from CSR index arrays) and msgat_edge_weight_grad{,_workspace_bytes} (the gradient of the stored
  *     values of a sparse adjacency); + msgat_attention_map, msgat_gacn_backward_edge_grad,
  *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights);
- *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]).
+ *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]);
+ *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -344,6 +345,37 @@ int msgat_attention_backward_edge_grad(const msgat_shape_t* shape, const msgat_g
 int msgat_edge_softmax_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, const float* q, const float* kW,
                             const float* lse, const float* dE_extra, int32_t n_sets, float* dadj, float* dval,
                             void* stream);
+
+/* ---- device: a gradient that arrives at the dense softmax map (attention.py:34 `att` as an autograd tensor) ----
+ * msgat_softmax_map_grad:  given dP [G,N,N] fp32 row-major, the gradient at P = msgat_attention_map's output,
+ *     r[n]  = sum_m P[n,m] dP[n,m]          dS = P (.) (dP - r)          dkW = dS q
+ *     dq_add[g,n,:]  += (dS^T kW + dkW Wg^T)[n,:]            ([G,N,T])
+ *     dWg_add[rel]   += sum_{g in rel} q_g^T dkW_g            ([R,T,T]; relation rel owns the groups rel*Bg .. rel*Bg+Bg-1)
+ *   both ADDED to what the buffers hold (zero them, or enqueue this after the backward that wrote them); both targets are
+ *   required.  `att` depends neither on the projection W nor on the adjacency, so nothing else receives a
+ *   share.  q, kW [G,N,T], lse [G,N] are what the forward saved, Wg [R,T,T] its parameter.  P is never stored: two passes
+ *   re-create it per 16 x 16 tile with msgat_attention_map's k-ordered fp32 chain on v_mfma_f32_16x16x4_f32 (at every N,
+ *   also where the forward formed lse with split operands) and form their products with q / kW on the matrix core; dP
+ *   is read twice (once along rows for r and dkW, once for the column product), 8 G N^2 bytes in all.  sum_m P q is
+ *   recomputed from the same P, not taken from the forward's pq, so that dS sums to zero along a row with the P in use.
+ *   Deterministic: every output element has one owner that adds in a fixed order, no atomics; repeated runs are
+ *   bit-identical.  Nothing is read back, so it may be captured in a HIP graph.  workspace:
+ *   msgat_softmax_map_grad_workspace_bytes() bytes (dkW, r and the dWg partials), 256-byte aligned.
+ *   Wg and dq_add are read / updated in 16-byte pieces and must be 16-byte aligned, else MSGAT_ERR_SHAPE (dP is read in
+ *   16-byte pieces when it is so aligned and N % 4 == 0, in 4-byte pieces otherwise; q, kW, lse need 4 bytes).
+ *   T in {4,8,12,16} and N*N < 2^31, else MSGAT_ERR_UNSUPPORTED; a short or misaligned workspace is MSGAT_ERR_WORKSPACE.
+ * msgat_gacn_backward_map_grad:  msgat_gacn_backward with dq_map [G,N,T] and dWg_map [R,T,T], both required,
+ *   the two outputs of msgat_softmax_map_grad on zeroed buffers: dq_map is added to the pooled signal's gradient where the
+ *   dense column pass has finished it, so that dx and dalpha carry it, dWg_map to dWg after its reduction.  The backward
+ *   is linear in its upstream gradients: no existing kernel changes.  The dense map is a weights form of its own, so no
+ *   edge gradient dE_extra arrives together with it.  For the attention core dq and dWg are outputs of msgat_attention_backward: enqueue
+ *   msgat_softmax_map_grad on them afterwards. */
+size_t msgat_softmax_map_grad_workspace_bytes(const msgat_shape_t* shape);
+int msgat_softmax_map_grad(const msgat_shape_t* shape, const float* q, const float* kW, const float* lse, const float* Wg,
+                           const float* dP, float* dq_add, float* dWg_add, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int msgat_gacn_backward_map_grad(const msgat_shape_t* shape, const msgat_graph_t* graph, const msgat_bwd_t* io,
+                                 const float* dq_map, const float* dWg_map, void* stream);
 
 /* ---- device: the individual stages (exposed for tests, profiling and bench.py) ----
  * Each is what the fused entry points enqueue, in order. */

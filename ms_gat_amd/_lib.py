@@ -90,6 +90,9 @@ _PROTOTYPES = {
                                            [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p, C.c_void_p]),
     "msgat_edge_softmax_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph)] + [C.c_void_p] * 4 +
                                 [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "msgat_softmax_map_grad_workspace_bytes": (C.c_size_t, [C.POINTER(Shape)]),
+    "msgat_softmax_map_grad": (C.c_int, [C.POINTER(Shape)] + [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    "msgat_gacn_backward_map_grad": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.POINTER(Bwd)] + [C.c_void_p] * 3),
     "msgat_edge_scratch_floats": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),
     "msgat_gacn_forward": (C.c_int, [C.POINTER(Shape), C.POINTER(Graph), C.POINTER(Fwd), C.c_void_p]),
     "msgat_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Shape), C.POINTER(Graph)]),

@@ -29,7 +29,8 @@ class GraphAttention(nn.Module):
 
     def forward(self, signals: torch.Tensor, adjacency: torch.Tensor, need_weights: bool = False, weights: str = "masked"):
         """`need_weights=True`: `(output, weights)`, the attention [B,N,N] -- "masked" (`att * adjacency`, sparse COO,
-        differentiable) or "softmax" (`att`, dense, no gradient); see `ops.gacn`."""
+        differentiable), "softmax" (`att`, dense, no gradient) or "softmax_grad" (the same dense `att` as an autograd
+        tensor: a loss on it reaches the signals, alpha and Wg); see `ops.gacn`."""
         return ops.gacn(signals, self.alpha, self.Wg, None, adjacency, need_weights=need_weights, weights=weights)
 
     def extra_repr(self) -> str:
@@ -51,7 +52,8 @@ class GACN(nn.Module):
         self.W = nn.Parameter(torch.empty(out_channels, in_channels))
 
     def forward(self, signals: torch.Tensor, adjacency: torch.Tensor, need_weights: bool = False, weights: str = "masked"):
-        """`need_weights` / `weights` as in `GraphAttention.forward`."""
+        """`need_weights` / `weights` as in `GraphAttention.forward`; a loss on a "softmax_grad" map does not reach W,
+        on which `att` does not depend."""
         return ops.gacn(signals, self.gatt.alpha, self.gatt.Wg, self.W, adjacency, need_weights=need_weights,
                         weights=weights)
 
@@ -88,7 +90,8 @@ class StackedGACN(nn.Module):
         return m.to(g0.W.device)
 
     def forward(self, signals: torch.Tensor, adjacency, need_weights: bool = False, weights: str = "masked"):
-        """`need_weights=True`: `(output, weights)` with weights [R,B,N,N] (see `GraphAttention.forward`)."""
+        """`need_weights=True`: `(output, weights)` with weights [R,B,N,N] in any of the three forms "masked", "softmax"
+        and "softmax_grad" (see `GraphAttention.forward`)."""
         R, B = signals.shape[:2]
         x = signals.reshape(R * B, *signals.shape[2:])
         if not need_weights:

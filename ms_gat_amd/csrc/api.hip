@@ -741,6 +741,25 @@ extern "C" int msgat_edge_softmax_grad(const msgat_shape_t* sh, const msgat_grap
                                   n_sets, sh->N, gr->nnz, sh->T, (hipStream_t)stream);
 }
 
+extern "C" size_t msgat_softmax_map_grad_workspace_bytes(const msgat_shape_t* sh) {
+  if (check_shape(sh) != MSGAT_OK) return 0;
+  return align256(map_grad_workspace_bytes(sh->R * sh->Bg, sh->N, sh->T));
+}
+
+extern "C" int msgat_softmax_map_grad(const msgat_shape_t* sh, const float* q, const float* kW, const float* lse,
+                                      const float* Wg, const float* dP, float* dq_add, float* dWg_add, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  int st = check_shape(sh);
+  if (st) return st;
+  if (!q || !kW || !lse || !Wg || !dP || !dq_add || !dWg_add || !workspace) return MSGAT_ERR_NULL;
+  if ((((uintptr_t)Wg | (uintptr_t)dq_add) & 15) != 0) return MSGAT_ERR_SHAPE;   // read / updated in 16-byte pieces
+  if ((int64_t)sh->N * sh->N >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;   // as msgat_attention_map
+  if (workspace_bytes < map_grad_workspace_bytes(sh->R * sh->Bg, sh->N, sh->T)) return MSGAT_ERR_WORKSPACE;
+  if (((uintptr_t)workspace & 255) != 0) return MSGAT_ERR_WORKSPACE;
+  return launch_map_grad(q, kW, lse, Wg, dP, dq_add, dWg_add, (float*)workspace, sh->R * sh->Bg, sh->Bg, sh->N, sh->T,
+                         (hipStream_t)stream);
+}
+
 // The dense column pass of the backward alone (what msgat_attention_backward / msgat_gacn_backward enqueue after the
 // edge gradients): dq[g,m] -= sum_n P[n,m] delta[n] kW[n] (+ the CSC edge term from gE).  For profiling and bench.py.
 extern "C" int msgat_stage_dense_column_pass(const msgat_shape_t* sh, const msgat_graph_t* gr, const float* q,
@@ -945,8 +964,10 @@ extern "C" int msgat_bwd_accepts_strided_dz(const msgat_shape_t* sh, const msgat
   return 0;
 }
 
+// dq_map [G,N,T] and dWg_map [R,T,T] (both or neither): what msgat_softmax_map_grad left of a gradient at the dense map; they
+// are added where dq and dWg are final, by launches of their own -- without them the launches are the plain ones
 static int gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io, const float* dEx,
-                         void* stream) {
+                         void* stream, const float* dq_map = nullptr, const float* dWg_map = nullptr) {
   int st = check_shape(sh);
   if (st) return st;
   st = check_graph(sh, gr);
@@ -1008,11 +1029,21 @@ static int gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const
   st = attention_core_backward(sh, gr, p, ws, fused, u, dv, dzgs, io->q, io->kW, io->lse, io->pq, io->E, io->Ec, io->Wg,
                                proj_first ? dvb : nullptr, dq, io->dWg, s, &jobs, dEx);
   if (st) return st;
+  if (dq_map != nullptr) {
+    st = launch_add_into(dq, dq_map, (size_t)G * P, s);
+    if (st) return st;
+  }
+  // the queued reductions, then the map's share of dWg on top of the reduced sum
+  auto finish = [&]() {
+    const int fs = launch_reduce_jobs(jobs, s);
+    if (fs || dWg_map == nullptr) return fs;
+    return launch_add_into(io->dWg, dWg_map, (size_t)sh->R * T * T, s);
+  };
 
   if (proj_first) {
     st = project_backward(dvb, dq, io->x, io->W, io->alpha, cpp, io->dW, io->dalpha, io->dx, G, Bg, C, Co, P, s, jobs);
     if (st) return st;
-    return launch_reduce_jobs(jobs, s);
+    return finish();
   }
   // PLAIN / AGG_FIRST:  dx = E^T dv + alpha (x) dq;  dalpha = dq . x -- from the same kernel (it holds dq) when the
   // slab form runs and the input has few channels, from a contraction otherwise
@@ -1026,7 +1057,7 @@ static int gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const
   else
     st = launch_chanpair(nullptr, dq, io->x, dap, nullptr, 0, io->dalpha, C, G, Bg, 1, C, P, s, &jobs);
   if (st) return st;
-  return launch_reduce_jobs(jobs, s);
+  return finish();
 }
 
 extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io,
@@ -1037,6 +1068,12 @@ extern "C" int msgat_gacn_backward(const msgat_shape_t* sh, const msgat_graph_t*
 extern "C" int msgat_gacn_backward_edge_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io,
                                              const float* dE_extra, void* stream) {
   return gacn_backward(sh, gr, io, dE_extra, stream);
+}
+
+extern "C" int msgat_gacn_backward_map_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, const msgat_bwd_t* io,
+                                            const float* dq_map, const float* dWg_map, void* stream) {
+  if (!dq_map || !dWg_map) return MSGAT_ERR_NULL;
+  return gacn_backward(sh, gr, io, nullptr, stream, dq_map, dWg_map);
 }
 
 // ---- the gated sum over the components (msgat.py:203-205) --------------------------------------------------------

@@ -278,6 +278,12 @@ int launch_attention_map(const float* q, const float* kW, const float* lse, floa
 // lands at (erow[e], col[e]), else dst is [V,nnz]
 int launch_edge_softmax_grad(const float* q, const float* kW, const float* lse, const float* dEx, const int* erow,
                              const int* col, float* dst, bool dense, int G, int V, int N, int nnz, int T, hipStream_t s);
+// attention_map.hip: the gradient dP [G,N,N] at the dense map, carried to q and Wg: dq_add[g,n,:] += dS^T kW + dkW Wg^T and
+// dWg_add[rel] += sum_{g in rel} q^T dkW; ws: map_grad_workspace_bytes() bytes (dkW, r, partials)
+size_t map_grad_workspace_bytes(int G, int N, int T);
+int launch_map_grad(const float* q, const float* kW, const float* lse, const float* Wg, const float* dP, float* dq_add,
+                    float* dWg_add, float* ws, int G, int Bg, int N, int T, hipStream_t s);
+int launch_add_into(float* dst, const float* src, size_t n, hipStream_t s);   // dst[i] += src[i]
 // edge_weight_grad.hip: dval[e] = sum_g P_g[n_e,m_e] sum_{c,t} dv[g,c,n_e,t] feat[g,c,m_e,t] at the CSR edges (erow, col),
 // deterministic; ws: edge_weight_grad_workspace_bytes(nnz, G) bytes (the per-split partial sums; 0 when not split)
 size_t edge_weight_grad_workspace_bytes(int nnz, int G);

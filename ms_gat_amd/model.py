@@ -362,8 +362,9 @@ class MSGAT(nn.Module):
     def attention_maps(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor, weights: str = "masked") -> Dict[str, torch.Tensor]:
         """The graph attention of every GACN for the inputs of `forward`, keyed by the reference's module names
         (`tpcs.{r}.tgacns.{l}.gacn`), one [B,N,N] tensor each: "masked" = `att * adjacency` as a sparse COO tensor,
-        "softmax" = `att`, dense (`ops.gacn`'s need_weights).  Runs the forward under torch.no_grad(), on whichever path
-        `forward` takes (stacked or component by component), and returns no prediction."""
+        "softmax" = `att`, dense (`ops.gacn`'s need_weights; "softmax_grad" is accepted and gives the same tensors).  Runs the
+        forward under torch.no_grad(), on whichever path `forward` takes (stacked or component by component), and returns
+        no prediction; for maps that carry a gradient wrap a grad-enabled `forward` in `ops.collect_weights("softmax_grad")`."""
         R, L = len(self.tpcs), len(self.tpcs[0].tgacns)
         B = X.shape[0]
         with torch.no_grad(), ops.collect_weights(weights) as seen:

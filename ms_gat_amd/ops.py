@@ -226,15 +226,33 @@ def _resolve_adjacency(adjacency, device, groups: int, relations: int, n_nodes: 
 # ---- reading the attention (need_weights) -----------------------------------------------------------------------------
 # The forward keeps E = softmax(S) * A at the edges ([G,nnz], CSR order) and q, kW, lse, from which the dense softmax is
 # re-created (msgat_attention_map).  "masked" hands out a copy of E as a sparse COO tensor on the graph's structure,
-# differentiable (its gradient reaches the backward as an extra edge gradient); "softmax" the dense map, without one.
+# differentiable (its gradient reaches the backward as an extra edge gradient); "softmax" the dense map, without one;
+# "softmax_grad" the same dense map from the same launch, differentiable: its gradient dP [G,N,N] goes through
+# msgat_softmax_map_grad, which re-creates P from q, kW, lse and hands back its share of dq and dWg (`_map_grad`).
 
-_WEIGHT_FORMS = ("masked", "softmax")
+_WEIGHT_FORMS = ("masked", "softmax", "softmax_grad")
 
 
 def _check_weights(weights: str) -> str:
     if weights not in _WEIGHT_FORMS:
-        raise ValueError(f"weights must be 'masked' or 'softmax', got {weights!r}")
+        raise ValueError(f"weights must be 'masked' or 'softmax' (or 'softmax_grad', the dense map with a gradient), "
+                         f"got {weights!r}")
     return weights
+
+
+def _map_grad(plan: _GacnPlan, q: int, kW: int, lse: int, Wg: torch.Tensor, dP: torch.Tensor, dq_add: torch.Tensor,
+              dWg_add: torch.Tensor, stream) -> None:
+    """dq_add [G,N,T] += and dWg_add [R,T,T] += the share of the gradient dP [G,N,N] at the dense map
+    (msgat_softmax_map_grad), enqueued on `stream`."""
+    L = _lib.lib()
+    shape = C.byref(plan.shape)
+    dP = dP.contiguous()
+    if dP.data_ptr() % 16:                  # the row pass reads 16-byte pieces when N % 4 == 0
+        dP = dP.clone()
+    nbytes = int(L.msgat_softmax_map_grad_workspace_bytes(shape))
+    ws = torch.empty(max(nbytes, 256), device=dP.device, dtype=torch.uint8)
+    _lib.check(L.msgat_softmax_map_grad(shape, q, kW, lse, _ptr(Wg), _ptr(dP), _ptr(dq_add), _ptr(dWg_add), _ptr(ws),
+                                        ws.numel(), stream), "msgat_softmax_map_grad")
 
 
 def _refuse_softmax_grad(*inputs) -> None:
@@ -270,9 +288,9 @@ def _weight_indices(graph, device, lead) -> torch.Tensor:
 
 def _weights_out(w: torch.Tensor, graph, weights: str, lead) -> torch.Tensor:
     """The tensor handed to the caller: the sparse COO [*lead,N,N] of the edge values w [G,nnz] ("masked"), or the dense
-    map w [G,N,N] viewed as [*lead,N,N] ("softmax")."""
+    map w [G,N,N] viewed as [*lead,N,N] ("softmax", "softmax_grad")."""
     N = graph.n_nodes
-    if weights == "softmax":
+    if weights != "masked":
         return w.view(*lead, N, N)
     return torch.sparse_coo_tensor(_weight_indices(graph, w.device, lead), w.reshape(-1), (*lead, N, N),
                                    is_coalesced=True)
@@ -297,7 +315,8 @@ class _GACNFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj_grad=None, adj=None, weights=None):
-        # graph: see graph_for.  weights: None, or "masked" / "softmax" -- then a second output (see _forward_weights)
+        # graph: see graph_for.  weights: None, or "masked" / "softmax" / "softmax_grad" -- then a second output (see
+        # _forward_weights), whose gradient arrives in backward as `dE`: [G,nnz] at the edges, or [G,N,N] at the dense map
         L = _lib.lib()
         dev = x.device
         G, Cin, N, T = x.shape
@@ -331,7 +350,7 @@ class _GACNFunction(torch.autograd.Function):
         _lib.check(st, "msgat_gacn_forward")
 
         if need_bwd:
-            ctx.plan, ctx.has_W, ctx.adj_grad = plan, W is not None, adj_grad
+            ctx.plan, ctx.has_W, ctx.adj_grad, ctx.weights = plan, W is not None, adj_grad, weights
             if W is not None:
                 ctx.save_for_backward(x, alpha, Wg, buf, W)
             else:
@@ -364,6 +383,9 @@ class _GACNFunction(torch.autograd.Function):
         shape, gstruct = plan.shape, plan.gstruct
         if dz is None:                        # only the attention weights reached the loss
             dz = torch.zeros((x.shape[0], plan.z_channels, shape.N, shape.T), device=dev, dtype=torch.float32)
+        dP = None
+        if dE is not None and ctx.weights == "softmax_grad":
+            dP, dE = dE, None                 # the gradient at the dense map: att depends on neither W nor the adjacency
         if dE is not None:
             dE = dE.contiguous()
         # a gradient that arrives as a channel slice dout[:, a:b] of a wider tensor is read in place where the library
@@ -380,7 +402,15 @@ class _GACNFunction(torch.autograd.Function):
         io = _lib.Bwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), q, kW, lse, pq, E, u, _ptr(dz), _ptr(dx), _ptr(dalpha),
                       _ptr(dWg), _ptr(dW), _ptr(ws), ws.numel(), dz_gs, Ec)
         stream = _stream_handle(dev)
-        if dE is None:
+        if dP is not None:
+            # its share of dq and dWg first, on zeroed buffers; the backward adds them where dq and dWg are final, so that
+            # dx and dalpha carry the map's term as well
+            dq_map = torch.zeros((x.shape[0], shape.N, shape.T), device=dev, dtype=torch.float32)
+            dWg_map = torch.zeros_like(Wg)
+            _map_grad(plan, q, kW, lse, Wg, dP, dq_map, dWg_map, stream)
+            st = L.msgat_gacn_backward_map_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dq_map),
+                                                _ptr(dWg_map), stream)
+        elif dE is None:
             st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
         else:
             st = L.msgat_gacn_backward_edge_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dE), stream)
@@ -422,7 +452,11 @@ def gacn(x: torch.Tensor, alpha: torch.Tensor, Wg: torch.Tensor, W: Optional[tor
     graph's structure in row-major order (a dense adjacency's non-zeros, a sparse one's stored indices, a batched one's
     union pattern with explicit zeros), differentiable -- a loss on it reaches x, alpha, Wg and the adjacency;
     weights="softmax" is `att` (attention.py:34), the dense row softmax over all N columns before the mask, without a
-    gradient (a ValueError if grad mode is on and an input requires grad).  `output` is the same either way.
+    gradient (a ValueError if grad mode is on and an input requires grad); weights="softmax_grad" is the same dense
+    map, bit for bit and from the same launch, as an ordinary autograd tensor: a loss on it -- an entropy or sparsity
+    penalty on the rows, supervision against a flow matrix, distillation -- reaches x, alpha and Wg, and neither W nor
+    the adjacency, on which `att` does not depend (msgat_softmax_map_grad re-creates the map from the saved q, kW, lse,
+    so an in-place edit of the returned tensor does not reach backward).  `output` is the same in every form.
     One relation may come without the leading axis -- alpha [C], Wg [T,T], W [Co,C], the reference's own parameter
     shapes (attention.py:29-30, msgat.py:23): the module classes call it that way, so that no view nodes sit between
     the parameters and the op (three `unsqueeze` forward and three more nodes backward were a sixth of a call's host time).
@@ -492,7 +526,9 @@ class collect_weights:
     (`weights` as for need_weights) in the list it yields, in call order, while returning only its output: how
     `MSGAT.attention_maps` reads the attention of every block on either evaluation path.  Meanwhile those calls run their
     autograd Function with the weights as a second output (its gradient None unless used): recorded "masked" weights
-    stay differentiable under grad mode, "softmax" ones never are.  `weights_of(entry, form, lead)` turns an entry into
+    stay differentiable under grad mode, "softmax" ones never are, "softmax_grad" ones are the differentiable dense maps
+    [G,N,N] -- around a grad-enabled `MSGAT.forward`, on the stacked path and the component loop alike, a training step
+    can put a regulariser on the map of every block.  `weights_of(entry, form, lead)` turns an entry into
     the caller's tensor.  Not re-entrant; calls in other threads are not affected."""
 
     def __init__(self, weights: str = "masked"):
@@ -1415,7 +1451,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
         _lib.check(L.msgat_stage_aggregate(shape, gstruct, Cu, _ptr(u), E, _ptr(z), _ptr(scratch), stream),
                    "msgat_stage_aggregate")
         if need_bwd:
-            ctx.plan, ctx.adj_grad = plan, adj_grad
+            ctx.plan, ctx.adj_grad, ctx.weights = plan, adj_grad, weights
             ctx.save_for_backward(u, q, Wg, buf)
         if weights is None:
             return z
@@ -1434,6 +1470,9 @@ class _AttentionCoreFunction(torch.autograd.Function):
         shape, gstruct = C.byref(plan.shape), C.byref(plan.gstruct)
         if dz is None:                        # only the attention weights reached the loss
             dz = torch.zeros_like(u)
+        dP = None
+        if dE is not None and ctx.weights == "softmax_grad":
+            dP, dE = dE, None                 # the gradient at the dense map (see _GACNFunction.backward)
         if dE is not None:
             dE = dE.contiguous()
         dz, dz_gs = _sliced_grad(dz, lambda: L.msgat_attention_bwd_accepts_strided_dv(shape, gstruct))
@@ -1450,6 +1489,8 @@ class _AttentionCoreFunction(torch.autograd.Function):
                                                       _ptr(Wg), _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(),
                                                       _ptr(dE), stream)
         _lib.check(st, "msgat_attention_backward")
+        if dP is not None:                    # dq and dWg are outputs here: the map's share is added to them
+            _map_grad(plan, _ptr(q), kW, lse, Wg, dP, dq, dWg, stream)
         dadj = None if ctx.adj_grad is None else ctx.adj_grad(plan, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, stream,
                                                               dE)
         return du, dq, dWg, None, None, None, dadj, None
@@ -1458,7 +1499,8 @@ class _AttentionCoreFunction(torch.autograd.Function):
 def attention_core(u: torch.Tensor, q: torch.Tensor, Wg: torch.Tensor, adjacency, need_weights: bool = False,
                    weights: str = "masked"):
     """Graph attention on already projected features `u` [G,Cu,N,T] with pooled signals `q` [G,N,T].  `adjacency` as in
-    `gacn`, its gradient included; `need_weights` / `weights` as in `gacn`."""
+    `gacn`, its gradient included; `need_weights` / `weights` as in `gacn` (a loss on a "softmax_grad" map reaches `q`
+    and `Wg`, not `u`)."""
     if need_weights and _check_weights(weights) == "softmax":
         _refuse_softmax_grad(u, q, Wg, adjacency, getattr(adjacency, "_msgat_edge_weight", None))
     _require_device_tensor("features", u)
