@@ -53,7 +53,8 @@ extern "C" {
  *     values of a sparse adjacency); + msgat_attention_map, msgat_gacn_backward_edge_grad,
  *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights);
  *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]);
- *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map).
+ *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map);
+ *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -728,6 +729,34 @@ int msgat_adam_step(float* const* chunk_param, const int64_t* chunk_off, const i
                     void* stream);
 int msgat_gather_scaled(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                         int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream);
+
+/* ---- device: the step tail with missing readings (no counterpart in the reference, whose only mask guards the MAPE's
+ * division, metrics.py:28) ----
+ * An entry of `truth` is VALID when it is not NaN and truth != null_value (PEMS files store 0 for a sensor that was
+ * down); null_value = NaN masks the NaN entries only.  pred, truth [rows, T_out] fp32, rows = B * N, 1 <= T_out <= 64,
+ * rows * T_out <= 2^24 (MSGAT_ERR_UNSUPPORTED beyond either), so every count below is exact in an fp32.
+ * msgat_masked_huber_metrics: one pass over the two tensors and a five-block finish launch, nothing read back:
+ *       valid[0] = the number of valid entries                                                        (fp32, device)
+ *       loss[0]  = sum_valid huber(e) / max(valid, 1),  e = pred - truth, huber as in msgat_huber_metrics   (fp32)
+ *       sums [T_out + 1, 5] fp64 running totals (the caller zeroes them per epoch; may be NULL): row t < T_out +=
+ *           {valid count, sum |e|, 100 sum_{truth > mask_value} |e / truth|, sum e^2, sum huber(e)} over the valid
+ *           entries of horizon t (element i has horizon i mod T_out); row T_out += the same over all horizons.
+ *     A batch without a valid entry gives loss 0 and valid 0.  `partials`: msgat_masked_huber_partial_doubles(rows,
+ *     T_out) doubles.  Fixed summation order (lane order inside a block, block order across blocks, horizon order for
+ *     the last row), no floating-point atomics: bitwise reproducible.
+ * msgat_masked_huber_grad: dpred = dloss[0] * clamp(e, -delta, delta) / max(valid[0], 1) at the valid entries and
+ *     exactly 0 at the others (a NaN of `truth` does not reach dpred).  valid[0] is read from device memory -- what
+ *     msgat_masked_huber_metrics wrote -- so a launch captured in a HIP graph follows the batch of every replay.
+ * msgat_gather_scaled_dev: msgat_gather_scaled with the scale read from device memory (scale[0]; it is also what
+ *     flat[weight_index] receives): a rank's weight in a masked data-parallel step is its batch's valid count. */
+size_t msgat_masked_huber_partial_doubles(int64_t rows, int32_t T_out);
+int msgat_masked_huber_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float delta,
+                               float null_value, float mask_value, double* partials, float* loss, float* valid,
+                               double* sums, void* stream);
+int msgat_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid, int64_t rows,
+                            int32_t T_out, float delta, float null_value, float* dpred, void* stream);
+int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                            int32_t n_chunks, const float* scale, float* flat, int64_t weight_index, void* stream);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,12 @@ _PROTOTYPES = {
     "msgat_adam_chunk_elems": (C.c_int, []),
     "msgat_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]),
     "msgat_gather_scaled": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "msgat_masked_huber_partial_doubles": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "msgat_masked_huber_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_float] * 3
+                                   + [C.c_void_p] * 5),
+    "msgat_masked_huber_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                                            C.c_void_p]),
+    "msgat_gather_scaled_dev": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1145,6 +1145,45 @@ extern "C" int msgat_gather_scaled(const float* const* chunk_src, const int64_t*
                               (hipStream_t)stream);
 }
 
+// ---- step tail with missing readings: masked Huber loss + per-horizon metric sums ------------------------------------
+constexpr int64_t kMaskedMaxEntries = int64_t(1) << 24;   // every count is exact in the fp32 `valid`
+
+static int check_masked(int64_t rows, int32_t T_out, float delta) {
+  if (rows <= 0 || T_out <= 0 || !(delta > 0.f)) return MSGAT_ERR_SHAPE;
+  if (T_out > 64 || rows > kMaskedMaxEntries / T_out) return MSGAT_ERR_UNSUPPORTED;
+  return MSGAT_OK;
+}
+
+extern "C" size_t msgat_masked_huber_partial_doubles(int64_t rows, int32_t T_out) {
+  return check_masked(rows, T_out, 1.f) == MSGAT_OK ? masked_huber_partial_doubles(rows, T_out) : 0;
+}
+
+extern "C" int msgat_masked_huber_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float delta,
+                                          float null_value, float mask_value, double* partials, float* loss,
+                                          float* valid, double* sums, void* stream) {
+  if (!pred || !truth || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_masked(rows, T_out, delta)) return st;
+  return launch_masked_huber_metrics(pred, truth, rows, T_out, delta, null_value, mask_value, partials, loss, valid, sums,
+                                     (hipStream_t)stream);
+}
+
+extern "C" int msgat_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                                       int64_t rows, int32_t T_out, float delta, float null_value, float* dpred,
+                                       void* stream) {
+  if (!pred || !truth || !dloss || !valid || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_masked(rows, T_out, delta)) return st;
+  return launch_masked_huber_grad(pred, truth, dloss, valid, rows, T_out, delta, null_value, dpred, (hipStream_t)stream);
+}
+
+extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                                       int32_t n_chunks, const float* scale, float* flat, int64_t weight_index,
+                                       void* stream) {
+  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
+  if (!chunk_src || !chunk_off || !chunk_len || !scale || !flat) return MSGAT_ERR_NULL;
+  return launch_gather_scaled_dev(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat, weight_index,
+                                  (hipStream_t)stream);
+}
+
 // ---- the tiny attention matrices of a MEAM block ----------------------------------------------------------------
 static int check_small(int32_t G, int32_t R, int32_t T) {
   if (G <= 0 || R <= 0 || G % R) return MSGAT_ERR_SHAPE;

@@ -461,5 +461,13 @@ int launch_adam(float* const* chunk_param, const long long* chunk_off, const int
                 hipStream_t s);
 int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                          float scale, float* flat, long long weight_index, hipStream_t s);
+size_t masked_huber_partial_doubles(long long rows, int T);
+int launch_masked_huber_metrics(const float* pred, const float* truth, long long rows, int T, float delta,
+                                float null_value, float mask_value, double* part, float* loss, float* valid,
+                                double* sums, hipStream_t s);
+int launch_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                             long long rows, int T, float delta, float null_value, float* dpred, hipStream_t s);
+int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
+                             const float* scale, float* flat, long long weight_index, hipStream_t s);
 
 }  // namespace msgat

@@ -308,4 +308,157 @@ int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_o
   return MSGAT_OK;
 }
 
+// ---- masked Huber loss + per-horizon metric sums ---------------------------------------------------------------------
+// An entry of the truth counts when it is a measurement: not NaN and not the null value (a PEMS reading of 0 = sensor
+// down).  With null_value = NaN only the NaN entries drop out (y != NaN holds for every y).
+//   k_masked_huber_metrics   the first (256 / T) * T lanes of a block walk the elements with a stride that is a multiple
+//                            of T, so a lane keeps ONE horizon (element i has horizon i mod T) and its five sums
+//                            {valid count, |e|, 100 |e / y| (y > mask), e^2, huber} stay in registers, while a block
+//                            trip still reads consecutive addresses.  The lanes of a horizon hand their sums over
+//                            through LDS once per block and are added in lane order: one record [5][T] per block,
+//                            stored column-major over the blocks (part[(c T + h) nblocks + b]).
+//   k_masked_huber_finish    block c adds column c: a wave per horizon, lane l takes blocks l, l + 64, ... in order, then
+//                            the butterfly of wave_sum; the all-horizon row is the sum of the horizon rows in horizon
+//                            order.  The block of the huber column adds the count column too and writes loss and valid.
+// Every sum has one fixed order: bitwise reproducible.  No floating-point atomics.
+constexpr int kMaskCols = 5;
+constexpr int kMaskMaxT = 64;
+constexpr int kMaskMaxBlocks = 512;
+constexpr int kMaskFinishBlock = 1024;
+
+__device__ __forceinline__ bool entry_valid(float y, float null_value) { return y == y && y != null_value; }
+
+__global__ __launch_bounds__(kTailBlock) void k_masked_huber_metrics(const float* __restrict__ pred,
+                                                                     const float* __restrict__ truth, long long n, int T,
+                                                                     int lanes, float delta, float null_value,
+                                                                     float mask_value, double* __restrict__ part) {
+  __shared__ double red[kMaskCols][kTailBlock];
+  double s[kMaskCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if ((int)threadIdx.x < lanes) {   // lanes % T == 0: i mod T == threadIdx.x mod T on every trip
+    const long long stride = (long long)gridDim.x * lanes;
+    for (long long i = (long long)blockIdx.x * lanes + threadIdx.x; i < n; i += stride) {
+      const float p = pred[i], y = truth[i];
+      if (!entry_valid(y, null_value)) continue;
+      const float e = p - y, a = fabsf(e);
+      s[0] += 1.0;
+      s[1] += a;
+      if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
+      s[3] += (double)e * (double)e;
+      s[4] += (a <= delta) ? 0.5f * a * a : delta * a - 0.5f * delta * delta;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kMaskCols; ++c) red[c][threadIdx.x] = s[c];
+  __syncthreads();
+  for (int o = threadIdx.x; o < kMaskCols * T; o += kTailBlock) {
+    const int c = o / T, h = o - c * T;
+    double t = 0.0;
+    for (int j = h; j < lanes; j += T) t += red[c][j];
+    part[(size_t)o * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(kMaskFinishBlock) void k_masked_huber_finish(const double* __restrict__ part, int nblocks,
+                                                                          int T, float* __restrict__ loss,
+                                                                          float* __restrict__ valid,
+                                                                          double* __restrict__ sums) {
+  __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (huber block)
+  const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool huber = c == kMaskCols - 1;
+  for (int q = 0; q < (huber ? 2 : 1); ++q) {
+    const int col = q == 0 ? c : 0;
+    for (int h = wave; h < T; h += kMaskFinishBlock / 64) {
+      const double* __restrict__ p = part + (size_t)(col * T + h) * nblocks;
+      double t = 0.0;
+      for (int b = lane; b < nblocks; b += 64) t += p[b];
+      t = wave_sum(t);
+      if (lane == 0) rows[q][h] = t;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < T && sums != nullptr) sums[(size_t)threadIdx.x * kMaskCols + c] += rows[0][threadIdx.x];
+  if (threadIdx.x != 0) return;
+  double total = 0.0, count = 0.0;
+  for (int h = 0; h < T; ++h) total += rows[0][h];
+  if (sums != nullptr) sums[(size_t)T * kMaskCols + c] += total;
+  if (!huber) return;
+  for (int h = 0; h < T; ++h) count += rows[1][h];
+  valid[0] = (float)count;
+  loss[0] = (float)(total / fmax(count, 1.0));
+}
+
+// dpred = dloss[0] * clamp(e, -delta, delta) / max(valid[0], 1) at the valid entries, +0 elsewhere (a NaN of the truth
+// ends in the select, not in the product); valid[0] comes from device memory: a captured launch follows its batch
+__global__ __launch_bounds__(kTailBlock) void k_masked_huber_grad(const float* __restrict__ pred,
+                                                                  const float* __restrict__ truth,
+                                                                  const float* __restrict__ dloss,
+                                                                  const float* __restrict__ valid, long long n,
+                                                                  float delta, float null_value,
+                                                                  float* __restrict__ dpred) {
+  const long long i = (long long)blockIdx.x * kTailBlock + threadIdx.x;
+  if (i >= n) return;
+  const float y = truth[i];
+  const float e = pred[i] - y;
+  const float g = fminf(fmaxf(e, -delta), delta);
+  dpred[i] = entry_valid(y, null_value) ? g * (dloss[0] / fmaxf(valid[0], 1.f)) : 0.f;
+}
+
+static int masked_huber_lanes(int T) { return (kTailBlock / T) * T; }
+
+static int masked_huber_blocks(long long n, int T) {
+  const long long per_block = (long long)masked_huber_lanes(T) * kTailPerThread;
+  const long long want = (n + per_block - 1) / per_block;
+  return (int)(want < 1 ? 1 : (want > kMaskMaxBlocks ? kMaskMaxBlocks : want));
+}
+
+size_t masked_huber_partial_doubles(long long rows, int T) {
+  return (size_t)masked_huber_blocks(rows * T, T) * kMaskCols * T;
+}
+
+int launch_masked_huber_metrics(const float* pred, const float* truth, long long rows, int T, float delta,
+                                float null_value, float mask_value, double* part, float* loss, float* valid,
+                                double* sums, hipStream_t s) {
+  const long long n = rows * T;
+  const int nb = masked_huber_blocks(n, T);
+  hipLaunchKernelGGL(k_masked_huber_metrics, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T, masked_huber_lanes(T),
+                     delta, null_value, mask_value, part);
+  MSGAT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_masked_huber_finish, dim3(kMaskCols), dim3(kMaskFinishBlock), 0, s, part, nb, T, loss, valid, sums);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+int launch_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                             long long rows, int T, float delta, float null_value, float* dpred, hipStream_t s) {
+  const long long n = rows * T;
+  hipLaunchKernelGGL(k_masked_huber_grad, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s,
+                     pred, truth, dloss, valid, n, delta, null_value, dpred);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+// k_gather_scaled with the scale read from device memory: the rank's weight of a masked step is its batch's valid
+// count, which only the device knows
+__global__ __launch_bounds__(kTailBlock) void k_gather_scaled_dev(const float* const* __restrict__ chunk_src,
+                                                                  const long long* __restrict__ chunk_off,
+                                                                  const int* __restrict__ chunk_len,
+                                                                  const float* __restrict__ scale,
+                                                                  float* __restrict__ flat, long long weight_index) {
+  const int c = blockIdx.x;
+  const float sc = scale[0];
+  const float* __restrict__ src = chunk_src[c];
+  float* __restrict__ dst = flat + chunk_off[c];
+  const int len = chunk_len[c];
+  for (int i = threadIdx.x; i < len; i += kTailBlock) dst[i] = sc * src[i];
+  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] = sc;
+}
+
+int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
+                             const float* scale, float* flat, long long weight_index, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_scaled_dev, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
+                     flat, weight_index);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
 }  // namespace msgat

@@ -15,6 +15,9 @@ Differences that are the point of this build:
     Adam updates every parameter in one launch over flat state buffers (`FlatAdam`).
   * under `torch.distributed` every rank runs its batch shard and the gradients are averaged with ONE
     flat all-reduce of the buffer Adam reads (`nn.DataParallel`, main.py:52-55, is not used).
+  * `null_value` (off by default) treats entries of the truth that are NaN or equal to it as missing readings: they
+    drop out of the loss, its gradient and the metrics, which are then kept per forecast horizon
+    (`ops.masked_huber_metrics`; the batch's valid count stays on the device, also as the rank's weight).
   * `hip_graph="auto"` (the default on the GPU) captures a step in a HIP graph once its batch shape recurs and replays it.
 CPU tensors (the host-logic tests run a small CPU `nn.Module` through this loop) take plain PyTorch
 ops for loss and optimizer; the library has no CPU path.
@@ -40,12 +43,37 @@ def huber_loss(output: torch.Tensor, target: torch.Tensor, delta: float = 1.0) -
     return torch.where(err <= delta, 0.5 * err * err, delta * err - 0.5 * delta * delta).mean()
 
 
+def valid_entries(target: torch.Tensor, null_value: float) -> torch.Tensor:
+    """The entries of the truth that are measurements: not NaN and not `null_value` (PEMS files store 0 for a sensor
+    that was down).  `null_value = nan` masks the NaN entries only."""
+    return ~torch.isnan(target) & (target != null_value)
+
+
+def masked_huber_loss(output: torch.Tensor, target: torch.Tensor, delta: float, null_value: float) -> torch.Tensor:
+    """Huber loss summed over the valid entries of `target` and divided by max(valid count, 1): 0 for a batch without a
+    valid entry.  The torch restatement of `ops.masked_huber_metrics` (what CPU tensors run)."""
+    valid = valid_entries(target, null_value)
+    zero = torch.zeros((), dtype=output.dtype, device=output.device)
+    err = torch.where(valid, output - target, zero).abs()
+    huber = torch.where(err <= delta, 0.5 * err * err, delta * err - 0.5 * delta * delta)
+    return torch.where(valid, huber, zero).sum() / valid.sum().clamp(min=1)
+
+
 class HuberLoss(nn.Module):
-    def __init__(self, delta: float = 1.0):
+    """Mean Huber loss.  `null_value` (default None: every entry counts, the reference's loss) drops the entries of the
+    target that are NaN or equal to it from the sum AND from the divisor."""
+
+    def __init__(self, delta: float = 1.0, null_value: Optional[float] = None):
         super().__init__()
         self.delta = delta
+        self.null_value = null_value
 
     def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.null_value is not None:
+            if output.is_cuda:
+                from . import ops
+                return ops.masked_huber_metrics(output, target, self.delta, self.null_value)
+            return masked_huber_loss(output, target, self.delta, self.null_value)
         if output.is_cuda:
             from . import ops
             return ops.huber_metrics(output, target, self.delta)
@@ -58,10 +86,20 @@ class Metrics:
     Totals [AE, APE, SE, sum of batch losses] accumulate on the device in float64; properties synchronise
     when read.  Under a process group a rank adds its share n_r / n_b of every global batch's loss
     (`loss_weight`), so the all-reduced total is the sum of the reference's per-batch mean losses
-    (engine.py:66-67) -- also for uneven shards -- and `batches` counts GLOBAL batches (every rank sees them all)."""
+    (engine.py:66-67) -- also for uneven shards -- and `batches` counts GLOBAL batches (every rank sees them all).
 
-    def __init__(self, mask_value: float = 0.0):
+    With `null_value` set, only the VALID entries of the truth count (not NaN, != null_value) and the totals are kept per
+    forecast horizon: a float64 [T_out + 1, 5] buffer whose row t < T_out holds, for horizon step t + 1,
+    {valid count, sum |e|, 100 sum_{y > mask_value} |e / y|, sum e^2, sum huber(e)} and whose last row holds the same
+    over all horizons (the layout `ops.masked_huber_metrics` adds to).  It is allocated on first use, zeroed by
+    `reset()` and reduced in place by `all_reduce()`.  MAE / MAPE / RMSE divide by the valid count read from the
+    buffer, and `loss` is the epoch's total Huber sum over its total valid count -- a ratio of totals, the same number
+    for any number of ranks and any sharding of the batches, which a mean of per-batch means is not once the batches'
+    valid counts differ.  `per_horizon()` / `at(steps)` give the metrics per horizon."""
+
+    def __init__(self, mask_value: float = 0.0, null_value: Optional[float] = None):
         self.mask_value = mask_value
+        self.null_value = null_value
         self.n = 0
         self.batches = 0
         self._sums: Optional[torch.Tensor] = None
@@ -72,7 +110,16 @@ class Metrics:
             self._sums.zero_()
         self.n = self.batches = 0
 
-    def totals(self, device) -> torch.Tensor:
+    def totals(self, device, t_out: Optional[int] = None) -> torch.Tensor:
+        """The totals buffer; with `null_value` set the first call must name the number of horizons `t_out`."""
+        if self.null_value is not None:
+            if self._sums is None:
+                if t_out is None:
+                    raise ValueError("Metrics(null_value=...): the first totals() call needs t_out")
+                self._sums = torch.zeros(int(t_out) + 1, 5, device=device, dtype=torch.float64)
+            elif t_out is not None and self._sums.shape[0] != int(t_out) + 1:
+                raise ValueError(f"Metrics holds totals for {self._sums.shape[0] - 1} horizons, got a batch with {t_out}")
+            return self._sums
         if self._sums is None:
             self._sums = torch.zeros(4, device=device, dtype=torch.float64)
         return self._sums
@@ -83,7 +130,15 @@ class Metrics:
         self.batches += 1
 
     def update(self, y_pred: torch.Tensor, y_true: torch.Tensor, loss: Optional[torch.Tensor] = None,
-               count: bool = True, loss_weight: float = 1.0) -> None:
+               count: bool = True, loss_weight: float = 1.0, delta: Optional[float] = None) -> None:
+        """Add a batch with torch ops (CPU tensors; the GPU path adds inside the fused loss kernel).  With `null_value`
+        set the Huber column is computed here from `delta` (`loss` and `loss_weight` are not used; without `delta` the
+        column, and with it `loss`, stays 0)."""
+        if self.null_value is not None:
+            self._update_masked(y_pred, y_true, delta)
+            if count:
+                self.count(y_true)
+            return
         err = (y_pred.detach() - y_true).double()
         truth = y_true.double()
         mask = truth > self.mask_value
@@ -95,10 +150,57 @@ class Metrics:
         if count:
             self.count(y_true)
 
+    def _update_masked(self, y_pred: torch.Tensor, y_true: torch.Tensor, delta: Optional[float]) -> None:
+        """What `ops.masked_huber_metrics` adds to the buffer, in float64 torch ops."""
+        t_out = y_true.shape[-1]
+        truth = y_true.double().reshape(-1, t_out)
+        valid = valid_entries(truth, self.null_value)
+        zero = torch.zeros_like(truth)
+        err = torch.where(valid, y_pred.detach().double().reshape(-1, t_out) - truth, zero)
+        mask = valid & (truth > self.mask_value)
+        ape = torch.where(mask, (err / torch.where(mask, truth, torch.ones_like(truth))).abs(), zero)
+        a = err.abs()
+        huber = zero if delta is None else torch.where(a <= delta, 0.5 * a * a, delta * a - 0.5 * delta * delta)
+        rows = torch.stack([valid.double().sum(0), a.sum(0), 100.0 * ape.sum(0), (err * err).sum(0), huber.sum(0)], dim=1)
+        sums = self.totals(y_pred.device, t_out)
+        sums[:t_out].add_(rows)
+        sums[t_out].add_(rows.sum(0))
+
     def _get(self, i: int) -> float:
         return 0.0 if self._sums is None else float(self._sums[i].item())
 
+    def _masked_total(self, column: int) -> float:
+        """Column `column` of the all-horizon row over the epoch's valid count (at least 1)."""
+        if self._sums is None:
+            return 0.0
+        last = self._sums[-1].tolist()
+        return last[column] / max(last[0], 1.0)
+
+    def per_horizon(self) -> Dict[str, List[float]]:
+        """MAE / MAPE / RMSE and the valid count of every forecast horizon: lists of length T_out (needs `null_value`)."""
+        if self.null_value is None:
+            raise ValueError("per-horizon metrics need Metrics(null_value=...): the unmasked totals are kept over all horizons")
+        if self._sums is None:
+            return {"MAE": [], "MAPE": [], "RMSE": [], "valid": []}
+        rows = self._sums[:-1].cpu()
+        n = rows[:, 0].clamp(min=1.0)
+        return {"MAE": (rows[:, 1] / n).tolist(), "MAPE": (rows[:, 2] / n).tolist(),
+                "RMSE": (rows[:, 3] / n).sqrt().tolist(), "valid": rows[:, 0].tolist()}
+
+    def at(self, steps) -> Dict[str, List[float]]:
+        """`per_horizon()` at the 1-based horizon steps `steps`, e.g. `at([3, 6, 12])`."""
+        every = self.per_horizon()
+        t_out = len(every["valid"])
+        for step in steps:
+            if not 1 <= int(step) <= t_out:
+                raise IndexError(f"horizon step {step} outside 1..{t_out}")
+        return {k: [v[int(step) - 1] for step in steps] for k, v in every.items()}
+
     def all_reduce(self) -> None:
+        if self.null_value is not None:
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and self._sums is not None:
+                dist.all_reduce(self._sums)    # the whole buffer, in place: captured kernels keep adding to it
+            return
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and self._sums is not None:
             buf = torch.cat([self._sums, self._sums.new_tensor([float(self.n)])])
             dist.all_reduce(buf)
@@ -107,19 +209,29 @@ class Metrics:
 
     @property
     def MAE(self) -> float:
+        if self.null_value is not None:
+            return self._masked_total(1)
         return self._get(0) / max(self.n, 1)
 
     @property
     def MAPE(self) -> float:
+        if self.null_value is not None:
+            return self._masked_total(2)
         return self._get(1) / max(self.n, 1)
 
     @property
     def RMSE(self) -> float:
+        if self.null_value is not None:
+            return self._masked_total(3) ** 0.5
         return (self._get(2) / max(self.n, 1)) ** 0.5
 
     @property
     def loss(self) -> float:
-        """Mean over the (global) batches of the batch-mean loss, the reference's `loss_ave` (engine.py:66-67)."""
+        """Mean over the (global) batches of the batch-mean loss, the reference's `loss_ave` (engine.py:66-67).
+        With `null_value` set: the epoch's total Huber sum divided by its total valid count (a ratio of totals, see
+        the class docstring)."""
+        if self.null_value is not None:
+            return self._masked_total(4)
         return self._get(3) / max(self.batches, 1)
 
     def todict(self):
@@ -229,7 +341,7 @@ class FlatAdam(optim.Optimizer):
             self._tables[key] = hit       # never evicted: a captured step may hold the addresses of an older table
         return hit
 
-    def _gather(self, grads: List[torch.Tensor], active: tuple, weight: float) -> None:
+    def _gather(self, grads: List[torch.Tensor], active: tuple, weight) -> None:
         """flat = weight * gradients, flat[-1] = weight, in ONE launch (`parallel.gather_scaled`)."""
         offsets = [o for o, on in zip(self._offsets, active) if on]
         parallel.gather_scaled(self.flat_grad, grads, offsets, weight, self.numel, self._gather_tables)
@@ -247,10 +359,13 @@ class FlatAdam(optim.Optimizer):
             self._host_steps[i] += int(on)
 
     @torch.no_grad()
-    def step(self, closure=None, rank_weight: Optional[float] = None):
+    def step(self, closure=None, rank_weight=None):
         """One update.  `rank_weight` (this rank's sample count) makes it a data-parallel step: the flat gradient
         buffer is all-reduced as sum(w g) / sum(w) -- the gradient of the mean loss over the global batch, also for
-        uneven shards -- before the update, in the one collective of the step."""
+        uneven shards -- before the update, in the one collective of the step.
+        A one-element float32 device tensor is accepted too (the valid count of a masked batch): the gather reads it on
+        the device, and the summed weight is clamped to at least 1 before it divides -- counts are integers, so the
+        clamp is exact whenever anything was valid, and a global batch without a valid entry gives a zero gradient."""
         from . import _lib
         loss = None
         if closure is not None:
@@ -266,11 +381,16 @@ class FlatAdam(optim.Optimizer):
             # element) and one after it (the update divides by the summed weight on the way in)
             if active != self._last_active:
                 self.flat_grad.zero_()           # parameters without a gradient contribute zeros on every rank
+            on_device = torch.is_tensor(rank_weight)
             if grads:
-                self._gather(grads, active, float(rank_weight))
+                self._gather(grads, active, rank_weight if on_device else float(rank_weight))
+            elif on_device:
+                self.flat_grad[self.numel:].copy_(rank_weight.reshape(1))
             else:
                 self.flat_grad[self.numel:].fill_(float(rank_weight))
             parallel.all_reduce_flat(self.flat_grad)
+            if on_device:
+                self.flat_grad[self.numel:].clamp_(min=1.0)
             divisor = self.flat_grad.data_ptr() + 4 * self.numel
         elif grads:
             torch._foreach_copy_([v for v, on in zip(self._grad_views, active) if on], grads)
@@ -401,9 +521,11 @@ class _GraphedStep:
 class Engine:
     __labels__ = {"train": "[Train   ]", "validate": "[Validate]", "evaluate": "[Evaluate]"}
 
-    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str):
+    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, null_value: Optional[float] = None):
         self.model = model
-        self.loss_fn, self.out_dir = HuberLoss(loss_delta), Path(out_dir)
+        self.null_value = null_value     # None: every entry of the truth counts (the reference's loss and metrics)
+        self._valid_count = None         # [1] fp32: the valid count of the last batch (device memory on the GPU)
+        self.loss_fn, self.out_dir = HuberLoss(loss_delta, null_value), Path(out_dir)
         self.out_dir.mkdir(parents=True, exist_ok=True)
         self.log_file = self.out_dir / "run.log"
         self.optimizer = None
@@ -429,7 +551,20 @@ class Engine:
     def _loss(self, pred: torch.Tensor, truth: torch.Tensor, metrics: Optional[Metrics],
               loss_weight: float = 1.0) -> torch.Tensor:
         """Huber loss of a batch; feeds `metrics` (engine.py:56,66-70).  On the GPU one library pass does both.
-        `loss_weight` = this rank's share of the global batch (1 without a process group)."""
+        `loss_weight` = this rank's share of the global batch (1 without a process group).
+        With `null_value` set: the masked loss and the per-horizon totals; the batch's valid count stays in
+        `_valid_count` (one buffer for every step, so captured kernels and the rank weight of a replay find it)."""
+        if self.null_value is not None:
+            mask_value = 0.0 if metrics is None else metrics.mask_value
+            if pred.is_cuda:
+                from . import ops
+                sums = None if metrics is None else metrics.totals(pred.device, pred.shape[-1])
+                return ops.masked_huber_metrics(pred, truth, self.loss_fn.delta, self.null_value, mask_value, sums,
+                                                self._valid_buffer(pred.device))
+            self._valid_count = valid_entries(truth, self.null_value).sum().to(torch.float32).reshape(1)
+            if metrics is not None:
+                metrics.update(pred, truth, count=False, delta=self.loss_fn.delta)   # counted by the caller
+            return masked_huber_loss(pred, truth, self.loss_fn.delta, self.null_value)
         if pred.is_cuda:
             from . import ops
             sums = None if metrics is None else metrics.totals(pred.device)
@@ -440,14 +575,23 @@ class Engine:
             metrics.update(pred, truth, loss, count=False, loss_weight=loss_weight)   # counted by the caller
         return loss
 
+    def _valid_buffer(self, device) -> torch.Tensor:
+        if self._valid_count is None or self._valid_count.device != device:
+            self._valid_count = torch.zeros(1, device=device, dtype=torch.float32)
+        return self._valid_count
+
     def _optimizer_step(self, n_samples: int, world: int) -> None:
+        # a rank's weight in the gradient mean: its sample count, or -- entries dropping out of a masked loss -- its
+        # batch's valid count, which is in device memory: sum_r v_r g_r / sum_r v_r is the gradient of the global
+        # masked mean for any split
+        weight = float(n_samples) if self.null_value is None else self._valid_count
         if isinstance(self.optimizer, FlatAdam):
-            self.optimizer.step(rank_weight=float(n_samples) if world > 1 else None)
+            self.optimizer.step(rank_weight=weight if world > 1 else None)
             return
         if world > 1:
             if self._grad_sync is None:
                 self._grad_sync = parallel.FlatGradAllReduce(self.model.parameters())
-            self._grad_sync(weight=float(n_samples))
+            self._grad_sync(weight=weight)
         self.optimizer.step()
 
     def run_epoch(self, data, gpu_id=None, epoch=None, mode: str = "train") -> float:
@@ -466,13 +610,14 @@ class Engine:
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(0 if epoch is None else int(epoch))
         if self._graph_metrics is None or not self.hip_graph or device.type != "cuda":
-            metrics = Metrics()
+            metrics = Metrics(null_value=self.null_value)
         else:
             metrics = self._graph_metrics       # captured kernels hold its totals buffer: re-use it, zeroed
             metrics.reset()
         if self.hip_graph and device.type == "cuda":
             self._graph_metrics = metrics
-            metrics.totals(device)
+            if self.null_value is None:
+                metrics.totals(device)
         # sizes of the GLOBAL batches behind pre-sharded ones (the sampler knows them); without a sampler the
         # shards are taken to be even
         global_sizes = iter(sampler.global_batch_sizes()) if presharded and hasattr(sampler, "global_batch_sizes") else None
@@ -491,6 +636,9 @@ class Engine:
                 batch = [t.to(device, non_blocking=True) for t in batch]
                 *inputs, truth = batch
                 graphed = None
+                if self.null_value is not None and device.type == "cuda":
+                    metrics.totals(device, truth.shape[-1])     # both exist before a capture can begin
+                    self._valid_buffer(device)
                 if self.hip_graph and device.type == "cuda":
                     key = (training, tuple(tuple(t.shape) for t in batch), n_global)
                     graphed = self._graphs.get(key)
@@ -522,16 +670,22 @@ class Engine:
                     self._optimizer_step(truth.shape[0], world)
                 metrics.count(truth)
         if world > 1:
-            if metrics._sums is None:
+            if metrics._sums is None and self.null_value is None:
                 metrics.totals(device)
             metrics.all_reduce()
         loss_ave = metrics.loss
         stats = {"loss": loss_ave, **metrics.todict()}
+        horizons = None if self.null_value is None else metrics.per_horizon()
         if rank == 0:
             if mode == "evaluate":
                 self.log_to_file(self.__labels__[mode], **stats)
             else:
                 self.log_to_file(self.__labels__[mode], epoch=epoch, **stats)
+            if horizons is not None and mode != "train":
+                per = {k: "/".join(f"{v:.6g}" for v in horizons[k]) for k in ("MAE", "MAPE", "RMSE")}
+                self.log_to_file(self.__labels__[mode], "per horizon", **({} if mode == "evaluate" else {"epoch": epoch}), **per)
+        if horizons is not None:
+            stats["horizons"] = horizons
         self.last_stats = stats
         return loss_ave
 
@@ -556,13 +710,18 @@ class Trainer(Engine):
     after epoch 20 (engine.py:104-133).  GPU parameters train with `FlatAdam` (one launch), CPU parameters (host-logic
     tests) with torch.optim.Adam -- same update, same checkpoint format."""
 
-    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto"):
-        """`hip_graph`: "auto" (default) -- on the GPU a training / validation step is captured in a HIP graph once its batch
+    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto",
+                 null_value: Optional[float] = None):
+        """`null_value` (default None: the reference's loss and metrics over every entry): entries of the truth that are
+        NaN or equal to it are missing readings -- they drop out of the loss, its gradient and the metrics, the metrics are
+        kept per forecast horizon (`last_stats["horizons"]`, one more log line per validation epoch), and under a process
+        group a rank's weight in the gradient mean is its batch's valid count.
+        `hip_graph`: "auto" (default) -- on the GPU a training / validation step is captured in a HIP graph once its batch
         shape has recurred `graph_after` (3) times and replayed from then on, other shapes are launched eagerly (a step of
         ~120 launches is host-bound wherever it is under ~3 ms of GPU work: msgat48 3.3 -> 2.8 ms, PEMSD4 2.7 -> 1.5 ms);
         True -- capture every shape at first sight; False -- eager launches only.  Graphs are keyed by (grad mode, batch
         shape, global batch size) and dropped when `load()` moves the optimizer's buffers."""
-        super().__init__(model, loss_delta=loss_delta, out_dir=out_dir)
+        super().__init__(model, loss_delta=loss_delta, out_dir=out_dir, null_value=null_value)
         on_gpu = next(model.parameters()).is_cuda
         if hip_graph is True and not on_gpu:
             raise ValueError("hip_graph=True needs the model on the GPU")
@@ -626,8 +785,9 @@ def default_grad_scaler_state() -> dict:
 
 
 class Evaluator(Engine):
-    def __init__(self, model: nn.Module, delta: float, out_dir: str, ckpt, hip_graph="auto"):
-        super().__init__(model, loss_delta=delta, out_dir=out_dir)
+    def __init__(self, model: nn.Module, delta: float, out_dir: str, ckpt, hip_graph="auto",
+                 null_value: Optional[float] = None):
+        super().__init__(model, loss_delta=delta, out_dir=out_dir, null_value=null_value)     # null_value: see Trainer
         states = torch.load(ckpt, map_location=next(model.parameters()).device, weights_only=False)
         model.load_state_dict(strip_data_parallel_prefix(states["model"]))
         self.hip_graph = hip_graph if next(model.parameters()).is_cuda else False   # see Trainer

@@ -1754,6 +1754,65 @@ def huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, mask_va
     return _HuberMetricsFunction.apply(pred, truth, delta, mask_value, sums, float(loss_weight))
 
 
+class _MaskedHuberMetricsFunction(torch.autograd.Function):
+    """pred, truth [..., T_out] -> Huber loss averaged over the VALID entries of truth (not NaN, != null_value); adds
+    the per-horizon and all-horizon {count, |e|, 100|e/y| (y > mask), e^2, huber} sums to the running fp64 totals
+    `sums` [T_out + 1, 5] and leaves the batch's valid count in `valid` [1], both on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, truth, delta: float, null_value: float, mask_value: float, sums, valid):
+        L = _lib.lib()
+        pred_c, truth_c = pred.contiguous(), truth.contiguous()
+        t_out = pred_c.shape[-1]
+        rows = pred_c.numel() // t_out
+        n_part = int(L.msgat_masked_huber_partial_doubles(rows, t_out))
+        part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        st = L.msgat_masked_huber_metrics(_ptr(pred_c), _ptr(truth_c), rows, t_out, float(delta), float(null_value),
+                                          float(mask_value), _ptr(part), _ptr(loss), _ptr(valid), _ptr(sums),
+                                          _stream_handle(pred.device))
+        _lib.check(st, "msgat_masked_huber_metrics")
+        ctx.delta, ctx.null_value = float(delta), float(null_value)
+        ctx.save_for_backward(pred_c, truth_c, valid)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, truth, valid = ctx.saved_tensors
+        dpred = torch.empty_like(pred)
+        t_out = pred.shape[-1]
+        st = _lib.lib().msgat_masked_huber_grad(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid),
+                                                pred.numel() // t_out, t_out, ctx.delta, ctx.null_value, _ptr(dpred),
+                                                _stream_handle(pred.device))
+        _lib.check(st, "msgat_masked_huber_grad")
+        return dpred, None, None, None, None, None, None
+
+
+def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, null_value: float,
+                         mask_value: float = 0.0, sums: Optional[torch.Tensor] = None,
+                         valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Huber loss of `pred` against `truth` [..., T_out] (e.g. [B, N, T_out]) averaged over the valid entries -- those
+    whose truth is neither NaN nor `null_value` -- in one pass that also feeds the epoch's per-horizon metric totals
+    `sums` (float64 [T_out + 1, 5], see `engine.Metrics`).  A batch without a valid entry gives 0.
+    `valid` (float32 [1] on the device, optional) receives the batch's valid count; the backward divides by it on the
+    device, so it must keep that value until the backward has run."""
+    _require_device_tensor("prediction", pred)
+    _require_device_tensor("target", truth, pred.device)
+    if pred.shape != truth.shape or pred.numel() == 0 or pred.dim() == 0:
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(truth.shape)} must match and be non-empty")
+    t_out = pred.shape[-1]
+    if t_out > 64:
+        raise ValueError(f"T_out = {t_out}: the masked step tail supports forecast horizons up to 64 steps")
+    if sums is not None and (sums.dtype != torch.float64 or tuple(sums.shape) != (t_out + 1, 5) or sums.device != pred.device
+                             or not sums.is_contiguous()):
+        raise ValueError(f"sums must be a contiguous float64 [{t_out + 1}, 5] tensor on the prediction's device")
+    if valid is None:
+        valid = torch.empty(1, device=pred.device, dtype=torch.float32)
+    elif valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != pred.device:
+        raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
+    return _MaskedHuberMetricsFunction.apply(pred, truth, delta, null_value, mask_value, sums, valid)
+
+
 # ---- boundary hygiene for every autograd.Function above -----------------------------------------------------------
 # (a) the library's launches act on the CURRENT HIP device (hipFuncSetAttribute for > 64 KB LDS, occupancy queries),
 #     while the reference's API lets the caller name any device (`run_epoch(..., gpu_id=k)`, engine.py:40,50):

@@ -138,12 +138,21 @@ class _GatherTable:
         self.current = bases
 
 
-def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Sequence[int], weight: float,
+def _device_weight(weight: torch.Tensor, device) -> torch.Tensor:
+    """A rank weight that lives in device memory (a masked step's valid count): one float32 element on `device`."""
+    if weight.numel() != 1 or weight.dtype != torch.float32 or weight.device != device:
+        raise ValueError(f"a tensor rank weight must be one float32 element on {device}, got {weight.dtype} "
+                         f"{tuple(weight.shape)} on {weight.device}")
+    return weight.reshape(1)
+
+
+def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Sequence[int], weight,
                   weight_index: int, cache: dict) -> None:
     """flat[offsets[i] : ...] = weight * grads[i] for every gradient and flat[weight_index] = weight, in ONE launch
     (`msgat_gather_scaled`, csrc/tail.hip).  `cache` keeps one persistent device table per gradient layout
     (`_GatherTable`): a replayed HIP graph or a warm caching allocator hands out the same pointers step after step and
-    nothing is uploaded; new pointers cost one asynchronous copy from pinned memory."""
+    nothing is uploaded; new pointers cost one asynchronous copy from pinned memory.
+    `weight`: a float, or a one-element float32 device tensor that the launch reads (`msgat_gather_scaled_dev`)."""
     from . import _lib
     keep = [g if g.is_contiguous() else g.contiguous() for g in grads]
     key = (tuple(g.numel() for g in keep), tuple(offsets))
@@ -151,6 +160,12 @@ def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Se
     if table is None:
         table = cache[key] = _GatherTable(key[0], key[1], flat.device)
     table.point_at(tuple(g.data_ptr() for g in keep))
+    if torch.is_tensor(weight):
+        st = _lib.lib().msgat_gather_scaled_dev(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
+                                                _device_weight(weight, flat.device).data_ptr(), flat.data_ptr(),
+                                                int(weight_index), torch.cuda.current_stream(flat.device).cuda_stream)
+        _lib.check(st, "msgat_gather_scaled_dev")
+        return
     st = _lib.lib().msgat_gather_scaled(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
                                         float(weight), flat.data_ptr(), int(weight_index),
                                         torch.cuda.current_stream(flat.device).cuda_stream)
@@ -161,7 +176,11 @@ class FlatGradAllReduce:
     """Averages the gradients of `params` across ranks through one contiguous fp32 buffer.
 
     The rank's weight (its sample count) rides in the last element of the same buffer, so a
-    step costs exactly one collective and no host synchronisation.
+    step costs exactly one collective and no host synchronisation.  A weight given as a one-element
+    tensor (the valid count of a masked batch, which only the device knows) is read where it lives;
+    the summed weight is then clamped to at least 1 before it divides, so a global batch without a
+    valid entry yields zero gradients instead of NaN (counts are integers: the clamp changes nothing
+    whenever anything was valid).
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter]):
@@ -182,11 +201,15 @@ class FlatGradAllReduce:
     def nbytes(self) -> int:
         return self.flat.numel() * 4
 
-    def __call__(self, weight: float = 1.0) -> None:
+    def __call__(self, weight=1.0) -> None:
         """grad <- sum_ranks(weight * grad) / sum_ranks(weight).  With `weight` = the rank's
         sample count the result is the gradient of the mean loss over the global batch,
-        also when the shards are uneven."""
+        also when the shards are uneven; with the valid counts of a masked loss (one-element
+        tensors) it is the gradient of the global masked mean, for any split."""
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return
+        if torch.is_tensor(weight):
+            self._weighted_by_tensor(_device_weight(weight, self.flat.device))
             return
         if self.flat.is_cuda and all(p.grad is not None for p in self.params):
             # device tensors: one launch in front of the collective, one behind it; the averaged gradients are
@@ -207,8 +230,31 @@ class FlatGradAllReduce:
         self.flat[self.numel] = weight
         dist.all_reduce(self.flat)
         self.flat[: self.numel].div_(self.flat[self.numel])
+        self._hand_back()
+
+    def _hand_back(self) -> None:
         for p, v in zip(self.params, self.views):
             if p.grad is None:
                 p.grad = v.clone()
             else:
                 p.grad.copy_(v)
+
+    def _weighted_by_tensor(self, weight: torch.Tensor) -> None:
+        """The same two paths with the weight read from `weight[0]` and the summed weight clamped to >= 1."""
+        if self.flat.is_cuda and all(p.grad is not None for p in self.params):
+            gather_scaled(self.flat, [p.grad for p in self.params], self.offsets, weight, self.numel, self._tables)
+            all_reduce_flat(self.flat)
+            self.flat[: self.numel].div_(self.flat[self.numel].clamp(min=1.0))
+            for p, v in zip(self.params, self.views):
+                p.grad = v
+            return
+        for p, v in zip(self.params, self.views):
+            if p.grad is None:
+                v.zero_()
+            else:
+                v.copy_(p.grad)
+        self.flat[: self.numel].mul_(weight)
+        self.flat[self.numel:].copy_(weight)
+        dist.all_reduce(self.flat)
+        self.flat[: self.numel].div_(self.flat[self.numel].clamp(min=1.0))
+        self._hand_back()
