@@ -4,11 +4,12 @@
 //   dA[v,n,m]  = sum_{g : g % n_sets == v}  P_g[n,m] H_g[n,m],    H_g[n,m] = sum_{c,t} dv[g,c,n,t] feat[g,c,m,t]
 //
 // P does not depend on A, so the gradient is dense: it is written for every (n, m), edge or not.  P is re-created
-// from what the forward saved (q, kW, lse in log2 units), the way k_bwd_dense_col7 does: nothing [N,N] is stored.
+// from what the forward saved (q, kW, lse in log2 units; softmax_recreate.hpp), the way k_bwd_dense_col7 does: nothing
+// [N,N] is stored.
 //
 // A block owns a 64 x 64 output tile and a contiguous range of the groups of one value set; its 4 waves own 32 x 32
 // quadrants (2 x 2 tiles of 16 x 16).  Per group, both products run on v_mfma_f32_16x16x4_f32:
-//   S  T/4 MFMAs per tile (A = kW rows * log2 e, B = q rows: the forward's k-ordered chain, the same score bits)
+//   S  T/4 MFMAs per tile (score_tile, A = kW rows, B = q rows: the forward's k-ordered chain, the same score bits)
 //   H  Cu*T/4 MFMAs per tile, chained.  The contraction runs over (c, t) in any order, so a staged step of 4 channels
 //      gives lane quad k channel k: MFMA s of the step takes t = s.  A lane then reads its A and B fragments of four
 //      MFMAs with ONE ds_read_b128 each, and the block stages dv rows / feat rows as plain 16-B loads of [T] rows.
@@ -18,7 +19,7 @@
 // Deterministic, no atomics: a block sums its groups in ascending order; when the tile grid alone is too small for the
 // chip (one [N,N] adjacency: 196 tiles at N = 883) the groups are split over up to kAgMaxSplit blocks per tile, each
 // writes its partial sum to the workspace, and k_reduce_partials / k_reduce_few add the partials in split order.
-#include "common.hpp"
+#include "softmax_recreate.hpp"
 
 namespace msgat {
 
@@ -29,10 +30,6 @@ constexpr int kAgCh = 4;             // channels per staged step: one per lane q
 constexpr int kAgTargetBlocks = 1024;   // 4 blocks per CU on a 256-CU part before the groups are split
 constexpr int kAgMaxSplit = 16;      // the partial sums stay in k_reduce_few's one-lane-per-column form
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 ag_mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ float f4get(const float4& v, int e) {
   return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
 }
@@ -108,11 +105,7 @@ __global__ __launch_bounds__(kAgBlock) void k_adjacency_grad(
       const float* qg = q + (size_t)g * NT;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int kk = 0; kk < T4; ++kk) {
-          ka[h][kk] = kWg[(size_t)rrow[h] * T + 4 * kk + quad] * kLog2e;
-          qb[h][kk] = qg[(size_t)rcol[h] * T + 4 * kk + quad];
-        }
+        score_frags<T>(kWg, rrow[h], qg, rcol[h], quad, ka[h], qb[h]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) ls[h][r] = lse[(size_t)g * N + min(n0 + wr + 16 * h + 4 * quad + r, N - 1)];
       }
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(kAgBlock) void k_adjacency_grad(
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-          for (int b = 0; b < 2; ++b) H[a][b] = ag_mfma(f4get(fa[a], e), f4get(fb[b], e), H[a][b]);
+          for (int b = 0; b < 2; ++b) H[a][b] = mfma_16x16x4(f4get(fa[a], e), f4get(fb[b], e), H[a][b]);
     }
 
     if (ch == nch - 1) {
@@ -144,9 +137,7 @@ __global__ __launch_bounds__(kAgBlock) void k_adjacency_grad(
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-          f32x4 S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int kk = 0; kk < T4; ++kk) S = ag_mfma(ka[a][kk], qb[b][kk], S);
+          const f32x4 S = score_tile<T>(ka[a], qb[b]);
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[a][b][r] += fast_exp2(S[r] - ls[a][r]) * H[a][b][r];
         }
@@ -167,14 +158,9 @@ __global__ __launch_bounds__(kAgBlock) void k_adjacency_grad(
     }
 }
 
-// groups of a value set split over `nsplit` blocks per tile, `per` consecutive groups each (no split is empty)
+// groups of a value set split over `nsplit` blocks per tile
 static void adjacency_grad_split(int N, int G, int V, int* nsplit, int* per) {
-  const int tiles = cdiv(N, kAgTile) * cdiv(N, kAgTile);
-  const int Gs = G / V;
-  const int want = max(1, cdiv(kAgTargetBlocks, tiles * V));
-  const int ns = min(min(Gs, kAgMaxSplit), want);
-  *per = cdiv(Gs, ns);
-  *nsplit = cdiv(Gs, *per);
+  group_split(cdiv(N, kAgTile) * cdiv(N, kAgTile) * V, G / V, kAgTargetBlocks, kAgMaxSplit, nsplit, per);
 }
 
 size_t adjacency_grad_workspace_bytes(int N, int G, int V) {
@@ -190,30 +176,14 @@ int launch_adjacency_grad(const float* dv, int dv_group_channels, const float* f
   const size_t dv_gstride = (size_t)(dv_group_channels > 0 ? dv_group_channels : Cu) * N * T;
   float* out = nsplit > 1 ? ws : dadj;
   const dim3 grid(cdiv(N, kAgTile), cdiv(N, kAgTile), V * nsplit);
-#define MSGAT_AG(TT)                                                                                                  \
-  hipLaunchKernelGGL(k_adjacency_grad<TT>, grid, dim3(kAgBlock), 0, s, dv, dv_gstride, feat, q, kW, lse, out, N, Cu, V, \
-                     G / V, per, nsplit)
-  switch (T) {
-    case 4: MSGAT_AG(4); break;
-    case 8: MSGAT_AG(8); break;
-    case 12: MSGAT_AG(12); break;
-    case 16: MSGAT_AG(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_AG
-  MSGAT_CHECK_LAUNCH();
-  if (nsplit == 1) return MSGAT_OK;
-  ReduceJobs jobs{};
-  jobs.n = 1;
-  jobs.job[0].part = ws;
-  jobs.job[0].R = V;
-  jobs.job[0].J = nsplit;
-  jobs.job[0].Wd = N * N;
-  jobs.job[0].dst0 = dadj;
-  jobs.job[0].n0 = N * N;
-  jobs.job[0].dst1 = nullptr;
-  jobs.job[0].n1 = 0;
-  return launch_reduce_jobs(jobs, s);
+  const int st = dispatch_T(T, [&](auto t) -> int {
+    hipLaunchKernelGGL(k_adjacency_grad<decltype(t)::value>, grid, dim3(kAgBlock), 0, s, dv, dv_gstride, feat, q, kW, lse,
+                       out, N, Cu, V, G / V, per, nsplit);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  });
+  if (st != MSGAT_OK || nsplit == 1) return st;
+  return launch_reduce_groups(ws, V, nsplit, N * N, dadj, s);
 }
 
 }  // namespace msgat

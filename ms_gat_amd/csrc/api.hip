@@ -156,76 +156,52 @@ extern "C" int msgat_adjacency_grad(const msgat_shape_t* sh, int32_t Cu, const f
                                Cu, sh->N, sh->T, (hipStream_t)stream);
 }
 
-// ---- gradient of a sparse adjacency's values -----------------------------------------------------
-static int check_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu) {
+// ---- gradient of a sparse adjacency's values [n_sets,nnz] (n_sets = 1: one [N,N] matrix) ---------------------------
+static int check_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, int32_t n_sets) {
   int st = check_shape(sh);
   if (st) return st;
   if (!gr) return MSGAT_ERR_NULL;
   if (Cu <= 0 || gr->n_nodes != sh->N || gr->nnz < 0) return MSGAT_ERR_SHAPE;
   if (Cu > kMaxC) return MSGAT_ERR_UNSUPPORTED;
   if ((int64_t)Cu * sh->N * sh->T >= (1ll << 31)) return MSGAT_ERR_UNSUPPORTED;
-  return MSGAT_OK;
-}
-
-extern "C" size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu) {
-  if (check_edge_weight_grad(sh, gr, Cu) != MSGAT_OK) return 0;
-  return edge_weight_grad_workspace_bytes(gr->nnz, sh->R * sh->Bg);
-}
-
-extern "C" int msgat_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, const float* dv,
-                                      int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
-                                      const float* lse, float* dval, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
-  int st = check_edge_weight_grad(sh, gr, Cu);
-  if (st) return st;
-  if (dv_group_channels < 0 || (dv_group_channels > 0 && dv_group_channels < Cu)) return MSGAT_ERR_SHAPE;
-  if (!dv || !feat || !q || !kW || !lse) return MSGAT_ERR_NULL;
-  if (gr->nnz > 0 && (!dval || !gr->erow || !gr->col)) return MSGAT_ERR_NULL;
-  const int G = sh->R * sh->Bg;
-  const size_t need = edge_weight_grad_workspace_bytes(gr->nnz, G);
-  if (need > 0 && !workspace) return MSGAT_ERR_NULL;
-  if (workspace_bytes < need) return MSGAT_ERR_WORKSPACE;
-  return launch_edge_weight_grad(dv, dv_group_channels, feat, q, kW, lse, gr->erow, gr->col, dval,
-                                 static_cast<float*>(workspace), G, Cu, sh->N, gr->nnz, sh->T, (hipStream_t)stream);
-}
-
-// ---- gradient of a per-sample sparse adjacency's values [n_sets,nnz] -------------------------------
-static int check_edge_weight_grad_sets(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, int32_t n_sets) {
-  int st = check_edge_weight_grad(sh, gr, Cu);
-  if (st) return st;
   if (n_sets != 1 && n_sets != sh->Bg && n_sets != sh->R * sh->Bg) return MSGAT_ERR_SHAPE;
   return MSGAT_OK;
 }
 
 extern "C" size_t msgat_edge_weight_grad_sets_workspace_bytes(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu,
                                                               int32_t n_sets) {
-  if (check_edge_weight_grad_sets(sh, gr, Cu, n_sets) != MSGAT_OK) return 0;
-  // one set: the groups are split over blocks as in msgat_edge_weight_grad; else every (set, edge) has one owner
-  return n_sets == 1 ? edge_weight_grad_workspace_bytes(gr->nnz, sh->R * sh->Bg) : 0;
+  if (check_edge_weight_grad(sh, gr, Cu, n_sets) != MSGAT_OK) return 0;
+  return edge_weight_grad_workspace_bytes(gr->nnz, sh->R * sh->Bg, n_sets);
 }
 
 extern "C" int msgat_edge_weight_grad_sets(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, const float* dv,
                                            int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
                                            const float* lse, const float* dE_extra, int32_t n_sets, float* dval,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-  int st = check_edge_weight_grad_sets(sh, gr, Cu, n_sets);
+  int st = check_edge_weight_grad(sh, gr, Cu, n_sets);
   if (st) return st;
   if (dv_group_channels < 0 || (dv_group_channels > 0 && dv_group_channels < Cu)) return MSGAT_ERR_SHAPE;
   if (!dv || !feat || !q || !kW || !lse) return MSGAT_ERR_NULL;
   if (gr->nnz > 0 && (!dval || !gr->erow || !gr->col)) return MSGAT_ERR_NULL;
   const int G = sh->R * sh->Bg;
-  hipStream_t s = (hipStream_t)stream;
-  if (n_sets != 1)
-    return launch_edge_weight_grad_sets(dv, dv_group_channels, feat, q, kW, lse, dE_extra, gr->erow, gr->col, dval, G,
-                                        n_sets, Cu, sh->N, gr->nnz, sh->T, s);
-  // one set is one [N,N] matrix: the split kernel of msgat_edge_weight_grad, then the share of dE_extra
-  const size_t need = edge_weight_grad_workspace_bytes(gr->nnz, G);
+  const size_t need = edge_weight_grad_workspace_bytes(gr->nnz, G, n_sets);   // 0 unless n_sets = 1
   if (need > 0 && !workspace) return MSGAT_ERR_NULL;
   if (workspace_bytes < need) return MSGAT_ERR_WORKSPACE;
-  st = launch_edge_weight_grad(dv, dv_group_channels, feat, q, kW, lse, gr->erow, gr->col, dval,
-                               static_cast<float*>(workspace), G, Cu, sh->N, gr->nnz, sh->T, s);
-  if (st || !dE_extra) return st;
-  return launch_edge_softmax_grad(q, kW, lse, dE_extra, gr->erow, gr->col, dval, false, G, 1, sh->N, gr->nnz, sh->T, s);
+  return launch_edge_weight_grad(dv, dv_group_channels, feat, q, kW, lse, dE_extra, gr->erow, gr->col, dval,
+                                 static_cast<float*>(workspace), G, n_sets, Cu, sh->N, gr->nnz, sh->T, (hipStream_t)stream);
+}
+
+// the one-matrix entry points of before the value sets: n_sets = 1, no dE_extra
+extern "C" size_t msgat_edge_weight_grad_workspace_bytes(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu) {
+  return msgat_edge_weight_grad_sets_workspace_bytes(sh, gr, Cu, 1);
+}
+
+extern "C" int msgat_edge_weight_grad(const msgat_shape_t* sh, const msgat_graph_t* gr, int32_t Cu, const float* dv,
+                                      int32_t dv_group_channels, const float* feat, const float* q, const float* kW,
+                                      const float* lse, float* dval, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return msgat_edge_weight_grad_sets(sh, gr, Cu, dv, dv_group_channels, feat, q, kW, lse, nullptr, 1, dval, workspace,
+                                     workspace_bytes, stream);
 }
 
 // ---- stages -------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@
 //   msgat_edge_softmax_grad:  dst[v,e] += sum_{g % V == v} P_g[e] dEx[g,e]   at the CSR edges e
 //                             (E = P (.) A at the edges, so dA picks up P dE there; attention.py:36).
 //
-// Both re-create P from what the forward saved (q, kW, lse in log2 units), as k_adjacency_grad / k_edge_weight_grad do.
+// Both re-create P from what the forward saved (q, kW, lse in log2 units), as k_adjacency_grad / k_edge_weight_grad do:
+// through softmax_recreate.hpp, the one definition of that arithmetic.
 //
 // k_attention_map is bound by its writes (4 N^2 bytes per group against 8 N T bytes of operands).  A block owns a
 // 64 x 64 tile of one group, its 4 waves 32 x 32 quadrants (2 x 2 tiles of 16 x 16), and each tile is ONE chain of T/4
@@ -13,15 +14,13 @@
 // columns m), B = kW rows * log2 e (the rows n).  The accumulator then holds S^T, so lane (j, quad) owns row n = j and
 // the four consecutive columns 4 quad .. 4 quad + 3: one 16-B store per lane and tile when N % 4 == 0 (the row starts
 // are then 16-B aligned), four 4-B stores of consecutive addresses otherwise.
-#include "common.hpp"
+#include "softmax_recreate.hpp"
 
 namespace msgat {
 
 constexpr int kAmWaves = 4;
 constexpr int kAmBlock = 64 * kAmWaves;
 constexpr int kAmTile = 64;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int T, bool VEC>
 __global__ __launch_bounds__(kAmBlock) void k_attention_map(const float* __restrict__ q, const float* __restrict__ kW,
@@ -43,11 +42,7 @@ __global__ __launch_bounds__(kAmBlock) void k_attention_map(const float* __restr
   for (int h = 0; h < 2; ++h) {
     const int nr = min(n0 + wr + 16 * h + j, N - 1);
     const int mr = min(m0 + wc + 16 * h + j, N - 1);
-#pragma unroll
-    for (int kk = 0; kk < T4; ++kk) {
-      kb[h][kk] = kWg[(size_t)nr * T + 4 * kk + quad] * kLog2e;
-      qa[h][kk] = qg[(size_t)mr * T + 4 * kk + quad];
-    }
+    score_frags<T>(kWg, nr, qg, mr, quad, kb[h], qa[h]);
     ls[h] = lse[g * N + nr];
   }
 
@@ -57,9 +52,7 @@ __global__ __launch_bounds__(kAmBlock) void k_attention_map(const float* __restr
     const int n = n0 + wr + 16 * a + j;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      f32x4 S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[b][kk], kb[a][kk], S, 0, 0, 0);
+      const f32x4 S = score_tile<T>(qa[b], kb[a]);
       const int m = m0 + wc + 16 * b + 4 * quad;
       if (n >= N || m >= N) continue;
       float* dst = og + (size_t)n * N + m;
@@ -81,25 +74,19 @@ int launch_attention_map(const float* q, const float* kW, const float* lse, floa
                          hipStream_t s) {
   const dim3 grid(cdiv(N, kAmTile), cdiv(N, kAmTile), G);
   const bool vec = (N & 3) == 0;
-#define MSGAT_AM(TT)                                                                                               \
-  if (vec)                                                                                                         \
-    hipLaunchKernelGGL((k_attention_map<TT, true>), grid, dim3(kAmBlock), 0, s, q, kW, lse, out, N);               \
-  else                                                                                                             \
-    hipLaunchKernelGGL((k_attention_map<TT, false>), grid, dim3(kAmBlock), 0, s, q, kW, lse, out, N)
-  switch (T) {
-    case 4: MSGAT_AM(4); break;
-    case 8: MSGAT_AM(8); break;
-    case 12: MSGAT_AM(12); break;
-    case 16: MSGAT_AM(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_AM
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return dispatch_T(T, [&](auto t) -> int {
+    constexpr int TT = decltype(t)::value;
+    if (vec)
+      hipLaunchKernelGGL((k_attention_map<TT, true>), grid, dim3(kAmBlock), 0, s, q, kW, lse, out, N);
+    else
+      hipLaunchKernelGGL((k_attention_map<TT, false>), grid, dim3(kAmBlock), 0, s, q, kW, lse, out, N);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  });
 }
 
 // One lane per (edge, value set): it walks the set's groups in ascending order, re-creates P_g at the edge with the
-// forward's k-ordered score sum (k_edge_weight_grad's), and adds P_g dEx[g,e] to its own output element -- no other lane
+// forward's k-ordered score sum (edge_prob), and adds P_g dEx[g,e] to its own output element -- no other lane
 // writes it, so there are no atomics and the sum has a fixed order.  DENSE: the element is dst[v, erow[e], col[e]] of a
 // [V,N,N] gradient, else dst[v, e].
 template <int T, bool DENSE>
@@ -107,7 +94,6 @@ __global__ __launch_bounds__(kBlock) void k_edge_softmax_grad(const float* __res
                                                               const float* __restrict__ lse, const float* __restrict__ dEx,
                                                               const int* __restrict__ erow, const int* __restrict__ col,
                                                               float* __restrict__ dst, int G, int V, int N, int nnz) {
-  constexpr int T4 = T / 4;
   const int e = blockIdx.x * kBlock + threadIdx.x;
   const int v = blockIdx.y;
   if (e >= nnz) return;
@@ -115,18 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_edge_softmax_grad(const float* __res
   const size_t NT = (size_t)N * T;
   float acc = 0.f;
   for (int g = v; g < G; g += V) {
-    const float4* kr = reinterpret_cast<const float4*>(kW + g * NT + (size_t)n * T);
-    const float4* qr = reinterpret_cast<const float4*>(q + g * NT + (size_t)m * T);
-    float sc = 0.f;
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) {
-      const float4 a = kr[t4], b = qr[t4];
-      sc = fmaf(a.x * kLog2e, b.x, sc);
-      sc = fmaf(a.y * kLog2e, b.y, sc);
-      sc = fmaf(a.z * kLog2e, b.z, sc);
-      sc = fmaf(a.w * kLog2e, b.w, sc);
-    }
-    acc = fmaf(fast_exp2(sc - lse[(size_t)g * N + n]), dEx[(size_t)g * nnz + e], acc);
+    acc = fmaf(edge_prob<T>(q, kW, lse, g, n, m, N, NT), dEx[(size_t)g * nnz + e], acc);
   }
   float* o = DENSE ? dst + (size_t)v * N * N + (size_t)n * N + m : dst + (size_t)v * nnz + e;
   *o += acc;
@@ -136,23 +111,17 @@ int launch_edge_softmax_grad(const float* q, const float* kW, const float* lse, 
                              const int* col, float* dst, bool dense, int G, int V, int N, int nnz, int T, hipStream_t s) {
   if (nnz == 0) return MSGAT_OK;
   const dim3 grid(cdiv(nnz, kBlock), V);
-#define MSGAT_ES(TT)                                                                                                 \
-  if (dense)                                                                                                         \
-    hipLaunchKernelGGL((k_edge_softmax_grad<TT, true>), grid, dim3(kBlock), 0, s, q, kW, lse, dEx, erow, col, dst, G, \
-                       V, N, nnz);                                                                                   \
-  else                                                                                                               \
-    hipLaunchKernelGGL((k_edge_softmax_grad<TT, false>), grid, dim3(kBlock), 0, s, q, kW, lse, dEx, erow, col, dst,  \
-                       G, V, N, nnz)
-  switch (T) {
-    case 4: MSGAT_ES(4); break;
-    case 8: MSGAT_ES(8); break;
-    case 12: MSGAT_ES(12); break;
-    case 16: MSGAT_ES(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_ES
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return dispatch_T(T, [&](auto t) -> int {
+    constexpr int TT = decltype(t)::value;
+    if (dense)
+      hipLaunchKernelGGL((k_edge_softmax_grad<TT, true>), grid, dim3(kBlock), 0, s, q, kW, lse, dEx, erow, col, dst, G, V,
+                         N, nnz);
+    else
+      hipLaunchKernelGGL((k_edge_softmax_grad<TT, false>), grid, dim3(kBlock), 0, s, q, kW, lse, dEx, erow, col, dst, G, V,
+                         N, nnz);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  });
 }
 
 
@@ -187,8 +156,7 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_rows(const float* __restr
   const int n = n0 + j, nr = min(n, N - 1);   // rows past N are clamped: their results are never written
 
   float kb[T4];
-#pragma unroll
-  for (int kk = 0; kk < T4; ++kk) kb[kk] = kWg[(size_t)nr * T + 4 * kk + quad] * kLog2e;
+  score_frag_kw<T>(kWg, nr, quad, kb);
   const float ls = lse[g * N + nr];
   const float* dPr = dP + g * N * N + (size_t)nr * N;
 
@@ -200,8 +168,7 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_rows(const float* __restr
     for (int b = 0; b < 4; ++b) {
       const int mt = m0 + 16 * b, m = mt + 4 * quad;
       const int mr = min(mt + j, N - 1);
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) qa[b][kk] = qg[(size_t)mr * T + 4 * kk + quad];
+      score_frag_q<T>(qg, mr, quad, qa[b]);
 #pragma unroll
       for (int v = 0; v < 4; ++v) qv[b][v] = j < T ? qg[(size_t)min(m + v, N - 1) * T + j] : 0.f;
       if (VEC) {   // N % 4 == 0 and dP 16-B aligned: m + 3 < N whenever m < N
@@ -215,9 +182,7 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_rows(const float* __restr
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int m = m0 + 16 * b + 4 * quad;
-      f32x4 S = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[b][kk], kb[kk], S, 0, 0, 0);
+      const f32x4 S = score_tile<T>(qa[b], kb);
       float p[4], x[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
@@ -227,8 +192,8 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_rows(const float* __restr
       rsum += (x[0] + x[1]) + (x[2] + x[3]);
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        accX = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[b][v], x[v], accX, 0, 0, 0);
-        accP = __builtin_amdgcn_mfma_f32_16x16x4f32(qv[b][v], p[v], accP, 0, 0, 0);
+        accX = mfma_16x16x4(qv[b][v], x[v], accX);
+        accP = mfma_16x16x4(qv[b][v], p[v], accP);
       }
     }
   }
@@ -260,8 +225,7 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_cols(const float* __restr
   const int m = c0 + j, mr = min(m, N - 1);   // columns past N are clamped: their results are never written
 
   float qb[T4];
-#pragma unroll
-  for (int kk = 0; kk < T4; ++kk) qb[kk] = qg[(size_t)mr * T + 4 * kk + quad];
+  score_frag_q<T>(qg, mr, quad, qb);
   const float* dPc = dP + g * N * N + mr;
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};   // [t = 4 quad + v][m = j]
@@ -271,8 +235,7 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_cols(const float* __restr
     for (int b = 0; b < 4; ++b) {
       const int nt = nb + 16 * b;
       const int na = min(nt + j, N - 1);
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) ka[b][kk] = kWg[(size_t)na * T + 4 * kk + quad] * kLog2e;
+      score_frag_kw<T>(kWg, na, quad, ka[b]);
       lsj[b] = lse[g * N + na];
       rj[b] = r[g * N + na];
 #pragma unroll
@@ -285,14 +248,12 @@ __global__ __launch_bounds__(kMgBlock) void k_map_grad_cols(const float* __restr
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int nt = nb + 16 * b;
-      f32x4 S = {0.f, 0.f, 0.f, 0.f};   // [n = 4 quad + v][m = j]
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[b][kk], qb[kk], S, 0, 0, 0);
+      const f32x4 S = score_tile<T>(ka[b], qb);   // [n = 4 quad + v][m = j]
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         const float lv = __shfl(lsj[b], 4 * quad + v), rv = __shfl(rj[b], 4 * quad + v);   // lane i < 16 holds row nt + i
         const float ds = nt + 4 * quad + v < N ? fast_exp2(S[v] - lv) * (d[b][v] - rv) : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kv[b][v], ds, acc, 0, 0, 0);
+        acc = mfma_16x16x4(kv[b][v], ds, acc);
       }
     }
   }
@@ -365,22 +326,18 @@ int launch_map_grad(const float* q, const float* kW, const float* lse, const flo
   float* part = r + mg_align((size_t)G * N);
   const dim3 grid(cdiv(N, kMgSpan), G);
   const bool vec = (N & 3) == 0 && ((uintptr_t)dP & 15) == 0;
-#define MSGAT_MG(TT)                                                                                                  \
-  if (vec)                                                                                                            \
-    hipLaunchKernelGGL((k_map_grad_rows<TT, true>), grid, dim3(kMgBlock), 0, s, q, kW, lse, dP, dkW, r, N);           \
-  else                                                                                                                \
-    hipLaunchKernelGGL((k_map_grad_rows<TT, false>), grid, dim3(kMgBlock), 0, s, q, kW, lse, dP, dkW, r, N);          \
-  MSGAT_CHECK_LAUNCH();                                                                                               \
-  hipLaunchKernelGGL((k_map_grad_cols<TT>), grid, dim3(kMgBlock), 0, s, q, kW, lse, Wg, dP, dkW, r, dq_add, N, Bg)
-  switch (T) {
-    case 4: MSGAT_MG(4); break;
-    case 8: MSGAT_MG(8); break;
-    case 12: MSGAT_MG(12); break;
-    case 16: MSGAT_MG(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_MG
-  MSGAT_CHECK_LAUNCH();
+  const int st = dispatch_T(T, [&](auto t) -> int {
+    constexpr int TT = decltype(t)::value;
+    if (vec)
+      hipLaunchKernelGGL((k_map_grad_rows<TT, true>), grid, dim3(kMgBlock), 0, s, q, kW, lse, dP, dkW, r, N);
+    else
+      hipLaunchKernelGGL((k_map_grad_rows<TT, false>), grid, dim3(kMgBlock), 0, s, q, kW, lse, dP, dkW, r, N);
+    MSGAT_CHECK_LAUNCH();
+    hipLaunchKernelGGL((k_map_grad_cols<TT>), grid, dim3(kMgBlock), 0, s, q, kW, lse, Wg, dP, dkW, r, dq_add, N, Bg);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  });
+  if (st != MSGAT_OK) return st;
   const int nchunk = cdiv(N, kMgChunk);
   hipLaunchKernelGGL(k_map_grad_dwg, dim3(nchunk, G), dim3(kBlock), 0, s, q, dkW, part, N, T);
   MSGAT_CHECK_LAUNCH();

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "msgat_hip.h"
 
@@ -91,7 +93,30 @@ inline int grant_dynamic_lds(K kernel, size_t lds, LdsGrant& granted) {
 // the MFMA projection's matrix (+ row-pointer table) may take this much LDS: two blocks per CU still fit 160 KiB
 constexpr int kProjLdsMax = 78 * 1024;
 
-inline bool t_supported(int T) { return T == 4 || T == 8 || T == 12 || T == 16; }
+// The supported timestep counts, once: f(std::integral_constant<int, T>{}) for T = 4, 8, 12 or 16 (a launcher's generic
+// lambda instantiates its kernel on decltype(t)::value and returns a status), MSGAT_ERR_UNSUPPORTED for any other T.
+template <typename F>
+inline int dispatch_T(int T, F&& f) {
+  switch (T) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    default: return MSGAT_ERR_UNSUPPORTED;
+  }
+}
+inline bool t_supported(int T) {
+  return dispatch_T(T, [](auto) -> int { return MSGAT_OK; }) == MSGAT_OK;
+}
+
+// `groups` summed per output tile, split over blocks when `tiles` alone are fewer than `target_blocks`: `nsplit` <=
+// max_split blocks per tile, `per` consecutive groups each (no split is empty)
+inline void group_split(int tiles, int groups, int target_blocks, int max_split, int* nsplit, int* per) {
+  const int want = std::max(1, cdiv(target_blocks, tiles));
+  const int ns = std::min(std::min(groups, max_split), want);
+  *per = cdiv(groups, ns);
+  *nsplit = cdiv(groups, *per);
+}
 
 // how many channels of an [N,T] fp32 slab fit the per-block LDS budget
 inline int slab_channels(int N, int T, int Cu, int budget_bytes) {
@@ -284,17 +309,14 @@ size_t map_grad_workspace_bytes(int G, int N, int T);
 int launch_map_grad(const float* q, const float* kW, const float* lse, const float* Wg, const float* dP, float* dq_add,
                     float* dWg_add, float* ws, int G, int Bg, int N, int T, hipStream_t s);
 int launch_add_into(float* dst, const float* src, size_t n, hipStream_t s);   // dst[i] += src[i]
-// edge_weight_grad.hip: dval[e] = sum_g P_g[n_e,m_e] sum_{c,t} dv[g,c,n_e,t] feat[g,c,m_e,t] at the CSR edges (erow, col),
-// deterministic; ws: edge_weight_grad_workspace_bytes(nnz, G) bytes (the per-split partial sums; 0 when not split)
-size_t edge_weight_grad_workspace_bytes(int nnz, int G);
+// edge_weight_grad.hip: dval[v,e] = sum_{g % V == v} P_g[n_e,m_e] (H_g[n_e,m_e] + dEx[g,e]) at the CSR edges (erow, col),
+// H_g[n,m] = sum_{c,t} dv[g,c,n,t] feat[g,c,m,t], dEx [G,nnz] or nullptr; deterministic.  V = 1: the groups are split over
+// blocks and ws holds edge_weight_grad_workspace_bytes(nnz, G, 1) bytes of partial sums (0 when not split); V > 1: one
+// owner per (v,e), no workspace
+size_t edge_weight_grad_workspace_bytes(int nnz, int G, int V);
 int launch_edge_weight_grad(const float* dv, int dv_group_channels, const float* feat, const float* q, const float* kW,
-                            const float* lse, const int* erow, const int* col, float* dval, float* ws, int G, int Cu,
-                            int N, int nnz, int T, hipStream_t s);
-// edge_weight_grad_sets.hip: dval[v,e] = sum_{g % V == v} P_g[e] (H_g[e] + dEx[g,e]) at the CSR edges, V > 1 value sets
-// (dEx [G,nnz] or nullptr); one owner per (v,e), no workspace, deterministic
-int launch_edge_weight_grad_sets(const float* dv, int dv_group_channels, const float* feat, const float* q,
-                                 const float* kW, const float* lse, const float* dEx, const int* erow, const int* col,
-                                 float* dval, int G, int V, int Cu, int N, int nnz, int T, hipStream_t s);
+                            const float* lse, const float* dEx, const int* erow, const int* col, float* dval, float* ws,
+                            int G, int V, int Cu, int N, int nnz, int T, hipStream_t s);
 int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, float* kW, float* lse,
                   float* pq, float* E, float* Ec, int G, int Bg, int N, int T, hipStream_t s,
                   const float* x = nullptr, const float* alpha = nullptr, int C = 0, float* qout = nullptr,

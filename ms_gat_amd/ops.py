@@ -128,20 +128,22 @@ def edge_adjacency(crow: torch.Tensor, col: torch.Tensor, weight: torch.Tensor) 
 class _AdjacencyGrad:
     """The gradient route of an adjacency that requires grad, built by `_resolve_adjacency`.  Called by backward with
     `(dv, feat, Cu)` and the saved q, kW, lse, it returns the gradient in the caller's own shape and layout: dense [N,N] /
-    [V,N,N] from msgat_adjacency_grad (n_sets = V, the convention of `val_sets`), or from msgat_edge_weight_grad at the
-    stored edges of a sparse adjacency -- dense [nnz] in input order for an `edge_adjacency` weight, else a sparse tensor
-    with the caller's layout and indices; a sparse [V,N,N] adjacency (`pattern` a `graph.SparseSets`) from
-    msgat_edge_weight_grad_sets at every sample's stored entries, [V,nnz] for an `edge_adjacency` weight.  Either is
-    enqueued on `stream` after the backward of the other inputs."""
+    [V,N,N] from msgat_adjacency_grad (n_sets = V, the convention of `val_sets`), or from msgat_edge_weight_grad_sets at
+    the stored entries of a sparse adjacency, [N,N] (n_sets = 1) or [V,N,N] (`pattern` a `graph.SparseSets`) -- dense
+    [nnz] / [V,nnz] in input order for an `edge_adjacency` weight, else a sparse tensor with the caller's layout and
+    indices.  Either is enqueued on `stream` after the backward of the other inputs."""
 
     def __init__(self, target: torch.Tensor, pattern=None, parts=None, sets: bool = False):
         self.shape, self.pattern, self.parts, self.sets = tuple(target.shape), pattern, parts, sets
-        self.n_sets = pattern.n_sets if sets else (1 if target.dim() == 2 else self.shape[0])
+        if pattern is None:
+            self.n_sets = 1 if target.dim() == 2 else self.shape[0]
+        else:
+            self.n_sets = pattern.n_sets if sets else 1
 
     def __call__(self, plan: _GacnPlan, Cu: int, dv: torch.Tensor, dv_gs: int, feat: int, q: int, kW: int, lse: int,
                  stream, dE: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`dE` [G,nnz]: the gradient at the returned attention weights (`need_weights`), or None; its share
-        sum_g P_g dE_g is added at the edges by msgat_edge_softmax_grad."""
+        sum_g P_g dE_g is added at the edges (msgat_edge_softmax_grad, inside the library for a sparse adjacency)."""
         L = _lib.lib()
         shape, dev = C.byref(plan.shape), dv.device
         gstruct = C.byref(plan.gstruct)
@@ -155,36 +157,16 @@ class _AdjacencyGrad:
                 _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), self.n_sets, _ptr(dadj), None,
                                                      stream), "msgat_edge_softmax_grad")
             return dadj.view(self.shape)
-        if self.sets:
-            return self._sets(plan, Cu, dv, dv_gs, feat, q, kW, lse, stream, dE)
-        dval = torch.empty(self.pattern.structure.nnz, device=dev, dtype=torch.float32)
-        nbytes = int(L.msgat_edge_weight_grad_workspace_bytes(shape, gstruct, Cu))
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-        _lib.check(L.msgat_edge_weight_grad(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dval), _ptr(ws),
-                                            nbytes, stream), "msgat_edge_weight_grad")
-        if dE is not None:
-            _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), 1, None, _ptr(dval), stream),
-                       "msgat_edge_softmax_grad")
-        dval = self.pattern.to_input_order(dval)
-        if self.parts is None:                            # the weight of an edge_adjacency
-            return dval
-        layout, idx = self.parts
-        if layout == "csr":
-            return torch.sparse_csr_tensor(idx[0], idx[1], dval, self.shape)
-        return torch.sparse_coo_tensor(idx[0], dval, self.shape, is_coalesced=True)
-
-    def _sets(self, plan, Cu, dv, dv_gs, feat, q, kW, lse, stream, dE):
-        """One value set per sample or per group: one launch for dval [n_sets, nnz_union] (the share of `dE` folded in),
-        gathered back to the stored entries."""
-        L = _lib.lib()
-        shape, gstruct, dev = C.byref(plan.shape), C.byref(plan.gstruct), dv.device
-        dval = torch.empty((self.n_sets, max(self.pattern.structure.nnz, 1)), device=dev, dtype=torch.float32)
+        # dval [n_sets, nnz] on the structure (the union of the samples' patterns), gathered back to the stored entries
+        nnz = self.pattern.structure.nnz
+        dval = torch.empty((self.n_sets, max(nnz, 1)), device=dev, dtype=torch.float32)
         nbytes = int(L.msgat_edge_weight_grad_sets_workspace_bytes(shape, gstruct, Cu, self.n_sets))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
         _lib.check(L.msgat_edge_weight_grad_sets(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dE), self.n_sets,
                                                  _ptr(dval), _ptr(ws), nbytes, stream), "msgat_edge_weight_grad_sets")
-        dval = self.pattern.to_input_order(dval[:, : self.pattern.structure.nnz])
-        if self.parts is None:                            # the weight [V,nnz] of an edge_adjacency
+        dval = dval[:, :nnz]
+        dval = self.pattern.to_input_order(dval if self.sets else dval.reshape(-1))
+        if self.parts is None:                            # the weight [nnz] / [V,nnz] of an edge_adjacency
             return dval.view(self.shape)
         layout, idx = self.parts
         if layout == "csr":

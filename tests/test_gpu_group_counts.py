@@ -139,7 +139,7 @@ def _edge_weight_grad_sets(R, Bg, V, extra):
     return _same_bits(outs, "dval"), F.edge_adjacency_grad(q, kW, lse, dv, feat, V, rows, cols, dEx)
 
 
-# groups per set -> the kernel's NG form (csrc/edge_weight_grad_sets.hip: up to 4 a template parameter, 0 = four at a
+# groups per set -> the kernel's NG form (csrc/edge_weight_grad.hip: up to 4 a template parameter, 0 = four at a
 # time with the slots past the last group skipped): 4; then 4 + 1, 4 + 4 and 4 + 4 + 1 groups per trip
 _NG_FORM = {4: 4, 5: 0, 8: 0, 9: 0}
 
