@@ -26,15 +26,12 @@
 // computes the edge scores, so edge pass and backward agree on every score bit for bit.
 #include "common.hpp"
 #include "halfsplit.hpp"
+#include "softmax_recreate.hpp"   // f32x4, mfma_16x16x4: the score chains here are built on the primitive of the kernels that re-create them
 
 #include <cstdlib>
 
 namespace msgat {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 // NOT inline asm: hipcc's hazard recognizer does not look inside an asm statement, so an asm v_max3 that
 // reads an MFMA result straight out of VGPRs gets no wait states after the MFMA and sees stale registers
 // (found with 8-wave blocks, where the accumulators live in VGPRs: the deferred re-base then missed new
@@ -228,6 +225,289 @@ static size_t balance_pad_bytes(int nblocks, size_t static_lds) {
   return pad & ~(size_t)255;
 }
 
+// ---- the steps the 8-wave kernels and the 7 + 1 kernels share ----------------------------------------------------------
+// What differs between the forms is a parameter: where the stream ends (N, or the owners' Ca / Ra), how many lanes stage a
+// chunk (NTHR: kDBlock, or the owners' 64 kHOwners), how many waves' maxima are folded (NW), how many rows a block owns
+// (ROWS), the LDS buffers, and whether the payload product runs on fp16 planes (F16P) with a ones row (ONES_ROW).
+// Staging is double-buffered through registers: the loads of chunk c+1 are issued before chunk c is multiplied and land
+// in LDS after it.  All blocks of the grid are resident at once, so a block's own critical path -- not throughput -- set
+// the kernel time while every chunk began with an exposed global-load round trip.
+constexpr int kF4 = kPS / 4;                                              // float4s per staged payload row
+template <int NTHR>
+constexpr int kStage = (kDMC * kF4 + NTHR - 1) / NTHR;                    // forward: staging float4s per lane per chunk
+
+// -- forward --
+// float4 i of the staged image [column][q(T) | zeros] of the columns [c0, c0 + cols).  ONES_COL: what index T of the staged
+// row carries -- kNoOnes: nothing, x = v keep (the 7 + 1 kernels, always on the fp16 planes); k_scores adds the fp32 payload
+// product's ones column into x with an fma in all its forms: kOnesCol the column's 1, kZeroCol a +0 (its fp16 forms).
+enum { kNoOnes = -1, kZeroCol = 0, kOnesCol = 1 };
+template <int T, int XC, int ONES_COL>
+__device__ __forceinline__ float4 staged_q4(const QRows<T, XC>& qrows, int c0, int cols, int i) {
+  constexpr int T4 = T / 4;
+  const int c = i / kF4, f = i - c * kF4;
+  const bool live = (c < cols) && (f < T4);
+  const float4 v = qrows.row4((size_t)(c0 + (live ? c : 0)), live ? f : 0);
+  const float keep = live ? 1.f : 0.f;  // multiply, not select: keeps the load out of a branch
+  const float onec = (ONES_COL == kOnesCol && c < cols && f == T4) ? 1.f : 0.f;
+  return make_float4(ONES_COL == kNoOnes ? v.x * keep : fmaf(v.x, keep, onec), v.y * keep, v.z * keep, v.w * keep);
+}
+// The loads of the chunk of columns [c0, min(c0 + kDMC, end)) into registers, by NTHR lanes; premax (WANTMAX) = the largest
+// |q| of this lane's share.
+template <int T, int XC, int NTHR, int ONES_COL, bool WANTMAX>
+__device__ __forceinline__ void prefetch_columns(const QRows<T, XC>& qrows, int c0, int end, float4 (&pre)[kStage<NTHR>],
+                                                 float& premax) {
+  const int cols = min(kDMC, end - c0);
+  premax = 0.f;
+#pragma unroll
+  for (int k = 0; k < kStage<NTHR>; ++k) {
+    pre[k] = staged_q4<T, XC, ONES_COL>(qrows, c0, cols, threadIdx.x + k * NTHR);
+    if (WANTMAX) premax = fmaxf(premax, max_abs4(pre[k]));
+  }
+}
+// ... and into LDS as [column][q(T) | zeros], once every wave is done with the chunk before
+template <int NTHR>
+__device__ __forceinline__ void store_columns(float4* buf, const float4 (&pre)[kStage<NTHR>]) {
+#pragma unroll
+  for (int k = 0; k < kStage<NTHR>; ++k) {
+    const int i = threadIdx.x + k * NTHR;
+    if (i < kDMC * kF4) buf[i] = pre[k];
+  }
+}
+// The payload product of one trip (two tiles of 16 staged items from i0; p: this lane's eight P values), both passes.
+// On the fp16 planes: A2[i = s][k] = the planes' (h | m) of items i0 + 4 quad .. +3 at payload row s = j;
+// B2[k][j = own] = (Ph | Pm), then (Pm | Ph); tile a adds into da, tile b into db.
+__device__ __forceinline__ void payload_f16(const float* p, const uint4* planes, int i0, int j, int quad, float one, f32x4& da,
+                                            f32x4& db) {
+  const uint4 Fa = split_p(p, one), A2a = planes[((i0 >> 4) * 4 + quad) * 16 + j];
+  da = mfma_h(A2a, Fa, da); da = mfma_h(A2a, swap_halves(Fa), da);
+  const uint4 Fb = split_p(p + 4, one), A2b = planes[((i0 >> 4) * 4 + 4 + quad) * 16 + j];
+  db = mfma_h(A2b, Fb, db); db = mfma_h(A2b, swap_halves(Fb), db);
+}
+// On four exact-fp32 MFMAs per tile: A2[i = s][k = quad] = rows[item iq + rr][s = j] (iq = i0 + 4 quad);
+// B2[k = quad][j = own] = p[rr]; one accumulator per item of a quad
+__device__ __forceinline__ void payload_f32(const float* p, const float* rows, int iq, int j, f32x4& da, f32x4& db, f32x4& dc,
+                                            f32x4& dd) {
+  da = mfma_16x16x4(rows[(iq + 0) * kPS + j], p[0], da);
+  db = mfma_16x16x4(rows[(iq + 1) * kPS + j], p[1], db);
+  dc = mfma_16x16x4(rows[(iq + 2) * kPS + j], p[2], dc);
+  dd = mfma_16x16x4(rows[(iq + 3) * kPS + j], p[3], dd);
+  da = mfma_16x16x4(rows[(iq + 16) * kPS + j], p[4], da);
+  db = mfma_16x16x4(rows[(iq + 17) * kPS + j], p[5], db);
+  dc = mfma_16x16x4(rows[(iq + 18) * kPS + j], p[6], dc);
+  dd = mfma_16x16x4(rows[(iq + 19) * kPS + j], p[7], dd);
+}
+// One trip = two score tiles of the staged columns m0 .. m0 + 31 of `buf`: one max / vote / re-base decision for 32
+// columns, and the second tile's score chain is independent of the first tile's exponentials.  An odd last tile is a
+// tile of padding columns (masked).  Score chain: T/4 MFMAs from C = 0, k ascending.  da .. dd: the payload accumulators
+// (da, db; the forms that can run the fp32 payload product pass dc, dd as well).
+template <int T, bool WITH_PQ, bool F16P, class... Acc>
+__device__ __forceinline__ void score_trip(const float* buf, const uint4* planes, int m0, int cols, const float (&bfrag)[T / 4],
+                                           int j, int quad, float one, float& m, float& mo, float& lsum, f32x4& da, f32x4& db,
+                                           Acc&... dcd) {
+  constexpr int T4 = T / 4;
+  constexpr bool ONES = WITH_PQ && T < 16;
+  constexpr bool HP = WITH_PQ && F16P;
+  constexpr float kPOff = HP ? kPOffF : 0.f;        // P = 2^(S - m) is carried times 2^kPOff through the fp16 payload product
+  f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
+#pragma unroll
+  for (int kk = 0; kk < T4; ++kk) S0 = mfma_16x16x4(buf[(m0 + j) * kPS + 4 * kk + quad], bfrag[kk], S0);
+#pragma unroll
+  for (int kk = 0; kk < T4; ++kk) S1 = mfma_16x16x4(buf[(m0 + 16 + j) * kPS + 4 * kk + quad], bfrag[kk], S1);
+  const int mq = m0 + 4 * quad;  // this lane's columns: mq .. mq+3 and mq+16 .. mq+19
+  float sv[8];
+  if (m0 + 32 > cols) {  // wave-uniform: only the chunk's last trip can hold padding columns
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      sv[rr] = (mq + rr < cols) ? S0[rr] : -3.0e38f;
+      sv[4 + rr] = (mq + 16 + rr < cols) ? S1[rr] : -3.0e38f;
+    }
+  } else {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) { sv[rr] = S0[rr]; sv[4 + rr] = S1[rr]; }
+  }
+  const float cm = max3(max3(sv[0], sv[1], sv[2]), max3(sv[3], sv[4], sv[5]), fmaxf(sv[6], sv[7]));
+  if (__any(cm > m + kDefer)) {  // rare (deferred re-base); the row's 4 quads must agree on m
+    float cx = fmaxf(cm, __shfl_xor(cm, 16));
+    cx = fmaxf(cx, __shfl_xor(cx, 32));
+    const float mn = fmaxf(m, cx);
+    const float sc = fast_exp2(m - mn);  // m at its floor on the first tile -> 0
+    m = mn;
+    mo = mn - kPOff;
+    lsum *= sc;
+    if (WITH_PQ) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) { da[rr] *= sc; db[rr] *= sc; ((dcd[rr] *= sc), ...); }
+    }
+  }
+  float p[8];
+#pragma unroll
+  for (int rr = 0; rr < 8; ++rr) p[rr] = fast_exp2(sv[rr] - mo);
+  if (!ONES) lsum += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+  if constexpr (HP) payload_f16(p, planes, m0, j, quad, one, da, db);
+  else if constexpr (WITH_PQ) payload_f32(p, buf, mq, j, da, db, dcd...);
+}
+// Edge coefficients of the block's ROWS rows from n0: one lane per CSR edge, coalesced over e.  The VALU chain is the
+// MFMA's k order starting from 0, exactly what the backward re-creates.  with_tail: the rows' extents go to tl_rp and --
+// returns true -- when the rows have at most kTailEdges edges, their columns and coefficients to tl_col / tl_E.
+template <int T, int XC, bool VS, int ROWS>
+__device__ __forceinline__ bool edge_pass(const QRows<T, XC>& qrows, const float (*kw2s)[T], const float* lse2s,
+                                          const int* rowptr, const int* col, const float* val, const int* erow, float* E,
+                                          const int* cpos, float* Ec, int g, int n0, int N, int nnz, int val_sets,
+                                          bool with_tail, int* tl_rp, int* tl_col, float* tl_E) {
+  constexpr int T4 = T / 4;
+  // the adjacency weights this group multiplies by: its sample's own value set when the graph is per sample (VS)
+  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
+  const int e0 = rowptr[min(n0, N)];
+  const int e1 = rowptr[min(n0 + ROWS, N)];
+  const bool tail_cached = with_tail && e1 - e0 <= kTailEdges;    // block-uniform
+  if (with_tail && (int)threadIdx.x <= min(ROWS, N - n0)) tl_rp[threadIdx.x] = rowptr[n0 + threadIdx.x];
+  for (int e = e0 + threadIdx.x; e < e1; e += kDBlock) {
+    const int nl = erow[e] - n0;
+    const size_t ce = (size_t)col[e];
+    float a = 0.f;
+#pragma unroll
+    for (int t4 = 0; t4 < T4; ++t4) {
+      const float4 v = qrows.row4(ce, t4);
+      a = fmaf(v.x, kw2s[nl][4 * t4 + 0], a);
+      a = fmaf(v.y, kw2s[nl][4 * t4 + 1], a);
+      a = fmaf(v.z, kw2s[nl][4 * t4 + 2], a);
+      a = fmaf(v.w, kw2s[nl][4 * t4 + 3], a);
+    }
+    const float ev = fast_exp2(a - lse2s[nl]) * vals[e];
+    E[(size_t)g * nnz + e] = ev;
+    // the same coefficient at its CSC position: the transposed passes of backward (du = E^T dv on the CSC) then
+    // start without a re-ordering launch
+    if (Ec != nullptr) Ec[(size_t)g * nnz + cpos[e]] = ev;
+    if (tail_cached) { tl_col[e - e0] = (int)ce; tl_E[e - e0] = ev; }
+  }
+  return tail_cached;
+}
+// The aggregate + projection tail of the block's rows (agg_proj_tail), behind the edge pass
+template <int T, int XC, int ROWS>
+__device__ __forceinline__ void block_tail(const QRows<T, XC>& qrows, bool tail_cached, const int* tl_rp, const int* tl_col,
+                                           const float* tl_E, const int* col, const float* E, const float* apW, int apCo,
+                                           float* apY, float* apZ, int g, int r, int n0, int N, int nnz) {
+  __syncthreads();                // the block's coefficients are in LDS (or, uncached, in memory)
+  const size_t NT = (size_t)N * T;
+  const float* Wr = apW + (size_t)r * apCo * XC;
+  float* yg = apY != nullptr ? apY + (size_t)g * XC * NT : nullptr;
+  float* zg = apZ + (size_t)g * apCo * NT;
+  if (tail_cached)
+    agg_proj_tail<T, XC, true>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg, n0,
+                               min(ROWS, N - n0), N);
+  else
+    agg_proj_tail<T, XC, false>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg,
+                                n0, min(ROWS, N - n0), N);
+}
+
+// -- both passes: the payload planes of a staged chunk --
+// largest |entry| of the chunk: every lane's own maximum -> wave maximum -> wmax[wave] (read by all after the staging barrier)
+__device__ __forceinline__ void post_wave_max(float v, float* wmax, int wave, int lane) {
+  const float wm = wave_max(v);
+  if (lane == 0) wmax[wave] = wm;
+}
+// ... the first NW waves' maxima -> block maximum -> the exponent the planes of this chunk would want
+template <int NW>
+__device__ __forceinline__ int chunk_scale_exp(const float* wmax) {
+  float cmax = wmax[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) cmax = fmaxf(cmax, wmax[w]);
+  return payload_scale_exp(cmax);
+}
+// ... and the running scale follows it (block-uniform arithmetic): at a larger entry than any before, the sums so far
+// move to the new scale (`scaled`: this lane's sums carry the scale -- the forward's ones row does not)
+__device__ __forceinline__ void follow_plane_scale(int ec, int& sexp, f32x4& da, f32x4& db, bool scaled) {
+  if (ec < sexp) {
+    const float f = pow2i(ec - sexp);
+    if (scaled) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) { da[rr] *= f; db[rr] *= f; }
+    }
+    sexp = ec;
+  }
+}
+
+// -- backward --
+// The loads of the chunk of rows [r0, min(r0 + kDMC, end)) into registers, one row per lane (lanes >= kDMC never stage):
+// kW, delta, and lse2 - kPOff (+inf past the end: exp2(s - inf) = 0); premax (WANTMAX) = the row's largest |delta kW|.
+template <int T, bool WANTMAX>
+__device__ __forceinline__ void prefetch_rows(const float* kWg, const float* delta, const float* lse, int g, int N, int r0, int end,
+                                              float kPOff, float4 (&prek)[T / 4], float& pred, float& prel, float& premax) {
+  constexpr int T4 = T / 4;
+  const int rows = min(kDMC, end - r0);
+  const bool live = (int)threadIdx.x < rows;
+  const int nr = r0 + (live ? (int)threadIdx.x : 0);
+  const float keep = live ? 1.f : 0.f;  // multiply, not select: keeps the loads out of a branch
+  const float4* kr = reinterpret_cast<const float4*>(kWg + (size_t)nr * T);
+#pragma unroll
+  for (int t4 = 0; t4 < T4; ++t4) {
+    const float4 v = kr[t4];
+    prek[t4] = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
+  }
+  pred = delta[(size_t)g * N + nr] * keep;
+  const float lv = lse[(size_t)g * N + nr];
+  prel = live ? lv - kPOff : INFINITY;
+  premax = 0.f;
+  if (WANTMAX) {
+#pragma unroll
+    for (int t4 = 0; t4 < T4; ++t4) premax = fmaxf(premax, max_abs4(prek[t4]));
+    premax *= fabsf(pred);
+  }
+}
+// ... and into LDS: [row][kW2(T)] (scaled by log2 e first), [row][delta kW(T) | zeros] (fp32, the source of the payload
+// planes), [row] lse2
+template <int T>
+__device__ __forceinline__ void store_rows(float4* kw4, float4* dk4, float* lsew, const float4 (&prek)[T / 4], float pred,
+                                           float prel) {
+  constexpr int T4 = T / 4;
+  if (threadIdx.x < kDMC) {
+    const int i = threadIdx.x;
+#pragma unroll
+    for (int t4 = 0; t4 < kF4; ++t4) {
+      const float4 v = (t4 < T4) ? prek[t4 < T4 ? t4 : 0] : f4zero();
+      if (t4 < T4) kw4[i * T4 + t4] = make_float4(v.x * kLog2e, v.y * kLog2e, v.z * kLog2e, v.w * kLog2e);
+      dk4[i * kF4 + t4] = make_float4(v.x * pred, v.y * pred, v.z * pred, v.w * pred);
+    }
+    lsew[i] = prel;
+  }
+}
+// One trip = two row tiles rb .. rb + 31 of the staged rows (rows past the end carry lse = +inf and zero payload, so an
+// odd last tile is harmless).  Same products in the same k order as the forward's edge pass, accumulator starting at 0:
+// the score is re-created bit for bit, so 2^(s - lse2) equals the forward's softmax value (rows that are one-hot on an
+// edge cancel against the sparse term; a 1e-4 slip in the exponent would not).  Accumulators as in score_trip; dk: the fp32 payload product's rows.
+template <int T, bool F16P, class... Acc>
+__device__ __forceinline__ void column_trip(const float* kw, const float* dk, const uint4* planes, const float4* l4s, int rb,
+                                            const float (&bfrag)[T / 4], int j, int quad, float one, f32x4& da, f32x4& db,
+                                            Acc&... dcd) {
+  constexpr int T4 = T / 4;
+  f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
+#pragma unroll
+  for (int kk = 0; kk < T4; ++kk) S0 = mfma_16x16x4(kw[(rb + j) * T + 4 * kk + quad], bfrag[kk], S0);
+#pragma unroll
+  for (int kk = 0; kk < T4; ++kk) S1 = mfma_16x16x4(kw[(rb + 16 + j) * T + 4 * kk + quad], bfrag[kk], S1);
+  const int rq = rb + 4 * quad;            // this lane's rows: rq .. rq+3 and rq+16 .. rq+19
+  const float4 l4 = l4s[rq >> 2], l5 = l4s[(rq + 16) >> 2];         // quad-uniform
+  const float p[8] = {fast_exp2(S0[0] - l4.x), fast_exp2(S0[1] - l4.y), fast_exp2(S0[2] - l4.z), fast_exp2(S0[3] - l4.w),
+                      fast_exp2(S1[0] - l5.x), fast_exp2(S1[1] - l5.y), fast_exp2(S1[2] - l5.z), fast_exp2(S1[3] - l5.w)};
+  if constexpr (F16P) payload_f16(p, planes, rb, j, quad, one, da, db);
+  else payload_f32(p, dk, rq, j, da, db, dcd...);
+}
+// The end of a column: D2[s = 4 quad + rr][column] -- this lane owns dq[mcol][4 quad .. +3] -- gets the sparse in-edge term
+// minus `dense`, the column's dense sum in true units
+template <int T>
+__device__ __forceinline__ void finish_column(const int* colptr, const int* crow, const int* cperm, const float* gEg,
+                                              const float* kWg, float* dq, int g, int N, int mcol, int quad,
+                                              const float4& dense) {
+  const float4 sp = in_edge_term<T>(colptr, crow, cperm, gEg, kWg, mcol, quad);
+  float4* dst = reinterpret_cast<float4*>(dq + ((size_t)g * N + mcol) * T) + quad;
+  float4 v = *dst;
+  v.x += sp.x - dense.x;
+  v.y += sp.y - dense.y;
+  v.z += sp.z - dense.z;
+  v.w += sp.w - dense.w;
+  *dst = v;
+}
+
 // ---- forward -----------------------------------------------------------------------------------------
 // Wave w owns rows n0 + 16w .. +15 (B operand of the score product: their kW2) and streams all
 // columns.  Score tile D[i = column][j = row]: lane (row j, quad) holds its row against columns
@@ -262,10 +542,11 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
   const int n = n0 + 16 * wave + j;  // this lane's row (shared by its 4 quads)
   const bool valid = n < N;
   const QRows<T, XC> qrows = make_qrows<T, XC>(q, alpha, g, r, N);
-  const float* wg = Wg + (size_t)r * T * T;
 
+  const float* wg = Wg + (size_t)r * T * T;
   MSGAT_STAMP(0);
-  // B fragment of the row: kW2[n][4*kk + quad]; kW itself is stored unscaled
+  // B fragment of the row: kW2[n][4*kk + quad]; kW itself is stored unscaled.  This block is written out here and in
+  // k_scores7: as a shared step it cost k_scores 0.13 us of 9.06 at T = 4 (profiles/dense_shared/lab_variants.txt)
   float bfrag[T4];
   {
     float qr[T];
@@ -294,127 +575,34 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
   // and three v_add per tile leave the VALU stream (which the fp32 MFMAs share an issue port with)
   constexpr bool ONES = WITH_PQ && T < 16;
   constexpr bool HP = WITH_PQ && F16P;              // the fp16 payload path
-  constexpr float kPOff = HP ? kPOffF : 0.f;        // P = 2^(S - m) is carried times 2^kPOff through the fp16 payload product
   float m = -3.0e38f;  // running max of the row, identical in its 4 quads; finite floor, not -inf
-  float mo = m;        // m - kPOff: what the exponent subtracts
+  float mo = m;        // m - kPOff (score_trip): what the exponent subtracts
   float lsum = 0.f;    // this quad's share of sum_m 2^(S - mo) (unused with ONES)
-  f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da, dc = da, dd = da;  // payload accumulators (fp16 path: tile a / tile b of a trip)
+  f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da, dc = da, dd = da;  // payload accumulators (score_trip)
   int sexp = 100;      // the payload planes carry q * 2^sexp (block-uniform; follows the largest |q| staged so far)
   if (HP)
     for (int i = threadIdx.x; i < kPlaneU4; i += kDBlock) pl4[i] = make_uint4(0u, 0u, 0u, 0u);   // rows past the ones row stay zero
 
-  // Staging is double-buffered through registers: the loads of chunk c+1 are issued before chunk c
-  // is multiplied and land in LDS after it.  All blocks of the grid are resident at once, so a
-  // block's own critical path -- not throughput -- set the kernel time while every chunk began
-  // with an exposed global-load round trip.
-  constexpr int kF4 = kPS / 4;                                   // float4s per staged column
-  constexpr int kSt = (kDMC * kF4 + kDBlock - 1) / kDBlock;       // staging float4s per lane per chunk
-  float4 pre[kSt];
+  float4 pre[kStage<kDBlock>];
   float premax = 0.f;   // largest |q| among this lane's share of the prefetched chunk
-  auto prefetch = [&](int c0) {
-    const int cols = min(kDMC, N - c0);
-    premax = 0.f;
-#pragma unroll
-    for (int k = 0; k < kSt; ++k) {
-      const int i = threadIdx.x + k * kDBlock;
-      const int c = i / kF4, f = i - c * kF4;
-      const bool live = (c < cols) && (f < T4);
-      const float4 v = qrows.row4((size_t)(c0 + (live ? c : 0)), live ? f : 0);
-      const float keep = live ? 1.f : 0.f;  // multiply, not select: keeps the load out of a branch
-      const float onec = (!F16P && ONES && c < cols && f == T4) ? 1.f : 0.f;  // fp32 payload: the ones column, at index T of the staged row
-      pre[k] = make_float4(fmaf(v.x, keep, onec), v.y * keep, v.z * keep, v.w * keep);
-      if (HP) premax = fmaxf(premax, max_abs4(pre[k]));
-    }
-  };
+  auto prefetch = [&](int c0) { prefetch_columns<T, XC, kDBlock, (!F16P && ONES) ? kOnesCol : kZeroCol, HP>(qrows, c0, N, pre, premax); };
   prefetch(0);
   for (int c0 = 0; c0 < N; c0 += kDMC) {
     const int cols = min(kDMC, N - c0);
     const int cols16 = (cols + 15) & ~15;
     prio_by_progress(c0, N);
     __syncthreads();  // every wave is done with the previous chunk
-#pragma unroll
-    for (int k = 0; k < kSt; ++k) {
-      const int i = threadIdx.x + k * kDBlock;
-      if (i < kDMC * kF4) qs4[i] = pre[k];
-    }
-    if (HP) {
-      const float wm = wave_max(premax);
-      if (lane == 0) wmax[wave] = wm;
-    }
+    store_columns<kDBlock>(qs4, pre);
+    if (HP) post_wave_max(premax, wmax, wave, lane);
     __syncthreads();
-    if (HP) {   // the chunk's payload planes, at the running scale (block-uniform arithmetic)
-      float cmax = wmax[0];
-#pragma unroll
-      for (int w = 1; w < kDWaves; ++w) cmax = fmaxf(cmax, wmax[w]);
-      const int ec = payload_scale_exp(cmax);
-      if (ec < sexp) {   // a larger entry than any before: the sums so far move to the new scale (the ones row does not)
-        const float f = pow2i(ec - sexp);
-        if (quad < T4) {
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) { da[rr] *= f; db[rr] *= f; }
-        }
-        sexp = ec;
-      }
+    if (HP) {   // the chunk's payload planes, at the running scale
+      follow_plane_scale(chunk_scale_exp<kDWaves>(wmax), sexp, da, db, quad < T4);
       build_payload_planes<T, ONES>(qsw, kPS, cols, pow2i(sexp), one, pl4, threadIdx.x, kDBlock);
       __syncthreads();
     }
     prefetch(min(c0 + kDMC, max(N - 1, 0) / kDMC * kDMC));  // next chunk (the last trip re-reads its own)
-    // two score tiles per trip: one max / vote / re-base decision for 32 columns, and the second tile's score chain
-    // is independent of the first tile's exponentials.  An odd last tile is a tile of padding columns (masked).
-    for (int m0 = 0; m0 < cols16; m0 += 32) {
-      f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S0 = mfma16(qsw[(m0 + j) * kPS + 4 * kk + quad], bfrag[kk], S0);
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S1 = mfma16(qsw[(m0 + 16 + j) * kPS + 4 * kk + quad], bfrag[kk], S1);
-      const int mq = m0 + 4 * quad;  // this lane's columns: mq .. mq+3 and mq+16 .. mq+19
-      float sv[8];
-      if (m0 + 32 > cols) {  // wave-uniform: only the chunk's last trip can hold padding columns
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          sv[rr] = (mq + rr < cols) ? S0[rr] : -3.0e38f;
-          sv[4 + rr] = (mq + 16 + rr < cols) ? S1[rr] : -3.0e38f;
-        }
-      } else {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) { sv[rr] = S0[rr]; sv[4 + rr] = S1[rr]; }
-      }
-      const float cm = max3(max3(sv[0], sv[1], sv[2]), max3(sv[3], sv[4], sv[5]), fmaxf(sv[6], sv[7]));
-      if (__any(cm > m + kDefer)) {  // rare (deferred re-base); the row's 4 quads must agree on m
-        float cx = fmaxf(cm, __shfl_xor(cm, 16));
-        cx = fmaxf(cx, __shfl_xor(cx, 32));
-        const float mn = fmaxf(m, cx);
-        const float sc = fast_exp2(m - mn);  // m at its floor on the first tile -> 0
-        m = mn;
-        mo = mn - kPOff;
-        lsum *= sc;
-        if (WITH_PQ) {
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) { da[rr] *= sc; db[rr] *= sc; dc[rr] *= sc; dd[rr] *= sc; }
-        }
-      }
-      float p[8];
-#pragma unroll
-      for (int rr = 0; rr < 8; ++rr) p[rr] = fast_exp2(sv[rr] - mo);
-      if (!ONES) lsum += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-      if (HP) {
-        // A2[i = s][k] = the planes' (h | m) of columns m0 + 4 quad .. +3 at row s = j; B2[k][j = row] = (Ph | Pm), then (Pm | Ph)
-        const uint4 Fa = split_p(p, one), A2a = pl4[((m0 >> 4) * 4 + quad) * 16 + j];
-        da = mfma_h(A2a, Fa, da); da = mfma_h(A2a, swap_halves(Fa), da);
-        const uint4 Fb = split_p(p + 4, one), A2b = pl4[((m0 >> 4) * 4 + 4 + quad) * 16 + j];
-        db = mfma_h(A2b, Fb, db); db = mfma_h(A2b, swap_halves(Fb), db);
-      } else if (WITH_PQ) {
-        // A2[i = s][k = quad] = q[column mq + rr][s = j]; B2[k = quad][j = row] = p[rr]
-        da = mfma16(qsw[(mq + 0) * kPS + j], p[0], da);
-        db = mfma16(qsw[(mq + 1) * kPS + j], p[1], db);
-        dc = mfma16(qsw[(mq + 2) * kPS + j], p[2], dc);
-        dd = mfma16(qsw[(mq + 3) * kPS + j], p[3], dd);
-        da = mfma16(qsw[(mq + 16) * kPS + j], p[4], da);
-        db = mfma16(qsw[(mq + 17) * kPS + j], p[5], db);
-        dc = mfma16(qsw[(mq + 18) * kPS + j], p[6], dc);
-        dd = mfma16(qsw[(mq + 19) * kPS + j], p[7], dd);
-      }
-    }
+    for (int m0 = 0; m0 < cols16; m0 += 32)
+      score_trip<T, WITH_PQ, F16P>(qsw, pl4, m0, cols, bfrag, j, quad, one, m, mo, lsum, da, db, dc, dd);
     if (c0 == 0) MSGAT_STAMP(2);
   }
 
@@ -440,51 +628,14 @@ __global__ __launch_bounds__(kDBlock) void k_scores(
   __syncthreads();
   MSGAT_STAMP(4);
 
-  // edge coefficients of this block's rows: one lane per CSR edge, coalesced over e.  The VALU
-  // chain below is the MFMA's k order starting from 0, exactly what k_bwd_dense_col re-creates.
-  // the adjacency weights this group multiplies by: its sample's own value set when the graph is per sample (VS)
-  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
-  const int e0 = rowptr[n0];
-  const int e1 = rowptr[min(n0 + kDRows, N)];
   __shared__ int tl_rp[XC > 0 ? kDRows + 1 : 1];
   __shared__ int tl_col[XC > 0 ? kTailEdges : 1];
   __shared__ float tl_E[XC > 0 ? kTailEdges : 1];
   const bool with_tail = XC > 0 && apZ != nullptr;               // kernel-uniform
-  const bool tail_cached = with_tail && e1 - e0 <= kTailEdges;    // block-uniform
-  if (with_tail && (int)threadIdx.x <= min(kDRows, N - n0)) tl_rp[threadIdx.x] = rowptr[n0 + threadIdx.x];
-  for (int e = e0 + threadIdx.x; e < e1; e += kDBlock) {
-    const int nl = erow[e] - n0;
-    const size_t ce = (size_t)col[e];
-    float a = 0.f;
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) {
-      const float4 v = qrows.row4(ce, t4);
-      a = fmaf(v.x, kw2s[nl][4 * t4 + 0], a);
-      a = fmaf(v.y, kw2s[nl][4 * t4 + 1], a);
-      a = fmaf(v.z, kw2s[nl][4 * t4 + 2], a);
-      a = fmaf(v.w, kw2s[nl][4 * t4 + 3], a);
-    }
-    const float ev = fast_exp2(a - lse2s[nl]) * vals[e];
-    E[(size_t)g * nnz + e] = ev;
-    // the same coefficient at its CSC position: the transposed passes of backward (du = E^T dv on the CSC) then
-    // start without a re-ordering launch
-    if (Ec != nullptr) Ec[(size_t)g * nnz + cpos[e]] = ev;
-    if (tail_cached) { tl_col[e - e0] = (int)ce; tl_E[e - e0] = ev; }
-  }
+  const bool tail_cached = edge_pass<T, XC, VS, kDRows>(qrows, kw2s, lse2s, rowptr, col, val, erow, E, cpos, Ec, g, n0, N, nnz,
+                                                        val_sets, with_tail, tl_rp, tl_col, tl_E);
   MSGAT_STAMP(5);
-  if (with_tail) {
-    __syncthreads();                // the block's coefficients are in LDS (or, uncached, in memory)
-    const size_t NT = (size_t)N * T;
-    const float* Wr = apW + (size_t)r * apCo * XC;
-    float* yg = apY != nullptr ? apY + (size_t)g * XC * NT : nullptr;
-    float* zg = apZ + (size_t)g * apCo * NT;
-    if (tail_cached)
-      agg_proj_tail<T, XC, true>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg, n0,
-                                 min(kDRows, N - n0), N);
-    else
-      agg_proj_tail<T, XC, false>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg,
-                                  n0, min(kDRows, N - n0), N);
-  }
+  if (with_tail) block_tail<T, XC, kDRows>(qrows, tail_cached, tl_rp, tl_col, tl_E, col, E, apW, apCo, apY, apZ, g, r, n0, N, nnz);
 }
 
 // ---- forward, 7 owner waves + 1 helper wave ---------------------------------------------------------------------
@@ -509,10 +660,12 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
     int val_sets) {   // see k_scores
   constexpr int T4 = T / 4;
   constexpr bool ONES = WITH_PQ && T < 16;
-  constexpr float kPOff = WITH_PQ ? kPOffF : 0.f;               // see k_scores
+  constexpr float kPOff = WITH_PQ ? kPOffF : 0.f;               // see score_trip
   constexpr int kOThreads = 64 * kHOwners;                      // lanes that stage the owners' chunks
-  __shared__ float4 qs4[kDMC * kPS / 4];  // owners' chunk of columns [0, Ca)
-  __shared__ float4 qh4[kDMC * kPS / 4];  // the helper's columns [Ca, N), staged once
+  constexpr int kBufF4 = kDMC * kPS / 4;
+  __shared__ float4 stage4[2 * kBufF4];   // both staging buffers; after the score loops, the tail's arrays (below)
+  float4* const qs4 = stage4;             // owners' chunk of columns [0, Ca)
+  float4* const qh4 = stage4 + kBufF4;    // the helper's columns [Ca, N), staged once
   __shared__ uint4 pl4[WITH_PQ ? kPlaneU4 : 1];   // payload planes of the owners' chunk (see build_payload_planes)
   __shared__ uint4 ph4[WITH_PQ ? kPlaneU4 : 1];   //                of the helper's columns, built once
   __shared__ float wmax[kDWaves];
@@ -533,113 +686,46 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
   const int n = n0 + 16 * wave + j;
   const bool valid = owner && n < N;
   const QRows<T, XC> qrows = make_qrows<T, XC>(q, alpha, g, r, N);
-  const float* wg = Wg + (size_t)r * T * T;
   const int colsh = N - Ca;             // 1 .. kDMC (host-checked)
   const int nchunk = cdiv(Ca, kDMC);
 
-  // columns [0, Ca) go through LDS in chunks, register-prefetched by the owners' lanes (see k_scores).  The first chunk is
+  // columns [0, Ca) go through LDS in chunks, register-prefetched by the owners' lanes.  The first chunk is
   // requested before anything else: its round trip then overlaps the helper's columns, their planes and the rows' kW -- all
   // 768 blocks start together, and as the FIRST thing after two barriers it was 9 K of a block's 90 K clocks (in-kernel stamps)
-  constexpr int kSt = (kDMC * (kPS / 4) + kOThreads - 1) / kOThreads;
-  float4 pre[kSt];
+  float4 pre[kStage<kOThreads>];
   float premax = 0.f;
-  auto prefetch = [&](int c0) {
-    constexpr int kF4p = kPS / 4;
-    const int cols = min(kDMC, Ca - c0);
-    premax = 0.f;
-#pragma unroll
-    for (int k = 0; k < kSt; ++k) {
-      const int i = threadIdx.x + k * kOThreads;
-      const int c = i / kF4p, f = i - c * kF4p;
-      const bool live = (c < cols) && (f < T4);
-      const float4 v = qrows.row4((size_t)(c0 + (live ? c : 0)), live ? f : 0);
-      const float keep = live ? 1.f : 0.f;
-      pre[k] = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
-      premax = fmaxf(premax, max_abs4(pre[k]));
-    }
-  };
+  auto prefetch = [&](int c0) { prefetch_columns<T, XC, kOThreads, kNoOnes, WITH_PQ>(qrows, c0, Ca, pre, premax); };
   if (owner) prefetch(0);
 
   // the helper's columns, by every lane of the block
-  constexpr int kF4 = kPS / 4;
   MSGAT_STAMP(0);
   float hmaxabs = 0.f;
   for (int i = threadIdx.x; i < kDMC * kF4; i += kDBlock) {
-    const int c = i / kF4, f = i - c * kF4;
-    const bool live = (c < colsh) && (f < T4);
-    const float4 v = qrows.row4((size_t)(Ca + (live ? c : 0)), live ? f : 0);
-    const float keep = live ? 1.f : 0.f;
-    const float4 w = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
+    const float4 w = staged_q4<T, XC, kNoOnes>(qrows, Ca, colsh, i);
     qh4[i] = w;
     hmaxabs = fmaxf(hmaxabs, max_abs4(w));
   }
   int sexp = 100, sexph = 100;   // scale exponents of the owners' planes (running) and of the helper's (fixed)
   if (WITH_PQ) {
     for (int i = threadIdx.x; i < kPlaneU4; i += kDBlock) { pl4[i] = make_uint4(0u, 0u, 0u, 0u); ph4[i] = make_uint4(0u, 0u, 0u, 0u); }
-    const float wm = wave_max(hmaxabs);
-    if (lane == 0) wmax[wave] = wm;
+    post_wave_max(hmaxabs, wmax, wave, lane);
     __syncthreads();
-    float cmax = wmax[0];
-#pragma unroll
-    for (int w = 1; w < kDWaves; ++w) cmax = fmaxf(cmax, wmax[w]);
-    sexph = payload_scale_exp(cmax);
+    sexph = chunk_scale_exp<kDWaves>(wmax);
     build_payload_planes<T, ONES>(qhw, kPS, colsh, pow2i(sexph), one, ph4, threadIdx.x, kDBlock);
     __syncthreads();   // (wmax is re-used by the owners' chunks)
   }
 
   float bfrag[T4];
-
   float m = -3.0e38f, mo = m;   // running max; mo = m - kPOff is what the exponent subtracts
   float lsum = 0.f;
   f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da;
-
-  // one trip = two score tiles of the staged columns m0 .. m0 + 31 of `buf` (k_scores' inner trip)
   auto trip = [&](const float* buf, const uint4* planes, int m0, int cols) {
-    f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
-#pragma unroll
-    for (int kk = 0; kk < T4; ++kk) S0 = mfma16(buf[(m0 + j) * kPS + 4 * kk + quad], bfrag[kk], S0);
-#pragma unroll
-    for (int kk = 0; kk < T4; ++kk) S1 = mfma16(buf[(m0 + 16 + j) * kPS + 4 * kk + quad], bfrag[kk], S1);
-    const int mq = m0 + 4 * quad;
-    float sv[8];
-    if (m0 + 32 > cols) {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        sv[rr] = (mq + rr < cols) ? S0[rr] : -3.0e38f;
-        sv[4 + rr] = (mq + 16 + rr < cols) ? S1[rr] : -3.0e38f;
-      }
-    } else {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) { sv[rr] = S0[rr]; sv[4 + rr] = S1[rr]; }
-    }
-    const float cm = max3(max3(sv[0], sv[1], sv[2]), max3(sv[3], sv[4], sv[5]), fmaxf(sv[6], sv[7]));
-    if (__any(cm > m + kDefer)) {
-      float cx = fmaxf(cm, __shfl_xor(cm, 16));
-      cx = fmaxf(cx, __shfl_xor(cx, 32));
-      const float mn = fmaxf(m, cx);
-      const float sc = fast_exp2(m - mn);
-      m = mn;
-      mo = mn - kPOff;
-      lsum *= sc;
-      if (WITH_PQ) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) { da[rr] *= sc; db[rr] *= sc; }
-      }
-    }
-    float p[8];
-#pragma unroll
-    for (int rr = 0; rr < 8; ++rr) p[rr] = fast_exp2(sv[rr] - mo);
-    if (!ONES) lsum += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-    if (WITH_PQ) {   // see k_scores
-      const uint4 Fa = split_p(p, one), A2a = planes[((m0 >> 4) * 4 + quad) * 16 + j];
-      da = mfma_h(A2a, Fa, da); da = mfma_h(A2a, swap_halves(Fa), da);
-      const uint4 Fb = split_p(p + 4, one), A2b = planes[((m0 >> 4) * 4 + 4 + quad) * 16 + j];
-      db = mfma_h(A2b, Fb, db); db = mfma_h(A2b, swap_halves(Fb), db);
-    }
+    score_trip<T, WITH_PQ, true>(buf, planes, m0, cols, bfrag, j, quad, one, m, mo, lsum, da, db);
   };
 
   if (owner) {
     // (the first chunk was requested at the top of the kernel; it lands while the rows' kW is computed)
+    const float* wg = Wg + (size_t)r * T * T;
     {
       float qr[T];
 #pragma unroll
@@ -666,29 +752,11 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
       const int cols16 = (cols + 15) & ~15;
       prio_by_progress(c0, Ca);
       __syncthreads();
-#pragma unroll
-      for (int k = 0; k < kSt; ++k) {
-        const int i = threadIdx.x + k * kOThreads;
-        if (i < kDMC * kF4) qs4[i] = pre[k];
-      }
-      if (WITH_PQ) {
-        const float wm = wave_max(premax);
-        if (lane == 0) wmax[wave] = wm;
-      }
+      store_columns<kOThreads>(qs4, pre);
+      if (WITH_PQ) post_wave_max(premax, wmax, wave, lane);
       __syncthreads();
-      if (WITH_PQ) {   // the chunk's payload planes at the running scale, by the owners' lanes (see k_scores)
-        float cmax = wmax[0];
-#pragma unroll
-        for (int w = 1; w < kHOwners; ++w) cmax = fmaxf(cmax, wmax[w]);
-        const int ec = payload_scale_exp(cmax);
-        if (ec < sexp) {
-          const float f = pow2i(ec - sexp);
-          if (quad < T4) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) { da[rr] *= f; db[rr] *= f; }
-          }
-          sexp = ec;
-        }
+      if (WITH_PQ) {   // the chunk's payload planes at the running scale, by the owners' lanes
+        follow_plane_scale(chunk_scale_exp<kHOwners>(wmax), sexp, da, db, quad < T4);
         build_payload_planes<T, ONES>(qsw, kPS, cols, pow2i(sexp), one, pl4, threadIdx.x, kOThreads);
         __syncthreads();
       }
@@ -759,50 +827,17 @@ __global__ __launch_bounds__(kDBlock) void k_scores7(
   __syncthreads();
   MSGAT_STAMP(4);
 
-  // edge coefficients of this block's rows (see k_scores)
-  const float* __restrict__ vals = VS ? val + (size_t)(g % val_sets) * nnz : val;
-  const int e0 = rowptr[min(n0, N)];
-  const int e1 = rowptr[min(n0 + kHRows, N)];
   // the tail's row extents / edge list / coefficients take over the staging buffers (dead behind the barrier above): with
   // LDS of their own the block would not fit three to a CU beside the payload planes
-  static_assert((kHRows + 4 + 2 * kTailEdges) * 4 <= (int)sizeof(float4) * 2 * (kDMC * kPS / 4), "tail arrays exceed the staging buffers");
-  int* tl_rp = reinterpret_cast<int*>(qs4);
+  static_assert((kHRows + 4 + 2 * kTailEdges) * 4 <= (int)sizeof(stage4), "tail arrays exceed the staging buffers");
+  int* tl_rp = reinterpret_cast<int*>(stage4);
   int* tl_col = tl_rp + kHRows + 4;
   float* tl_E = reinterpret_cast<float*>(tl_col + kTailEdges);
   const bool with_tail = XC > 0 && apZ != nullptr;               // kernel-uniform
-  const bool tail_cached = with_tail && e1 - e0 <= kTailEdges;    // block-uniform
-  if (with_tail && (int)threadIdx.x <= min(kHRows, N - n0)) tl_rp[threadIdx.x] = rowptr[n0 + threadIdx.x];
-  for (int e = e0 + threadIdx.x; e < e1; e += kDBlock) {
-    const int nl = erow[e] - n0;
-    const size_t ce = (size_t)col[e];
-    float a = 0.f;
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) {
-      const float4 v = qrows.row4(ce, t4);
-      a = fmaf(v.x, kw2s[nl][4 * t4 + 0], a);
-      a = fmaf(v.y, kw2s[nl][4 * t4 + 1], a);
-      a = fmaf(v.z, kw2s[nl][4 * t4 + 2], a);
-      a = fmaf(v.w, kw2s[nl][4 * t4 + 3], a);
-    }
-    const float ev = fast_exp2(a - lse2s[nl]) * vals[e];
-    E[(size_t)g * nnz + e] = ev;
-    if (Ec != nullptr) Ec[(size_t)g * nnz + cpos[e]] = ev;
-    if (tail_cached) { tl_col[e - e0] = (int)ce; tl_E[e - e0] = ev; }
-  }
+  const bool tail_cached = edge_pass<T, XC, VS, kHRows>(qrows, kw2s, lse2s, rowptr, col, val, erow, E, cpos, Ec, g, n0, N, nnz,
+                                                        val_sets, with_tail, tl_rp, tl_col, tl_E);
   MSGAT_STAMP(5);
-  if (with_tail) {   // see k_scores
-    __syncthreads();
-    const size_t NT = (size_t)N * T;
-    const float* Wr = apW + (size_t)r * apCo * XC;
-    float* yg = apY != nullptr ? apY + (size_t)g * XC * NT : nullptr;
-    float* zg = apZ + (size_t)g * apCo * NT;
-    if (tail_cached)
-      agg_proj_tail<T, XC, true>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg, n0,
-                                 min(kHRows, N - n0), N);
-    else
-      agg_proj_tail<T, XC, false>(qrows, (lds_ci)tl_rp, (lds_ci)tl_col, (lds_cf)tl_E, col, E + (size_t)g * nnz, Wr, apCo, yg, zg,
-                                  n0, min(kHRows, N - n0), N);
-  }
+  if (with_tail) block_tail<T, XC, kHRows>(qrows, tail_cached, tl_rp, tl_col, tl_E, col, E, apW, apCo, apY, apZ, g, r, n0, N, nnz);
 }
 
 // Column split of the 7 + 1 form: the helper takes Th = 2 round(Tn / 18) of the Tn = ceil(N / 16) column tiles (an even
@@ -835,12 +870,12 @@ static int launch_scores_x(const msgat_graph_t& gr, const float* q, const float*
     const size_t lds7 = sizeof(float) * (2 * kDMC * kPS + kHRows * T + 3 * kHRows + kHRows * 17 + kDWaves) +
                         (pq != nullptr ? 2 * sizeof(uint4) * kPlaneU4 : 2 * sizeof(uint4));   // + the payload planes (the tail re-uses the staging buffers)
     const size_t pad7 = balance_pad_bytes((int)(grid7.x * grid7.y), lds7);
-    if (pq != nullptr)
-      hipLaunchKernelGGL((k_scores7<T, true, XC, VS>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
-    else
-      hipLaunchKernelGGL((k_scores7<T, false, XC, VS>), grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                         gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
+    auto launch7 = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid7, dim3(kDBlock), pad7, s, q, Wg, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse, pq, E,
+                         gr.cpos, Ec, Bg, N, gr.nnz, Ca, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
+    };
+    if (pq != nullptr) launch7(k_scores7<T, true, XC, VS>);
+    else launch7(k_scores7<T, false, XC, VS>);
     MSGAT_CHECK_LAUNCH();
     return MSGAT_OK;
   }
@@ -850,15 +885,14 @@ static int launch_scores_x(const msgat_graph_t& gr, const float* q, const float*
                             (pq != nullptr ? sizeof(uint4) * kPlaneU4 : sizeof(uint4)) +
                             (XC > 0 ? sizeof(int) * (kDRows + 1 + 2 * kTailEdges) : 0);
   const size_t pad = balance_pad_bytes((int)(grid.x * grid.y), static_lds);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val, gr.erow, kW, lse, pq, E, gr.cpos,
+                       Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
+  };
   if (pq != nullptr && (int)(grid.x * grid.y) <= device_cu_count())   // a grid that leaves CUs empty: the fp32 payload product
-    hipLaunchKernelGGL((k_scores<T, true, XC, false, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
-  else if (pq != nullptr)
-    hipLaunchKernelGGL((k_scores<T, true, XC, true, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
-  else
-    hipLaunchKernelGGL((k_scores<T, false, XC, true, VS>), grid, dim3(kDBlock), pad, s, q, Wg, gr.rowptr, gr.col, gr.val,
-                       gr.erow, kW, lse, pq, E, gr.cpos, Ec, Bg, N, gr.nnz, alpha, qout, apW, apCo, apY, apZ, 1.0f, vsets);
+    launch(k_scores<T, true, XC, false, VS>);
+  else if (pq != nullptr) launch(k_scores<T, true, XC, true, VS>);
+  else launch(k_scores<T, false, XC, true, VS>);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
@@ -914,51 +948,9 @@ int launch_scores(const msgat_graph_t& gr, const float* q, const float* Wg, floa
   }
   if (x != nullptr && (!scores_take_x(C, apZ != nullptr) || alpha == nullptr || qout == nullptr)) return MSGAT_ERR_UNSUPPORTED;
   if (apZ != nullptr && (x == nullptr || apW == nullptr || apCo <= 0)) return MSGAT_ERR_UNSUPPORTED;
-  switch (T) {
-    case 4: return launch_scores_t<4>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
-    case 8: return launch_scores_t<8>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
-    case 12: return launch_scores_t<12>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
-    case 16: return launch_scores_t<16>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
-}
-
-// The sparse part of the column pass: sum over the in-edges of column m of g_e kW[row_e], this lane's four timesteps.
-// Four edges per trip with clamped, unconditional loads (the surplus masked by a zero coefficient): a trip is two
-// dependent round trips (edge ids, then coefficient and kW row) behind the column extent, whatever the degree.  As one
-// edge per iteration the loop was 2 x degree dependent round trips at the END of a kernel whose blocks are all resident
-// -- pure tail.  Same order of the sum, same bits.
-template <int T>
-__device__ __forceinline__ float4 in_edge_term(const int* __restrict__ colptr, const int* __restrict__ crow,
-                                               const int* __restrict__ cperm, const float* __restrict__ gEg,
-                                               const float* __restrict__ kWg, int mcol, int quad) {
-  const int c0 = colptr[mcol], c1 = colptr[mcol + 1];
-  float4 sp = f4zero();
-  for (int k = c0; k < c1; k += 4) {
-    int ep[4], er[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int kk = min(k + i, c1 - 1);
-      ep[i] = cperm[kk];
-      er[i] = crow[kk];
-    }
-    float ge[4];
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float raw = gEg[ep[i]];
-      ge[i] = (k + i < c1) ? raw : 0.f;
-      v[i] = reinterpret_cast<const float4*>(kWg + (size_t)er[i] * T)[quad];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      sp.x = fmaf(ge[i], v[i].x, sp.x);
-      sp.y = fmaf(ge[i], v[i].y, sp.y);
-      sp.z = fmaf(ge[i], v[i].z, sp.z);
-      sp.w = fmaf(ge[i], v[i].w, sp.w);
-    }
-  }
-  return sp;
+  return dispatch_T(T, [&](auto t) -> int {
+    return launch_scores_t<decltype(t)::value>(gr, q, Wg, kW, lse, pq, E, Ec, G, Bg, N, s, x, alpha, C, qout, apW, apCo, apY, apZ);
+  });
 }
 
 // ---- backward: dense column pass ------------------------------------------------------------------------
@@ -995,120 +987,40 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col(
 #pragma unroll
   for (int kk = 0; kk < T4; ++kk) bfrag[kk] = valid ? qg[(size_t)mcol * T + 4 * kk + quad] : 0.f;
 
-  f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da, dc = da, dd = da;  // payload accumulators (fp16 path: row tile a / b of a trip)
+  f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da, dc = da, dd = da;  // payload accumulators (column_trip)
   int sexp = 100;                              // the planes carry delta kW * 2^sexp (running, see k_scores)
   constexpr float kPOff = F16P ? kPOffB : 0.f;
   if (F16P)
     for (int i = threadIdx.x; i < kPlaneU4; i += kDBlock) pl4[i] = make_uint4(0u, 0u, 0u, 0u);   // rows s >= T stay zero
 
-  // register-prefetched staging (see k_scores): one row per lane per chunk
   static_assert(kDMC <= kDBlock, "at most one staged row per lane");
   float4 prek[T4];
   float pred = 0.f, prel = 0.f, premax = 0.f;
-  auto prefetch = [&](int r0) {
-    const int rows = min(kDMC, N - r0);
-    const bool live = (int)threadIdx.x < rows;  // lanes >= kDMC never stage
-    const int nr = r0 + (live ? (int)threadIdx.x : 0);
-    const float keep = live ? 1.f : 0.f;  // multiply, not select: keeps the loads out of a branch
-    const float4* kr = reinterpret_cast<const float4*>(kWg + (size_t)nr * T);
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) {
-      const float4 v = kr[t4];
-      prek[t4] = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
-    }
-    pred = delta[(size_t)g * N + nr] * keep;
-    const float lv = lse[(size_t)g * N + nr];
-    prel = live ? lv - kPOff : INFINITY;  // exp2(s - inf) = 0 for rows past the end
-    premax = 0.f;
-    if (F16P) {
-#pragma unroll
-      for (int t4 = 0; t4 < T4; ++t4) premax = fmaxf(premax, max_abs4(prek[t4]));
-      premax *= fabsf(pred);
-    }
-  };
+  auto prefetch = [&](int r0) { prefetch_rows<T, F16P>(kWg, delta, lse, g, N, r0, N, kPOff, prek, pred, prel, premax); };
   prefetch(0);
   for (int r0 = 0; r0 < N; r0 += kDMC) {
     const int rows = min(kDMC, N - r0);
     const int rows16 = (rows + 15) & ~15;
     prio_by_progress(r0, N);
     __syncthreads();  // every wave is done with the previous chunk
-    if (threadIdx.x < kDMC) {
-      const int i = threadIdx.x;
-#pragma unroll
-      for (int t4 = 0; t4 < kPS / 4; ++t4) {
-        const float4 v = (t4 < T4) ? prek[t4 < T4 ? t4 : 0] : f4zero();
-        if (t4 < T4) kwr4[i * T4 + t4] = make_float4(v.x * kLog2e, v.y * kLog2e, v.z * kLog2e, v.w * kLog2e);
-        dkr4[i * (kPS / 4) + t4] = make_float4(v.x * pred, v.y * pred, v.z * pred, v.w * pred);
-      }
-      lsew[i] = prel;
-    }
-    if (F16P) {
-      const float wm = wave_max(premax);
-      if (lane == 0) wmax[wave] = wm;
-    }
+    store_rows<T>(kwr4, dkr4, lsew, prek, pred, prel);
+    if (F16P) post_wave_max(premax, wmax, wave, lane);
     __syncthreads();
-    if (F16P) {   // the chunk's payload planes at the running scale (see k_scores)
-      float cmax = wmax[0];
-#pragma unroll
-      for (int w = 1; w < kDWaves; ++w) cmax = fmaxf(cmax, wmax[w]);
-      const int ec = payload_scale_exp(cmax);
-      if (ec < sexp) {
-        const float f = pow2i(ec - sexp);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) { da[rr] *= f; db[rr] *= f; }
-        sexp = ec;
-      }
+    if (F16P) {   // the chunk's payload planes at the running scale
+      follow_plane_scale(chunk_scale_exp<kDWaves>(wmax), sexp, da, db, true);
       build_payload_planes<T, false>(dkr, kPS, rows, pow2i(sexp), one, pl4, threadIdx.x, kDBlock);
       __syncthreads();
     }
     prefetch(min(r0 + kDMC, max(N - 1, 0) / kDMC * kDMC));  // next chunk (the last trip re-reads its own)
-    // same products in the same k order as the forward's edge pass, accumulator starting at 0: the
-    // score is re-created bit for bit, so 2^(s - lse2) equals the forward's softmax value (rows that
-    // are one-hot on an edge cancel against the sparse term; a 1e-4 slip in the exponent would not).
-    // two row tiles per trip (rows past the end carry lse = +inf and zero payload, so an odd last tile is harmless)
-    for (int rb = 0; rb < rows16; rb += 32) {
-      f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S0 = mfma16(kwr[(rb + j) * T + 4 * kk + quad], bfrag[kk], S0);
-#pragma unroll
-      for (int kk = 0; kk < T4; ++kk) S1 = mfma16(kwr[(rb + 16 + j) * T + 4 * kk + quad], bfrag[kk], S1);
-      const int rq = rb + 4 * quad;            // this lane's rows: rq .. rq+3 and rq+16 .. rq+19
-      const float4 l4 = lse4[rq >> 2], l5 = lse4[(rq + 16) >> 2];         // quad-uniform
-      const float p0 = fast_exp2(S0[0] - l4.x), p1 = fast_exp2(S0[1] - l4.y);
-      const float p2 = fast_exp2(S0[2] - l4.z), p3 = fast_exp2(S0[3] - l4.w);
-      const float p4 = fast_exp2(S1[0] - l5.x), p5 = fast_exp2(S1[1] - l5.y);
-      const float p6 = fast_exp2(S1[2] - l5.z), p7 = fast_exp2(S1[3] - l5.w);
-      // A2[i = s][k] = the planes' (h | m) of rows rb + 4 quad .. +3 at s = j; B2[k][j = column] = (Ph | Pm), then (Pm | Ph)
-      if (F16P) {
-        const float pa[4] = {p0, p1, p2, p3}, pb[4] = {p4, p5, p6, p7};
-        const uint4 Fa = split_p(pa, one), A2a = pl4[((rb >> 4) * 4 + quad) * 16 + j];
-        da = mfma_h(A2a, Fa, da); da = mfma_h(A2a, swap_halves(Fa), da);
-        const uint4 Fb = split_p(pb, one), A2b = pl4[((rb >> 4) * 4 + 4 + quad) * 16 + j];
-        db = mfma_h(A2b, Fb, db); db = mfma_h(A2b, swap_halves(Fb), db);
-      } else {   // A2[i = s][k = quad] = (delta kW)[row rq + rr][s = j]; B2[k = quad][j = column] = p[rr]
-        da = mfma16(dkr[(rq + 0) * kPS + j], p0, da);
-        db = mfma16(dkr[(rq + 1) * kPS + j], p1, db);
-        dc = mfma16(dkr[(rq + 2) * kPS + j], p2, dc);
-        dd = mfma16(dkr[(rq + 3) * kPS + j], p3, dd);
-        da = mfma16(dkr[(rq + 16) * kPS + j], p4, da);
-        db = mfma16(dkr[(rq + 17) * kPS + j], p5, db);
-        dc = mfma16(dkr[(rq + 18) * kPS + j], p6, dc);
-        dd = mfma16(dkr[(rq + 19) * kPS + j], p7, dd);
-      }
-    }
+    for (int rb = 0; rb < rows16; rb += 32) column_trip<T, F16P>(kwr, dkr, pl4, lse4, rb, bfrag, j, quad, one, da, db, dc, dd);
   }
   if (!valid || quad >= T4) return;
   const float unscale = F16P ? pow2i(-sexp - (int)kPOffB) : 1.f;   // the planes' scale and P's 2^14
-
-  // D2[s = 4*quad + rr][column]: this lane owns dq[mcol][4*quad .. +3]; add the sparse in-edge term
-  const float4 sp = in_edge_term<T>(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, mcol, quad);
-  float4* dst = reinterpret_cast<float4*>(dq + ((size_t)g * N + mcol) * T) + quad;
-  float4 v = *dst;
-  v.x += sp.x - ((da[0] + db[0]) + (dc[0] + dd[0])) * unscale;
-  v.y += sp.y - ((da[1] + db[1]) + (dc[1] + dd[1])) * unscale;
-  v.z += sp.z - ((da[2] + db[2]) + (dc[2] + dd[2])) * unscale;
-  v.w += sp.w - ((da[3] + db[3]) + (dc[3] + dd[3])) * unscale;
-  *dst = v;
+  finish_column<T>(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, dq, g, N, mcol, quad,
+                   make_float4(((da[0] + db[0]) + (dc[0] + dd[0])) * unscale,
+                               ((da[1] + db[1]) + (dc[1] + dd[1])) * unscale,
+                               ((da[2] + db[2]) + (dc[2] + dd[2])) * unscale,
+                               ((da[3] + db[3]) + (dc[3] + dd[3])) * unscale));
 }
 
 // ---- backward column pass, 7 owner waves + 1 helper wave (see k_scores7) -------------------------------------------
@@ -1136,7 +1048,6 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col7(
   const float* dkr = reinterpret_cast<const float*>(dkr4);
   float* lsew = reinterpret_cast<float*>(lse4);
   const float* kwh = reinterpret_cast<const float*>(kwh4);
-  const float* dkh = dkr;   // the helper's fp32 delta kW rows pass through the owners' staging buffer: they are only the source of ph4
   float* lshw = reinterpret_cast<float*>(lsh4);
 
   const int g = blockIdx.y;
@@ -1151,76 +1062,35 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col7(
   const int rowsh = N - Ra;   // 1 .. kDMC
   const int nchunk = cdiv(Ra, kDMC);
 
-  // the owners' first chunk is requested before anything else (see k_scores7)
-  // rows [0, Ra) in chunks, one staged row per lane of the first two owner waves (see k_bwd_dense_col)
+  // rows [0, Ra) in chunks, one staged row per lane of the first two owner waves; the owners' first chunk is requested
+  // before anything else (see k_scores7)
   static_assert(kDMC <= kOThreads, "at most one staged row per owner lane");
   float4 prek[T4];
   float pred = 0.f, prel = 0.f, premax = 0.f;
-  auto prefetch = [&](int r0) {
-    const int rows = min(kDMC, Ra - r0);
-    const bool live = (int)threadIdx.x < rows;
-    const int nr = r0 + (live ? (int)threadIdx.x : 0);
-    const float keep = live ? 1.f : 0.f;
-    const float4* kr = reinterpret_cast<const float4*>(kWg + (size_t)nr * T);
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) {
-      const float4 v = kr[t4];
-      prek[t4] = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
-    }
-    pred = delta[(size_t)g * N + nr] * keep;
-    const float lv = lse[(size_t)g * N + nr];
-    prel = live ? lv - kPOffB : INFINITY;
-    premax = 0.f;
-#pragma unroll
-    for (int t4 = 0; t4 < T4; ++t4) premax = fmaxf(premax, max_abs4(prek[t4]));
-    premax *= fabsf(pred);
-  };
+  auto prefetch = [&](int r0) { prefetch_rows<T, true>(kWg, delta, lse, g, N, r0, Ra, kPOffB, prek, pred, prel, premax); };
   if (owner) prefetch(0);
 
-  // the helper's rows and the block's q rows, by every lane
-  float hmaxabs = 0.f;
-  if (threadIdx.x < kDMC) {
-    const int i = threadIdx.x;
-    const bool live = i < rowsh;
-    const int nr = Ra + (live ? i : 0);
-    const float keep = live ? 1.f : 0.f;
-    const float pd = delta[(size_t)g * N + nr] * keep;
-    const float lv = lse[(size_t)g * N + nr];
-    const float4* kr = reinterpret_cast<const float4*>(kWg + (size_t)nr * T);
-#pragma unroll
-    for (int t4 = 0; t4 < kPS / 4; ++t4) {
-      float4 v = f4zero();
-      if (t4 < T4) {
-        v = kr[t4 < T4 ? t4 : 0];
-        v = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
-        kwh4[i * T4 + t4] = make_float4(v.x * kLog2e, v.y * kLog2e, v.z * kLog2e, v.w * kLog2e);
-      }
-      const float4 w = make_float4(v.x * pd, v.y * pd, v.z * pd, v.w * pd);
-      dkr4[i * (kPS / 4) + t4] = w;
-      hmaxabs = fmaxf(hmaxabs, max_abs4(w));
-    }
-    lshw[i] = live ? lv - kPOffB : INFINITY;
+  // the helper's rows and the block's q rows, by every lane.  The helper's fp32 delta kW rows pass through the owners'
+  // staging buffer: they are only the source of ph4.  On purpose the shared pair as it is: lanes >= kDMC load row Ra and
+  // keep nothing of it (before, they were guarded out), and preh lives beside the owners' prek until the store.
+  {
+    float4 preh[T4];
+    float predh, prelh, hmaxabs;
+    prefetch_rows<T, true>(kWg, delta, lse, g, N, Ra, N, kPOffB, preh, predh, prelh, hmaxabs);
+    store_rows<T>(kwh4, dkr4, lshw, preh, predh, prelh);
+    post_wave_max(hmaxabs, wmax, wave, lane);
   }
   for (int i = threadIdx.x; i < kPlaneU4; i += kDBlock) { pl4[i] = make_uint4(0u, 0u, 0u, 0u); ph4[i] = make_uint4(0u, 0u, 0u, 0u); }
-  {
-    const float wm = wave_max(hmaxabs);
-    if (lane == 0) wmax[wave] = wm;
-  }
   for (int i = threadIdx.x; i < kHRows * T; i += kDBlock) {
     const int cl = i / T, t = i - cl * T;
     qfs[cl][t] = (m0c + cl < N) ? qg[(size_t)(m0c + cl) * T + t] : 0.f;
   }
 
   __syncthreads();
-  int sexp = 100, sexph;   // scale exponents of the owners' planes (running) and of the helper's (fixed)
-  {
-    float cmax = wmax[0];
-#pragma unroll
-    for (int w = 1; w < kDWaves; ++w) cmax = fmaxf(cmax, wmax[w]);
-    sexph = payload_scale_exp(cmax);
-    build_payload_planes<T, false>(dkh, kPS, rowsh, pow2i(sexph), one, ph4, threadIdx.x, kDBlock);
-    __syncthreads();   // (wmax is re-used by the owners' chunks)
-  }
+  int sexp = 100;                                     // scale exponent of the owners' planes (running)
+  const int sexph = chunk_scale_exp<kDWaves>(wmax);   //                of the helper's (fixed)
+  build_payload_planes<T, false>(dkr, kPS, rowsh, pow2i(sexph), one, ph4, threadIdx.x, kDBlock);
+  __syncthreads();   // (wmax and the staging buffer are re-used by the owners' chunks)
 
   float bfrag[T4];
   if (owner) {
@@ -1228,25 +1098,8 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col7(
     for (int kk = 0; kk < T4; ++kk) bfrag[kk] = valid ? qg[(size_t)mcol * T + 4 * kk + quad] : 0.f;
   }
   f32x4 da = {0.f, 0.f, 0.f, 0.f}, db = da;
-
-  // one trip = two row tiles rb .. rb + 31 of the staged rows (k_bwd_dense_col's inner trip)
   auto trip = [&](const float* kw, const uint4* planes, const float4* l4s, int rb) {
-    f32x4 S0 = {0.f, 0.f, 0.f, 0.f}, S1 = S0;
-#pragma unroll
-    for (int kk = 0; kk < T4; ++kk) S0 = mfma16(kw[(rb + j) * T + 4 * kk + quad], bfrag[kk], S0);
-#pragma unroll
-    for (int kk = 0; kk < T4; ++kk) S1 = mfma16(kw[(rb + 16 + j) * T + 4 * kk + quad], bfrag[kk], S1);
-    const int rq = rb + 4 * quad;
-    const float4 l4 = l4s[rq >> 2], l5 = l4s[(rq + 16) >> 2];
-    const float p0 = fast_exp2(S0[0] - l4.x), p1 = fast_exp2(S0[1] - l4.y);
-    const float p2 = fast_exp2(S0[2] - l4.z), p3 = fast_exp2(S0[3] - l4.w);
-    const float p4 = fast_exp2(S1[0] - l5.x), p5 = fast_exp2(S1[1] - l5.y);
-    const float p6 = fast_exp2(S1[2] - l5.z), p7 = fast_exp2(S1[3] - l5.w);
-    const float pa[4] = {p0, p1, p2, p3}, pb[4] = {p4, p5, p6, p7};   // see k_bwd_dense_col
-    const uint4 Fa = split_p(pa, one), A2a = planes[((rb >> 4) * 4 + quad) * 16 + j];
-    da = mfma_h(A2a, Fa, da); da = mfma_h(A2a, swap_halves(Fa), da);
-    const uint4 Fb = split_p(pb, one), A2b = planes[((rb >> 4) * 4 + 4 + quad) * 16 + j];
-    db = mfma_h(A2b, Fb, db); db = mfma_h(A2b, swap_halves(Fb), db);
+    column_trip<T, true>(kw, dkr, planes, l4s, rb, bfrag, j, quad, one, da, db);
   };
 
   if (owner) {
@@ -1256,35 +1109,13 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col7(
       const int rows16 = (rows + 15) & ~15;
       prio_by_progress(r0, Ra);
       __syncthreads();
-      if (threadIdx.x < kDMC) {
-        const int i = threadIdx.x;
-#pragma unroll
-        for (int t4 = 0; t4 < kPS / 4; ++t4) {
-          const float4 v = (t4 < T4) ? prek[t4 < T4 ? t4 : 0] : f4zero();
-          if (t4 < T4) kwr4[i * T4 + t4] = make_float4(v.x * kLog2e, v.y * kLog2e, v.z * kLog2e, v.w * kLog2e);
-          dkr4[i * (kPS / 4) + t4] = make_float4(v.x * pred, v.y * pred, v.z * pred, v.w * pred);
-        }
-        lsew[i] = prel;
-      }
-      {
-        const float wm = wave_max(premax);
-        if (lane == 0) wmax[wave] = wm;
-      }
+      store_rows<T>(kwr4, dkr4, lsew, prek, pred, prel);
+      post_wave_max(premax, wmax, wave, lane);
       __syncthreads();
-      {   // the chunk's payload planes at the running scale, by the owners' lanes
-        float cmax = wmax[0];
-#pragma unroll
-        for (int w = 1; w < kHOwners; ++w) cmax = fmaxf(cmax, wmax[w]);
-        const int ec = payload_scale_exp(cmax);
-        if (ec < sexp) {
-          const float f = pow2i(ec - sexp);
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) { da[rr] *= f; db[rr] *= f; }
-          sexp = ec;
-        }
-        build_payload_planes<T, false>(dkr, kPS, rows, pow2i(sexp), one, pl4, threadIdx.x, kOThreads);
-        __syncthreads();
-      }
+      // the chunk's payload planes at the running scale, by the owners' lanes
+      follow_plane_scale(chunk_scale_exp<kHOwners>(wmax), sexp, da, db, true);
+      build_payload_planes<T, false>(dkr, kPS, rows, pow2i(sexp), one, pl4, threadIdx.x, kOThreads);
+      __syncthreads();
       prefetch(min(r0 + kDMC, max(Ra - 1, 0) / kDMC * kDMC));
       for (int rb = 0; rb < rows16; rb += 32) trip(kwr, pl4, lse4, rb);
     }
@@ -1308,15 +1139,12 @@ __global__ __launch_bounds__(kDBlock) void k_bwd_dense_col7(
   if (!valid || quad >= T4) return;
 
   const int cl = 16 * wave + j;
-  const float4 sp = in_edge_term<T>(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, mcol, quad);
-  float4* dst = reinterpret_cast<float4*>(dq + ((size_t)g * N + mcol) * T) + quad;
-  float4 v = *dst;
   const float unscale = pow2i(-sexp - (int)kPOffB);   // the own sums to true units (the helper's are already)
-  v.x += sp.x - ((da[0] + db[0]) * unscale + hpay[cl][4 * quad + 0]);
-  v.y += sp.y - ((da[1] + db[1]) * unscale + hpay[cl][4 * quad + 1]);
-  v.z += sp.z - ((da[2] + db[2]) * unscale + hpay[cl][4 * quad + 2]);
-  v.w += sp.w - ((da[3] + db[3]) * unscale + hpay[cl][4 * quad + 3]);
-  *dst = v;
+  finish_column<T>(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, dq, g, N, mcol, quad,
+                   make_float4((da[0] + db[0]) * unscale + hpay[cl][4 * quad + 0],
+                               (da[1] + db[1]) * unscale + hpay[cl][4 * quad + 1],
+                               (da[2] + db[2]) * unscale + hpay[cl][4 * quad + 2],
+                               (da[3] + db[3]) * unscale + hpay[cl][4 * quad + 3]));
 }
 
 int launch_bwd_dense_col(const msgat_graph_t& gr, const float* q, const float* kW,
@@ -1326,48 +1154,32 @@ int launch_bwd_dense_col(const msgat_graph_t& gr, const float* q, const float* k
     if (scratch == nullptr) return MSGAT_ERR_WORKSPACE;
     return launch_bwd_dense_col_b(gr, q, kW, lse, delta, gE, dq, G, N, s, scratch);
   }
+  return dispatch_T(T, [&](auto t) -> int {
+    constexpr int TT = decltype(t)::value;
 #ifndef MSGAT_NO_SCORES7
-  if (const int Ra = scores7_owner_columns(N, G)) {   // the same split, over rows
-    dim3 grid7(cdiv(N, kHRows), G);
-    const size_t lds7 = sizeof(float) * (2 * (kDMC * T + kDMC) + kDMC * kPS + kHRows * T + kHRows * 17 + kDWaves) +
-                        2 * sizeof(uint4) * kPlaneU4;
-    const size_t pad7 = balance_pad_bytes((int)(grid7.x * grid7.y), lds7);
-#define MSGAT_DCOL7(TT)                                                                                    \
-  hipLaunchKernelGGL(k_bwd_dense_col7<TT>, grid7, dim3(kDBlock), pad7, s, q, kW, lse, delta, gE, gr.colptr, \
-                     gr.crow, gr.cperm, dq, N, gr.nnz, Ra, 1.0f)
-    switch (T) {
-      case 4: MSGAT_DCOL7(4); break;
-      case 8: MSGAT_DCOL7(8); break;
-      case 12: MSGAT_DCOL7(12); break;
-      case 16: MSGAT_DCOL7(16); break;
-      default: return MSGAT_ERR_UNSUPPORTED;
+    if (const int Ra = scores7_owner_columns(N, G)) {   // the same split, over rows
+      dim3 grid7(cdiv(N, kHRows), G);
+      const size_t lds7 = sizeof(float) * (2 * (kDMC * TT + kDMC) + kDMC * kPS + kHRows * TT + kHRows * 17 + kDWaves) +
+                          2 * sizeof(uint4) * kPlaneU4;
+      const size_t pad7 = balance_pad_bytes((int)(grid7.x * grid7.y), lds7);
+      hipLaunchKernelGGL(k_bwd_dense_col7<TT>, grid7, dim3(kDBlock), pad7, s, q, kW, lse, delta, gE, gr.colptr, gr.crow,
+                         gr.cperm, dq, N, gr.nnz, Ra, 1.0f);
+      MSGAT_CHECK_LAUNCH();
+      return MSGAT_OK;
     }
-#undef MSGAT_DCOL7
+#endif
+    dim3 grid(cdiv(N, kDRows), G);
+    const size_t static_lds = sizeof(float) * (kDMC * TT + kDMC * kPS + kDMC + kDWaves) + sizeof(uint4) * kPlaneU4;
+    const size_t pad = balance_pad_bytes((int)(grid.x * grid.y), static_lds);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(kDBlock), pad, s, q, kW, lse, delta, gE, gr.colptr, gr.crow, gr.cperm, dq, N, gr.nnz,
+                         1.0f);
+    };
+    if ((int)(grid.x * grid.y) > device_cu_count()) launch(k_bwd_dense_col<TT, true>);   // see k_scores: F16P
+    else launch(k_bwd_dense_col<TT, false>);
     MSGAT_CHECK_LAUNCH();
     return MSGAT_OK;
-  }
-#endif
-  dim3 grid(cdiv(N, kDRows), G);
-  const size_t static_lds = sizeof(float) * (kDMC * T + kDMC * kPS + kDMC + kDWaves) + sizeof(uint4) * kPlaneU4;
-  const size_t pad = balance_pad_bytes((int)(grid.x * grid.y), static_lds);
-  const bool f16p = (int)(grid.x * grid.y) > device_cu_count();   // see k_scores: F16P
-#define MSGAT_DCOL(TT)                                                                                                       \
-  if (f16p)                                                                                                                  \
-    hipLaunchKernelGGL((k_bwd_dense_col<TT, true>), grid, dim3(kDBlock), pad, s, q, kW, lse, delta, gE, gr.colptr, gr.crow, \
-                       gr.cperm, dq, N, gr.nnz, 1.0f);                                                                       \
-  else                                                                                                                       \
-    hipLaunchKernelGGL((k_bwd_dense_col<TT, false>), grid, dim3(kDBlock), pad, s, q, kW, lse, delta, gE, gr.colptr, gr.crow, \
-                       gr.cperm, dq, N, gr.nnz, 1.0f)
-  switch (T) {
-    case 4: MSGAT_DCOL(4); break;
-    case 8: MSGAT_DCOL(8); break;
-    case 12: MSGAT_DCOL(12); break;
-    case 16: MSGAT_DCOL(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_DCOL
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  });
 }
 
 }  // namespace msgat

@@ -457,35 +457,7 @@ __global__ __launch_bounds__(kBBlock) void k_scores_b(
 // Wave w owns columns m0 + 16w .. +15 (B side: role-A fragments of their q); the rows stream through LDS as records of
 // [kW log2e role B | delta kW payload | lse2].  Score tile D[i = row][j = column]; payload tile D2[i = s][j = column].
 //   dq[m] += sum_{e into m} g_e kW[row_e]  -  sum_n 2^(S[n,m] - lse2[n]) delta[n] kW[n]
-// the sparse in-edge term (as dense.hip's in_edge_term; T = 12)
-__device__ __forceinline__ float4 in_edge_term_b(const int* __restrict__ colptr, const int* __restrict__ crow,
-                                                 const int* __restrict__ cperm, const float* __restrict__ gEg,
-                                                 const float* __restrict__ kWg, int mcol, int quad) {
-  constexpr int T = kBT;
-  const int c0 = colptr[mcol], c1 = colptr[mcol + 1];
-  float4 sp = f4zero();
-  for (int k = c0; k < c1; k += 4) {
-    int ep[4], er[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int kk = min(k + i, c1 - 1);
-      ep[i] = cperm[kk];
-      er[i] = crow[kk];
-    }
-    float ge[4];
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float raw = gEg[ep[i]];
-      ge[i] = (k + i < c1) ? raw : 0.f;
-      v[i] = reinterpret_cast<const float4*>(kWg + (size_t)er[i] * T)[quad];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f4fma(ge[i], v[i], sp);
-  }
-  return sp;
-}
-
+// the sparse in-edge term: in_edge_term (halfsplit.hpp)
 __global__ __launch_bounds__(kBBlock) void k_bwd_dense_col_b(
     const float* __restrict__ q, const float* __restrict__ kW, const uint4* __restrict__ img,
     const float* __restrict__ gE, const int* __restrict__ colptr, const int* __restrict__ crow,
@@ -562,7 +534,7 @@ __global__ __launch_bounds__(kBBlock) void k_bwd_dense_col_b(
   if (!valid || quad >= T4) return;
   const float unscale = scales[g].y * 6.103515625e-05f;   // 1 / (payload scale * 2^14)
   const float* kWg = kW + (size_t)g * N * T;
-  const float4 sp = in_edge_term_b(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, mcol, quad);
+  const float4 sp = in_edge_term<kBT>(colptr, crow, cperm, gE + (size_t)g * nnz, kWg, mcol, quad);
   float4* dst = reinterpret_cast<float4*>(dq + ((size_t)g * N + mcol) * T) + quad;
   float4 v = *dst;
   v.x += sp.x - (da[0] + db[0]) * unscale;

@@ -8,6 +8,7 @@
 // two that puts its largest entry at 2^13 .. 2^14 (fp16 has no range to spare).  Two v_mfma_f32_16x16x32_f16 per tile:
 //     instr 0:  payload (h | m)  x  P (h | m)  =  q_h P_h + q_m P_m        instr 1:  payload (h | m)  x  P (m | h)
 // one payload fragment serving both (the second P fragment is the first with its halves exchanged), fp32 accumulate.
+// Also here, because both files need it: the sparse in-edge term of their backward column passes (in_edge_term).
 #pragma once
 #include "common.hpp"
 
@@ -56,5 +57,39 @@ __device__ __forceinline__ int payload_scale_exp(float absmax) {
   return 13 - (e - 127);
 }
 __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((uint32_t)(127 + min(max(e, -126), 127)) << 23); }
+
+// The sparse part of the backward column pass (k_bwd_dense_col, k_bwd_dense_col7, k_bwd_dense_col_b): sum over the in-edges
+// of column m of g_e kW[row_e], this lane's four timesteps.
+// Four edges per trip with clamped, unconditional loads (the surplus masked by a zero coefficient): a trip is two
+// dependent round trips (edge ids, then coefficient and kW row) behind the column extent, whatever the degree.  As one
+// edge per iteration the loop was 2 x degree dependent round trips at the END of a kernel whose blocks are all resident
+// -- pure tail.  Same order of the sum, same bits.
+template <int T>
+__device__ __forceinline__ float4 in_edge_term(const int* __restrict__ colptr, const int* __restrict__ crow,
+                                               const int* __restrict__ cperm, const float* __restrict__ gEg,
+                                               const float* __restrict__ kWg, int mcol, int quad) {
+  const int c0 = colptr[mcol], c1 = colptr[mcol + 1];
+  float4 sp = f4zero();
+  for (int k = c0; k < c1; k += 4) {
+    int ep[4], er[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kk = min(k + i, c1 - 1);
+      ep[i] = cperm[kk];
+      er[i] = crow[kk];
+    }
+    float ge[4];
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float raw = gEg[ep[i]];
+      ge[i] = (k + i < c1) ? raw : 0.f;
+      v[i] = reinterpret_cast<const float4*>(kWg + (size_t)er[i] * T)[quad];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f4fma(ge[i], v[i], sp);
+  }
+  return sp;
+}
 
 }  // namespace msgat

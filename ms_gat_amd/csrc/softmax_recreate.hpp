@@ -10,9 +10,11 @@
 // matrix-core form (score_tile) is dense.hip's score chain: T/4 v_mfma_f32_16x16x4_f32 from C = 0, instruction kk
 // taking k = 4 kk .. 4 kk + 3 (lane quad `quad` supplies k = 4 kk + quad), which adds the same products in the same
 // order.  Which operand is the MFMA's A and which its B only transposes the tile.  Both end in v_exp_f32 (fast_exp2) of
-// S - lse, one subtraction.  Nothing outside this header applies kLog2e or chains a score in the kernels that include
-// it; a change here changes all of them together, and tests/test_gpu_score_edges.py (bits against the forward's E at
+// S - lse, one subtraction.  Nothing outside this header applies kLog2e or chains a score in the kernels that re-create
+// P; a change here changes all of them together, and tests/test_gpu_score_edges.py (bits against the forward's E at
 // the edges, large scores) and tests/test_gpu_group_counts.py (every kernel at training group counts) pin the result.
+// dense.hip, which defines the order, includes this header too and builds its own chains (score_trip, column_trip: the
+// A operand comes out of LDS there) on the same f32x4 / mfma_16x16x4.
 #pragma once
 #include "common.hpp"
 
