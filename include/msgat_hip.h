@@ -54,7 +54,8 @@ extern "C" {
  *     msgat_attention_backward_edge_grad and msgat_edge_softmax_grad (reading the attention weights);
  *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]);
  *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map);
- *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings).
+ *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings);
+ *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -757,6 +758,40 @@ int msgat_masked_huber_grad(const float* pred, const float* truth, const float* 
                             int32_t T_out, float delta, float null_value, float* dpred, void* stream);
 int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                             int32_t n_chunks, const float* scale, float* flat, int64_t weight_index, void* stream);
+
+/* ---- device: the guard on the optimizer step (off unless a caller uses msgat_grad_guard and msgat_adam_step_guarded) ----
+ * The reference trains under GradScaler (engine.py:61-63), whose step() leaves the update out when a gradient is Inf or
+ * NaN; this build trains in fp32 without a scaler, so that protection -- and global-norm clipping, which cannot be added
+ * from outside a captured step or a multi-rank step whose mean gradient exists only in the flat buffer -- lives here.
+ * `guard`: MSGAT_GUARD_FLOATS fp32 in device memory that the caller allocates and zeroes once:
+ *       guard[0] = the gradient's global L2 norm of this step, before clipping
+ *       guard[1] = coef, what the gradient is scaled by (0 for a step that is left out)
+ *       guard[2] = the number of steps left out so far (+1 per non-finite step; exact up to 2^24)
+ *       guard[3] = the largest finite guard[0] since the caller last zeroed this element
+ *       guard[4] = 1 if this step's sum of squares is finite, else 0
+ * msgat_grad_guard: two launches, nothing read back.  (1) One block per chunk of the chunk table msgat_adam_step takes
+ *     (chunk_off, chunk_len; a parameter without a gradient has no chunk and its stale part of `grad` is not read) squares
+ *     its elements and adds them in double -- a finite gradient of 1e30 gives a finite norm -- into partials[c].
+ *     (2) S = the partials added in index order in double; D = grad_divisor[0] if given (the summed rank weights of a
+ *     data-parallel step, whose `grad` holds sum_r w_r g_r) else 1; norm = (float)(sqrt(S) / D);
+ *     coef = min(1, max_norm / (norm + 1e-6)) in fp32, exactly torch.nn.utils.clip_grad_norm_'s; max_norm = INFINITY
+ *     asks for no clipping (coef = 1).  max_norm <= 0 or NaN: MSGAT_ERR_SHAPE; guard NULL: MSGAT_ERR_NULL.
+ *     `partials`: msgat_grad_guard_partial_doubles(n_chunks) doubles.  Every sum has one fixed order and there are no
+ *     atomics: equal inputs give equal bits on every launch and, after the all-reduce, on every rank.
+ * msgat_adam_step_guarded: msgat_adam_step reading guard[1] and guard[4] from device memory.  Finite step:
+ *     g = weight_decay * w + coef * (grad / D) -- the clipping acts on the raw gradient before the L2 term, as
+ *     clip_grad_norm_ followed by optim.Adam does -- and with coef == 1 every result has the bits msgat_adam_step gives.
+ *     Non-finite step: NOTHING is written, no parameter, no moment, no step count (GradScaler.step's behaviour; it
+ *     differs on purpose from clip_grad_norm_, which would scale every gradient by NaN). */
+#define MSGAT_GUARD_FLOATS 5
+size_t msgat_grad_guard_partial_doubles(int32_t n_chunks);
+int msgat_grad_guard(const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks, const float* grad,
+                     const float* grad_divisor, float max_norm, double* partials, float* guard, void* stream);
+int msgat_adam_step_guarded(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                            const int32_t* chunk_tensor, int32_t n_chunks, const int32_t* active_tensors,
+                            int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq, float* steps,
+                            const float* lr, double beta1, double beta2, double eps, double weight_decay,
+                            const float* grad_divisor, const float* guard, void* stream);
 
 #ifdef __cplusplus
 }

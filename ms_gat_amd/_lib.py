@@ -23,6 +23,7 @@ c_int_p = C.POINTER(C.c_int32)
 
 
 SELL_SLACK = 512  # MSGAT_SELL_SLACK
+GUARD_FLOATS = 5  # MSGAT_GUARD_FLOATS: {norm, coef, skipped steps, largest finite norm, finite}
 
 
 class Sell(C.Structure):
@@ -173,6 +174,11 @@ _PROTOTYPES = {
     "msgat_masked_huber_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p,
                                                             C.c_void_p]),
     "msgat_gather_scaled_dev": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "msgat_grad_guard_partial_doubles": (C.c_size_t, [C.c_int32]),
+    "msgat_grad_guard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "msgat_adam_step_guarded": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                + [C.c_double] * 4 + [C.c_void_p] * 3),
 }
 
 _lock = threading.Lock()

@@ -1113,6 +1113,38 @@ extern "C" int msgat_adam_step(float* const* chunk_param, const int64_t* chunk_o
                      grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, (hipStream_t)stream);
 }
 
+// ---- the guard on the optimizer step: global-norm clipping, non-finite steps left out -------------------------------
+static_assert(kGuardFloats == MSGAT_GUARD_FLOATS, "guard state layout");
+
+extern "C" size_t msgat_grad_guard_partial_doubles(int32_t n_chunks) { return n_chunks > 0 ? (size_t)n_chunks : 0; }
+
+extern "C" int msgat_grad_guard(const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks, const float* grad,
+                                const float* grad_divisor, float max_norm, double* partials, float* guard,
+                                void* stream) {
+  if (n_chunks < 0) return MSGAT_ERR_SHAPE;
+  if (!(max_norm > 0.f)) return MSGAT_ERR_SHAPE;   // <= 0 and NaN; +inf = no clipping
+  if (!guard) return MSGAT_ERR_NULL;
+  if (n_chunks > 0 && (!chunk_off || !chunk_len || !grad || !partials)) return MSGAT_ERR_NULL;
+  return launch_grad_guard((const long long*)chunk_off, chunk_len, n_chunks, grad, grad_divisor, max_norm, partials, guard,
+                           (hipStream_t)stream);
+}
+
+extern "C" int msgat_adam_step_guarded(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                                       const int32_t* chunk_tensor, int32_t n_chunks, const int32_t* active_tensors,
+                                       int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                       float* steps, const float* lr, double beta1, double beta2, double eps,
+                                       double weight_decay, const float* grad_divisor, const float* guard,
+                                       void* stream) {
+  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
+  if (!steps || !lr || !guard) return MSGAT_ERR_NULL;
+  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
+  if (n_chunks > 0 && (!chunk_param || !chunk_off || !chunk_len || !chunk_tensor || !grad || !exp_avg || !exp_avg_sq)) return MSGAT_ERR_NULL;
+  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
+  return launch_adam_guarded(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors,
+                             n_active, grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor,
+                             guard, (hipStream_t)stream);
+}
+
 extern "C" int msgat_gather_scaled(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                                    int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
   if (n_chunks <= 0) return MSGAT_ERR_SHAPE;

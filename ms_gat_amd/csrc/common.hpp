@@ -481,6 +481,13 @@ int launch_adam(float* const* chunk_param, const long long* chunk_off, const int
                 int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
                 const float* lr, double beta1, double beta2, double eps, double weight_decay, const float* grad_divisor,
                 hipStream_t s);
+constexpr int kGuardFloats = 5;   // MSGAT_GUARD_FLOATS
+int launch_grad_guard(const long long* chunk_off, const int* chunk_len, int nchunks, const float* grad,
+                      const float* grad_divisor, float max_norm, double* part, float* guard, hipStream_t s);
+int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                        const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
+                        float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
+                        double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s);
 int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                          float scale, float* flat, long long weight_index, hipStream_t s);
 size_t masked_huber_partial_doubles(long long rows, int T);

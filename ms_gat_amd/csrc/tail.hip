@@ -11,6 +11,10 @@
 //                        gradient, bias correction, eps outside the square root) for every parameter tensor at once,
 //                        driven by a chunk table; the step counter and the learning rate live in device memory so the
 //                        launch is capturable in a HIP graph.
+//   guard (optional)     k_grad_sumsq + k_guard_finish: the global norm of the flat gradient, its clipping coefficient
+//                        (torch.nn.utils.clip_grad_norm_'s) and whether it is finite, left in device memory; the guarded
+//                        forms of k_adam_advance / k_adam read them there and scale the gradient or -- like
+//                        GradScaler.step (reference engine.py:61-63) -- leave a non-finite step out altogether.
 #include "common.hpp"
 
 namespace msgat {
@@ -223,11 +227,88 @@ int launch_gate_sum_bwd(const float* dout, const float* pred, const long long* H
 // lr[0] = learning rate.  Both live in device memory, so a captured launch follows the scheduler.
 constexpr int kAdamChunk = 2048;
 
-__global__ void k_adam_advance(float* __restrict__ steps, const int* __restrict__ active, int n_active) {
+// ---- the guard on the update: global gradient norm, clipping coefficient, finiteness ---------------------------------
+// guard [kGuardFloats] fp32, device: {pre-clip norm of this step, coef, steps skipped so far, largest finite pre-clip
+// norm since the caller zeroed it, 1 if this step's sum of squares is finite else 0}.
+//   k_grad_sumsq     block c squares chunk c of the flat gradient (the chunk table of k_adam: a parameter without a
+//                    gradient has no chunk, its stale flat contents are never read) in double -- (1e30)^2 is no overflow
+//                    there -- lane by lane with stride 256, the butterfly of wave_sum, then the four waves in order.
+//   k_guard_finish   lane 0 adds the partials in index order (staged through LDS 1024 at a time by the whole block, so
+//                    the serial part is ~1000 dependent adds, not ~1000 dependent loads), then
+//                    norm = sqrt(S) / D, coef = min(1, max_norm / (norm + 1e-6)) in fp32 as clip_grad_norm_ computes it
+//                    (max_norm = +inf: 1).  A step whose S is not finite counts as skipped.
+// One fixed order throughout and no atomics: equal inputs give equal bits, on every launch and on every rank.
+constexpr int kGuardNorm = 0, kGuardCoef = 1, kGuardSkipped = 2, kGuardMax = 3, kGuardFinite = 4;
+constexpr int kGuardTile = 1024;
+
+__global__ __launch_bounds__(kTailBlock) void k_grad_sumsq(const long long* __restrict__ chunk_off,
+                                                           const int* __restrict__ chunk_len,
+                                                           const float* __restrict__ grad, double* __restrict__ part) {
+  __shared__ double red[kTailBlock / 64];
+  const int c = blockIdx.x;
+  const float* __restrict__ g = grad + chunk_off[c];
+  const int len = chunk_len[c];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < len; i += kTailBlock) {
+    const double x = (double)g[i];
+    s += x * x;
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kTailBlock / 64; ++w) t += red[w];
+    part[c] = t;
+  }
+}
+
+__global__ __launch_bounds__(kTailBlock) void k_guard_finish(const double* __restrict__ part, int nparts,
+                                                             const float* __restrict__ grad_divisor, float max_norm,
+                                                             float* __restrict__ guard) {
+  __shared__ double tile[kGuardTile];
+  double S = 0.0;
+  for (int base = 0; base < nparts; base += kGuardTile) {   // nparts is kernel-uniform: every lane meets every barrier
+    const int m = nparts - base < kGuardTile ? nparts - base : kGuardTile;
+    for (int i = threadIdx.x; i < m; i += kTailBlock) tile[i] = part[base + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < m; ++i) S += tile[i];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double D = grad_divisor != nullptr ? (double)grad_divisor[0] : 1.0;
+  const bool finite = isfinite(S);
+  const float norm = (float)(sqrt(S) / D);
+  guard[kGuardNorm] = norm;
+  guard[kGuardCoef] = finite ? fminf(1.f, max_norm / (norm + 1e-6f)) : 0.f;
+  guard[kGuardFinite] = finite ? 1.f : 0.f;
+  if (!finite) guard[kGuardSkipped] += 1.f;
+  else if (isfinite(norm)) guard[kGuardMax] = fmaxf(guard[kGuardMax], norm);
+}
+
+int launch_grad_guard(const long long* chunk_off, const int* chunk_len, int nchunks, const float* grad,
+                      const float* grad_divisor, float max_norm, double* part, float* guard, hipStream_t s) {
+  if (nchunks > 0) {
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_off, chunk_len, grad, part);
+    MSGAT_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_guard_finish, dim3(1), dim3(kTailBlock), 0, s, part, nchunks, grad_divisor, max_norm, guard);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+// kGuard: a step whose gradient norm is not finite advances no step count and (k_adam) writes nothing at all
+template <bool kGuard>
+__global__ void k_adam_advance(float* __restrict__ steps, const int* __restrict__ active, int n_active,
+                               const float* __restrict__ guard) {
+  if (kGuard && guard[kGuardFinite] == 0.f) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_active) steps[active[i]] += 1.0f;
 }
 
+template <bool kGuard>
 __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ chunk_param,
                                                      const long long* __restrict__ chunk_off,
                                                      const int* __restrict__ chunk_len,
@@ -236,7 +317,11 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
                                                      float* __restrict__ v, const float* __restrict__ steps,
                                                      const float* __restrict__ lrp, double beta1d, double beta2d,
                                                      float eps, float weight_decay,
-                                                     const float* __restrict__ grad_divisor) {
+                                                     const float* __restrict__ grad_divisor,
+                                                     const float* __restrict__ guard) {
+  if (kGuard && guard[kGuardFinite] == 0.f) return;   // kernel-uniform
+  // clip_grad_norm_ scales the raw gradient, optim.Adam then adds the L2 term: coef acts before weight_decay * w
+  const float coef = kGuard ? guard[kGuardCoef] : 1.f;
   const int c = blockIdx.x;
   float* p = chunk_param[c];
   const long long off = chunk_off[c];
@@ -254,7 +339,8 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
   const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
   for (int i = threadIdx.x; i < len; i += kTailBlock) {
     const float w = p[i];
-    const float gin = scaled ? grad[off + i] / div : grad[off + i];
+    float gin = scaled ? grad[off + i] / div : grad[off + i];
+    if (kGuard) gin = coef * gin;                     // coef == 1: the same bits as the unguarded kernel
     const float g = fmaf(weight_decay, w, gin);
     float mi = m[off + i], vi = v[off + i];
     mi = fmaf(g - mi, omb1, mi);                      // exp_avg.lerp_(grad, 1 - beta1)
@@ -266,20 +352,39 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
   }
 }
 
+template <bool kGuard>
+static int launch_adam_form(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                            const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad,
+                            float* m, float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
+                            double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s) {
+  if (n_active > 0) {
+    hipLaunchKernelGGL(k_adam_advance<kGuard>, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active,
+                       n_active, guard);
+    MSGAT_CHECK_LAUNCH();
+  }
+  if (nchunks > 0) {
+    hipLaunchKernelGGL(k_adam<kGuard>, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len,
+                       chunk_tensor, grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor,
+                       guard);
+    MSGAT_CHECK_LAUNCH();
+  }
+  return MSGAT_OK;
+}
+
 int launch_adam(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, const int* chunk_tensor,
                 int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
                 const float* lr, double beta1, double beta2, double eps, double weight_decay, const float* grad_divisor,
                 hipStream_t s) {
-  if (n_active > 0) {
-    hipLaunchKernelGGL(k_adam_advance, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active, n_active);
-    MSGAT_CHECK_LAUNCH();
-  }
-  if (nchunks > 0) {
-    hipLaunchKernelGGL(k_adam, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len, chunk_tensor,
-                       grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor);
-    MSGAT_CHECK_LAUNCH();
-  }
-  return MSGAT_OK;
+  return launch_adam_form<false>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad, m, v,
+                                 steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, nullptr, s);
+}
+
+int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                        const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
+                        float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
+                        double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s) {
+  return launch_adam_form<true>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad, m, v,
+                                steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard, s);
 }
 
 int adam_chunk_elems() { return kAdamChunk; }

@@ -18,6 +18,10 @@ Differences that are the point of this build:
   * `null_value` (off by default) treats entries of the truth that are NaN or equal to it as missing readings: they
     drop out of the loss, its gradient and the metrics, which are then kept per forecast horizon
     (`ops.masked_huber_metrics`; the batch's valid count stays on the device, also as the rank's weight).
+  * `max_grad_norm` / `skip_nonfinite` (both off by default) put a guard on the optimizer step: the global gradient norm is
+    taken on the device, the gradient is clipped to `max_grad_norm` as `torch.nn.utils.clip_grad_norm_` would, and a step
+    whose norm is Inf or NaN is left out whole, as the reference's `GradScaler.step` leaves it out (engine.py:61-63) --
+    inside a captured step and after the one all-reduce of a multi-rank step, with nothing read back (`FlatAdam`).
   * `hip_graph="auto"` (the default on the GPU) captures a step in a HIP graph once its batch shape recurs and replays it.
 CPU tensors (the host-logic tests run a small CPU `nn.Module` through this loop) take plain PyTorch
 ops for loss and optimizer; the library has no CPU path.
@@ -238,6 +242,11 @@ class Metrics:
         return {"MAE": self.MAE, "MAPE": self.MAPE, "RMSE": self.RMSE}
 
 
+def check_max_grad_norm(max_grad_norm) -> None:
+    if max_grad_norm is not None and not float(max_grad_norm) > 0.0:      # also refuses NaN
+        raise ValueError(f"max_grad_norm must be a positive number or None, not {max_grad_norm!r}")
+
+
 class FlatAdam(optim.Optimizer):
     """`torch.optim.Adam` (engine.py:106; L2 weight decay on the gradient, bias correction, eps outside the
     square root) as ONE launch over flat state buffers (`msgat_adam_step`, csrc/tail.hip).
@@ -247,12 +256,31 @@ class FlatAdam(optim.Optimizer):
     of the parameter bank (`stacked.ParamBank`) -- reached through a device table of 2048-element chunks.  The
     step count and the learning rate live in device memory: a captured launch follows `StepLR`.
     `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format (per-parameter `step`, `exp_avg`,
-    `exp_avg_sq`), so checkpoints interchange with the reference's optimizer."""
+    `exp_avg_sq`), so checkpoints interchange with the reference's optimizer.
 
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    The guard (`max_grad_norm`, `skip_nonfinite`; off unless one is set, and then nothing here changes): two more launches
+    (`msgat_grad_guard`) take the global L2 norm of the flat gradient -- on one GPU after the copy into the flat views, with
+    several ranks after the all-reduce and the clamp of the divisor, so every rank decides from the same bits and the norm
+    is that of the global-batch mean gradient -- and leave `coef = min(1, max_grad_norm / (norm + 1e-6))` (1 without
+    `max_grad_norm`) and a finite flag in device memory, where the update (`msgat_adam_step_guarded`) reads them:
+    `g = weight_decay * w + coef * grad`, i.e. `clip_grad_norm_` followed by `optim.Adam`.  While the guard is active a
+    step whose norm is Inf or NaN writes nothing -- no parameter, no moment, no step count; only the skipped counter
+    moves -- which is `GradScaler.step`'s behaviour and on purpose NOT `clip_grad_norm_`'s (it would scale every gradient
+    by NaN).  Nothing is read back: `guard_stats()` is the only call that synchronises.  The host cannot know which
+    steps were left out, so with the guard on the step counts in device memory are the truth and `state_dict()` reads
+    them back."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise ValueError("FlatAdam takes one parameter group (the reference trains with one, engine.py:106)")
+        check_max_grad_norm(max_grad_norm)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self._guard = None            # [GUARD_FLOATS] fp32 on the device: norm, coef, skipped steps, largest norm, finite
+        self._guard_partials = None   # one double per chunk of the whole layout
         self._params: List[nn.Parameter] = []
         self._loaded_steps: Dict[int, float] = {}    # steps that arrived through load_state_dict, by id(param)
         self._host_steps: List[int] = []             # host mirror of the per-parameter step counts
@@ -294,6 +322,16 @@ class FlatAdam(optim.Optimizer):
             self._dev_lr = torch.tensor([float(self.param_groups[0]["lr"])], device=dev)
             self._tables.clear()
             self._gather_tables.clear()
+            if self.guarded:          # here, not at the first guarded step: they exist before any capture
+                from . import _lib
+                chunk = int(_lib.lib().msgat_adam_chunk_elems())
+                n_chunks = sum(-(-p.numel() // chunk) for p in self._params)
+                old_guard = self._guard
+                self._guard = torch.zeros(_lib.GUARD_FLOATS, device=dev, dtype=torch.float32)
+                if old_guard is not None:     # new buffers (another layout or device): the counts so far go along
+                    self._guard.copy_(old_guard)
+                self._guard_partials = torch.zeros(int(_lib.lib().msgat_grad_guard_partial_doubles(n_chunks)), device=dev,
+                                                   dtype=torch.float64)
         self._grad_views = [self.flat_grad[o:o + p.numel()].view_as(p) for p, o in zip(self._params, self._offsets)]
         self._lr_on_device = float(self.param_groups[0]["lr"])
         for i, (p, o) in enumerate(zip(self._params, self._offsets)):
@@ -312,8 +350,11 @@ class FlatAdam(optim.Optimizer):
         """Addresses a captured step graph depends on; a change means such graphs must be dropped."""
         if self.flat_grad is None:
             return ()
-        return (self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self._dev_steps.data_ptr(), self._dev_lr.data_ptr())
+        token = (self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                 self._dev_steps.data_ptr(), self._dev_lr.data_ptr())
+        if self.guarded:
+            token += (self._guard.data_ptr(), self._guard_partials.data_ptr())
+        return token
 
     def _table(self, active: tuple):
         """Device chunk table of the parameters that have a gradient (torch's Adam skips the others)."""
@@ -398,12 +439,27 @@ class FlatAdam(optim.Optimizer):
         self.sync_lr()
         ptrs, offs, lens, tens, act, n, n_act = self._table(active)
         g = self.param_groups[0]
-        st = _lib.lib().msgat_adam_step(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n, act.data_ptr(),
-                                        n_act, self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                        self._dev_steps.data_ptr(), self._dev_lr.data_ptr(), float(g["betas"][0]),
-                                        float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), divisor,
-                                        torch.cuda.current_stream(self.flat_grad.device).cuda_stream)
-        _lib.check(st, "msgat_adam_step")
+        stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
+        if self.guarded:
+            # the norm of what the update is about to consume: the flat views (one GPU) or the all-reduced sum over
+            # its clamped divisor (several ranks: the same bits, hence the same decision, on every rank)
+            max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
+            st = _lib.lib().msgat_grad_guard(offs.data_ptr(), lens.data_ptr(), n, self.flat_grad.data_ptr(), divisor, max_norm,
+                                             self._guard_partials.data_ptr(), self._guard.data_ptr(), stream)
+            _lib.check(st, "msgat_grad_guard")
+            st = _lib.lib().msgat_adam_step_guarded(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n,
+                                                    act.data_ptr(), n_act, self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                                                    self.exp_avg_sq.data_ptr(), self._dev_steps.data_ptr(),
+                                                    self._dev_lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]),
+                                                    float(g["eps"]), float(g["weight_decay"]), divisor,
+                                                    self._guard.data_ptr(), stream)
+            _lib.check(st, "msgat_adam_step_guarded")
+        else:
+            st = _lib.lib().msgat_adam_step(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n, act.data_ptr(),
+                                            n_act, self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                            self._dev_steps.data_ptr(), self._dev_lr.data_ptr(), float(g["betas"][0]),
+                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), divisor, stream)
+            _lib.check(st, "msgat_adam_step")
         if torch.cuda.is_current_stream_capturing():
             self._captured_active = active
         else:
@@ -419,6 +475,9 @@ class FlatAdam(optim.Optimizer):
 
     # -- torch.optim.Adam's checkpoint format ------------------------------------------------------------------
     def state_dict(self):
+        if self.guarded and self._params and self.flat_grad is not None:
+            # the host mirror counted every launch, the device only the steps that were not left out
+            self._host_steps = [int(t) for t in self._dev_steps.tolist()]
         for p, t in zip(self._params, self._host_steps):
             self.state[p]["step"] = torch.tensor(float(t))
         sd = super().state_dict()
@@ -443,6 +502,38 @@ class FlatAdam(optim.Optimizer):
         self._host_steps = list(steps)
         self._dev_steps.copy_(torch.tensor([float(t) for t in steps]))
 
+    # -- the guard ---------------------------------------------------------------------------------------------
+    def guard_stats(self) -> Dict[str, float]:
+        """What the guard saw: the last step's pre-clip norm and coefficient, the steps left out so far and the largest
+        finite norm since `reset_guard_stats()`.  Reads device memory: the one call of the guard that synchronises."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdam was built without max_grad_norm / skip_nonfinite: there is no guard to report")
+        norm, coef, skipped, largest = (0.0, 1.0, 0.0, 0.0) if self._guard is None else self._guard[:4].tolist()
+        return {"grad_norm": norm, "clip_coef": coef, "skipped_steps": int(skipped), "grad_norm_max": largest}
+
+    def reset_guard_stats(self) -> None:
+        """Start the running maximum of the norm afresh (the skipped count is cumulative and stays)."""
+        if self._guard is not None:
+            self._guard[3:4].zero_()
+
+    def guard_snapshot(self):
+        """Device step counts and guard state, for `guard_restore` (None: guard off, or nothing built yet)."""
+        if self._guard is None:
+            return None
+        return self._dev_steps.clone(), self._guard.clone()
+
+    def guard_restore(self, snapshot) -> None:
+        """Undo guarded steps that must not count (the warm-up of a graph capture): a poisoned warm-up batch was left
+        out on the device, so neither the host's step counts nor a second skipped count may survive it."""
+        if self._guard is None:
+            return
+        if snapshot is None:
+            self._guard.zero_()
+            return
+        self._dev_steps.copy_(snapshot[0])
+        self._guard.copy_(snapshot[1])
+        self._host_steps = [int(t) for t in snapshot[0].tolist()]
+
 
 class _GraphedStep:
     """One captured step for one batch shape: static input buffers, `replay()` per batch.
@@ -466,6 +557,7 @@ class _GraphedStep:
             saved_state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state.get(p, {}).items()}
                            for group in opt.param_groups for p in group["params"]}
             saved_steps = list(getattr(opt, "_host_steps", []))
+            saved_guard = opt.guard_snapshot() if isinstance(opt, FlatAdam) else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -490,6 +582,7 @@ class _GraphedStep:
                             v.copy_(old) if old is not None else v.zero_()
                 if isinstance(opt, FlatAdam) and step_in_graph:
                     opt.set_steps(saved_steps if saved_steps else [0] * len(opt._host_steps))
+                    opt.guard_restore(saved_guard)   # a warm-up batch the guard left out counts once: at its replay
             opt.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -535,6 +628,10 @@ class Engine:
         self._graph_seen = {}
         self._graphs = {}
         self._graph_metrics = None   # the Metrics whose device totals the captured loss kernels add to
+        self.max_grad_norm: Optional[float] = None   # the guard on the optimizer step (see Trainer); off by default
+        self.skip_nonfinite = False
+        self._cpu_guard = {"grad_norm": 0.0, "clip_coef": 1.0, "skipped_steps": 0, "grad_norm_max": 0.0}
+        self._skipped_reported = 0   # the cumulative skipped count at the last end of a training epoch
 
     # -- helpers -------------------------------------------------------------------------
     def _device(self, gpu_id):
@@ -592,7 +689,45 @@ class Engine:
             if self._grad_sync is None:
                 self._grad_sync = parallel.FlatGradAllReduce(self.model.parameters())
             self._grad_sync(weight=weight)
+        if self._guarded() and not self._cpu_guard_passes():
+            return
         self.optimizer.step()
+
+    def _guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _cpu_guard_passes(self) -> bool:
+        """The guard in torch ops (CPU parameters under torch.optim.Adam; after the gradient all-reduce, so every rank sees
+        the same norm): False = a non-finite norm, the step is left out; otherwise the gradients are clipped in place."""
+        params = [p for group in self.optimizer.param_groups for p in group["params"] if p.grad is not None]
+        g = self._cpu_guard
+        if not params:
+            g.update(grad_norm=0.0, clip_coef=1.0)
+            return True
+        norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params]))
+        g["grad_norm"] = float(norm)
+        if not bool(torch.isfinite(norm)):
+            g["clip_coef"] = 0.0
+            g["skipped_steps"] += 1
+            return False
+        g["grad_norm_max"] = max(g["grad_norm_max"], g["grad_norm"])
+        g["clip_coef"] = 1.0
+        if self.max_grad_norm is not None:
+            nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+            g["clip_coef"] = min(1.0, self.max_grad_norm / (g["grad_norm"] + 1e-6))
+        return True
+
+    def guard_stats(self) -> Dict[str, float]:
+        """`FlatAdam.guard_stats()`, or the same figures of the torch path: synchronises on the GPU."""
+        if isinstance(self.optimizer, FlatAdam):
+            return self.optimizer.guard_stats()
+        return dict(self._cpu_guard)
+
+    def _reset_guard_max(self) -> None:
+        if isinstance(self.optimizer, FlatAdam):
+            self.optimizer.reset_guard_stats()
+        else:
+            self._cpu_guard["grad_norm_max"] = 0.0
 
     def run_epoch(self, data, gpu_id=None, epoch=None, mode: str = "train") -> float:
         """One pass over `data` (an iterable of (X, H, D, Y) batches).  Returns the mean batch loss.
@@ -623,6 +758,9 @@ class Engine:
         global_sizes = iter(sampler.global_batch_sizes()) if presharded and hasattr(sampler, "global_batch_sizes") else None
         guard = torch.cuda.device(device) if device.type == "cuda" else _NullContext()
         pred = loss = None
+        guarded = training and self._guarded()
+        if guarded:
+            self._reset_guard_max()
         with guard, torch.set_grad_enabled(training):
             for batch in data:
                 n_global = batch[0].shape[0]
@@ -686,6 +824,14 @@ class Engine:
                 self.log_to_file(self.__labels__[mode], "per horizon", **({} if mode == "evaluate" else {"epoch": epoch}), **per)
         if horizons is not None:
             stats["horizons"] = horizons
+        if guarded:      # the epoch's one read of the guard state; every rank took the same decisions
+            seen = self.guard_stats()
+            stats["skipped_steps"] = seen["skipped_steps"] - self._skipped_reported
+            stats["grad_norm_max"] = seen["grad_norm_max"]
+            self._skipped_reported = seen["skipped_steps"]
+            if rank == 0:
+                self.log_to_file(self.__labels__[mode], "guard", epoch=epoch, skipped_steps=stats["skipped_steps"],
+                                 grad_norm_max=stats["grad_norm_max"])
         self.last_stats = stats
         return loss_ave
 
@@ -711,8 +857,18 @@ class Trainer(Engine):
     tests) with torch.optim.Adam -- same update, same checkpoint format."""
 
     def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto",
-                 null_value: Optional[float] = None):
-        """`null_value` (default None: the reference's loss and metrics over every entry): entries of the truth that are
+                 null_value: Optional[float] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
+        """`max_grad_norm`, `skip_nonfinite` (default None / False: the step as the reference's optimizer takes it): a guard on
+        the optimizer step, active when either is set.  The global L2 norm of the gradient -- of the global batch's mean
+        gradient under a process group -- is taken before the update; the gradient is scaled by
+        `min(1, max_grad_norm / (norm + 1e-6))` like `torch.nn.utils.clip_grad_norm_` (`skip_nonfinite` alone: never
+        scaled), and a step whose norm is Inf or NaN (one NaN in X is enough) is left out whole -- parameters, moments and
+        step counts untouched -- as `GradScaler.step` of the reference leaves it out; `clip_grad_norm_` would have scaled
+        every gradient by NaN instead.  On the GPU all of it happens in the library, inside a captured step too
+        (`FlatAdam`).  A training epoch then adds `skipped_steps` (this epoch's) and `grad_norm_max` to `last_stats` and one
+        `guard` line to run.log.
+        `null_value` (default None: the reference's loss and metrics over every entry): entries of the truth that are
         NaN or equal to it are missing readings -- they drop out of the loss, its gradient and the metrics, the metrics are
         kept per forecast horizon (`last_stats["horizons"]`, one more log line per validation epoch), and under a process
         group a rank's weight in the gradient mean is its batch's valid count.
@@ -729,8 +885,14 @@ class Trainer(Engine):
             raise ValueError(f"hip_graph must be True, False or 'auto', not {hip_graph!r}")
         self.hip_graph = hip_graph if on_gpu else False
         parallel.sync_parameters(model)     # data-parallel replicas start from rank 0's weights (no-op for one process)
-        adam = FlatAdam if on_gpu else optim.Adam
-        self.optimizer = adam(model.parameters(), lr=1e-3, weight_decay=5e-4)
+        check_max_grad_norm(max_grad_norm)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if on_gpu:
+            self.optimizer = FlatAdam(model.parameters(), lr=1e-3, weight_decay=5e-4, max_grad_norm=self.max_grad_norm,
+                                      skip_nonfinite=self.skip_nonfinite)
+        else:
+            self.optimizer = optim.Adam(model.parameters(), lr=1e-3, weight_decay=5e-4)
         self.scheduler = lr_scheduler.StepLR(self.optimizer, step_size=30, gamma=0.1)
         self.best = {"epoch": 0, "loss": float("inf"), "ckpt": ""}
         self.epoch = 1
