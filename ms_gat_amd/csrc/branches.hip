@@ -1,5 +1,5 @@
 // The temporal and channel branches of MEAM: the streaming kernels that
-// the hot path's channel-mixing kernels (project.hip / mfma.hip) do not already cover.
+// the hot path's channel-mixing kernels (project.hip / mfma.hip / contract.hip) do not already cover.
 //
 // Reference: TemporalAttention /root/reference/src/models/attention.py:58-66, ChannelAttention :88-94,
 // TACN src/models/msgat.py:57-80 (attention, then causal dilated [1,2] convolutions), CACN :83-100.
@@ -139,7 +139,6 @@ constexpr int kTdaUnroll = 8;  // k-steps (of 4 rows) whose loads are in flight 
 template <int T>
 __global__ __launch_bounds__(kBlock) void k_tmix_dA(const float* __restrict__ dout, const float* __restrict__ y,
                                                     float* __restrict__ part, int Co, int K, int N, int dout_gs) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   __shared__ float red[kBlock / kWave][256];
   const int g = blockIdx.z, k = blockIdx.y;
   const int rows = Co * N;
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_tmix_dA(const float* __restrict__ do
       b[u] = ybase[(size_t)rc * T] * keep;
     }
 #pragma unroll
-    for (int u = 0; u < kTdaUnroll; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], acc, 0, 0, 0);
+    for (int u = 0; u < kTdaUnroll; ++u) acc = mfma_16x16x4(a[u], b[u], acc);
   }
   // D[t = 4 * (lane >> 4) + reg][i = lane & 15]; the four waves' tiles are added in a fixed order
 #pragma unroll
@@ -388,7 +387,6 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd(const float* __restrict__ x
                                                      const float* __restrict__ bias, float* __restrict__ out,
                                                      int C, int N, int To, int Bg, const float* __restrict__ lnw,
                                                      const float* __restrict__ lnb, float eps, float* __restrict__ xn) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   constexpr int T4 = T / 4;
   __shared__ float Wl[kHeadFwdCC * T * kHeadTo];
   const int b = blockIdx.y;
@@ -444,10 +442,10 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd(const float* __restrict__ x
       for (int u = 0; u < kHeadFwdUn; ++u)
         if (cc + u < cn) {  // wave-uniform; no loads inside
           const float* wl = Wl + ((cc + u) * T + 4 * kqc) * kHeadTo + m;
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].x, wl[0 * kHeadTo] * kmask, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].y, wl[1 * kHeadTo] * kmask, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].z, wl[2 * kHeadTo] * kmask, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].w, wl[3 * kHeadTo] * kmask, acc, 0, 0, 0);
+          acc = mfma_16x16x4(av[u].x, wl[0 * kHeadTo] * kmask, acc);
+          acc = mfma_16x16x4(av[u].y, wl[1 * kHeadTo] * kmask, acc);
+          acc = mfma_16x16x4(av[u].z, wl[2 * kHeadTo] * kmask, acc);
+          acc = mfma_16x16x4(av[u].w, wl[3 * kHeadTo] * kmask, acc);
         }
     }
   }
@@ -466,7 +464,6 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restri
                                                      const float* __restrict__ bias, float* __restrict__ out,
                                                      int C, int N, int To, int Bg, const float* __restrict__ lnw,
                                                      const float* __restrict__ lnb, float eps, float* __restrict__ xn) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   constexpr int T4 = T / 4, OW = kHeadTo * OT, CC = head_fwd_cc<OT>();
   __shared__ float Wl[CC * T * OW];
   const int b = blockIdx.y;
@@ -530,13 +527,13 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restri
         if (cc + u < cn) {  // wave-uniform; no loads inside
           const float* wl = Wl + ((cc + u) * T + 4 * kqc) * OW + m;
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].x, wl[0 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].x, wl[0 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].y, wl[1 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].y, wl[1 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].z, wl[2 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].z, wl[2 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u].w, wl[3 * OW + kHeadTo * ot], acc[ot], 0, 0, 0);
+          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].w, wl[3 * OW + kHeadTo * ot], acc[ot]);
         }
     }
   }
@@ -749,7 +746,6 @@ constexpr int kHeadChunks = 8;    // sample chunks per (relation, channel): 95.7
 template <int T>
 __global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ dout, const float* __restrict__ x,
                                                     float* __restrict__ part, int B, int C, int N, int To) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   __shared__ float red[kBlock / kWave][256];
   const int c = blockIdx.y, j = blockIdx.x, rel = blockIdx.z;   // B = samples per relation
   const int b0 = rel * B + (int)((long long)B * j / gridDim.x), b1 = rel * B + (int)((long long)B * (j + 1) / gridDim.x);
@@ -773,7 +769,7 @@ __global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ do
         bv[u] = xsrc[(size_t)nc * T] * (keep * tmask);
       }
 #pragma unroll
-      for (int u = 0; u < kTdaUnroll; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+      for (int u = 0; u < kTdaUnroll; ++u) acc = mfma_16x16x4(av[u], bv[u], acc);
     }
   }
   // D[o = 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order
@@ -792,7 +788,6 @@ __global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ do
 template <int T, int OT>
 __global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restrict__ dout, const float* __restrict__ x,
                                                     float* __restrict__ part, int B, int C, int N, int To) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   __shared__ float red[kBlock / kWave][256 * OT];
   const int c = blockIdx.y, j = blockIdx.x, rel = blockIdx.z;   // B = samples per relation
   const int b0 = rel * B + (int)((long long)B * j / gridDim.x), b1 = rel * B + (int)((long long)B * (j + 1) / gridDim.x);
@@ -836,7 +831,7 @@ __global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restric
 #pragma unroll
       for (int u = 0; u < kTdaUnroll; ++u)
 #pragma unroll
-        for (int ot = 0; ot < OT; ++ot) acc[ot] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ot][u], bv[u], acc[ot], 0, 0, 0);
+        for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[ot][u], bv[u], acc[ot]);
     }
   }
   // D[o = 16 ot + 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order

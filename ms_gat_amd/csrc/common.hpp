@@ -5,6 +5,9 @@
 
 #include <algorithm>
 #include <atomic>
+#ifdef MSGAT_LAB
+#include <cstdlib>
+#endif
 #include <type_traits>
 
 #include "msgat_hip.h"
@@ -90,6 +93,13 @@ inline int grant_dynamic_lds(K kernel, size_t lds, LdsGrant& granted) {
   return MSGAT_OK;
 }
 
+#ifdef MSGAT_LAB
+inline int lab_env(const char* name, int dflt) {   // lab builds only: a launch parameter from the environment
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+#endif
+
 // the MFMA projection's matrix (+ row-pointer table) may take this much LDS: two blocks per CU still fit 160 KiB
 constexpr int kProjLdsMax = 78 * 1024;
 
@@ -104,6 +114,13 @@ inline int dispatch_T(int T, F&& f) {
     case 16: return f(std::integral_constant<int, 16>{});
     default: return MSGAT_ERR_UNSUPPORTED;
   }
+}
+// An integer of a small range, once: f(std::integral_constant<int, V>{}) for the V in [LO, HI] that equals v (a launcher's
+// generic lambda instantiates its kernel on decltype(v)::value), MSGAT_ERR_UNSUPPORTED for a v outside the range.
+template <int LO, int HI, typename F>
+inline int dispatch_range(int v, F&& f) {
+  if constexpr (LO > HI) return MSGAT_ERR_UNSUPPORTED;
+  else return v == LO ? f(std::integral_constant<int, LO>{}) : dispatch_range<LO + 1, HI>(v, f);
 }
 inline bool t_supported(int T) {
   return dispatch_T(T, [](auto) -> int { return MSGAT_OK; }) == MSGAT_OK;
@@ -135,6 +152,22 @@ inline bool sell_usable(const msgat_sell_t& j, int nnz, int N, int T) {
 }
 
 #if defined(__HIPCC__)
+// The fp32 matrix core, once for every kernel file: v_mfma_f32_16x16x4_f32 is exact fp32, bit for bit an fmaf chain over
+// its 4 k-values.  A = a[row = lane & 15][k = lane >> 4], B = b[k = lane >> 4][column = lane & 15]; D register `reg` of a
+// lane is row 4 (lane >> 4) + reg, column lane & 15.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 f32x4_zero() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+// A dword-aligned 16-B load from the global address space (a float4 of a row that starts at any element): the explicit
+// address space keeps it a global_load, which counts on vmcnt alone (see load_global, mfma.hip).
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef const f32x4_a4 __attribute__((address_space(1)))* gf4_in_a4;
+__device__ __forceinline__ float4 load_global_a4(const float* p) {
+  const f32x4_a4 v = *(gf4_in_a4)(const f32x4_a4*)p;
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
 // Workgroup barrier for LDS hand-offs that leaves global loads in flight: __syncthreads() makes hipcc drain vmcnt(0)
 // first, which would serialise a register prefetch -- or an LDS-DMA ring -- against the barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -262,7 +295,7 @@ int launch_project_epi(const float* in, const float* M, int m_in_major, const fl
 int launch_project_seg(const SegList& in, const float* M, int m_in_major, const float* qvec, const float* addvec,
                        const float* extra, const SegList& out, float* q, int G, int Bg, int P,
                        const MixEpilogue& epi, hipStream_t s);
-// MFMA forms (mfma.hip); launch_project / launch_chanpair dispatch to them
+// MFMA forms (projection: mfma.hip, contraction: contract.hip); launch_project / launch_chanpair dispatch to them
 size_t project_mfma_lds_bytes(int Ci, int Co, bool has_extra);
 int launch_project_mfma(const SegList& in, const float* M, int m_in_major, const float* qvec,
                         const float* addvec, const float* extra, const SegList& out, float* q, int G, int Bg,

@@ -26,7 +26,7 @@
 // computes the edge scores, so edge pass and backward agree on every score bit for bit.
 #include "common.hpp"
 #include "halfsplit.hpp"
-#include "softmax_recreate.hpp"   // f32x4, mfma_16x16x4: the score chains here are built on the primitive of the kernels that re-create them
+#include "softmax_recreate.hpp"   // the score chains here are built on the primitive (common.hpp: f32x4, mfma_16x16x4) of the kernels that re-create them
 
 #include <cstdlib>
 

@@ -5,7 +5,7 @@
 //   dalpha[r,c]  = sum_{g in r, p}  dq[g,p]  x[g,c,p]
 //
 // All three are "channel-pair" contractions over a long position axis.  Each wave reduces
-// a span of positions to a [Ca x Cb] partial (MFMA, mfma.hip), written with plain stores; a
+// a span of positions to a [Ca x Cb] partial (MFMA, contract.hip), written with plain stores; a
 // second small kernel sums the partials in a fixed order, so the gradients are bitwise
 // reproducible run to run (no float atomics).
 #include "common.hpp"
@@ -167,7 +167,7 @@ int launch_reduce_groups(const float* part, int R, int J, int Wd, float* dst, hi
 }
 
 // ---- channel-pair contraction over positions --------------------------------------------------------
-// k_chanpair_mfma (mfma.hip) leaves one [Ca x Cb] partial per block of its persistent grid; the
+// k_chanpair_mfma (contract.hip) leaves one [Ca x Cb] partial per block of its persistent grid; the
 // fixed-order sum over a relation's blocks happens here.
 size_t chanpair_partial_floats(int G, int Bg, int Ca, int Cb) {
   const int R = G / Bg;

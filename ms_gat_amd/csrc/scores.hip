@@ -239,7 +239,6 @@ __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
   // As 144 lanes walking all 256 rows (two LDS reads per fma, one dependent chain per lane) this tail cost 2.6-3 us of a
   // 13-18 us launch (lab build without it, round 4).
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = lane & 15, kq = lane >> 4;
     const int ic = i < T ? i : 0;
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(kRowBlock) void k_bwd_rows(
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const int row = 64 * wave + 4 * k + kq;
-      d = __builtin_amdgcn_mfma_f32_16x16x4f32(qs[row * T + ic] * keep, ds[row * T + ic] * keep, d, 0, 0, 0);
+      d = mfma_16x16x4(qs[row * T + ic] * keep, ds[row * T + ic] * keep, d);
     }
     __syncthreads();          // everyone is done reading qs: it now carries the four tiles
     static_assert(kRowBlock == 256 && kRowBlock * 4 >= 4 * 256, "four waves, one 16x16 tile each");

@@ -14,16 +14,11 @@
 // P; a change here changes all of them together, and tests/test_gpu_score_edges.py (bits against the forward's E at
 // the edges, large scores) and tests/test_gpu_group_counts.py (every kernel at training group counts) pin the result.
 // dense.hip, which defines the order, includes this header too and builds its own chains (score_trip, column_trip: the
-// A operand comes out of LDS there) on the same f32x4 / mfma_16x16x4.
+// A operand comes out of LDS there) on the same f32x4 / mfma_16x16x4 (common.hpp).
 #pragma once
 #include "common.hpp"
 
 namespace msgat {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // ---- at one (n, m): the edge kernels ----------------------------------------------------------------------------------
 // P_g[n,m] from [G,N,T] q / kW and [G,N] lse; NT = (size_t)N * T, hoisted by the caller

@@ -144,6 +144,7 @@ def test_tacn_module(B, Ci, Co, N, T, dil):
     (3, 2, 24, 24, 883, 12, 2), (1, 3, 16, 16, 307, 12, 4), (2, 1, 32, 32, 64, 12, 1), (1, 2, 24, 16, 13, 8, 2),
     (1, 2, 16, 24, 50, 16, 4), (2, 2, 24, 24, 5, 4, 1), (1, 2, 16, 16, 20, 4, 4), (1, 1, 24, 24, 1, 12, 3),
     (1, 2, 40, 72, 33, 12, 2),
+    (1, 2, 24, 40, 33, 12, 2),   # 40 gradient rows = 80 virtual ones against 24 / 25 columns, P = 396: the shifted <5,NB,false,128> form
 ])
 def test_causal_conv_is_the_dilated_convolution_and_its_autograd_in_one_pass_each(R, Bg, Ci, Co, N, T, d):
     """ops.causal_conv = Conv2d(Ci, Co, [1,2], padding=[0,d], dilation=[1,d]) + Chomp(d) (msgat.py:69-74) for R parameter

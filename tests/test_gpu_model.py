@@ -205,7 +205,7 @@ def test_whole_model_matches_the_dense_op_sequence(factory, cin, R, N):
     """Every width / dilation recipe of the reference's factories (msgat.py:220-229; msgat96 stacks four
     convolutions in its first TACN) through the library, against the same parameters evaluated with the
     reference's dense op sequence (oracle/dense_torch.py) in float64: prediction and every gradient.  N = 64 gives
-    768 positions per channel slab: every width then runs its LDS-DMA one-pass backward forms (mfma.hip
+    768 positions per channel slab: every width then runs its LDS-DMA one-pass backward forms (contract.hip
     MSGAT_GLDS_FORMS; below 512 positions the register-staged kernels run)."""
     from ms_gat_amd import model
     from oracle import dense_torch
