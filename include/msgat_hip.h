@@ -55,7 +55,8 @@ extern "C" {
  *     + msgat_edge_weight_grad_sets{,_workspace_bytes} (the gradient of a per-sample sparse adjacency's values [n_sets,nnz]);
  *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map);
  *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings);
- *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out).
+ *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out);
+ *     + msgat_window_gather (a step's input windows from a series resident in device memory).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -792,6 +793,28 @@ int msgat_adam_step_guarded(float* const* chunk_param, const int64_t* chunk_off,
                             int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq, float* steps,
                             const float* lr, double beta1, double beta2, double eps, double weight_decay,
                             const float* grad_divisor, const float* guard, void* stream);
+
+/* ---- device: the input windows of a batch (replaces data_loader.py:92-115, TimeSeriesSlice, and the host collate) ----
+ * msgat_window_gather: one launch builds the batch of B forecast origins from a series that stays in device memory.
+ *       series  [T_total, C, N] fp32   the normalised series, TIME-MAJOR (the host keeps [C, N, T_total]; the caller
+ *                                      transposes once): every read is then coalesced over the (channel, node) rows
+ *       target  [N, T_total]    fp32   channel 0 of the raw series, as the host keeps it
+ *       origins [B]  int64, device     the forecast origins t_b
+ *       offsets [R]  int64, device     offsets[r] = hours[r] * tau, how far component r looks back; history = their
+ *                                      largest (a POD: the clamp below must not depend on device data being read back)
+ *     writes, with t_b = origins[b] CLAMPED into [history, T_total - q]:
+ *       X [B, R, C, N, tau] fp32   X[b,r,c,n,k] = series[t_b - offsets[r] + k, c, n]
+ *       Y [B, N, q]         fp32   Y[b,n,j]     = target[n, t_b + j]
+ *       H [B], D [B]        int64  (t_b / tau) % 24 and (t_b / tau / 24) % 7
+ *     The clamp makes ANY content of `origins` safe: no origin can make the launch read outside the two arrays (a window
+ *     start is clamped into [0, T_total - tau] as well, so neither can a table with offsets[r] > history); a clamped
+ *     origin yields the batch of the nearest valid origin.  Values move as 32-bit words: NaNs keep their bits.  Every
+ *     offset is 64-bit (a series of 8192 nodes passes 2^31 elements).  tau in {4, 8, 12, 16} (MSGAT_ERR_UNSUPPORTED
+ *     otherwise), 1 <= q <= 64, any B, R >= 1, C * N and N * q below 2^31 - 256; T_total >= history + q (MSGAT_ERR_SHAPE otherwise).
+ *     X must be 16-byte aligned. */
+int msgat_window_gather(const float* series, const float* target, const int64_t* origins, const int64_t* offsets,
+                        float* X, int64_t* H, int64_t* D, float* Y, int32_t B, int32_t R, int32_t C, int32_t N,
+                        int64_t T_total, int32_t tau, int32_t q, int64_t history, void* stream);
 
 #ifdef __cplusplus
 }

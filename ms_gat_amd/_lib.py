@@ -179,6 +179,8 @@ _PROTOTYPES = {
                                    C.c_void_p]),
     "msgat_adam_step_guarded": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
                                 + [C.c_double] * 4 + [C.c_void_p] * 3),
+    "msgat_window_gather": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                                         C.c_void_p]),
 }
 
 _lock = threading.Lock()

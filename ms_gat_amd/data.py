@@ -78,7 +78,7 @@ class MSGATData:
     """
 
     def __init__(self, name: str, in_hours: List[int], out_timesteps: int, batch_size: int, num_workers: int = 0,
-                 meta_file: str = "data/meta.yaml", meta: dict | None = None):
+                 meta_file: str = "data/meta.yaml", meta: dict | None = None, device=None):
         if meta is None:
             with open(meta_file) as f:
                 meta = yaml.safe_load(f)[name]
@@ -88,7 +88,7 @@ class MSGATData:
         self.adj = load_adjacency_csv(meta["adj-file"], self.num_nodes)
         raw = torch.from_numpy(np.load(meta["data-file"])["data"]).float().transpose(0, -1)  # [C,N,T_total]
         self.training, self.validation, self.evaluation = make_loaders(
-            raw, self.in_hours, out_timesteps, self.timesteps_per_hour, batch_size, num_workers)
+            raw, self.in_hours, out_timesteps, self.timesteps_per_hour, batch_size, num_workers, device=device)
 
 
 class ShardedBatchSampler(Sampler):
@@ -133,19 +133,102 @@ class ShardedBatchSampler(Sampler):
             yield order[b + lo: b + hi]
 
 
+def upload_series(inputs: torch.Tensor, target: torch.Tensor, device):
+    """The two arrays `DeviceWindows` reads, as it keeps them on `device`: inputs [C,N,T_total] -> TIME-MAJOR
+    [T_total,C,N] (a window is then tau rows read coalesced over the (channel, node) axis, and a block of the gather
+    kernel writes one contiguous piece of X), target [N,T_total] as it is.  4 * T_total * N * (C + 1) bytes."""
+    device = torch.device(device)
+    if inputs.dim() != 3 or inputs.dtype != torch.float32 or target.dtype != torch.float32 \
+            or tuple(target.shape) != (inputs.shape[1], inputs.shape[2]):
+        raise ValueError(f"inputs {tuple(inputs.shape)} {inputs.dtype} must be float32 [C,N,T_total] and target "
+                         f"{tuple(target.shape)} {target.dtype} float32 [N,T_total]")
+    return inputs.to(device).permute(2, 0, 1).contiguous(), target.to(device).contiguous()
+
+
+def _windows_torch(series_tm: torch.Tensor, target: torch.Tensor, origins: torch.Tensor, hours, tau: int, q: int):
+    """`ops.window_gather` restated with torch indexing (bit-equal to collated `PeriodicWindows` items); serves
+    `DeviceWindows(device="cpu")` and states what the kernel must give."""
+    back = torch.tensor([h * tau for h in hours], dtype=torch.int64, device=origins.device)
+    rows = origins[:, None, None] - back[None, :, None] + torch.arange(tau, device=origins.device)     # [B,R,tau]
+    x = series_tm[rows].permute(0, 1, 3, 4, 2).contiguous()                                            # [B,R,C,N,tau]
+    y = target[:, origins[:, None] + torch.arange(q, device=origins.device)].permute(1, 0, 2).contiguous()
+    hour = origins // tau
+    return x, hour % 24, (hour // 24) % 7, y
+
+
+class DeviceWindows:
+    """A loader whose series lives on the device: every batch is built there from its forecast origins, by one launch
+    of `ops.window_gather` -- no per-sample Python, no collate, no pinning, no host-to-device copy of the batch.
+
+    Takes what a split of `make_loaders` takes (the normalised series [C,N,T_total], `raw[0]`, the interval of origins,
+    hours, q, tau) and always walks `ShardedBatchSampler(len, batch_size, shuffle, rank, world, seed)`; it yields the
+    batches `DataLoader(PeriodicWindows(...), batch_sampler=<that sampler>)` yields, on `device`.  The whole index order
+    of an epoch goes to the device in ONE copy at `__iter__`; a batch's origins are a slice of it.  `Engine.run_epoch`
+    finds `batch_sampler` (`set_epoch`, `global_batch_sizes`) and `msgat_sharded` as on a sharded DataLoader.
+    `resident`: the pair `upload_series` returned, to share one upload among several splits.
+    With `device="cpu"` the batches come from `_windows_torch`: the host logic is the same."""
+
+    def __init__(self, inputs: torch.Tensor, target: torch.Tensor, interval: Tuple[int, int], hours: Sequence[int],
+                 out_timesteps: int, timesteps_per_hour: int, batch_size: int, shuffle: bool = False, rank: int = 0,
+                 world: int = 1, seed: int = 0, device="cuda", resident=None):
+        self.dataset = PeriodicWindows(inputs, target, interval, hours, out_timesteps, timesteps_per_hour)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        history = timesteps_per_hour * max(hours)
+        if not history <= interval[0] <= interval[1] <= inputs.shape[-1] - out_timesteps + 1:
+            raise ValueError(f"origins {tuple(interval)} leave the series: they must lie in [{history}, "
+                             f"{inputs.shape[-1] - out_timesteps}]")
+        self.series, self.target = upload_series(inputs, target, self.device) if resident is None else resident
+        if self.series.device != self.device or tuple(self.series.shape) != (inputs.shape[2], *inputs.shape[:2]):
+            raise ValueError("resident arrays do not belong to this series and device")
+        self.resident_bytes = self.series.numel() * 4 + self.target.numel() * 4
+        self.batch_sampler = ShardedBatchSampler(len(self.dataset), batch_size, shuffle, rank, world, seed)
+        self.msgat_sharded = world > 1
+        self._offsets = None
+        if self.device.type == "cuda":
+            from . import ops
+            self._offsets = ops.window_offsets(hours, timesteps_per_hour, self.device)
+
+    def __len__(self) -> int:
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        ds = self.dataset
+        batches = list(self.batch_sampler)
+        if not batches:
+            return
+        order = (torch.tensor([i for b in batches for i in b], dtype=torch.int64) + ds.start).to(self.device)
+        at = 0
+        for b in batches:
+            origins = order[at: at + len(b)]
+            at += len(b)
+            if self.device.type == "cuda":
+                from . import ops
+                yield ops.window_gather(self.series, self.target, origins, ds.hours, ds.tau, ds.q, offsets=self._offsets)
+            else:
+                yield _windows_torch(self.series, self.target, origins, ds.hours, ds.tau, ds.q)
+
+
 def make_loaders(raw: torch.Tensor, in_hours, out_timesteps, tau, batch_size, num_workers=0, pin_memory=True,
-                 rank: int | None = None, world: int | None = None, seed: int = 0):
+                 rank: int | None = None, world: int | None = None, seed: int = 0, device=None):
     """raw [C,N,T_total] -> (training, validation, evaluation) loaders; only training shuffles (data_loader.py:80-89).
 
     `batch_size` is the GLOBAL batch (the reference's `-b`).  Under an initialised process group (or explicit
     `rank` / `world`) the loaders are sharded (`ShardedBatchSampler`, attribute `msgat_sharded`): every rank loads
-    only its part of each global batch."""
+    only its part of each global batch.
+    `device` given: three `DeviceWindows` over ONE upload of the series to that device instead of DataLoaders."""
     import torch.distributed as dist
     if world is None:
         on = dist.is_available() and dist.is_initialized()
         rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
     intervals, train_end = split_intervals(raw.size(-1), in_hours, out_timesteps, tau)
     normed = zscore(raw, split=train_end)
+    if device is not None:
+        resident = upload_series(normed, raw[0], device)
+        return [DeviceWindows(normed, raw[0], iv, in_hours, out_timesteps, tau, batch_size, shuffle=(i == 0), rank=rank,
+                              world=world, seed=seed, device=resident[0].device, resident=resident)
+                for i, iv in enumerate(intervals)]
     pin = pin_memory and torch.cuda.is_available()
     loaders = []
     for i, iv in enumerate(intervals):
@@ -165,7 +248,7 @@ class SyntheticPEMS:
 
     def __init__(self, n_nodes: int, n_edges: int, n_channels: int, in_hours: List[int], out_timesteps: int = 12,
                  batch_size: int = 32, timesteps_per_hour: int = 12, days: int = 14, seed: int = 0,
-                 num_workers: int = 0):
+                 num_workers: int = 0, device=None):
         self.num_nodes, self.num_channels, self.timesteps_per_hour = n_nodes, n_channels, timesteps_per_hour
         self.in_hours, self.out_timesteps = list(in_hours), out_timesteps
         self.adj = synthetic_adjacency(n_nodes, n_edges, seed)
@@ -177,4 +260,4 @@ class SyntheticPEMS:
         raw = base * (1 + 0.4 * daily) + 15 * torch.randn(n_channels, n_nodes, total, generator=g)
         self.raw = raw.clamp_min(1.0)
         self.training, self.validation, self.evaluation = make_loaders(
-            self.raw, self.in_hours, out_timesteps, timesteps_per_hour, batch_size, num_workers)
+            self.raw, self.in_hours, out_timesteps, timesteps_per_hour, batch_size, num_workers, device=device)

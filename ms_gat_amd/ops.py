@@ -1795,6 +1795,64 @@ def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, 
     return _MaskedHuberMetricsFunction.apply(pred, truth, delta, null_value, mask_value, sums, valid)
 
 
+# ---- input windows of a batch from a series resident in device memory ---------------------------------------------
+def window_offsets(hours, tau: int, device) -> torch.Tensor:
+    """`hours[r] * tau` as the int64 device array `window_gather` reads; a loader builds it once and passes it on."""
+    return torch.tensor([int(h) * int(tau) for h in hours], dtype=torch.int64).to(device)
+
+
+def window_gather(inputs_dev: torch.Tensor, target_dev: torch.Tensor, origins: torch.Tensor, hours, tau: int, q: int,
+                  offsets: Optional[torch.Tensor] = None):
+    """The batch `(X [B,R,C,N,tau], H [B], D [B], Y [B,N,q])` of the forecast origins `origins` [B] (int64, on the device)
+    in one launch (`msgat_window_gather`): what collating `data.PeriodicWindows` items gives, without the host.
+
+    `inputs_dev` is the normalised series TIME-MAJOR, [T_total, C, N] float32 (`data.upload_series` makes it from the
+    host's [C, N, T_total]); `target_dev` [N, T_total] float32 is channel 0 of the raw series; `hours` a sequence of
+    ints; `offsets`: what `window_offsets(hours, tau, device)` gave, for a caller that keeps it (without it the array
+    is built, and copied to the device, by this call).  Origins outside [tau * max(hours), T_total - q] are clamped into
+    it by the kernel.  No autograd: data."""
+    for name, t in (("inputs_dev", inputs_dev), ("target_dev", target_dev)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"window_gather: {name} must be float32, got {t.dtype}")
+    if origins.dtype != torch.int64:
+        raise TypeError(f"window_gather: origins must be int64, got {origins.dtype}")
+    if target_dev.device != inputs_dev.device or origins.device != inputs_dev.device:
+        raise ValueError(f"window_gather: inputs_dev on {inputs_dev.device}, target_dev on {target_dev.device} and origins "
+                         f"on {origins.device} must share one device")
+    hours = [int(h) for h in hours]
+    if not hours or min(hours) < 1:
+        raise ValueError(f"window_gather: hours {hours} must be a non-empty sequence of positive ints")
+    if tau not in (4, 8, 12, 16) or not 1 <= q <= 64:
+        raise ValueError(f"window_gather: tau = {tau} must be 4, 8, 12 or 16 and q = {q} between 1 and 64")
+    if inputs_dev.dim() != 3 or target_dev.dim() != 2 or origins.dim() != 1 or origins.numel() == 0:
+        raise ValueError(f"window_gather: inputs_dev {tuple(inputs_dev.shape)} must be [T_total, C, N], target_dev "
+                         f"{tuple(target_dev.shape)} [N, T_total] and origins {tuple(origins.shape)} a non-empty [B]")
+    T_total, C_, N = inputs_dev.shape
+    if tuple(target_dev.shape) != (N, T_total):
+        raise ValueError(f"window_gather: target_dev {tuple(target_dev.shape)} does not fit inputs_dev [T_total = {T_total}, "
+                         f"C = {C_}, N = {N}]: expected [{N}, {T_total}]")
+    history = tau * max(hours)
+    if T_total < history + q:
+        raise ValueError(f"window_gather: a series of {T_total} steps is shorter than tau * max(hours) + q = {history + q}")
+    if not (inputs_dev.is_contiguous() and target_dev.is_contiguous() and origins.is_contiguous()):
+        raise ValueError("window_gather: inputs_dev, target_dev and origins must be contiguous")
+    _require_device_tensor("inputs_dev", inputs_dev)
+    dev, B, R = inputs_dev.device, origins.numel(), len(hours)
+    if offsets is None:
+        offsets = window_offsets(hours, tau, dev)
+    elif offsets.dtype != torch.int64 or offsets.device != dev or tuple(offsets.shape) != (R,) or not offsets.is_contiguous():
+        raise ValueError(f"window_gather: offsets must be a contiguous int64 [{R}] tensor on {dev}")
+    X = torch.empty((B, R, C_, N, tau), device=dev, dtype=torch.float32)
+    Y = torch.empty((B, N, q), device=dev, dtype=torch.float32)
+    HD = torch.empty((2, B), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        st = _lib.lib().msgat_window_gather(_ptr(inputs_dev), _ptr(target_dev), _ptr(origins), _ptr(offsets), _ptr(X),
+                                            _ptr(HD[0]), _ptr(HD[1]), _ptr(Y), B, R, C_, N, T_total, tau, q, history,
+                                            _stream_handle(dev))
+    _lib.check(st, "msgat_window_gather")
+    return X, HD[0], HD[1], Y
+
+
 # ---- boundary hygiene for every autograd.Function above -----------------------------------------------------------
 # (a) the library's launches act on the CURRENT HIP device (hipFuncSetAttribute for > 64 KB LDS, occupancy queries),
 #     while the reference's API lets the caller name any device (`run_epoch(..., gpu_id=k)`, engine.py:40,50):
