@@ -56,7 +56,8 @@ extern "C" {
  *     + msgat_softmax_map_grad{,_workspace_bytes} and msgat_gacn_backward_map_grad (a gradient at the dense softmax map);
  *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings);
  *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out);
- *     + msgat_window_gather (a step's input windows from a series resident in device memory).
+ *     + msgat_window_gather (a step's input windows from a series resident in device memory);
+ *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -759,6 +760,33 @@ int msgat_masked_huber_grad(const float* pred, const float* truth, const float* 
                             int32_t T_out, float delta, float null_value, float* dpred, void* stream);
 int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                             int32_t n_chunks, const float* scale, float* flat, int64_t weight_index, void* stream);
+
+/* ---- device: the Gauss loss in the step tail, plain and masked (GaussLoss / gauss_loss, loss.py:55-95) ----
+ * The reference's robust loss, whose weight on an entry saturates where Huber's grows without bound.  With
+ * e = pred - truth, sigma finite and > 0, delta finite and >= 0 (0: the saturating term alone):
+ *       g(e)  = sigma^2 (1 - exp(-e^2 / (2 sigma^2))) + delta |e|                       (the value of one entry)
+ *       g'(e) = e exp(-e^2 / (2 sigma^2)) + delta sgn(e),  sgn(0) = 0                    (torch's abs backward)
+ * The four entry points mirror msgat_huber_metrics, msgat_huber_grad, msgat_masked_huber_metrics and
+ * msgat_masked_huber_grad argument for argument, with sigma in front of delta, and run the same kernels with another
+ * loss: the same launches, summation order, status codes and limits, `partials` sized by the SAME
+ * msgat_huber_partial_doubles(n) / msgat_masked_huber_partial_doubles(rows, T_out) with the same layout, and the same
+ * totals -- sums [4] with sums[3] += loss_weight * loss[0], sums [T_out + 1, 5] with column 4 = sum g(e).
+ *       plain    loss[0] = mean over n of g(e)   (= sigma^2 mean(1 - exp(...)) + delta mean |e|, loss.py:94-95);
+ *                dpred = dloss[0] g'(e) / n
+ *       masked   loss[0] = sum_valid g(e) / max(valid, 1);  dpred = dloss[0] g'(e) / max(valid[0], 1) at the valid
+ *                entries and exactly +0 at the others
+ * g and g' are evaluated per entry in fp32 -- 1 - exp(-t) as -expm1f(-t), which keeps its precision for |e| << sigma
+ * where 1 - expf(-t) cancels -- and added in fp64; sigma^2 and 1 / (2 sigma^2) are formed in double and rounded once.
+ * sigma or delta outside their ranges (NaN included): MSGAT_ERR_SHAPE, before any launch. */
+int msgat_gauss_metrics(const float* pred, const float* truth, int64_t n, float sigma, float delta, float mask_value,
+                        double* partials, float* loss, double* sums, float loss_weight, void* stream);
+int msgat_gauss_grad(const float* pred, const float* truth, const float* dloss, int64_t n, float sigma, float delta,
+                     float* dpred, void* stream);
+int msgat_masked_gauss_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float sigma, float delta,
+                               float null_value, float mask_value, double* partials, float* loss, float* valid,
+                               double* sums, void* stream);
+int msgat_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid, int64_t rows,
+                            int32_t T_out, float sigma, float delta, float null_value, float* dpred, void* stream);
 
 /* ---- device: the guard on the optimizer step (off unless a caller uses msgat_grad_guard and msgat_adam_step_guarded) ----
  * The reference trains under GradScaler (engine.py:61-63), whose step() leaves the update out when a gradient is Inf or

@@ -179,6 +179,13 @@ _PROTOTYPES = {
                                    C.c_void_p]),
     "msgat_adam_step_guarded": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
                                 + [C.c_double] * 4 + [C.c_void_p] * 3),
+    "msgat_gauss_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 3
+                            + [C.c_float, C.c_void_p]),
+    "msgat_gauss_grad": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "msgat_masked_gauss_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_float] * 4
+                                   + [C.c_void_p] * 5),
+    "msgat_masked_gauss_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                                            C.c_void_p, C.c_void_p]),
     "msgat_window_gather": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                                          C.c_void_p]),
 }

@@ -2,6 +2,7 @@
 // Argument checks happen on the host before anything is enqueued: a bad shape must come
 // back as a status code, never as a faulting kernel.
 #include "common.hpp"
+#include <cmath>
 #include <cstdio>
 
 using namespace msgat;
@@ -1097,6 +1098,29 @@ extern "C" int msgat_huber_grad(const float* pred, const float* truth, const flo
   return launch_huber_grad(pred, truth, dloss, n, delta, dpred, (hipStream_t)stream);
 }
 
+// the Gauss loss in the same tail: sigma finite and > 0, delta finite and >= 0 (0: the saturating term alone)
+static int check_gauss(float sigma, float delta) {
+  return std::isfinite(sigma) && sigma > 0.f && std::isfinite(delta) && delta >= 0.f ? MSGAT_OK : MSGAT_ERR_SHAPE;
+}
+
+extern "C" int msgat_gauss_metrics(const float* pred, const float* truth, int64_t n, float sigma, float delta,
+                                   float mask_value, double* partials, float* loss, double* sums, float loss_weight,
+                                   void* stream) {
+  if (!pred || !truth || !partials || !loss) return MSGAT_ERR_NULL;
+  if (n <= 0 || !(loss_weight >= 0.f)) return MSGAT_ERR_SHAPE;
+  if (int st = check_gauss(sigma, delta)) return st;
+  return launch_gauss_metrics(pred, truth, n, sigma, delta, mask_value, partials, loss, sums, loss_weight,
+                              (hipStream_t)stream);
+}
+
+extern "C" int msgat_gauss_grad(const float* pred, const float* truth, const float* dloss, int64_t n, float sigma,
+                                float delta, float* dpred, void* stream) {
+  if (!pred || !truth || !dloss || !dpred) return MSGAT_ERR_NULL;
+  if (n <= 0) return MSGAT_ERR_SHAPE;
+  if (int st = check_gauss(sigma, delta)) return st;
+  return launch_gauss_grad(pred, truth, dloss, n, sigma, delta, dpred, (hipStream_t)stream);
+}
+
 extern "C" int msgat_adam_chunk_elems(void) { return adam_chunk_elems(); }
 
 extern "C" int msgat_adam_step(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
@@ -1181,6 +1205,26 @@ extern "C" int msgat_masked_huber_grad(const float* pred, const float* truth, co
   if (!pred || !truth || !dloss || !valid || !dpred) return MSGAT_ERR_NULL;
   if (int st = check_masked(rows, T_out, delta)) return st;
   return launch_masked_huber_grad(pred, truth, dloss, valid, rows, T_out, delta, null_value, dpred, (hipStream_t)stream);
+}
+
+extern "C" int msgat_masked_gauss_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float sigma,
+                                          float delta, float null_value, float mask_value, double* partials,
+                                          float* loss, float* valid, double* sums, void* stream) {
+  if (!pred || !truth || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_gauss(sigma, delta)) return st;
+  if (int st = check_masked(rows, T_out, 1.f)) return st;
+  return launch_masked_gauss_metrics(pred, truth, rows, T_out, sigma, delta, null_value, mask_value, partials, loss, valid,
+                                     sums, (hipStream_t)stream);
+}
+
+extern "C" int msgat_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                                       int64_t rows, int32_t T_out, float sigma, float delta, float null_value,
+                                       float* dpred, void* stream) {
+  if (!pred || !truth || !dloss || !valid || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_gauss(sigma, delta)) return st;
+  if (int st = check_masked(rows, T_out, 1.f)) return st;
+  return launch_masked_gauss_grad(pred, truth, dloss, valid, rows, T_out, sigma, delta, null_value, dpred,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,

@@ -509,6 +509,11 @@ int launch_huber_metrics(const float* pred, const float* truth, long long n, flo
                          double* part, float* loss, double* sums, float loss_weight, hipStream_t s);
 int launch_huber_grad(const float* pred, const float* truth, const float* dloss, long long n, float delta,
                       float* dpred, hipStream_t s);
+// the same launches, partial layout and totals with the Gauss loss (sigma, delta: the host's doubles)
+int launch_gauss_metrics(const float* pred, const float* truth, long long n, double sigma, double delta,
+                         float mask_value, double* part, float* loss, double* sums, float loss_weight, hipStream_t s);
+int launch_gauss_grad(const float* pred, const float* truth, const float* dloss, long long n, double sigma, double delta,
+                      float* dpred, hipStream_t s);
 int adam_chunk_elems();
 int launch_adam(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, const int* chunk_tensor,
                 int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
@@ -529,6 +534,12 @@ int launch_masked_huber_metrics(const float* pred, const float* truth, long long
                                 double* sums, hipStream_t s);
 int launch_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
                              long long rows, int T, float delta, float null_value, float* dpred, hipStream_t s);
+int launch_masked_gauss_metrics(const float* pred, const float* truth, long long rows, int T, double sigma, double delta,
+                                float null_value, float mask_value, double* part, float* loss, float* valid,
+                                double* sums, hipStream_t s);
+int launch_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                             long long rows, int T, double sigma, double delta, float null_value, float* dpred,
+                             hipStream_t s);
 int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                              const float* scale, float* flat, long long weight_index, hipStream_t s);
 

@@ -5,9 +5,11 @@
 //                        beyond), engine.py:66-70 + metrics.py:20-35: per batch `loss.item()` and three more `.item()`
 //                        sums (|e|, 100 |e / y| where y > mask, e^2) -- four host syncs and ~10 elementwise / reduce
 //                        launches; engine.py:106 optim.Adam(lr 1e-3, weight_decay 5e-4).
-//   here                 k_huber_metrics: every block folds its elements into four double partials (fixed order inside
-//                        the block), k_huber_finish adds the partials in block order: deterministic, nothing read back.
-//                        k_huber_grad: the loss gradient.  k_adam: torch.optim.Adam's update (L2 decay folded into the
+//   here                 k_loss_metrics: every block folds its elements into four double partials (fixed order inside
+//                        the block), k_loss_finish adds the partials in block order: deterministic, nothing read back.
+//                        k_loss_grad: the loss gradient.  The first and the last take the loss as a policy (Huber,
+//                        Gauss: below), as do their masked forms further down.
+//                        k_adam: torch.optim.Adam's update (L2 decay folded into the
 //                        gradient, bias correction, eps outside the square root) for every parameter tensor at once,
 //                        driven by a chunk table; the step counter and the learning rate live in device memory so the
 //                        launch is capturable in a HIP graph.
@@ -28,17 +30,52 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-__global__ __launch_bounds__(kTailBlock) void k_huber_metrics(const float* __restrict__ pred,
-                                                              const float* __restrict__ truth, long long n,
-                                                              float delta, float mask_value,
-                                                              double* __restrict__ part) {
+// ---- the loss of the step tail: a policy of the metrics and gradient kernels, plain and masked -------------------------
+// value(a) is the loss of one entry at |e| = a, slope(e) its derivative at e; both are evaluated per entry in fp32 and the
+// values are added into double partials.  A policy is a few floats that travel as one by-value kernel argument, like the
+// lone `delta` before it.  The finish kernels only add partials: they know no loss.
+//   Huber   loss.py:51-52   e^2 / 2 inside delta, delta |e| - delta^2 / 2 beyond; slope clamp(e, -delta, delta)
+//   Gauss   loss.py:94-95   sigma^2 (1 - exp(-e^2 / 2 sigma^2)) + delta |e|; slope e exp(-e^2 / 2 sigma^2) + delta sgn(e)
+//           with sgn(0) = 0 (torch's abs backward).  1 - exp(-t) is taken as -expm1f(-t): for |e| << sigma,
+//           1.f - expf(-t) keeps only the few bits of t that survive next to 1 (|e| = 1e-3 sigma: 3.5e-3 relative error
+//           of the loss at delta = 0, against 2e-8).  The accurate library functions, not __expf.  sigma^2 and
+//           1 / (2 sigma^2) are rounded to fp32 once from the host's doubles.
+struct Huber {
+  float delta;
+  __device__ __forceinline__ float value(float a) const {
+    return (a <= delta) ? 0.5f * a * a : delta * a - 0.5f * delta * delta;
+  }
+  __device__ __forceinline__ float slope(float e) const { return fminf(fmaxf(e, -delta), delta); }
+};
+
+struct Gauss {
+  float sigma2, inv_2sigma2, delta;
+  __device__ __forceinline__ float value(float a) const {
+    const float t = a * a * inv_2sigma2;
+    return sigma2 * -expm1f(-t) + delta * a;
+  }
+  __device__ __forceinline__ float slope(float e) const {
+    const float t = e * e * inv_2sigma2;
+    return e * expf(-t) + (e == 0.f ? 0.f : copysignf(delta, e));   // e = 0: exactly 0
+  }
+};
+
+static Gauss gauss_of(double sigma, double delta) {
+  return Gauss{(float)(sigma * sigma), (float)(1.0 / (2.0 * sigma * sigma)), (float)delta};
+}
+
+template <class Loss>
+__global__ __launch_bounds__(kTailBlock) void k_loss_metrics(const float* __restrict__ pred,
+                                                             const float* __restrict__ truth, long long n,
+                                                             Loss loss, float mask_value,
+                                                             double* __restrict__ part) {
   __shared__ double red[4][kTailBlock / 64];
-  double s[4] = {0.0, 0.0, 0.0, 0.0};  // huber, |e|, 100 |e / y| (y > mask), e^2
+  double s[4] = {0.0, 0.0, 0.0, 0.0};  // loss, |e|, 100 |e / y| (y > mask), e^2
   const long long stride = (long long)gridDim.x * kTailBlock;
   for (long long i = (long long)blockIdx.x * kTailBlock + threadIdx.x; i < n; i += stride) {
     const float p = pred[i], y = truth[i];
     const float e = p - y, a = fabsf(e);
-    s[0] += (a <= delta) ? 0.5f * a * a : delta * a - 0.5f * delta * delta;
+    s[0] += loss.value(a);
     s[1] += a;
     if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
     s[3] += (double)e * (double)e;
@@ -58,11 +95,11 @@ __global__ __launch_bounds__(kTailBlock) void k_huber_metrics(const float* __res
   }
 }
 
-// loss[0] = mean Huber loss (fp32, what the reference's loss tensor holds); sums[0..2] += AE, APE, SE and
+// loss[0] = mean loss (fp32, what the reference's loss tensor holds); sums[0..2] += AE, APE, SE and
 // sums[3] += loss_weight * that mean (the epoch's running total of batch losses; a rank that holds n_r of a global
 // batch's n_b samples passes n_r / n_b, so the sum over ranks is the global batch's mean loss), all double
-__global__ void k_huber_finish(const double* __restrict__ part, int nblocks, long long n, float* __restrict__ loss,
-                               double* __restrict__ sums, float loss_weight) {
+__global__ void k_loss_finish(const double* __restrict__ part, int nblocks, long long n, float* __restrict__ loss,
+                              double* __restrict__ sums, float loss_weight) {
   // wave k adds sum k: lane l takes blocks l, l + 64, ... in order, then the lanes are combined by the fixed butterfly
   // of wave_sum (a serial loop over up to 1024 partials by one lane took 19 us)
   const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -78,14 +115,15 @@ __global__ void k_huber_finish(const double* __restrict__ part, int nblocks, lon
   }
 }
 
-__global__ __launch_bounds__(kTailBlock) void k_huber_grad(const float* __restrict__ pred,
-                                                           const float* __restrict__ truth,
-                                                           const float* __restrict__ dloss, long long n, float delta,
-                                                           float* __restrict__ dpred) {
+template <class Loss>
+__global__ __launch_bounds__(kTailBlock) void k_loss_grad(const float* __restrict__ pred,
+                                                          const float* __restrict__ truth,
+                                                          const float* __restrict__ dloss, long long n, Loss loss,
+                                                          float* __restrict__ dpred) {
   const long long i = (long long)blockIdx.x * kTailBlock + threadIdx.x;
   if (i >= n) return;
   const float e = pred[i] - truth[i];
-  const float g = fminf(fmaxf(e, -delta), delta);  // d/de of the Huber function
+  const float g = loss.slope(e);  // d/de of the entry's loss
   dpred[i] = g * (dloss[0] / (float)n);
 }
 
@@ -96,22 +134,44 @@ static int huber_blocks(long long n) {
 
 size_t huber_partial_doubles(long long n) { return (size_t)huber_blocks(n) * 4; }
 
-int launch_huber_metrics(const float* pred, const float* truth, long long n, float delta, float mask_value,
-                         double* part, float* loss, double* sums, float loss_weight, hipStream_t s) {
+template <class Loss>
+static int launch_loss_metrics(const float* pred, const float* truth, long long n, Loss lf, float mask_value,
+                               double* part, float* loss, double* sums, float loss_weight, hipStream_t s) {
   const int nb = huber_blocks(n);
-  hipLaunchKernelGGL(k_huber_metrics, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, delta, mask_value, part);
+  hipLaunchKernelGGL(k_loss_metrics<Loss>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, lf, mask_value, part);
   MSGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_huber_finish, dim3(1), dim3(256), 0, s, part, nb, n, loss, sums, loss_weight);
+  hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(256), 0, s, part, nb, n, loss, sums, loss_weight);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
 
-int launch_huber_grad(const float* pred, const float* truth, const float* dloss, long long n, float delta,
-                      float* dpred, hipStream_t s) {
-  hipLaunchKernelGGL(k_huber_grad, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s, pred,
-                     truth, dloss, n, delta, dpred);
+template <class Loss>
+static int launch_loss_grad(const float* pred, const float* truth, const float* dloss, long long n, Loss lf,
+                            float* dpred, hipStream_t s) {
+  hipLaunchKernelGGL(k_loss_grad<Loss>, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s, pred,
+                     truth, dloss, n, lf, dpred);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
+}
+
+int launch_huber_metrics(const float* pred, const float* truth, long long n, float delta, float mask_value,
+                         double* part, float* loss, double* sums, float loss_weight, hipStream_t s) {
+  return launch_loss_metrics(pred, truth, n, Huber{delta}, mask_value, part, loss, sums, loss_weight, s);
+}
+
+int launch_huber_grad(const float* pred, const float* truth, const float* dloss, long long n, float delta,
+                      float* dpred, hipStream_t s) {
+  return launch_loss_grad(pred, truth, dloss, n, Huber{delta}, dpred, s);
+}
+
+int launch_gauss_metrics(const float* pred, const float* truth, long long n, double sigma, double delta,
+                         float mask_value, double* part, float* loss, double* sums, float loss_weight, hipStream_t s) {
+  return launch_loss_metrics(pred, truth, n, gauss_of(sigma, delta), mask_value, part, loss, sums, loss_weight, s);
+}
+
+int launch_gauss_grad(const float* pred, const float* truth, const float* dloss, long long n, double sigma, double delta,
+                      float* dpred, hipStream_t s) {
+  return launch_loss_grad(pred, truth, dloss, n, gauss_of(sigma, delta), dpred, s);
 }
 
 // ---- the gated sum over the components (msgat.py:203-205, embeddings.py:36-39) --------------------------------------
@@ -413,18 +473,18 @@ int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_o
   return MSGAT_OK;
 }
 
-// ---- masked Huber loss + per-horizon metric sums ---------------------------------------------------------------------
+// ---- masked loss (Huber or Gauss: the policies above) + per-horizon metric sums ---------------------------------------------------------------------
 // An entry of the truth counts when it is a measurement: not NaN and not the null value (a PEMS reading of 0 = sensor
 // down).  With null_value = NaN only the NaN entries drop out (y != NaN holds for every y).
-//   k_masked_huber_metrics   the first (256 / T) * T lanes of a block walk the elements with a stride that is a multiple
+//   k_masked_loss_metrics    the first (256 / T) * T lanes of a block walk the elements with a stride that is a multiple
 //                            of T, so a lane keeps ONE horizon (element i has horizon i mod T) and its five sums
-//                            {valid count, |e|, 100 |e / y| (y > mask), e^2, huber} stay in registers, while a block
+//                            {valid count, |e|, 100 |e / y| (y > mask), e^2, loss} stay in registers, while a block
 //                            trip still reads consecutive addresses.  The lanes of a horizon hand their sums over
 //                            through LDS once per block and are added in lane order: one record [5][T] per block,
 //                            stored column-major over the blocks (part[(c T + h) nblocks + b]).
-//   k_masked_huber_finish    block c adds column c: a wave per horizon, lane l takes blocks l, l + 64, ... in order, then
+//   k_masked_loss_finish     block c adds column c: a wave per horizon, lane l takes blocks l, l + 64, ... in order, then
 //                            the butterfly of wave_sum; the all-horizon row is the sum of the horizon rows in horizon
-//                            order.  The block of the huber column adds the count column too and writes loss and valid.
+//                            order.  The block of the loss column adds the count column too and writes loss and valid.
 // Every sum has one fixed order: bitwise reproducible.  No floating-point atomics.
 constexpr int kMaskCols = 5;
 constexpr int kMaskMaxT = 64;
@@ -433,10 +493,11 @@ constexpr int kMaskFinishBlock = 1024;
 
 __device__ __forceinline__ bool entry_valid(float y, float null_value) { return y == y && y != null_value; }
 
-__global__ __launch_bounds__(kTailBlock) void k_masked_huber_metrics(const float* __restrict__ pred,
-                                                                     const float* __restrict__ truth, long long n, int T,
-                                                                     int lanes, float delta, float null_value,
-                                                                     float mask_value, double* __restrict__ part) {
+template <class Loss>
+__global__ __launch_bounds__(kTailBlock) void k_masked_loss_metrics(const float* __restrict__ pred,
+                                                                    const float* __restrict__ truth, long long n, int T,
+                                                                    int lanes, Loss loss, float null_value,
+                                                                    float mask_value, double* __restrict__ part) {
   __shared__ double red[kMaskCols][kTailBlock];
   double s[kMaskCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
   if ((int)threadIdx.x < lanes) {   // lanes % T == 0: i mod T == threadIdx.x mod T on every trip
@@ -449,7 +510,7 @@ __global__ __launch_bounds__(kTailBlock) void k_masked_huber_metrics(const float
       s[1] += a;
       if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
       s[3] += (double)e * (double)e;
-      s[4] += (a <= delta) ? 0.5f * a * a : delta * a - 0.5f * delta * delta;
+      s[4] += loss.value(a);
     }
   }
 #pragma unroll
@@ -463,14 +524,14 @@ __global__ __launch_bounds__(kTailBlock) void k_masked_huber_metrics(const float
   }
 }
 
-__global__ __launch_bounds__(kMaskFinishBlock) void k_masked_huber_finish(const double* __restrict__ part, int nblocks,
-                                                                          int T, float* __restrict__ loss,
-                                                                          float* __restrict__ valid,
-                                                                          double* __restrict__ sums) {
-  __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (huber block)
+__global__ __launch_bounds__(kMaskFinishBlock) void k_masked_loss_finish(const double* __restrict__ part, int nblocks,
+                                                                         int T, float* __restrict__ loss,
+                                                                         float* __restrict__ valid,
+                                                                         double* __restrict__ sums) {
+  __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (loss block)
   const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool huber = c == kMaskCols - 1;
-  for (int q = 0; q < (huber ? 2 : 1); ++q) {
+  const bool is_loss = c == kMaskCols - 1;
+  for (int q = 0; q < (is_loss ? 2 : 1); ++q) {
     const int col = q == 0 ? c : 0;
     for (int h = wave; h < T; h += kMaskFinishBlock / 64) {
       const double* __restrict__ p = part + (size_t)(col * T + h) * nblocks;
@@ -486,25 +547,26 @@ __global__ __launch_bounds__(kMaskFinishBlock) void k_masked_huber_finish(const 
   double total = 0.0, count = 0.0;
   for (int h = 0; h < T; ++h) total += rows[0][h];
   if (sums != nullptr) sums[(size_t)T * kMaskCols + c] += total;
-  if (!huber) return;
+  if (!is_loss) return;
   for (int h = 0; h < T; ++h) count += rows[1][h];
   valid[0] = (float)count;
   loss[0] = (float)(total / fmax(count, 1.0));
 }
 
-// dpred = dloss[0] * clamp(e, -delta, delta) / max(valid[0], 1) at the valid entries, +0 elsewhere (a NaN of the truth
+// dpred = dloss[0] * slope(e) / max(valid[0], 1) at the valid entries, +0 elsewhere (a NaN of the truth
 // ends in the select, not in the product); valid[0] comes from device memory: a captured launch follows its batch
-__global__ __launch_bounds__(kTailBlock) void k_masked_huber_grad(const float* __restrict__ pred,
-                                                                  const float* __restrict__ truth,
-                                                                  const float* __restrict__ dloss,
-                                                                  const float* __restrict__ valid, long long n,
-                                                                  float delta, float null_value,
-                                                                  float* __restrict__ dpred) {
+template <class Loss>
+__global__ __launch_bounds__(kTailBlock) void k_masked_loss_grad(const float* __restrict__ pred,
+                                                                 const float* __restrict__ truth,
+                                                                 const float* __restrict__ dloss,
+                                                                 const float* __restrict__ valid, long long n,
+                                                                 Loss loss, float null_value,
+                                                                 float* __restrict__ dpred) {
   const long long i = (long long)blockIdx.x * kTailBlock + threadIdx.x;
   if (i >= n) return;
   const float y = truth[i];
   const float e = pred[i] - y;
-  const float g = fminf(fmaxf(e, -delta), delta);
+  const float g = loss.slope(e);
   dpred[i] = entry_valid(y, null_value) ? g * (dloss[0] / fmaxf(valid[0], 1.f)) : 0.f;
 }
 
@@ -520,26 +582,52 @@ size_t masked_huber_partial_doubles(long long rows, int T) {
   return (size_t)masked_huber_blocks(rows * T, T) * kMaskCols * T;
 }
 
-int launch_masked_huber_metrics(const float* pred, const float* truth, long long rows, int T, float delta,
-                                float null_value, float mask_value, double* part, float* loss, float* valid,
-                                double* sums, hipStream_t s) {
+template <class Loss>
+static int launch_masked_loss_metrics(const float* pred, const float* truth, long long rows, int T, Loss lf,
+                                      float null_value, float mask_value, double* part, float* loss, float* valid,
+                                      double* sums, hipStream_t s) {
   const long long n = rows * T;
   const int nb = masked_huber_blocks(n, T);
-  hipLaunchKernelGGL(k_masked_huber_metrics, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T, masked_huber_lanes(T),
-                     delta, null_value, mask_value, part);
+  hipLaunchKernelGGL(k_masked_loss_metrics<Loss>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T,
+                     masked_huber_lanes(T), lf, null_value, mask_value, part);
   MSGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_masked_huber_finish, dim3(kMaskCols), dim3(kMaskFinishBlock), 0, s, part, nb, T, loss, valid, sums);
+  hipLaunchKernelGGL(k_masked_loss_finish, dim3(kMaskCols), dim3(kMaskFinishBlock), 0, s, part, nb, T, loss, valid, sums);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
 
-int launch_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
-                             long long rows, int T, float delta, float null_value, float* dpred, hipStream_t s) {
+template <class Loss>
+static int launch_masked_loss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                                   long long rows, int T, Loss lf, float null_value, float* dpred, hipStream_t s) {
   const long long n = rows * T;
-  hipLaunchKernelGGL(k_masked_huber_grad, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s,
-                     pred, truth, dloss, valid, n, delta, null_value, dpred);
+  hipLaunchKernelGGL(k_masked_loss_grad<Loss>, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s,
+                     pred, truth, dloss, valid, n, lf, null_value, dpred);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
+}
+
+int launch_masked_huber_metrics(const float* pred, const float* truth, long long rows, int T, float delta,
+                                float null_value, float mask_value, double* part, float* loss, float* valid,
+                                double* sums, hipStream_t s) {
+  return launch_masked_loss_metrics(pred, truth, rows, T, Huber{delta}, null_value, mask_value, part, loss, valid, sums, s);
+}
+
+int launch_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                             long long rows, int T, float delta, float null_value, float* dpred, hipStream_t s) {
+  return launch_masked_loss_grad(pred, truth, dloss, valid, rows, T, Huber{delta}, null_value, dpred, s);
+}
+
+int launch_masked_gauss_metrics(const float* pred, const float* truth, long long rows, int T, double sigma, double delta,
+                                float null_value, float mask_value, double* part, float* loss, float* valid,
+                                double* sums, hipStream_t s) {
+  return launch_masked_loss_metrics(pred, truth, rows, T, gauss_of(sigma, delta), null_value, mask_value, part, loss, valid,
+                                    sums, s);
+}
+
+int launch_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                             long long rows, int T, double sigma, double delta, float null_value, float* dpred,
+                             hipStream_t s) {
+  return launch_masked_loss_grad(pred, truth, dloss, valid, rows, T, gauss_of(sigma, delta), null_value, dpred, s);
 }
 
 // k_gather_scaled with the scale read from device memory: the rank's weight of a masked step is its batch's valid

@@ -3,7 +3,7 @@
 Reference: /root/reference/src/engine.py -- `Engine.run_epoch(data, gpu_id, epoch, mode)` (:40),
 `Trainer(model, loss_delta, out_dir).fit((train, val), gpu_id)` (:104-133), `.save/.load(ckpt)`
 (:135-157), `Evaluator(model, delta, out_dir, ckpt).eval(loader, gpu_id)` (:160-168);
-src/loss.py:51-52 (Huber), src/metrics.py:20-35 (MAE / MAPE / RMSE).
+src/loss.py:51-52 (Huber), :55-95 (Gauss), src/metrics.py:20-35 (MAE / MAPE / RMSE).
 
 Differences that are the point of this build:
   * fp32 end to end (the reference wraps the forward in CUDA AMP, engine.py:54; the parity bar of
@@ -18,6 +18,8 @@ Differences that are the point of this build:
   * `null_value` (off by default) treats entries of the truth that are NaN or equal to it as missing readings: they
     drop out of the loss, its gradient and the metrics, which are then kept per forecast horizon
     (`ops.masked_huber_metrics`; the batch's valid count stays on the device, also as the rank's weight).
+  * `loss=GaussLoss(sigma, delta)` (off by default: Huber) trains and evaluates with the reference's other loss, in the same
+    library tail -- one pass with metrics, masked or not, the valid count on the device, captured steps.
   * `max_grad_norm` / `skip_nonfinite` (both off by default) put a guard on the optimizer step: the global gradient norm is
     taken on the device, the gradient is clipped to `max_grad_norm` as `torch.nn.utils.clip_grad_norm_` would, and a step
     whose norm is Inf or NaN is left out whole, as the reference's `GradScaler.step` leaves it out (engine.py:61-63) --
@@ -29,6 +31,7 @@ ops for loss and optimizer; the library has no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from pathlib import Path
 from time import localtime, strftime
 from typing import Dict, List, Optional, Tuple
@@ -63,6 +66,30 @@ def masked_huber_loss(output: torch.Tensor, target: torch.Tensor, delta: float, 
     return torch.where(valid, huber, zero).sum() / valid.sum().clamp(min=1)
 
 
+def gauss_entry(err: torch.Tensor, sigma: float, delta: float) -> torch.Tensor:
+    """The Gauss loss of every entry at the absolute errors `err`: sigma^2 (1 - exp(-err^2 / 2 sigma^2)) + delta err,
+    written as the reference writes it (loss.py:94-95).  In fp32 the VALUE carries the reference's cancellation for
+    err << sigma (3.5e-3 relative at err = 1e-3 sigma, delta = 0; the library's kernels take -expm1f instead); its
+    gradient err exp(-err^2 / 2 sigma^2) + delta does not, which torch.expm1's backward (out + 1) would lose in the tail."""
+    return sigma ** 2 * (1 - torch.exp(-(err * err) / (2 * sigma ** 2))) + delta * err
+
+
+def gauss_loss(output: torch.Tensor, target: torch.Tensor, sigma: float = 1.0, delta: float = 5e-2) -> torch.Tensor:
+    """Mean Gauss loss (loss.py:94-95): sigma^2 mean(1 - exp(-e^2 / 2 sigma^2)) + delta mean |e|, a robust loss whose
+    weight on an entry saturates where Huber's grows without bound."""
+    return gauss_entry((output - target).abs(), sigma, delta).mean()
+
+
+def masked_gauss_loss(output: torch.Tensor, target: torch.Tensor, sigma: float, delta: float,
+                      null_value: float) -> torch.Tensor:
+    """Gauss loss summed over the valid entries of `target` and divided by max(valid count, 1).  The torch restatement
+    of `ops.masked_gauss_metrics` (what CPU tensors run)."""
+    valid = valid_entries(target, null_value)
+    zero = torch.zeros((), dtype=output.dtype, device=output.device)
+    err = torch.where(valid, output - target, zero).abs()
+    return torch.where(valid, gauss_entry(err, sigma, delta), zero).sum() / valid.sum().clamp(min=1)
+
+
 class HuberLoss(nn.Module):
     """Mean Huber loss.  `null_value` (default None: every entry counts, the reference's loss) drops the entries of the
     target that are NaN or equal to it from the sum AND from the divisor."""
@@ -73,15 +100,53 @@ class HuberLoss(nn.Module):
         self.null_value = null_value
 
     def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        if self.null_value is not None:
-            if output.is_cuda:
-                from . import ops
-                return ops.masked_huber_metrics(output, target, self.delta, self.null_value)
-            return masked_huber_loss(output, target, self.delta, self.null_value)
         if output.is_cuda:
-            from . import ops
-            return ops.huber_metrics(output, target, self.delta)
+            return self.fused(output, target, 0.0, None)
+        if self.null_value is not None:
+            return masked_huber_loss(output, target, self.delta, self.null_value)
         return huber_loss(output, target, self.delta)
+
+    def entry(self, err: torch.Tensor) -> torch.Tensor:
+        """The loss of every entry at the absolute errors `err` (what `Metrics` sums on CPU tensors)."""
+        return torch.where(err <= self.delta, 0.5 * err * err, self.delta * err - 0.5 * self.delta * self.delta)
+
+    def fused(self, pred, truth, mask_value, sums, loss_weight=1.0, valid=None) -> torch.Tensor:
+        """The library's one pass over device tensors: the loss, and `sums` fed (`valid`: the masked form's count)."""
+        from . import ops
+        if self.null_value is not None:
+            return ops.masked_huber_metrics(pred, truth, self.delta, self.null_value, mask_value, sums, valid)
+        return ops.huber_metrics(pred, truth, self.delta, mask_value, sums, loss_weight)
+
+
+class GaussLoss(nn.Module):
+    """Mean Gauss loss (loss.py:55-95), sigma^2 (1 - exp(-e^2 / 2 sigma^2)) + delta |e| per entry.  `null_value` as in
+    `HuberLoss`.  On device tensors it is `ops.gauss_metrics` / `ops.masked_gauss_metrics`."""
+
+    def __init__(self, sigma: float = 1.0, delta: float = 5e-2, null_value: Optional[float] = None):
+        super().__init__()
+        from . import ops
+        ops.gauss_params(sigma, delta)      # ValueError for what the kernels refuse
+        self.sigma, self.delta = sigma, delta
+        self.null_value = null_value
+
+    def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if output.is_cuda:
+            return self.fused(output, target, 0.0, None)
+        if self.null_value is not None:
+            return masked_gauss_loss(output, target, self.sigma, self.delta, self.null_value)
+        return gauss_loss(output, target, self.sigma, self.delta)
+
+    def extra_repr(self) -> str:
+        return f"sigma={self.sigma}, delta={self.delta}"
+
+    def entry(self, err: torch.Tensor) -> torch.Tensor:
+        return gauss_entry(err, self.sigma, self.delta)
+
+    def fused(self, pred, truth, mask_value, sums, loss_weight=1.0, valid=None) -> torch.Tensor:
+        from . import ops
+        if self.null_value is not None:
+            return ops.masked_gauss_metrics(pred, truth, self.sigma, self.delta, self.null_value, mask_value, sums, valid)
+        return ops.gauss_metrics(pred, truth, self.sigma, self.delta, mask_value, sums, loss_weight)
 
 
 class Metrics:
@@ -94,16 +159,18 @@ class Metrics:
 
     With `null_value` set, only the VALID entries of the truth count (not NaN, != null_value) and the totals are kept per
     forecast horizon: a float64 [T_out + 1, 5] buffer whose row t < T_out holds, for horizon step t + 1,
-    {valid count, sum |e|, 100 sum_{y > mask_value} |e / y|, sum e^2, sum huber(e)} and whose last row holds the same
-    over all horizons (the layout `ops.masked_huber_metrics` adds to).  It is allocated on first use, zeroed by
-    `reset()` and reduced in place by `all_reduce()`.  MAE / MAPE / RMSE divide by the valid count read from the
-    buffer, and `loss` is the epoch's total Huber sum over its total valid count -- a ratio of totals, the same number
+    {valid count, sum |e|, 100 sum_{y > mask_value} |e / y|, sum e^2, sum loss(e)} and whose last row holds the same
+    over all horizons (the layout `ops.masked_huber_metrics` / `ops.masked_gauss_metrics` add to; `loss` is whichever
+    loss ran).  It is allocated on first use, zeroed by `reset()` and reduced in place by `all_reduce()`.  MAE / MAPE / RMSE divide by the valid count read from the
+    buffer, and `loss` is the epoch's total loss sum over its total valid count -- a ratio of totals, the same number
     for any number of ranks and any sharding of the batches, which a mean of per-batch means is not once the batches'
-    valid counts differ.  `per_horizon()` / `at(steps)` give the metrics per horizon."""
+    valid counts differ.  `per_horizon()` / `at(steps)` give the metrics per horizon; a Metrics that was told its loss
+    (`loss_fn`, here or in `update`) also gives a "loss" list there, column 4 over the valid count."""
 
-    def __init__(self, mask_value: float = 0.0, null_value: Optional[float] = None):
+    def __init__(self, mask_value: float = 0.0, null_value: Optional[float] = None, loss_fn: Optional[nn.Module] = None):
         self.mask_value = mask_value
         self.null_value = null_value
+        self.loss_fn = loss_fn
         self.n = 0
         self.batches = 0
         self._sums: Optional[torch.Tensor] = None
@@ -134,12 +201,16 @@ class Metrics:
         self.batches += 1
 
     def update(self, y_pred: torch.Tensor, y_true: torch.Tensor, loss: Optional[torch.Tensor] = None,
-               count: bool = True, loss_weight: float = 1.0, delta: Optional[float] = None) -> None:
+               count: bool = True, loss_weight: float = 1.0, delta: Optional[float] = None,
+               loss_fn: Optional[nn.Module] = None) -> None:
         """Add a batch with torch ops (CPU tensors; the GPU path adds inside the fused loss kernel).  With `null_value`
-        set the Huber column is computed here from `delta` (`loss` and `loss_weight` are not used; without `delta` the
-        column, and with it `loss`, stays 0)."""
+        set the loss column is computed here: with `loss_fn` (a `HuberLoss` or `GaussLoss`; it is kept) or this Metrics'
+        own from that loss, otherwise as the Huber loss of `delta` (`loss` and `loss_weight` are not used; without any of
+        them the column, and with it `loss`, stays 0)."""
+        if loss_fn is not None:
+            self.loss_fn = loss_fn
         if self.null_value is not None:
-            self._update_masked(y_pred, y_true, delta)
+            self._update_masked(y_pred, y_true, delta, self.loss_fn)
             if count:
                 self.count(y_true)
             return
@@ -154,8 +225,9 @@ class Metrics:
         if count:
             self.count(y_true)
 
-    def _update_masked(self, y_pred: torch.Tensor, y_true: torch.Tensor, delta: Optional[float]) -> None:
-        """What `ops.masked_huber_metrics` adds to the buffer, in float64 torch ops."""
+    def _update_masked(self, y_pred: torch.Tensor, y_true: torch.Tensor, delta: Optional[float],
+                       loss_fn: Optional[nn.Module] = None) -> None:
+        """What `ops.masked_huber_metrics` / `ops.masked_gauss_metrics` add to the buffer, in float64 torch ops."""
         t_out = y_true.shape[-1]
         truth = y_true.double().reshape(-1, t_out)
         valid = valid_entries(truth, self.null_value)
@@ -164,8 +236,11 @@ class Metrics:
         mask = valid & (truth > self.mask_value)
         ape = torch.where(mask, (err / torch.where(mask, truth, torch.ones_like(truth))).abs(), zero)
         a = err.abs()
-        huber = zero if delta is None else torch.where(a <= delta, 0.5 * a * a, delta * a - 0.5 * delta * delta)
-        rows = torch.stack([valid.double().sum(0), a.sum(0), 100.0 * ape.sum(0), (err * err).sum(0), huber.sum(0)], dim=1)
+        if loss_fn is not None:
+            entry = loss_fn.entry(a)          # 0 at a = 0, where the entries that are not valid sit
+        else:
+            entry = zero if delta is None else torch.where(a <= delta, 0.5 * a * a, delta * a - 0.5 * delta * delta)
+        rows = torch.stack([valid.double().sum(0), a.sum(0), 100.0 * ape.sum(0), (err * err).sum(0), entry.sum(0)], dim=1)
         sums = self.totals(y_pred.device, t_out)
         sums[:t_out].add_(rows)
         sums[t_out].add_(rows.sum(0))
@@ -181,15 +256,19 @@ class Metrics:
         return last[column] / max(last[0], 1.0)
 
     def per_horizon(self) -> Dict[str, List[float]]:
-        """MAE / MAPE / RMSE and the valid count of every forecast horizon: lists of length T_out (needs `null_value`)."""
+        """MAE / MAPE / RMSE and the valid count of every forecast horizon: lists of length T_out (needs `null_value`).
+        With `loss_fn` known also "loss": the horizon's loss sum over its valid count, for whichever loss ran."""
         if self.null_value is None:
             raise ValueError("per-horizon metrics need Metrics(null_value=...): the unmasked totals are kept over all horizons")
+        named = {} if self.loss_fn is None else {"loss": []}
         if self._sums is None:
-            return {"MAE": [], "MAPE": [], "RMSE": [], "valid": []}
+            return {"MAE": [], "MAPE": [], "RMSE": [], "valid": [], **named}
         rows = self._sums[:-1].cpu()
         n = rows[:, 0].clamp(min=1.0)
+        if named:
+            named["loss"] = (rows[:, 4] / n).tolist()
         return {"MAE": (rows[:, 1] / n).tolist(), "MAPE": (rows[:, 2] / n).tolist(),
-                "RMSE": (rows[:, 3] / n).sqrt().tolist(), "valid": rows[:, 0].tolist()}
+                "RMSE": (rows[:, 3] / n).sqrt().tolist(), "valid": rows[:, 0].tolist(), **named}
 
     def at(self, steps) -> Dict[str, List[float]]:
         """`per_horizon()` at the 1-based horizon steps `steps`, e.g. `at([3, 6, 12])`."""
@@ -232,7 +311,7 @@ class Metrics:
     @property
     def loss(self) -> float:
         """Mean over the (global) batches of the batch-mean loss, the reference's `loss_ave` (engine.py:66-67).
-        With `null_value` set: the epoch's total Huber sum divided by its total valid count (a ratio of totals, see
+        With `null_value` set: the epoch's total loss sum divided by its total valid count (a ratio of totals, see
         the class docstring)."""
         if self.null_value is not None:
             return self._masked_total(4)
@@ -614,11 +693,25 @@ class _GraphedStep:
 class Engine:
     __labels__ = {"train": "[Train   ]", "validate": "[Validate]", "evaluate": "[Evaluate]"}
 
-    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, null_value: Optional[float] = None):
+    def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, null_value: Optional[float] = None,
+                 loss: Optional[nn.Module] = None):
         self.model = model
+        self._loss_given = loss is not None     # then the per-horizon statistics carry the loss too
+        if loss is None:
+            loss = HuberLoss(loss_delta, null_value)
+        elif not isinstance(loss, (HuberLoss, GaussLoss)):
+            raise TypeError(f"loss must be a HuberLoss or a GaussLoss (the fused step tail runs the losses it knows), "
+                            f"not {type(loss).__name__}")
+        else:
+            theirs = loss.null_value
+            if null_value is not None and theirs is not None and not (
+                    float(theirs) == float(null_value) or (math.isnan(theirs) and math.isnan(null_value))):
+                raise ValueError(f"null_value = {null_value!r} but the loss was built with null_value = {theirs!r}")
+            null_value = theirs if null_value is None else null_value
+            loss.null_value = null_value         # one switch: the engine's, or the loss's own where the engine got none
         self.null_value = null_value     # None: every entry of the truth counts (the reference's loss and metrics)
         self._valid_count = None         # [1] fp32: the valid count of the last batch (device memory on the GPU)
-        self.loss_fn, self.out_dir = HuberLoss(loss_delta, null_value), Path(out_dir)
+        self.loss_fn, self.out_dir = loss, Path(out_dir)
         self.out_dir.mkdir(parents=True, exist_ok=True)
         self.log_file = self.out_dir / "run.log"
         self.optimizer = None
@@ -647,30 +740,38 @@ class Engine:
 
     def _loss(self, pred: torch.Tensor, truth: torch.Tensor, metrics: Optional[Metrics],
               loss_weight: float = 1.0) -> torch.Tensor:
-        """Huber loss of a batch; feeds `metrics` (engine.py:56,66-70).  On the GPU one library pass does both.
+        """The loss of a batch (`loss_fn`: Huber or Gauss); feeds `metrics` (engine.py:56,66-70).  On the GPU one library
+        pass does both.
         `loss_weight` = this rank's share of the global batch (1 without a process group).
         With `null_value` set: the masked loss and the per-horizon totals; the batch's valid count stays in
         `_valid_count` (one buffer for every step, so captured kernels and the rank weight of a replay find it)."""
+        mask_value = 0.0 if metrics is None else metrics.mask_value
         if self.null_value is not None:
-            mask_value = 0.0 if metrics is None else metrics.mask_value
             if pred.is_cuda:
-                from . import ops
                 sums = None if metrics is None else metrics.totals(pred.device, pred.shape[-1])
-                return ops.masked_huber_metrics(pred, truth, self.loss_fn.delta, self.null_value, mask_value, sums,
-                                                self._valid_buffer(pred.device))
+                return self.loss_fn.fused(pred, truth, mask_value, sums, valid=self._valid_buffer(pred.device))
             self._valid_count = valid_entries(truth, self.null_value).sum().to(torch.float32).reshape(1)
             if metrics is not None:
-                metrics.update(pred, truth, count=False, delta=self.loss_fn.delta)   # counted by the caller
-            return masked_huber_loss(pred, truth, self.loss_fn.delta, self.null_value)
+                self._update_masked_on_cpu(metrics, pred, truth)
+            return self.loss_fn(pred, truth)
         if pred.is_cuda:
-            from . import ops
             sums = None if metrics is None else metrics.totals(pred.device)
-            return ops.huber_metrics(pred, truth, self.loss_fn.delta, 0.0 if metrics is None else metrics.mask_value, sums,
-                                     loss_weight)
-        loss = huber_loss(pred, truth, self.loss_fn.delta)
+            return self.loss_fn.fused(pred, truth, mask_value, sums, loss_weight)
+        loss = self.loss_fn(pred, truth)
         if metrics is not None:
             metrics.update(pred, truth, loss, count=False, loss_weight=loss_weight)   # counted by the caller
         return loss
+
+    def _update_masked_on_cpu(self, metrics: Metrics, pred: torch.Tensor, truth: torch.Tensor) -> None:
+        """The masked totals of a CPU batch (counted by the caller): the loss column from the loss itself; for the default
+        loss through `delta=`, as before there was a choice."""
+        if self._loss_given:
+            metrics.update(pred, truth, count=False, loss_fn=self.loss_fn)
+        else:
+            metrics.update(pred, truth, count=False, delta=self.loss_fn.delta)
+
+    def _new_metrics(self) -> Metrics:
+        return Metrics(null_value=self.null_value, loss_fn=self.loss_fn if self._loss_given else None)
 
     def _valid_buffer(self, device) -> torch.Tensor:
         if self._valid_count is None or self._valid_count.device != device:
@@ -745,7 +846,7 @@ class Engine:
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(0 if epoch is None else int(epoch))
         if self._graph_metrics is None or not self.hip_graph or device.type != "cuda":
-            metrics = Metrics(null_value=self.null_value)
+            metrics = self._new_metrics()
         else:
             metrics = self._graph_metrics       # captured kernels hold its totals buffer: re-use it, zeroed
             metrics.reset()
@@ -858,8 +959,13 @@ class Trainer(Engine):
 
     def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto",
                  null_value: Optional[float] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
-        """`max_grad_norm`, `skip_nonfinite` (default None / False: the step as the reference's optimizer takes it): a guard on
+                 skip_nonfinite: bool = False, loss: Optional[nn.Module] = None):
+        """`loss` (default None: `HuberLoss(loss_delta, null_value)`, the reference's training loss): a `HuberLoss` or a
+        `GaussLoss` instance to train with instead; `loss_delta` is then not read.  It runs in the same step tail -- one
+        library pass with the metrics, masked or not, captured or not -- and takes the engine's `null_value` (or gives the
+        engine its own where the engine got none; two different ones: ValueError).  `last_stats["horizons"]` then also has
+        a "loss" list.  Anything else is a TypeError: the fused tail runs the losses it knows.
+        `max_grad_norm`, `skip_nonfinite` (default None / False: the step as the reference's optimizer takes it): a guard on
         the optimizer step, active when either is set.  The global L2 norm of the gradient -- of the global batch's mean
         gradient under a process group -- is taken before the update; the gradient is scaled by
         `min(1, max_grad_norm / (norm + 1e-6))` like `torch.nn.utils.clip_grad_norm_` (`skip_nonfinite` alone: never
@@ -877,7 +983,7 @@ class Trainer(Engine):
         ~120 launches is host-bound wherever it is under ~3 ms of GPU work: msgat48 3.3 -> 2.8 ms, PEMSD4 2.7 -> 1.5 ms);
         True -- capture every shape at first sight; False -- eager launches only.  Graphs are keyed by (grad mode, batch
         shape, global batch size) and dropped when `load()` moves the optimizer's buffers."""
-        super().__init__(model, loss_delta=loss_delta, out_dir=out_dir, null_value=null_value)
+        super().__init__(model, loss_delta=loss_delta, out_dir=out_dir, null_value=null_value, loss=loss)
         on_gpu = next(model.parameters()).is_cuda
         if hip_graph is True and not on_gpu:
             raise ValueError("hip_graph=True needs the model on the GPU")
@@ -948,8 +1054,9 @@ def default_grad_scaler_state() -> dict:
 
 class Evaluator(Engine):
     def __init__(self, model: nn.Module, delta: float, out_dir: str, ckpt, hip_graph="auto",
-                 null_value: Optional[float] = None):
-        super().__init__(model, loss_delta=delta, out_dir=out_dir, null_value=null_value)     # null_value: see Trainer
+                 null_value: Optional[float] = None, loss: Optional[nn.Module] = None):
+        # null_value, loss: see Trainer (with `loss` given, `delta` is not read)
+        super().__init__(model, loss_delta=delta, out_dir=out_dir, null_value=null_value, loss=loss)
         states = torch.load(ckpt, map_location=next(model.parameters()).device, weights_only=False)
         model.load_state_dict(strip_data_parallel_prefix(states["model"]))
         self.hip_graph = hip_graph if next(model.parameters()).is_cuda else False   # see Trainer

@@ -9,6 +9,7 @@ arithmetic step runs in libmsgat_hip.so through the C ABI of include/msgat_hip.h
 from __future__ import annotations
 
 import ctypes as C
+import math
 import threading
 from typing import Optional
 
@@ -1693,23 +1694,37 @@ def relayout(t: torch.Tensor, perm) -> torch.Tensor:
     return _Relayout.apply(t, tuple(perm))
 
 
-# ---- step tail: fused Huber loss + metric sums ---------------------------------------
+# ---- step tail: fused loss + metric sums ----------------------------------------------
+# The tail runs one of two losses (csrc/tail.hip: a policy of the same kernels), named here by the prefix of its entry
+# points and the parameters in front of which they are called: ("huber", (delta,)) or ("gauss", (sigma, delta)).
 
-class _HuberMetricsFunction(torch.autograd.Function):
-    """pred, truth (same shape) -> mean Huber loss (0-dim); adds |e|, 100|e/y| (y > mask) and e^2 sums plus the loss
-    itself to the running fp64 totals `sums` [4] on the device (engine.py:56,66-70; loss.py:51-52; metrics.py:20-35)."""
+def gauss_params(sigma, delta) -> tuple:
+    """(sigma, delta) as floats, or ValueError: sigma finite and > 0, delta finite and >= 0 (0: no linear term)."""
+    sigma, delta = float(sigma), float(delta)
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"sigma must be a finite number > 0, not {sigma!r}")
+    if not (math.isfinite(delta) and delta >= 0.0):
+        raise ValueError(f"delta must be a finite number >= 0, not {delta!r}")
+    return sigma, delta
+
+
+class _LossMetricsFunction(torch.autograd.Function):
+    """pred, truth (same shape) -> mean loss (0-dim); adds |e|, 100|e/y| (y > mask) and e^2 sums plus the loss
+    itself to the running fp64 totals `sums` [4] on the device (engine.py:56,66-70; loss.py:51-52 or :94-95;
+    metrics.py:20-35)."""
 
     @staticmethod
-    def forward(ctx, pred, truth, delta: float, mask_value: float, sums, loss_weight: float = 1.0):
+    def forward(ctx, pred, truth, kind: str, params: tuple, mask_value: float, sums, loss_weight: float = 1.0):
         L = _lib.lib()
         pred_c, truth_c = pred.contiguous(), truth.contiguous()
         n = pred_c.numel()
         part = torch.empty(max(int(L.msgat_huber_partial_doubles(n)), 1), device=pred.device, dtype=torch.float64)
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        st = L.msgat_huber_metrics(_ptr(pred_c), _ptr(truth_c), n, float(delta), float(mask_value), _ptr(part), _ptr(loss),
-                                   _ptr(sums), float(loss_weight), _stream_handle(pred.device))
-        _lib.check(st, "msgat_huber_metrics")
-        ctx.delta = float(delta)
+        name = f"msgat_{kind}_metrics"
+        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), n, *params, float(mask_value), _ptr(part), _ptr(loss),
+                              _ptr(sums), float(loss_weight), _stream_handle(pred.device))
+        _lib.check(st, name)
+        ctx.kind, ctx.params = kind, params
         ctx.save_for_backward(pred_c, truth_c)
         return loss
 
@@ -1717,32 +1732,44 @@ class _HuberMetricsFunction(torch.autograd.Function):
     def backward(ctx, dloss):
         pred, truth = ctx.saved_tensors
         dpred = torch.empty_like(pred)
-        st = _lib.lib().msgat_huber_grad(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), pred.numel(), ctx.delta,
-                                         _ptr(dpred), _stream_handle(pred.device))
-        _lib.check(st, "msgat_huber_grad")
-        return dpred, None, None, None, None, None
+        name = f"msgat_{ctx.kind}_grad"
+        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), pred.numel(), *ctx.params,
+                                       _ptr(dpred), _stream_handle(pred.device))
+        _lib.check(st, name)
+        return dpred, None, None, None, None, None, None
 
 
-def huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, mask_value: float = 0.0,
-                  sums: Optional[torch.Tensor] = None, loss_weight: float = 1.0) -> torch.Tensor:
-    """Mean Huber loss of `pred` against `truth` in one pass that also feeds the epoch's metric totals.
-    `loss_weight` scales what is added to the running loss total (a rank's share n_r / n_b of a global batch)."""
+def _loss_metrics(kind: str, params: tuple, pred, truth, mask_value, sums, loss_weight) -> torch.Tensor:
     _require_device_tensor("prediction", pred)
     _require_device_tensor("target", truth, pred.device)
     if pred.shape != truth.shape or pred.numel() == 0:
         raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(truth.shape)} must match and be non-empty")
     if sums is not None and (sums.dtype != torch.float64 or sums.numel() != 4 or sums.device != pred.device):
         raise ValueError("sums must be a float64 [4] tensor on the prediction's device")
-    return _HuberMetricsFunction.apply(pred, truth, delta, mask_value, sums, float(loss_weight))
+    return _LossMetricsFunction.apply(pred, truth, kind, params, mask_value, sums, float(loss_weight))
 
 
-class _MaskedHuberMetricsFunction(torch.autograd.Function):
-    """pred, truth [..., T_out] -> Huber loss averaged over the VALID entries of truth (not NaN, != null_value); adds
-    the per-horizon and all-horizon {count, |e|, 100|e/y| (y > mask), e^2, huber} sums to the running fp64 totals
+def huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, mask_value: float = 0.0,
+                  sums: Optional[torch.Tensor] = None, loss_weight: float = 1.0) -> torch.Tensor:
+    """Mean Huber loss of `pred` against `truth` in one pass that also feeds the epoch's metric totals.
+    `loss_weight` scales what is added to the running loss total (a rank's share n_r / n_b of a global batch)."""
+    return _loss_metrics("huber", (float(delta),), pred, truth, mask_value, sums, loss_weight)
+
+
+def gauss_metrics(pred: torch.Tensor, truth: torch.Tensor, sigma: float, delta: float, mask_value: float = 0.0,
+                  sums: Optional[torch.Tensor] = None, loss_weight: float = 1.0) -> torch.Tensor:
+    """`huber_metrics` with the Gauss loss (loss.py:94-95): the mean of sigma^2 (1 - exp(-e^2 / 2 sigma^2)) + delta |e|.
+    `sigma` finite and > 0, `delta` finite and >= 0 (ValueError otherwise)."""
+    return _loss_metrics("gauss", gauss_params(sigma, delta), pred, truth, mask_value, sums, loss_weight)
+
+
+class _MaskedLossMetricsFunction(torch.autograd.Function):
+    """pred, truth [..., T_out] -> the loss averaged over the VALID entries of truth (not NaN, != null_value); adds
+    the per-horizon and all-horizon {count, |e|, 100|e/y| (y > mask), e^2, loss} sums to the running fp64 totals
     `sums` [T_out + 1, 5] and leaves the batch's valid count in `valid` [1], both on the device."""
 
     @staticmethod
-    def forward(ctx, pred, truth, delta: float, null_value: float, mask_value: float, sums, valid):
+    def forward(ctx, pred, truth, kind: str, params: tuple, null_value: float, mask_value: float, sums, valid):
         L = _lib.lib()
         pred_c, truth_c = pred.contiguous(), truth.contiguous()
         t_out = pred_c.shape[-1]
@@ -1750,11 +1777,12 @@ class _MaskedHuberMetricsFunction(torch.autograd.Function):
         n_part = int(L.msgat_masked_huber_partial_doubles(rows, t_out))
         part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        st = L.msgat_masked_huber_metrics(_ptr(pred_c), _ptr(truth_c), rows, t_out, float(delta), float(null_value),
-                                          float(mask_value), _ptr(part), _ptr(loss), _ptr(valid), _ptr(sums),
-                                          _stream_handle(pred.device))
-        _lib.check(st, "msgat_masked_huber_metrics")
-        ctx.delta, ctx.null_value = float(delta), float(null_value)
+        name = f"msgat_masked_{kind}_metrics"
+        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), rows, t_out, *params, float(null_value),
+                              float(mask_value), _ptr(part), _ptr(loss), _ptr(valid), _ptr(sums),
+                              _stream_handle(pred.device))
+        _lib.check(st, name)
+        ctx.kind, ctx.params, ctx.null_value = kind, params, float(null_value)
         ctx.save_for_backward(pred_c, truth_c, valid)
         return loss
 
@@ -1763,21 +1791,15 @@ class _MaskedHuberMetricsFunction(torch.autograd.Function):
         pred, truth, valid = ctx.saved_tensors
         dpred = torch.empty_like(pred)
         t_out = pred.shape[-1]
-        st = _lib.lib().msgat_masked_huber_grad(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid),
-                                                pred.numel() // t_out, t_out, ctx.delta, ctx.null_value, _ptr(dpred),
-                                                _stream_handle(pred.device))
-        _lib.check(st, "msgat_masked_huber_grad")
-        return dpred, None, None, None, None, None, None
+        name = f"msgat_masked_{ctx.kind}_grad"
+        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid),
+                                       pred.numel() // t_out, t_out, *ctx.params, ctx.null_value, _ptr(dpred),
+                                       _stream_handle(pred.device))
+        _lib.check(st, name)
+        return dpred, None, None, None, None, None, None, None
 
 
-def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, null_value: float,
-                         mask_value: float = 0.0, sums: Optional[torch.Tensor] = None,
-                         valid: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Huber loss of `pred` against `truth` [..., T_out] (e.g. [B, N, T_out]) averaged over the valid entries -- those
-    whose truth is neither NaN nor `null_value` -- in one pass that also feeds the epoch's per-horizon metric totals
-    `sums` (float64 [T_out + 1, 5], see `engine.Metrics`).  A batch without a valid entry gives 0.
-    `valid` (float32 [1] on the device, optional) receives the batch's valid count; the backward divides by it on the
-    device, so it must keep that value until the backward has run."""
+def _masked_loss_metrics(kind: str, params: tuple, pred, truth, null_value, mask_value, sums, valid) -> torch.Tensor:
     _require_device_tensor("prediction", pred)
     _require_device_tensor("target", truth, pred.device)
     if pred.shape != truth.shape or pred.numel() == 0 or pred.dim() == 0:
@@ -1792,7 +1814,25 @@ def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, 
         valid = torch.empty(1, device=pred.device, dtype=torch.float32)
     elif valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != pred.device:
         raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
-    return _MaskedHuberMetricsFunction.apply(pred, truth, delta, null_value, mask_value, sums, valid)
+    return _MaskedLossMetricsFunction.apply(pred, truth, kind, params, null_value, mask_value, sums, valid)
+
+
+def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, null_value: float,
+                         mask_value: float = 0.0, sums: Optional[torch.Tensor] = None,
+                         valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Huber loss of `pred` against `truth` [..., T_out] (e.g. [B, N, T_out]) averaged over the valid entries -- those
+    whose truth is neither NaN nor `null_value` -- in one pass that also feeds the epoch's per-horizon metric totals
+    `sums` (float64 [T_out + 1, 5], see `engine.Metrics`).  A batch without a valid entry gives 0.
+    `valid` (float32 [1] on the device, optional) receives the batch's valid count; the backward divides by it on the
+    device, so it must keep that value until the backward has run."""
+    return _masked_loss_metrics("huber", (float(delta),), pred, truth, null_value, mask_value, sums, valid)
+
+
+def masked_gauss_metrics(pred: torch.Tensor, truth: torch.Tensor, sigma: float, delta: float, null_value: float,
+                         mask_value: float = 0.0, sums: Optional[torch.Tensor] = None,
+                         valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`masked_huber_metrics` with the Gauss loss (see `gauss_metrics`): column 4 of `sums` receives its sums."""
+    return _masked_loss_metrics("gauss", gauss_params(sigma, delta), pred, truth, null_value, mask_value, sums, valid)
 
 
 # ---- input windows of a batch from a series resident in device memory ---------------------------------------------
