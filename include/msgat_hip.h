@@ -57,7 +57,8 @@ extern "C" {
  *     + msgat_masked_huber_{partial_doubles,metrics,grad} and msgat_gather_scaled_dev (the step tail with missing readings);
  *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out);
  *     + msgat_window_gather (a step's input windows from a series resident in device memory);
- *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail).
+ *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail);
+ *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -719,6 +720,25 @@ int msgat_gate_sum(const float* pred, const int64_t* H, const int64_t* D, const 
 int msgat_gate_sum_backward(const float* dout, const float* pred, const int64_t* H, const int64_t* D, const float* h_w,
                             const float* d_w, float* dpred, float* dh_w, float* dd_w, int32_t R, int32_t B, int64_t E,
                             int32_t nh, int32_t nd, void* stream);
+/* msgat_edge_time_weights: one weight per stored edge AND per sample from the sample's hour of day and day of week, the
+ *     idiom of the time embedding (embeddings.py:30-36: h_ebd(H) + d_ebd(D)) applied to the edges of one sparse pattern:
+ *       out[b,e] = (base[e] + h_w[H[b]][e]) + d_w[D[b]][e],   e < nnz -- plain fp32 adds in that order, no contraction: the
+ *     bits of the torch expression (base + h_w[H]) + d_w[D].  base [nnz]; h_w [nh,nnz], d_w [nd,nnz] row-major as
+ *     nn.Embedding keeps them; H, D [B] int64, clamped into [0, nh) / [0, nd) as msgat_gate_sum clamps them; out [B,nnz]
+ *     contiguous in the order of (crow, col), which msgat_graph_t.val with val_sets = B reads where it is.
+ *     d_w = D = NULL: the hour table only.  B = 0 or nnz = 0: nothing is launched, MSGAT_OK; a negative size is
+ *     MSGAT_ERR_SHAPE.
+ * msgat_edge_time_weights_backward: dbase[e] = sum_b dout[b,e] and the DENSE table gradients dh_w [nh,nnz], dd_w [nd,nnz]:
+ *     dh_w[r][e] = sum over the samples with H[b] = r of dout[b,e], likewise dd_w.  Every sum starts at +0 and adds in
+ *     ascending b (no atomics: the bits are a function of the inputs), every row of both tables is written -- a row no
+ *     sample selected is zero -- so the caller zeroes nothing, and nothing is read back (capturable).  Any output may be
+ *     NULL.  nnz = 0 launches nothing; B = 0 with nnz > 0 writes the zeros.
+ *     The torch ops this replaces: 2 gathers + 2 adds forward; a batch sum, 2 zero fills and 2 embedding scatters
+ *     (atomic, in no promised order) backward; one launch each here. */
+int msgat_edge_time_weights(const float* base, const float* h_w, const float* d_w, const int64_t* H, const int64_t* D,
+                            float* out, int32_t B, int64_t nnz, int32_t nh, int32_t nd, void* stream);
+int msgat_edge_time_weights_backward(const float* dout, const int64_t* H, const int64_t* D, float* dbase, float* dh_w,
+                                     float* dd_w, int32_t B, int64_t nnz, int32_t nh, int32_t nd, void* stream);
 size_t msgat_huber_partial_doubles(int64_t n);
 int msgat_huber_metrics(const float* pred, const float* truth, int64_t n, float delta, float mask_value,
                         double* partials, float* loss, double* sums, float loss_weight, void* stream);

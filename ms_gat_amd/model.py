@@ -14,7 +14,7 @@ Parameter names and shapes are the reference's (`tpcs.{r}.tgacns.{l}.gacn.gatt.W
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+from typing import Dict, List, Sequence, Union
 
 import torch
 from torch import nn
@@ -303,6 +303,37 @@ class TimeEmbedding(nn.Module):
         return gate.view(-1, self.n_components, self.n_nodes, self.n_timesteps)
 
 
+class EdgeTimeEmbedding(nn.Module):
+    """Hour-of-day + day-of-week weights on the stored edges of one sparse pattern: the idiom of `TimeEmbedding`
+    (embeddings.py:30-36) applied to the graph, `w[b,e] = weight[e] + h_ebd(H[b])[e] + d_ebd(D[b])[e]`.
+
+    `crow` [N+1], `col` [nnz]: the CSR pattern (buffers); `init` [nnz]: the static weights the parameter `weight` starts
+    from.  Both tables start at zero, so a fresh module is the static graph.  `forward(H, D)` is the batched CSR adjacency
+    [B,N,N] that every op and module accepts (`ops.edge_adjacency` on `weights(H, D)`); the three parameters get dense
+    gradients from one launch (`ops.edge_time_weights`)."""
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, init: torch.Tensor, n_hours: int = 24, n_days: int = 7):
+        super().__init__()
+        if init.dim() != 1 or col.shape != init.shape or crow.dim() != 1:
+            raise ValueError(f"EdgeTimeEmbedding: crow {tuple(crow.shape)}, col {tuple(col.shape)} and init {tuple(init.shape)} "
+                             "must be [N+1], [nnz] and [nnz]")
+        self.register_buffer("crow", crow.detach().clone())
+        self.register_buffer("col", col.detach().clone())
+        self.weight = nn.Parameter(init.detach().clone().float())
+        self.h_ebd = nn.Embedding(n_hours, init.numel())
+        self.d_ebd = nn.Embedding(n_days, init.numel())
+        with torch.no_grad():
+            self.h_ebd.weight.zero_()
+            self.d_ebd.weight.zero_()
+
+    def weights(self, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
+        """[B,nnz] in the order of (crow, col)."""
+        return ops.edge_time_weights(self.weight, self.h_ebd.weight, self.d_ebd.weight, H, D)
+
+    def forward(self, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
+        return ops.edge_adjacency(self.crow, self.col, self.weights(H, D))
+
+
 class MSGAT(nn.Module):
     """X [B,R,C,N,T], H [B], D [B] -> [B,N,T_out]  (msgat.py:166-217).
 
@@ -313,10 +344,18 @@ class MSGAT(nn.Module):
     the index buffers `edge_crow` / `edge_col` and the weights, initialised from `adj`, as the parameter `edge_weight`
     [nnz].  The forward hands every block the sparse CSR adjacency built from them, whose gradient is computed at the
     edges only (msgat_edge_weight_grad).  `adj` stays as the frozen dense parameter of the reference's layout.
+
+    `learn_edge_weights="time"` lets those weights depend on the sample's hour of day and day of week (`EdgeTimeEmbedding`'s
+    arithmetic): `edge_crow`, `edge_col` and `edge_weight` as above -- `edge_weight` is the base -- plus the tables
+    `edge_h_ebd.weight` [24,nnz] and `edge_d_ebd.weight` [7,nnz], zero at the start, so a fresh model computes what a `True`
+    model computes and a `True` model's checkpoint loads with `strict=False`.  The [B,nnz] weights of a batch are built once
+    per forward (`ops.edge_time_weights`) and shared by the R components and by every block.
     """
 
     def __init__(self, components: Sequence[Dict], in_timesteps: int, out_timesteps: int, use_te: bool,
-                 adj: torch.Tensor, learn_edge_weights: bool = False):
+                 adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False):
+        if not (isinstance(learn_edge_weights, bool) or learn_edge_weights == "time"):
+            raise ValueError(f'learn_edge_weights must be False, True or "time", got {learn_edge_weights!r}')
         super().__init__()
         n_nodes = len(adj)
         if use_te:
@@ -329,22 +368,34 @@ class MSGAT(nn.Module):
             TPC(channels=c["channels"], n_nodes=n_nodes, in_timesteps=in_timesteps, out_timesteps=out_timesteps,
                 dilations=c["dilations"]) for c in components)
         self.stack_components = True   # False: evaluate the components one by one, as the reference does
-        self.learn_edge_weights = bool(learn_edge_weights)
+        self.learn_edge_weights = learn_edge_weights
         if self.learn_edge_weights:
             pattern = self.adj.detach().cpu().to_sparse_csr()
             self.register_buffer("edge_crow", pattern.crow_indices().clone())
             self.register_buffer("edge_col", pattern.col_indices().clone())
             self.edge_weight = nn.Parameter(pattern.values().clone())
+        if self.learn_edge_weights == "time":
+            self.edge_h_ebd = nn.Embedding(24, self.edge_weight.numel())
+            self.edge_d_ebd = nn.Embedding(7, self.edge_weight.numel())
         self.reset_parameters()
         if self.learn_edge_weights:
-            # after reset_parameters, which re-initialises every 1-D trainable tensor
+            # after reset_parameters, which re-initialises every 1-D trainable tensor (and every table)
             with torch.no_grad():
                 self.edge_weight.copy_(self.adj.detach().cpu().to_sparse_csr().values())
+                if self.learn_edge_weights == "time":
+                    self.edge_h_ebd.weight.zero_()
+                    self.edge_d_ebd.weight.zero_()
 
-    def adjacency(self):
-        """What the blocks get: the frozen dense `adj`, or the sparse CSR adjacency of the learned edge weights."""
+    def adjacency(self, H: torch.Tensor = None, D: torch.Tensor = None):
+        """What the blocks get: the frozen dense `adj`, the sparse CSR adjacency of the learned edge weights, or ("time")
+        the batched CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D`."""
         if not self.learn_edge_weights:
             return self.adj
+        if self.learn_edge_weights == "time":
+            if H is None or D is None:
+                raise ValueError('learn_edge_weights="time": the adjacency depends on the batch, pass its H and D')
+            weights = ops.edge_time_weights(self.edge_weight, self.edge_h_ebd.weight, self.edge_d_ebd.weight, H, D)
+            return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
         return ops.edge_adjacency(self.edge_crow, self.edge_col, self.edge_weight)
 
     def forward(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
@@ -352,7 +403,7 @@ class MSGAT(nn.Module):
             # all components in each kernel launch (stacked.py) instead of the reference's loop (msgat.py:204)
             return stacked.forward(self, X, H, D)
         gates = self.te(H, D).unbind(1) if self.te is not None else self.W.unbind(0)
-        adjacency = self.adjacency()
+        adjacency = self.adjacency(H, D)
         out = None
         for tpc, x, gate in zip(self.tpcs, X.unbind(1), gates):
             term = tpc(x, adjacency) * gate

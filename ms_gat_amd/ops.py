@@ -1251,6 +1251,61 @@ def gate_sum(pred: torch.Tensor, H: Optional[torch.Tensor], D: Optional[torch.Te
     return _GateSumFunction.apply(pred, H, D, h_weight, d_weight)
 
 
+class _EdgeTimeWeightsFunction(torch.autograd.Function):
+    """base [nnz], h_w [nh,nnz], d_w [nd,nnz], H [B], D [B] -> (base + h_w[H]) + d_w[D] [B,nnz], one launch each way."""
+
+    @staticmethod
+    def forward(ctx, base, h_w, d_w, H, D):
+        L = _lib.lib()
+        base, h_w, d_w = base.contiguous(), h_w.contiguous(), d_w.contiguous()
+        B, nnz = H.shape[0], base.shape[0]
+        nh, nd = h_w.shape[0], d_w.shape[0]
+        out = _new(base, B, nnz)
+        st = L.msgat_edge_time_weights(_ptr(base), _ptr(h_w), _ptr(d_w), _ptr(H), _ptr(D), _ptr(out), B, nnz, nh, nd,
+                                       _stream_handle(base.device))
+        _lib.check(st, "msgat_edge_time_weights")
+        ctx.dims = (B, nnz, nh, nd)
+        ctx.save_for_backward(H, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        H, D = ctx.saved_tensors
+        B, nnz, nh, nd = ctx.dims
+        need = ctx.needs_input_grad
+        dout = dout.contiguous()
+        dbase = _new(dout, nnz) if need[0] else None
+        dh = _new(dout, nh, nnz) if need[1] else None
+        dd = _new(dout, nd, nnz) if need[2] else None
+        st = L.msgat_edge_time_weights_backward(_ptr(dout), _ptr(H), _ptr(D), _ptr(dbase), _ptr(dh), _ptr(dd), B, nnz, nh, nd,
+                                                _stream_handle(dout.device))
+        _lib.check(st, "msgat_edge_time_weights_backward")
+        return dbase, dh, dd, None, None
+
+
+def edge_time_weights(base: torch.Tensor, h_weight: torch.Tensor, d_weight: torch.Tensor, H: torch.Tensor,
+                      D: torch.Tensor) -> torch.Tensor:
+    """`(base + h_weight[H]) + d_weight[D]` [B,nnz]: a weight per stored edge and per sample from the sample's hour of day
+    and day of week -- the time embedding's `h_ebd(H) + d_ebd(D)` (embeddings.py:30-36) on the edges of one sparse pattern --
+    as one launch forward (the bits of that torch expression) and one backward: `base` [nnz] gets the batch sum, the tables
+    [24,nnz] / [7,nnz] dense gradients summed in sample order, every row written (msgat_edge_time_weights_backward).  The
+    result is contiguous in the order of (crow, col): `edge_adjacency(crow, col, weights)` reads it where it is.  Indices
+    outside a table are clamped to its ends, as `gate_sum` does."""
+    _require_device_tensor("base", base)
+    _require_device_tensor("h_weight", h_weight, base.device)
+    _require_device_tensor("d_weight", d_weight, base.device)
+    if H.dtype in (torch.int32, torch.int16, torch.uint8) and D.dtype in (torch.int32, torch.int16, torch.uint8):
+        H, D = H.long(), D.long()                          # nn.Embedding takes these too
+    nnz = base.numel()
+    if (base.dim() != 1 or h_weight.dim() != 2 or d_weight.dim() != 2 or h_weight.shape[1] != nnz or d_weight.shape[1] != nnz
+            or h_weight.shape[0] < 1 or d_weight.shape[0] < 1 or H.dim() != 1 or D.shape != H.shape
+            or H.dtype != torch.int64 or D.dtype != torch.int64 or H.device != base.device or D.device != base.device):
+        raise ValueError(f"edge_time_weights: base {tuple(base.shape)}, tables {tuple(h_weight.shape)} / {tuple(d_weight.shape)}, "
+                         f"H {tuple(H.shape)} {H.dtype}, D {tuple(D.shape)} {D.dtype} do not match")
+    return _EdgeTimeWeightsFunction.apply(base, h_weight, d_weight, H.contiguous(), D.contiguous())
+
+
 # ---- channel axes assembled from several tensors: one pass instead of cat / several mixes -------------------
 
 def _sliced_grad(dz: torch.Tensor, accepts):
