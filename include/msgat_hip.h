@@ -58,7 +58,8 @@ extern "C" {
  *     + msgat_grad_guard{,_partial_doubles} and msgat_adam_step_guarded (global-norm clipping, non-finite steps left out);
  *     + msgat_window_gather (a step's input windows from a series resident in device memory);
  *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail);
- *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern).
+ *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern);
+ *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -739,6 +740,29 @@ int msgat_edge_time_weights(const float* base, const float* h_w, const float* d_
                             float* out, int32_t B, int64_t nnz, int32_t nh, int32_t nd, void* stream);
 int msgat_edge_time_weights_backward(const float* dout, const int64_t* H, const int64_t* D, float* dbase, float* dh_w,
                                      float* dd_w, int32_t B, int64_t nnz, int32_t nh, int32_t nd, void* stream);
+/* msgat_edge_signal_weights: one weight per stored edge AND per sample from the sample's own node signals, the edge strength
+ *     of the dynamic-graph models as a rank-d bilinear form on the edges of `graph`'s pattern:
+ *       out[b,e] = base[e] + sum_{k<d} a[b,row(e),k] * b[b,col(e),k],   e < nnz in the graph's CSR edge order,
+ *     with ab [B,N,2d] contiguous, a = ab[..., :d] (the row side) and b = ab[..., d:] (the column side) -- the caller's
+ *     projection f @ P.T of the node features, P [2d,F].  base [nnz]; out [B,nnz], which msgat_graph_t.val with
+ *     val_sets = B reads where it is.  Reads graph->erow and graph->col; graph->val is not read.  One launch.
+ *     Every product is rounded to fp32, the products are added in ascending k and base[e] is added last (no contraction):
+ *     the bits of fp32 torch ops applied in that order.
+ * msgat_edge_signal_weights_backward: from dout [B,nnz]
+ *       dbase[e]   = sum_b dout[b,e]                                      (starts at +0, adds in ascending b: defined bits)
+ *       da[b,i,:]  = sum_{e in row i}    dout[b,e] * b[b,col(e),:]        (ascending CSR edge order: rowptr, col)
+ *       db[b,j,:]  = sum_{e in column j} dout[b,e] * a[b,row(e),:]        (ascending CSC position: colptr, crow, cperm)
+ *     written as dab [B,N,2d] = (da, db) in the layout of ab.  No atomics, nothing zeroed by the caller, nothing read back
+ *     (capturable): every element of dab is written, +0 for a node without a stored edge in its row / column, and dbase
+ *     wholly.  dbase = NULL or dab = NULL skips that output.  One launch.
+ *     d must be a multiple of 4 (rows are read as 16-byte pieces) and at most 32: else MSGAT_ERR_UNSUPPORTED; B < 0 or
+ *     d <= 0: MSGAT_ERR_SHAPE; graph = NULL, or a needed pointer NULL with work to do: MSGAT_ERR_NULL -- all decided on the
+ *     host before any launch.  B = 0: MSGAT_OK, nothing written.  nnz = 0 with B > 0: MSGAT_OK, the forward writes nothing
+ *     and the backward writes dab as zeros. */
+int msgat_edge_signal_weights(const msgat_graph_t* graph, const float* base, const float* ab, int32_t B, int32_t d,
+                              float* out, void* stream);
+int msgat_edge_signal_weights_backward(const msgat_graph_t* graph, const float* dout, const float* ab, int32_t B, int32_t d,
+                                       float* dbase, float* dab, void* stream);
 size_t msgat_huber_partial_doubles(int64_t n);
 int msgat_huber_metrics(const float* pred, const float* truth, int64_t n, float delta, float mask_value,
                         double* partials, float* loss, double* sums, float loss_weight, void* stream);

@@ -683,6 +683,25 @@ def sparse_sets_of(adjacency: torch.Tensor, sell: str = "auto") -> SparseSets:
     return _SPARSE.remember(key, adjacency, (sets, idx))[0]
 
 
+def edge_pattern_of(crow: torch.Tensor, col: torch.Tensor, sell: str = "auto") -> SparsePattern:
+    """Cached `SparsePattern` of the CSR index tensors `crow` [N+1], `col` [nnz] themselves: the pattern -- and through
+    `_pattern` the very structure -- that `sparse_sets_of` gives an `ops.edge_adjacency(crow, col, weights)`, for an op that
+    forms those weights.  Keyed and kept like every entry of `_SPARSE`; the first sight inside a HIP-graph capture raises."""
+    if crow.dim() != 1 or col.dim() != 1 or crow.numel() < 1:
+        raise ValueError(f"crow {tuple(crow.shape)} and col {tuple(col.shape)} must be [N+1] and [nnz]")
+    n = crow.numel() - 1
+    key = ("edge-pattern", n, sell, _tensor_key(crow), _tensor_key(col))
+    hit, _ = _SPARSE.lookup(key, crow)
+    if hit is not None:
+        return hit[0]
+    if _capturing(crow):
+        raise _not_cached("the structure of this edge pattern is not cached yet")
+    host_crow, host_col = (t.detach().to(device="cpu", dtype=torch.int64) for t in (crow, col))
+    if int(host_crow[-1]) != host_col.numel():
+        raise ValueError("malformed sparse adjacency indices")
+    return _SPARSE.remember(key, crow, (_pattern(host_crow, host_col, n, sell), (crow, col)))[0]
+
+
 def _check_sets(adjacency, groups: int, relations: int) -> None:
     V, Bg = int(adjacency.shape[0]), groups // relations
     if V not in (1, Bg, groups):

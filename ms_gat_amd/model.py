@@ -334,6 +334,47 @@ class EdgeTimeEmbedding(nn.Module):
         return ops.edge_adjacency(self.crow, self.col, self.weights(H, D))
 
 
+class EdgeSignalWeights(nn.Module):
+    """Signal-dependent weights on the stored edges of one sparse pattern, the edge strength of the dynamic-graph traffic
+    models as a rank-`rank` bilinear form of the readings at the edge's two ends: with `ab = proj(f)` [B,N,2*rank],
+    `w[b,e] = weight[e] + sum_k ab[b,row(e),k] * ab[b,col(e),rank+k]`.
+
+    `crow` [N+1], `col` [nnz]: the CSR pattern (buffers); `init` [nnz]: the static weights the parameter `weight` starts
+    from; `f` [B,N,in_features]: the node features of each sample.  The rows `rank:` of `proj.weight` (the column side) start
+    at zero, so a fresh module is the static graph; their gradient is not zero, so training moves -- the column side at the
+    first step, the row side from then on.  `forward(f)` is the batched CSR adjacency [B,N,N] that every op and module
+    accepts (`ops.edge_adjacency` on `weights(f)`); the projection is one torch matmul, the edge work one launch each way
+    (`ops.edge_signal_weights`)."""
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, init: torch.Tensor, in_features: int, rank: int = 8):
+        super().__init__()
+        if init.dim() != 1 or col.shape != init.shape or crow.dim() != 1:
+            raise ValueError(f"EdgeSignalWeights: crow {tuple(crow.shape)}, col {tuple(col.shape)} and init {tuple(init.shape)} "
+                             "must be [N+1], [nnz] and [nnz]")
+        _check_edge_rank(rank)
+        self.rank = rank
+        self.register_buffer("crow", crow.detach().clone())
+        self.register_buffer("col", col.detach().clone())
+        self.weight = nn.Parameter(init.detach().clone().float())
+        self.proj = nn.Linear(in_features, 2 * rank, bias=False)
+        with torch.no_grad():
+            self.proj.weight[rank:].zero_()
+
+    def weights(self, f: torch.Tensor) -> torch.Tensor:
+        """[B,nnz] in the order of (crow, col)."""
+        if f.dim() != 3 or f.shape[1] != self.crow.numel() - 1 or f.shape[2] != self.proj.in_features:
+            raise ValueError(f"EdgeSignalWeights: f {tuple(f.shape)} must be [B, {self.crow.numel() - 1}, {self.proj.in_features}]")
+        return ops.edge_signal_weights(self.weight, self.proj(f), self.crow, self.col)
+
+    def forward(self, f: torch.Tensor) -> torch.Tensor:
+        return ops.edge_adjacency(self.crow, self.col, self.weights(f))
+
+
+def _check_edge_rank(rank) -> None:
+    if isinstance(rank, bool) or not isinstance(rank, int) or rank < 4 or rank > 32 or rank % 4:
+        raise ValueError(f"the edge rank must be one of 4, 8, ..., 32 (rows are read as 16-byte pieces), got {rank!r}")
+
+
 class MSGAT(nn.Module):
     """X [B,R,C,N,T], H [B], D [B] -> [B,N,T_out]  (msgat.py:166-217).
 
@@ -350,12 +391,22 @@ class MSGAT(nn.Module):
     `edge_h_ebd.weight` [24,nnz] and `edge_d_ebd.weight` [7,nnz], zero at the start, so a fresh model computes what a `True`
     model computes and a `True` model's checkpoint loads with `strict=False`.  The [B,nnz] weights of a batch are built once
     per forward (`ops.edge_time_weights`) and shared by the R components and by every block.
+
+    `learn_edge_weights="signal"` lets them depend on the traffic itself (`EdgeSignalWeights`' arithmetic): `edge_crow`,
+    `edge_col` and `edge_weight` as above plus `edge_proj.weight` [2*edge_rank, C*T_in], which projects every node's most
+    recent input window (`edge_features`) to a row-side and a column-side vector of `edge_rank` values; the weight of edge
+    i -> j is `edge_weight` plus the dot product of i's row side and j's column side.  The column half of `edge_proj.weight`
+    starts at zero, so a fresh model computes what a `True` model computes and a `True` model's checkpoint loads with
+    `strict=False`.  Built once per forward (`ops.edge_signal_weights`), shared by the R components and by every block.
     """
 
     def __init__(self, components: Sequence[Dict], in_timesteps: int, out_timesteps: int, use_te: bool,
-                 adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False):
-        if not (isinstance(learn_edge_weights, bool) or learn_edge_weights == "time"):
-            raise ValueError(f'learn_edge_weights must be False, True or "time", got {learn_edge_weights!r}')
+                 adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False, edge_rank: int = 8):
+        if not (isinstance(learn_edge_weights, bool)
+                or (isinstance(learn_edge_weights, str) and learn_edge_weights in ("time", "signal"))):
+            raise ValueError(f'learn_edge_weights must be False, True, "time" or "signal", got {learn_edge_weights!r}')
+        if learn_edge_weights == "signal":
+            _check_edge_rank(edge_rank)
         super().__init__()
         n_nodes = len(adj)
         if use_te:
@@ -377,6 +428,9 @@ class MSGAT(nn.Module):
         if self.learn_edge_weights == "time":
             self.edge_h_ebd = nn.Embedding(24, self.edge_weight.numel())
             self.edge_d_ebd = nn.Embedding(7, self.edge_weight.numel())
+        if self.learn_edge_weights == "signal":
+            self.edge_rank = edge_rank
+            self.edge_proj = nn.Linear(components[0]["channels"][0] * in_timesteps, 2 * edge_rank, bias=False)
         self.reset_parameters()
         if self.learn_edge_weights:
             # after reset_parameters, which re-initialises every 1-D trainable tensor (and every table)
@@ -385,12 +439,26 @@ class MSGAT(nn.Module):
                 if self.learn_edge_weights == "time":
                     self.edge_h_ebd.weight.zero_()
                     self.edge_d_ebd.weight.zero_()
+                if self.learn_edge_weights == "signal":      # the row half keeps its Xavier values
+                    self.edge_proj.weight[self.edge_rank:].zero_()
 
-    def adjacency(self, H: torch.Tensor = None, D: torch.Tensor = None):
-        """What the blocks get: the frozen dense `adj`, the sparse CSR adjacency of the learned edge weights, or ("time")
-        the batched CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D`."""
+    @staticmethod
+    def edge_features(X: torch.Tensor) -> torch.Tensor:
+        """X [B,R,C,N,T] -> f [B,N,C*T], f[b,n,c*T+t] = X[b,0,c,n,t]: every node's window of the most recent component."""
+        x = X[:, 0]
+        return x.permute(0, 2, 1, 3).reshape(x.shape[0], x.shape[2], x.shape[1] * x.shape[3])
+
+    def adjacency(self, H: torch.Tensor = None, D: torch.Tensor = None, X: torch.Tensor = None):
+        """What the blocks get: the frozen dense `adj`, the sparse CSR adjacency of the learned edge weights, or the batched
+        CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D` ("time") or of its inputs `X` ("signal")."""
         if not self.learn_edge_weights:
             return self.adj
+        if self.learn_edge_weights == "signal":
+            if X is None:
+                raise ValueError('learn_edge_weights="signal": the adjacency depends on the batch, pass its inputs X')
+            weights = ops.edge_signal_weights(self.edge_weight, self.edge_proj(self.edge_features(X)), self.edge_crow,
+                                              self.edge_col)
+            return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
         if self.learn_edge_weights == "time":
             if H is None or D is None:
                 raise ValueError('learn_edge_weights="time": the adjacency depends on the batch, pass its H and D')
@@ -398,12 +466,16 @@ class MSGAT(nn.Module):
             return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
         return ops.edge_adjacency(self.edge_crow, self.edge_col, self.edge_weight)
 
+    def batch_adjacency(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor):
+        """`adjacency` for one batch of `forward`'s inputs; only "signal" is handed X."""
+        return self.adjacency(H, D, X) if self.learn_edge_weights == "signal" else self.adjacency(H, D)
+
     def forward(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
         if self.stack_components and stacked.can_stack(self):
             # all components in each kernel launch (stacked.py) instead of the reference's loop (msgat.py:204)
             return stacked.forward(self, X, H, D)
         gates = self.te(H, D).unbind(1) if self.te is not None else self.W.unbind(0)
-        adjacency = self.adjacency(H, D)
+        adjacency = self.batch_adjacency(X, H, D)
         out = None
         for tpc, x, gate in zip(self.tpcs, X.unbind(1), gates):
             term = tpc(x, adjacency) * gate

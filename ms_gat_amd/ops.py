@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import stream_handle as _stream_handle
-from .graph import _dense_graph_for, is_sparse_adjacency, sparse_graph_for, sparse_parts
+from .graph import _dense_graph_for, edge_pattern_of, is_sparse_adjacency, sparse_graph_for, sparse_parts
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1304,6 +1304,67 @@ def edge_time_weights(base: torch.Tensor, h_weight: torch.Tensor, d_weight: torc
         raise ValueError(f"edge_time_weights: base {tuple(base.shape)}, tables {tuple(h_weight.shape)} / {tuple(d_weight.shape)}, "
                          f"H {tuple(H.shape)} {H.dtype}, D {tuple(D.shape)} {D.dtype} do not match")
     return _EdgeTimeWeightsFunction.apply(base, h_weight, d_weight, H.contiguous(), D.contiguous())
+
+
+class _EdgeSignalWeightsFunction(torch.autograd.Function):
+    """base [nnz], ab [B,N,2d] -> base[e] + <a[b,row(e)], b[b,col(e)]> [B,nnz] on `pattern`'s structure, one launch each way.
+    Values cross in the caller's order of (crow, col); a pattern whose order inside a row is not the library's is permuted
+    with torch gathers on either side of the launch."""
+
+    @staticmethod
+    def forward(ctx, base, ab, pattern):
+        L = _lib.lib()
+        base, ab = base.contiguous(), ab.contiguous()
+        B, N, d = ab.shape[0], ab.shape[1], ab.shape[2] // 2
+        nnz = pattern.structure.nnz
+        gstruct, keep = pattern.structure.on(ab.device)
+        perm = None if pattern.identity else pattern._perm(ab.device)        # (library edge -> input position, its inverse)
+        if perm is not None:
+            base = base.index_select(0, perm[0])
+        out = _new(ab, B, nnz)
+        st = L.msgat_edge_signal_weights(C.byref(gstruct), _ptr(base), _ptr(ab), B, d, _ptr(out), _stream_handle(ab.device))
+        _lib.check(st, "msgat_edge_signal_weights")
+        ctx.call = (gstruct, keep, perm, B, N, d, nnz)
+        ctx.save_for_backward(ab)
+        return out if perm is None else out.index_select(1, perm[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        ab, = ctx.saved_tensors
+        gstruct, _, perm, B, N, d, nnz = ctx.call
+        need = ctx.needs_input_grad
+        dout = dout.contiguous() if perm is None else dout.index_select(1, perm[0])
+        dbase = _new(dout, nnz) if need[0] else None
+        dab = _new(dout, B, N, 2 * d) if need[1] else None
+        st = L.msgat_edge_signal_weights_backward(C.byref(gstruct), _ptr(dout), _ptr(ab), B, d, _ptr(dbase), _ptr(dab),
+                                                  _stream_handle(dout.device))
+        _lib.check(st, "msgat_edge_signal_weights_backward")
+        if dbase is not None and perm is not None:
+            dbase = dbase.index_select(0, perm[1])
+        return dbase, dab, None
+
+
+def edge_signal_weights(base: torch.Tensor, ab: torch.Tensor, crow: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+    """`base[e] + sum_k a[b,row(e),k] * b[b,col(e),k]` [B,nnz]: a weight per stored edge and per sample from the sample's own
+    node signals at the edge's two ends -- the edge strength of the dynamic-graph traffic models as a rank-d bilinear form
+    on the edges of one sparse pattern.  `ab` [B,N,2d] is the node projection, `a = ab[..., :d]` the row side and
+    `b = ab[..., d:]` the column side, d in {4, 8, ..., 32}; `base` [nnz] and the result follow the order of (`crow` [N+1],
+    `col` [nnz]), the result contiguous: `edge_adjacency(crow, col, weights)` reads it where it is, on the structure this op
+    resolved (crow, col) to.  One launch forward; one backward for `base` (the batch sum, in sample order) and `ab` (row
+    sums in CSR order, column sums in CSC order, every node written), no atomics (msgat_edge_signal_weights{,_backward})."""
+    _require_device_tensor("base", base)
+    _require_device_tensor("ab", ab, base.device)
+    if crow.device != base.device or col.device != base.device:
+        raise ValueError(f"edge_signal_weights: crow is on {crow.device} and col on {col.device}, base on {base.device}")
+    if (base.dim() != 1 or ab.dim() != 3 or crow.dim() != 1 or col.dim() != 1 or col.numel() != base.numel()
+            or crow.numel() != ab.shape[1] + 1 or ab.shape[2] % 2):
+        raise ValueError(f"edge_signal_weights: base {tuple(base.shape)}, ab {tuple(ab.shape)}, crow {tuple(crow.shape)} and "
+                         f"col {tuple(col.shape)} must be [nnz], [B, N, 2d], [N+1] and [nnz]")
+    d = ab.shape[2] // 2
+    if d < 4 or d > 32 or d % 4:
+        raise ValueError(f"edge_signal_weights: the rank d = {d} (ab {tuple(ab.shape)}) must be one of 4, 8, ..., 32")
+    return _EdgeSignalWeightsFunction.apply(base, ab, edge_pattern_of(crow, col))
 
 
 # ---- channel axes assembled from several tensors: one pass instead of cat / several mixes -------------------

@@ -203,7 +203,7 @@ def forward(model, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor) -> torch.T
     R, B = len(tpcs), X.shape[0]
     P = _all_views(_bank(model)).__getitem__
     x = X.transpose(0, 1).reshape(R * B, *X.shape[2:])                                 # relation-major groups
-    adjacency = model.adjacency(H, D)
+    adjacency = model.batch_adjacency(X, H, D)
     for level, m0 in enumerate(tpcs[0].tgacns):
         x = _meam(P, f"tgacns.{level}.", m0, x, adjacency, R, B, relu_input=level > 0)
     pred = ops.ln_head(x, P("ln.weight"), P("ln.bias"), tpcs[0].ln.eps, P("fc.weight"), P("fc.bias"),
