@@ -59,7 +59,8 @@ extern "C" {
  *     + msgat_window_gather (a step's input windows from a series resident in device memory);
  *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail);
  *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern);
- *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends).
+ *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends);
+ *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -887,6 +888,23 @@ int msgat_adam_step_guarded(float* const* chunk_param, const int64_t* chunk_off,
 int msgat_window_gather(const float* series, const float* target, const int64_t* origins, const int64_t* offsets,
                         float* X, int64_t* H, int64_t* D, float* Y, int32_t B, int32_t R, int32_t C, int32_t N,
                         int64_t T_total, int32_t tau, int32_t q, int64_t history, void* stream);
+
+/* msgat_window_gather_imputed: msgat_window_gather for a series whose missing readings are stored as NaN -- the same
+ * launch fills them in and, on request, appends a validity channel.
+ *       climatology [period, C, N] fp32   what a missing reading of slot s = (absolute step) % period becomes
+ *                                         (period = 1: one value per (channel, node)); read for missing entries only
+ *     writes, with t_b clamped as above, s = t_b - offsets[r] + k (the window start clamped as above) and C' = C + 1 if
+ *     mask_channel != 0, else C:
+ *       X [B, R, C', N, tau] fp32   X[b,r,c,n,k] = series[s, c, n], or climatology[s % period, c, n] where that word is a
+ *                                   NaN ((w & 0x7fffffff) > 0x7f800000); every other word keeps its bits
+ *                                   X[b,r,C,n,k] = 1.0f where no channel of series[s, :, n] is a NaN, else 0.0f
+ *       Y, H, D                     as msgat_window_gather writes them: Y keeps the raw target, null values included
+ *     Arguments as msgat_window_gather, and period >= 1 (MSGAT_ERR_SHAPE otherwise), climatology non-NULL, (C + 1) * N
+ *     below 2^31 - 256 (MSGAT_ERR_UNSUPPORTED otherwise) whether or not the validity channel is asked for. */
+int msgat_window_gather_imputed(const float* series, const float* climatology, const float* target,
+                                const int64_t* origins, const int64_t* offsets, float* X, int64_t* H, int64_t* D,
+                                float* Y, int32_t B, int32_t R, int32_t C, int32_t N, int64_t T_total, int32_t tau,
+                                int32_t q, int64_t history, int32_t period, int32_t mask_channel, void* stream);
 
 #ifdef __cplusplus
 }

@@ -188,7 +188,9 @@ _PROTOTYPES = {
                                                             C.c_void_p, C.c_void_p]),
     "msgat_window_gather": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                                          C.c_void_p]),
-    "msgat_edge_time_weights": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "msgat_window_gather_imputed": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32,
+                                                                 C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "msgat_edge_time_weights":(C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "msgat_edge_time_weights_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "msgat_edge_signal_weights": (C.c_int, [C.POINTER(Graph), C.c_void_p, C.c_void_p] + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "msgat_edge_signal_weights_backward": (C.c_int, [C.POINTER(Graph), C.c_void_p, C.c_void_p] + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),

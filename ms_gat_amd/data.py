@@ -38,6 +38,47 @@ def zscore(series: torch.Tensor, split: int) -> torch.Tensor:
     return (series - mean) / std
 
 
+def missing_entries(series: torch.Tensor, input_null_value: float) -> torch.Tensor:
+    """The entries of a series that are no measurements: NaN, or equal to `input_null_value` (what
+    `engine.valid_entries` says for the truth, negated).  `input_null_value = nan` marks the NaN entries only."""
+    return torch.isnan(series) | (series == input_null_value)
+
+
+def prepare_missing(raw: torch.Tensor, split: int, input_null_value: float, period: int):
+    """raw [C,N,T_total] with missing readings -> (normed [C,N,T_total], climatology [period,C,N]), both float32.
+
+    `normed`: the z-score per (channel, node) with the statistics of the VALID entries among the first `split` steps
+    (float64, unbiased std, rounded once), every missing entry stored as NaN.  A row with fewer than two valid training
+    entries or without spread gets std 1 and as mean its single valid value, or 0.
+    `climatology[s]`: the mean (float64, rounded once) of the valid normalised entries at the steps t < split with
+    t % period == s; 0, the mean of a z-score, where there is none.  It is what the gather puts in a missing reading's
+    place (`ops.window_gather_imputed`, `_windows_torch`)."""
+    if raw.dim() != 3 or period < 1 or not 0 <= split <= raw.shape[-1]:
+        raise ValueError(f"prepare_missing: raw {tuple(raw.shape)} must be [C,N,T_total], period = {period} >= 1 and "
+                         f"split = {split} within the series")
+    valid = ~missing_entries(raw, input_null_value)
+    x = torch.where(valid, raw, torch.zeros((), dtype=raw.dtype)).double()
+    head, head_valid = x[..., :split], valid[..., :split]
+    count = head_valid.sum(-1, keepdim=True)
+    mean = head.sum(-1, keepdim=True) / count.clamp(min=1)
+    dev2 = (torch.where(head_valid, head - mean, torch.zeros((), dtype=torch.float64)) ** 2).sum(-1, keepdim=True)
+    std = (dev2 / (count - 1).clamp(min=1)).sqrt()
+    std = torch.where((count < 2) | ~(std > 0), torch.ones_like(std), std)
+    mean, std = mean.float(), std.float()
+    std = torch.where(std > 0, std, torch.ones_like(std))        # a spread that rounds to 0 in float32
+    nan = torch.full((), float("nan"), dtype=torch.float32)
+    normed = torch.where(valid, (raw.float() - mean) / std, nan)
+    slot = torch.arange(split) % period
+    sums = torch.zeros((period, *raw.shape[:2]), dtype=torch.float64)
+    counts = torch.zeros((period, *raw.shape[:2]), dtype=torch.float64)
+    train = normed[..., :split].permute(2, 0, 1)                 # [split,C,N]
+    train_valid = head_valid.permute(2, 0, 1)
+    sums.index_add_(0, slot, torch.where(train_valid, train, torch.zeros((), dtype=torch.float32)).double())
+    counts.index_add_(0, slot, train_valid.double())
+    climatology = torch.where(counts > 0, sums / counts.clamp(min=1), torch.zeros((), dtype=torch.float64)).float()
+    return normed, climatology
+
+
 def split_intervals(total_steps: int, in_hours: Sequence[int], out_timesteps: int, tau: int):
     """Training / validation / evaluation [start, stop) of forecast origins (data_loader.py:69-78)."""
     history = tau * max(in_hours)
@@ -51,21 +92,37 @@ class PeriodicWindows(Dataset):
 
     Component r looks `hours[r]` hours back: X[r] = inputs[..., t - hours[r]*tau : t - hours[r]*tau + tau].
     The target is channel 0 of the raw (un-normalised) series.
+    `climatology` [period,C,N] given (`prepare_missing`): a NaN of a window becomes the table's entry of its step,
+    `climatology[step % period]`, and with `mask_channel` X is [R,C+1,N,tau], its last channel 1.0 where all C channels
+    of the node at that step are observed, else 0.0.
     """
 
     def __init__(self, inputs: torch.Tensor, target: torch.Tensor, interval: Tuple[int, int],
-                 hours: Sequence[int], out_timesteps: int, timesteps_per_hour: int):
+                 hours: Sequence[int], out_timesteps: int, timesteps_per_hour: int,
+                 climatology: torch.Tensor | None = None, mask_channel: bool = False):
         self.inputs, self.target = inputs, target
         self.start, self.stop = interval
         self.hours, self.q, self.tau = list(hours), out_timesteps, timesteps_per_hour
+        self.climatology, self.mask_channel = climatology, bool(mask_channel) and climatology is not None
 
     def __len__(self) -> int:
         return self.stop - self.start
 
+    def _window(self, s: int) -> torch.Tensor:
+        x = self.inputs[..., s: s + self.tau]
+        if self.climatology is None:
+            return x
+        missing = torch.isnan(x)
+        slots = torch.arange(s, s + self.tau) % self.climatology.shape[0]
+        x = torch.where(missing, self.climatology[slots].permute(1, 2, 0), x)
+        if self.mask_channel:
+            x = torch.cat([x, (~missing.any(0, keepdim=True)).to(x.dtype)])
+        return x
+
     def __getitem__(self, i: int):
         t = i + self.start
         hour = t // self.tau
-        x = torch.stack([self.inputs[..., t - h * self.tau: t - h * self.tau + self.tau] for h in self.hours])
+        x = torch.stack([self._window(t - h * self.tau) for h in self.hours])
         y = self.target[..., t: t + self.q]
         return x, torch.tensor(hour % 24), torch.tensor((hour // 24) % 7), y
 
@@ -75,20 +132,25 @@ class MSGATData:
 
     `meta` is the reference's `data/meta.yaml` entry (adj-file, data-file, num-nodes, num-channels,
     timesteps-per-hour) or a path to such a yaml plus `name`.
+    `input_null_value`, `impute`, `mask_channel`: `make_loaders`' handling of missing input readings; `input_channels`
+    is what the model's `in_channels` must be (`num_channels`, plus one with the validity channel).
     """
 
     def __init__(self, name: str, in_hours: List[int], out_timesteps: int, batch_size: int, num_workers: int = 0,
-                 meta_file: str = "data/meta.yaml", meta: dict | None = None, device=None):
+                 meta_file: str = "data/meta.yaml", meta: dict | None = None, device=None,
+                 input_null_value: float | None = None, impute: str = "period", mask_channel: bool = True):
         if meta is None:
             with open(meta_file) as f:
                 meta = yaml.safe_load(f)[name]
         self.num_nodes, self.num_channels = meta["num-nodes"], meta["num-channels"]
+        self.input_channels = self.num_channels + int(input_null_value is not None and bool(mask_channel))
         self.timesteps_per_hour = meta["timesteps-per-hour"]
         self.in_hours, self.out_timesteps = list(in_hours), out_timesteps
         self.adj = load_adjacency_csv(meta["adj-file"], self.num_nodes)
         raw = torch.from_numpy(np.load(meta["data-file"])["data"]).float().transpose(0, -1)  # [C,N,T_total]
         self.training, self.validation, self.evaluation = make_loaders(
-            raw, self.in_hours, out_timesteps, self.timesteps_per_hour, batch_size, num_workers, device=device)
+            raw, self.in_hours, out_timesteps, self.timesteps_per_hour, batch_size, num_workers, device=device,
+            input_null_value=input_null_value, impute=impute, mask_channel=mask_channel)
 
 
 class ShardedBatchSampler(Sampler):
@@ -145,12 +207,21 @@ def upload_series(inputs: torch.Tensor, target: torch.Tensor, device):
     return inputs.to(device).permute(2, 0, 1).contiguous(), target.to(device).contiguous()
 
 
-def _windows_torch(series_tm: torch.Tensor, target: torch.Tensor, origins: torch.Tensor, hours, tau: int, q: int):
+def _windows_torch(series_tm: torch.Tensor, target: torch.Tensor, origins: torch.Tensor, hours, tau: int, q: int,
+                   climatology: torch.Tensor | None = None, mask_channel: bool = False):
     """`ops.window_gather` restated with torch indexing (bit-equal to collated `PeriodicWindows` items); serves
-    `DeviceWindows(device="cpu")` and states what the kernel must give."""
+    `DeviceWindows(device="cpu")` and states what the kernel must give.  With `climatology` [period,C,N] it restates
+    `ops.window_gather_imputed`: a NaN becomes the table's entry of its step, and `mask_channel` appends the validity
+    channel (1.0 where all C channels of the node at that step are observed)."""
     back = torch.tensor([h * tau for h in hours], dtype=torch.int64, device=origins.device)
     rows = origins[:, None, None] - back[None, :, None] + torch.arange(tau, device=origins.device)     # [B,R,tau]
-    x = series_tm[rows].permute(0, 1, 3, 4, 2).contiguous()                                            # [B,R,C,N,tau]
+    x = series_tm[rows]                                                                                # [B,R,tau,C,N]
+    if climatology is not None:
+        missing = torch.isnan(x)
+        x = torch.where(missing, climatology[rows % climatology.shape[0]], x)
+        if mask_channel:
+            x = torch.cat([x, (~missing.any(3, keepdim=True)).to(x.dtype)], dim=3)
+    x = x.permute(0, 1, 3, 4, 2).contiguous()                                                          # [B,R,C,N,tau]
     y = target[:, origins[:, None] + torch.arange(q, device=origins.device)].permute(1, 0, 2).contiguous()
     hour = origins // tau
     return x, hour % 24, (hour // 24) % 7, y
@@ -166,12 +237,17 @@ class DeviceWindows:
     of an epoch goes to the device in ONE copy at `__iter__`; a batch's origins are a slice of it.  `Engine.run_epoch`
     finds `batch_sampler` (`set_epoch`, `global_batch_sizes`) and `msgat_sharded` as on a sharded DataLoader.
     `resident`: the pair `upload_series` returned, to share one upload among several splits.
-    With `device="cpu"` the batches come from `_windows_torch`: the host logic is the same."""
+    With `device="cpu"` the batches come from `_windows_torch`: the host logic is the same.
+    `climatology` [period,C,N] given (`prepare_missing`; `inputs` then holds NaN at its missing readings): the batches
+    come from `ops.window_gather_imputed`, with the validity channel if `mask_channel`; the table lives on the device
+    too, `resident` is then the triple (series, target, table) and `resident_bytes` counts the table."""
 
     def __init__(self, inputs: torch.Tensor, target: torch.Tensor, interval: Tuple[int, int], hours: Sequence[int],
                  out_timesteps: int, timesteps_per_hour: int, batch_size: int, shuffle: bool = False, rank: int = 0,
-                 world: int = 1, seed: int = 0, device="cuda", resident=None):
-        self.dataset = PeriodicWindows(inputs, target, interval, hours, out_timesteps, timesteps_per_hour)
+                 world: int = 1, seed: int = 0, device="cuda", resident=None, climatology: torch.Tensor | None = None,
+                 mask_channel: bool = False):
+        self.dataset = PeriodicWindows(inputs, target, interval, hours, out_timesteps, timesteps_per_hour,
+                                       climatology=climatology, mask_channel=mask_channel)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -179,10 +255,23 @@ class DeviceWindows:
         if not history <= interval[0] <= interval[1] <= inputs.shape[-1] - out_timesteps + 1:
             raise ValueError(f"origins {tuple(interval)} leave the series: they must lie in [{history}, "
                              f"{inputs.shape[-1] - out_timesteps}]")
-        self.series, self.target = upload_series(inputs, target, self.device) if resident is None else resident
+        self.climatology, self.mask_channel = None, self.dataset.mask_channel
+        if climatology is None:
+            self.series, self.target = upload_series(inputs, target, self.device) if resident is None else resident
+        else:
+            if climatology.dim() != 3 or climatology.dtype != torch.float32 or climatology.shape[0] < 1 \
+                    or tuple(climatology.shape[1:]) != tuple(inputs.shape[:2]):
+                raise ValueError(f"climatology {tuple(climatology.shape)} {climatology.dtype} must be float32 "
+                                 f"[period, {inputs.shape[0]}, {inputs.shape[1]}]")
+            self.series, self.target, self.climatology = resident if resident is not None else (
+                *upload_series(inputs, target, self.device), climatology.to(self.device).contiguous())
+            if self.climatology.device != self.device or self.climatology.shape != climatology.shape:
+                raise ValueError("resident arrays do not belong to this series and device")
         if self.series.device != self.device or tuple(self.series.shape) != (inputs.shape[2], *inputs.shape[:2]):
             raise ValueError("resident arrays do not belong to this series and device")
         self.resident_bytes = self.series.numel() * 4 + self.target.numel() * 4
+        if self.climatology is not None:
+            self.resident_bytes += self.climatology.numel() * 4
         self.batch_sampler = ShardedBatchSampler(len(self.dataset), batch_size, shuffle, rank, world, seed)
         self.msgat_sharded = world > 1
         self._offsets = None
@@ -203,36 +292,58 @@ class DeviceWindows:
         for b in batches:
             origins = order[at: at + len(b)]
             at += len(b)
-            if self.device.type == "cuda":
-                from . import ops
+            if self.device.type != "cuda":
+                yield _windows_torch(self.series, self.target, origins, ds.hours, ds.tau, ds.q,
+                                     climatology=self.climatology, mask_channel=self.mask_channel)
+                continue
+            from . import ops
+            if self.climatology is None:
                 yield ops.window_gather(self.series, self.target, origins, ds.hours, ds.tau, ds.q, offsets=self._offsets)
             else:
-                yield _windows_torch(self.series, self.target, origins, ds.hours, ds.tau, ds.q)
+                yield ops.window_gather_imputed(self.series, self.climatology, self.target, origins, ds.hours, ds.tau,
+                                                ds.q, mask_channel=self.mask_channel, offsets=self._offsets)
 
 
 def make_loaders(raw: torch.Tensor, in_hours, out_timesteps, tau, batch_size, num_workers=0, pin_memory=True,
-                 rank: int | None = None, world: int | None = None, seed: int = 0, device=None):
+                 rank: int | None = None, world: int | None = None, seed: int = 0, device=None,
+                 input_null_value: float | None = None, impute: str = "period", mask_channel: bool = True):
     """raw [C,N,T_total] -> (training, validation, evaluation) loaders; only training shuffles (data_loader.py:80-89).
 
     `batch_size` is the GLOBAL batch (the reference's `-b`).  Under an initialised process group (or explicit
     `rank` / `world`) the loaders are sharded (`ShardedBatchSampler`, attribute `msgat_sharded`): every rank loads
     only its part of each global batch.
-    `device` given: three `DeviceWindows` over ONE upload of the series to that device instead of DataLoaders."""
+    `device` given: three `DeviceWindows` over ONE upload of the series to that device instead of DataLoaders.
+    `input_null_value` given: the readings of `raw` that are NaN or equal to it are missing (`prepare_missing`): they
+    stay out of the z-score's statistics, and in X each becomes the training span's mean of its slot of the week
+    (`impute="period"`, period = 7 * 24 * tau) or the z-score mean 0 (`impute="mean"`); with `mask_channel` X gains a
+    channel that is 1.0 where the node's reading is observed, so the model's `in_channels` is C + 1.  Y stays the raw
+    target (`Trainer(null_value=...)` masks it).  Without `input_null_value` the other two options have no effect
+    (an `impute` that is neither of the two is a ValueError all the same)."""
     import torch.distributed as dist
+    if impute not in ("period", "mean"):
+        raise ValueError(f"impute = {impute!r} must be 'period' or 'mean'")
     if world is None:
         on = dist.is_available() and dist.is_initialized()
         rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
     intervals, train_end = split_intervals(raw.size(-1), in_hours, out_timesteps, tau)
-    normed = zscore(raw, split=train_end)
+    if input_null_value is None:
+        normed, missing = zscore(raw, split=train_end), {}
+    else:
+        normed, table = prepare_missing(raw, train_end, input_null_value, 7 * 24 * tau if impute == "period" else 1)
+        if impute == "mean":
+            table.zero_()
+        missing = dict(climatology=table, mask_channel=bool(mask_channel))
     if device is not None:
         resident = upload_series(normed, raw[0], device)
+        if missing:
+            resident = (*resident, missing["climatology"].to(resident[0].device).contiguous())
         return [DeviceWindows(normed, raw[0], iv, in_hours, out_timesteps, tau, batch_size, shuffle=(i == 0), rank=rank,
-                              world=world, seed=seed, device=resident[0].device, resident=resident)
+                              world=world, seed=seed, device=resident[0].device, resident=resident, **missing)
                 for i, iv in enumerate(intervals)]
     pin = pin_memory and torch.cuda.is_available()
     loaders = []
     for i, iv in enumerate(intervals):
-        ds = PeriodicWindows(normed, raw[0], iv, in_hours, out_timesteps, tau)
+        ds = PeriodicWindows(normed, raw[0], iv, in_hours, out_timesteps, tau, **missing)
         if world > 1:
             loader = DataLoader(ds, batch_sampler=ShardedBatchSampler(len(ds), batch_size, i == 0, rank, world, seed),
                                 pin_memory=pin, num_workers=num_workers)
@@ -244,12 +355,21 @@ def make_loaders(raw: torch.Tensor, in_hours, out_timesteps, tau, batch_size, nu
 
 
 class SyntheticPEMS:
-    """Seeded stand-in for a PEMS dataset: same tensors, shapes and loaders, no files."""
+    """Seeded stand-in for a PEMS dataset: same tensors, shapes and loaders, no files.
+
+    `missing` > 0: that share of the (node, step) readings, in runs of 1 to 2 tau - 1 steps, is written as 0 into all
+    channels of `raw`, as a PEMS file stores a sensor that was down; `dead_sensors` nodes are 0 throughout.  Both come from
+    a generator of their own (`seed + 2`): the series without them keeps its bits.  `input_null_value`, `impute`,
+    `mask_channel` and `input_channels` as in `MSGATData`."""
 
     def __init__(self, n_nodes: int, n_edges: int, n_channels: int, in_hours: List[int], out_timesteps: int = 12,
                  batch_size: int = 32, timesteps_per_hour: int = 12, days: int = 14, seed: int = 0,
-                 num_workers: int = 0, device=None):
+                 num_workers: int = 0, device=None, missing: float = 0.0, dead_sensors: int = 0,
+                 input_null_value: float | None = None, impute: str = "period", mask_channel: bool = True):
+        if not 0.0 <= missing < 1.0 or not 0 <= dead_sensors <= n_nodes:
+            raise ValueError(f"missing = {missing} must lie in [0, 1) and dead_sensors = {dead_sensors} in [0, {n_nodes}]")
         self.num_nodes, self.num_channels, self.timesteps_per_hour = n_nodes, n_channels, timesteps_per_hour
+        self.input_channels = n_channels + int(input_null_value is not None and bool(mask_channel))
         self.in_hours, self.out_timesteps = list(in_hours), out_timesteps
         self.adj = synthetic_adjacency(n_nodes, n_edges, seed)
         g = torch.Generator().manual_seed(seed + 1)
@@ -259,5 +379,24 @@ class SyntheticPEMS:
         base = 200 + 80 * torch.rand(n_channels, n_nodes, 1, generator=g)
         raw = base * (1 + 0.4 * daily) + 15 * torch.randn(n_channels, n_nodes, total, generator=g)
         self.raw = raw.clamp_min(1.0)
+        if missing > 0 or dead_sensors > 0:
+            self.raw[:, self.outages(n_nodes, total, timesteps_per_hour, missing, dead_sensors, seed + 2)] = 0.0
         self.training, self.validation, self.evaluation = make_loaders(
-            self.raw, self.in_hours, out_timesteps, timesteps_per_hour, batch_size, num_workers, device=device)
+            self.raw, self.in_hours, out_timesteps, timesteps_per_hour, batch_size, num_workers, device=device,
+            input_null_value=input_null_value, impute=impute, mask_channel=mask_channel)
+
+    @staticmethod
+    def outages(n_nodes: int, total: int, tau: int, missing: float, dead_sensors: int, seed: int) -> torch.Tensor:
+        """bool [n_nodes, total]: runs of 1 to 2 tau - 1 steps (tau on average) at seeded places, as many as make up
+        the share `missing` if none overlapped, plus `dead_sensors` whole rows."""
+        g = torch.Generator().manual_seed(seed)
+        n_runs = round(missing * n_nodes * total / tau)
+        node, start = torch.randint(n_nodes, (n_runs,), generator=g), torch.randint(total, (n_runs,), generator=g)
+        stop = (start + torch.randint(1, 2 * tau, (n_runs,), generator=g)).clamp(max=total)
+        edges = torch.zeros(n_nodes, total + 1, dtype=torch.int64)
+        ones = torch.ones(n_runs, dtype=torch.int64)
+        edges.index_put_((node, start), ones, accumulate=True)
+        edges.index_put_((node, stop), -ones, accumulate=True)
+        down = edges.cumsum(1)[:, :total] > 0
+        down[torch.randperm(n_nodes, generator=g)[:dead_sensors]] = True
+        return down

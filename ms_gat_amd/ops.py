@@ -1967,45 +1967,75 @@ def window_gather(inputs_dev: torch.Tensor, target_dev: torch.Tensor, origins: t
     ints; `offsets`: what `window_offsets(hours, tau, device)` gave, for a caller that keeps it (without it the array
     is built, and copied to the device, by this call).  Origins outside [tau * max(hours), T_total - q] are clamped into
     it by the kernel.  No autograd: data."""
-    for name, t in (("inputs_dev", inputs_dev), ("target_dev", target_dev)):
+    return _window_gather("window_gather", inputs_dev, target_dev, origins, hours, tau, q, offsets)
+
+
+def window_gather_imputed(inputs_dev: torch.Tensor, climatology_dev: torch.Tensor, target_dev: torch.Tensor,
+                          origins: torch.Tensor, hours, tau: int, q: int, mask_channel: bool = True,
+                          offsets: Optional[torch.Tensor] = None):
+    """`window_gather` for a series whose missing readings are stored as NaN (`data.prepare_missing`), in one launch
+    (`msgat_window_gather_imputed`): a NaN of a window becomes `climatology_dev[step % period, c, n]`, every other value
+    keeps its bits, and with `mask_channel` X is `[B, R, C + 1, N, tau]`, its last channel 1.0 where all C channels of
+    that node at that step are observed and 0.0 elsewhere.  H, D and Y as `window_gather` gives them.
+
+    `climatology_dev` is float32 `[period, C, N]` on the device of the series (period = 1: one value per row); the
+    other arguments are `window_gather`'s.  No autograd: data."""
+    return _window_gather("window_gather_imputed", inputs_dev, target_dev, origins, hours, tau, q, offsets,
+                          climatology_dev, bool(mask_channel))
+
+
+def _window_gather(what, inputs_dev, target_dev, origins, hours, tau, q, offsets, climatology_dev=None, mask_channel=False):
+    """The argument checks and the launch of `window_gather` and, with a table, of `window_gather_imputed`."""
+    floats = [("inputs_dev", inputs_dev), ("target_dev", target_dev)]
+    if climatology_dev is not None:
+        floats.append(("climatology_dev", climatology_dev))
+    for name, t in floats:
         if t.dtype != torch.float32:
-            raise TypeError(f"window_gather: {name} must be float32, got {t.dtype}")
+            raise TypeError(f"{what}: {name} must be float32, got {t.dtype}")
     if origins.dtype != torch.int64:
-        raise TypeError(f"window_gather: origins must be int64, got {origins.dtype}")
-    if target_dev.device != inputs_dev.device or origins.device != inputs_dev.device:
-        raise ValueError(f"window_gather: inputs_dev on {inputs_dev.device}, target_dev on {target_dev.device} and origins "
-                         f"on {origins.device} must share one device")
+        raise TypeError(f"{what}: origins must be int64, got {origins.dtype}")
+    for name, t in floats[1:] + [("origins", origins)]:
+        if t.device != inputs_dev.device:
+            raise ValueError(f"{what}: inputs_dev on {inputs_dev.device} and {name} on {t.device} must share one device")
     hours = [int(h) for h in hours]
     if not hours or min(hours) < 1:
-        raise ValueError(f"window_gather: hours {hours} must be a non-empty sequence of positive ints")
+        raise ValueError(f"{what}: hours {hours} must be a non-empty sequence of positive ints")
     if tau not in (4, 8, 12, 16) or not 1 <= q <= 64:
-        raise ValueError(f"window_gather: tau = {tau} must be 4, 8, 12 or 16 and q = {q} between 1 and 64")
+        raise ValueError(f"{what}: tau = {tau} must be 4, 8, 12 or 16 and q = {q} between 1 and 64")
     if inputs_dev.dim() != 3 or target_dev.dim() != 2 or origins.dim() != 1 or origins.numel() == 0:
-        raise ValueError(f"window_gather: inputs_dev {tuple(inputs_dev.shape)} must be [T_total, C, N], target_dev "
+        raise ValueError(f"{what}: inputs_dev {tuple(inputs_dev.shape)} must be [T_total, C, N], target_dev "
                          f"{tuple(target_dev.shape)} [N, T_total] and origins {tuple(origins.shape)} a non-empty [B]")
     T_total, C_, N = inputs_dev.shape
     if tuple(target_dev.shape) != (N, T_total):
-        raise ValueError(f"window_gather: target_dev {tuple(target_dev.shape)} does not fit inputs_dev [T_total = {T_total}, "
+        raise ValueError(f"{what}: target_dev {tuple(target_dev.shape)} does not fit inputs_dev [T_total = {T_total}, "
                          f"C = {C_}, N = {N}]: expected [{N}, {T_total}]")
+    if climatology_dev is not None and (climatology_dev.dim() != 3 or climatology_dev.shape[0] < 1
+                                        or tuple(climatology_dev.shape[1:]) != (C_, N)):
+        raise ValueError(f"{what}: climatology_dev {tuple(climatology_dev.shape)} must be [period >= 1, {C_}, {N}]")
     history = tau * max(hours)
     if T_total < history + q:
-        raise ValueError(f"window_gather: a series of {T_total} steps is shorter than tau * max(hours) + q = {history + q}")
-    if not (inputs_dev.is_contiguous() and target_dev.is_contiguous() and origins.is_contiguous()):
-        raise ValueError("window_gather: inputs_dev, target_dev and origins must be contiguous")
+        raise ValueError(f"{what}: a series of {T_total} steps is shorter than tau * max(hours) + q = {history + q}")
+    if not all(t.is_contiguous() for _, t in floats + [("origins", origins)]):
+        raise ValueError(f"{what}: {', '.join(name for name, _ in floats)} and origins must be contiguous")
     _require_device_tensor("inputs_dev", inputs_dev)
     dev, B, R = inputs_dev.device, origins.numel(), len(hours)
     if offsets is None:
         offsets = window_offsets(hours, tau, dev)
     elif offsets.dtype != torch.int64 or offsets.device != dev or tuple(offsets.shape) != (R,) or not offsets.is_contiguous():
-        raise ValueError(f"window_gather: offsets must be a contiguous int64 [{R}] tensor on {dev}")
-    X = torch.empty((B, R, C_, N, tau), device=dev, dtype=torch.float32)
+        raise ValueError(f"{what}: offsets must be a contiguous int64 [{R}] tensor on {dev}")
+    X = torch.empty((B, R, C_ + int(mask_channel), N, tau), device=dev, dtype=torch.float32)
     Y = torch.empty((B, N, q), device=dev, dtype=torch.float32)
     HD = torch.empty((2, B), device=dev, dtype=torch.int64)
+    outs, dims = (_ptr(X), _ptr(HD[0]), _ptr(HD[1]), _ptr(Y)), (B, R, C_, N, T_total, tau, q, history)
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_window_gather(_ptr(inputs_dev), _ptr(target_dev), _ptr(origins), _ptr(offsets), _ptr(X),
-                                            _ptr(HD[0]), _ptr(HD[1]), _ptr(Y), B, R, C_, N, T_total, tau, q, history,
-                                            _stream_handle(dev))
-    _lib.check(st, "msgat_window_gather")
+        if climatology_dev is None:
+            st = _lib.lib().msgat_window_gather(_ptr(inputs_dev), _ptr(target_dev), _ptr(origins), _ptr(offsets), *outs,
+                                                *dims, _stream_handle(dev))
+        else:
+            st = _lib.lib().msgat_window_gather_imputed(_ptr(inputs_dev), _ptr(climatology_dev), _ptr(target_dev),
+                                                        _ptr(origins), _ptr(offsets), *outs, *dims,
+                                                        climatology_dev.shape[0], int(mask_channel), _stream_handle(dev))
+    _lib.check(st, f"msgat_{what}")
     return X, HD[0], HD[1], Y
 
 

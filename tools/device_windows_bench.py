@@ -1,6 +1,6 @@
 """Times the device-resident input windows (`ops.window_gather`, `data.DeviceWindows`) on one GPU:
 
-    python tools/device_windows_bench.py [--launches 256] [--steps 200] [--repeats 3] [--only kernel|epoch]
+    python tools/device_windows_bench.py [--launches 256] [--steps 200] [--repeats 3] [--only kernel|imputed|epoch]
 
 Shape: the PEMSD7 training shape, B = 32, in_hours = [1, 2, 3, 24, 168], C = 3, N = 883, tau = q = 12, a seeded synthetic
 series (28224 steps for the epoch: 299 MB normalised + 100 MB target).
@@ -13,6 +13,9 @@ series (28224 steps for the epoch: 299 MB normalised + 100 MB target).
     from a contiguous read, equally cold).  For contrast the WARM figures (one origin set, one pair of buffers, over and
     over: everything cache-resident) and the eager call (`ops.window_gather`: three allocations and the launch, host
     time included).
+(i) imputed: `msgat_window_gather_imputed` (missing readings filled in, with and without the validity channel) beside the
+    plain gather on one series with 1 % missing readings and two dead sensors, cold and warm as in (a), with the bytes
+    each variant asks for.
 (b) epoch: `Trainer.run_epoch(mode="train")` of msgat72 (R = 5, hip_graph="auto", one model and trainer throughout) over
     `--steps` steps after the step's graph is captured, host clock around the epoch ending in a synchronise, fed by
       host0 / host2 / host4   `make_loaders(...)` DataLoaders with num_workers = 0 / 2 / 4 (pinned, copied per step)
@@ -148,6 +151,90 @@ def kernel_part(dev, launches, repeats):
     return out
 
 
+def imputed_part(dev, launches, repeats):
+    """`msgat_window_gather_imputed` beside `msgat_window_gather`, in one process on one series: the 4 x 28224 steps of
+    `kernel_part`, z-scored, with 1 % of its (node, step) readings in runs and two dead sensors stored as NaN
+    (`SyntheticPEMS.outages`), and a table of one week's slots (2016 x C x N, 21 MB; random values: they do not matter to
+    the time).  COLD and WARM as in `kernel_part`; the plain gather copies the same series, NaNs included.  Next to the
+    times the bytes each variant asks for per launch: X reads B R tau C N words (once more for the validity channel, whose
+    lanes read the C words of their node again), Y reads what it writes, X writes B R C' N tau words."""
+    from ms_gat_amd import _lib
+    s = dict(SHAPE, T_total=4 * SHAPE["T_total"])
+    raw = series(s["T_total"])
+    intervals, train_end = data.split_intervals(s["T_total"], s["hours"], s["q"], s["tau"])
+    normed = data.zscore(raw, split=train_end)
+    down = data.SyntheticPEMS.outages(s["N"], s["T_total"], s["tau"], 0.01, 2, seed=2)
+    normed[:, down] = float("nan")
+    resident = data.upload_series(normed, raw[0], dev)
+    period = 7 * 24 * s["tau"]
+    table = torch.randn(period, s["C"], s["N"], generator=torch.Generator().manual_seed(3)).to(dev)
+    missing_share = float(down.float().mean())
+    del raw, normed, down
+    n_sets = 32
+    lo, hi = intervals[0]
+    order = (torch.randperm(hi - lo, generator=torch.Generator().manual_seed(1))[: n_sets * s["B"]] + lo).to(dev)
+    sets = [order[i * s["B"]: (i + 1) * s["B"]] for i in range(n_sets)]
+    offsets = ops.window_offsets(s["hours"], s["tau"], dev)
+    outs = {"plain": [ops.window_gather(*resident, o, s["hours"], s["tau"], s["q"], offsets=offsets) for o in sets]}
+    for name, mask in (("imputed", False), ("imputed_mask", True)):
+        outs[name] = [ops.window_gather_imputed(resident[0], table, resident[1], o, s["hours"], s["tau"], s["q"],
+                                                mask_channel=mask, offsets=offsets) for o in sets]
+    assert not any(bool(torch.isnan(out[0]).any()) for out in outs["imputed_mask"])
+    L, stream = _lib.lib(), _lib.stream_handle
+    dims = (s["B"], len(s["hours"]), s["C"], s["N"], s["T_total"], s["tau"], s["q"], s["tau"] * max(s["hours"]))
+
+    def launch(name, o, out):     # the C entry points into fixed outputs: nothing but the launch
+        x, h, d, y = out
+        if name == "plain":
+            st = L.msgat_window_gather(resident[0].data_ptr(), resident[1].data_ptr(), o.data_ptr(), offsets.data_ptr(),
+                                       x.data_ptr(), h.data_ptr(), d.data_ptr(), y.data_ptr(), *dims, stream(dev))
+        else:
+            st = L.msgat_window_gather_imputed(resident[0].data_ptr(), table.data_ptr(), resident[1].data_ptr(), o.data_ptr(),
+                                               offsets.data_ptr(), x.data_ptr(), h.data_ptr(), d.data_ptr(), y.data_ptr(),
+                                               *dims, period, int(name == "imputed_mask"), stream(dev))
+        _lib.check(st, name)
+
+    def cold(name):
+        def run():
+            for o, out in zip(sets, outs[name]):
+                launch(name, o, out)
+        return run
+
+    def warm(name):
+        def run():
+            for _ in range(n_sets):
+                launch(name, sets[0], outs[name][0])
+        return run
+
+    calls = max(1, -(-launches // n_sets))
+    runs = {f"{name}_{k}": graph_of(make(name)).replay for k, make in (("cold", cold), ("warm", warm)) for name in outs}
+    times = {k: [] for k in runs}
+    for r in range(repeats):
+        for k, fn in runs.items():       # alternated
+            times[k].append(event_us(fn, calls, n_sets))
+        print(f"imputed round {r + 1}: " + "  ".join(f"{k} {v[-1]:7.2f} us" for k, v in times.items()), flush=True)
+    x_words = s["B"] * len(s["hours"]) * s["C"] * s["N"] * s["tau"]
+    y_bytes = 4 * s["B"] * s["N"] * s["q"]
+    asked = {"plain": {"read": 4 * x_words + y_bytes, "written": 4 * x_words + y_bytes + 16 * s["B"]}}
+    asked["imputed"] = {"read": asked["plain"]["read"] + round(4 * x_words * missing_share), "written": asked["plain"]["written"]}
+    asked["imputed_mask"] = {"read": asked["imputed"]["read"] + 4 * x_words,
+                             "written": asked["plain"]["written"] + 4 * x_words // s["C"]}
+    out = {"T_total": s["T_total"], "period": period, "missing_share": round(missing_share, 5),
+           "launches_per_figure": calls * n_sets, "origin_sets": n_sets, "bytes_asked_per_launch": asked}
+    for k, v in times.items():
+        out[f"{k}_us_median"] = round(statistics.median(v), 2)
+        out[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+    for k in ("cold", "warm"):
+        plain = out[f"plain_{k}_us_median"]
+        out[f"plain_{k}_spread"] = round((max(times[f"plain_{k}"]) - min(times[f"plain_{k}"])) / plain, 4)
+        for name in ("imputed", "imputed_mask"):
+            out[f"{name}_over_plain_{k}"] = round(out[f"{name}_{k}_us_median"] / plain, 3)
+    for name in ("imputed", "imputed_mask"):
+        out[f"{name}_over_plain_bytes_written"] = round(asked[name]["written"] / asked["plain"]["written"], 3)
+        out[f"{name}_over_plain_bytes_moved"] = round(sum(asked[name].values()) / sum(asked["plain"].values()), 3)
+    return out
+
+
 class _First:
     """The first `n` batches of a loader, with what `Engine.run_epoch` looks for on it."""
 
@@ -201,16 +288,19 @@ def main():
     ap.add_argument("--launches", type=int, default=256)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--only", choices=["kernel", "epoch"])
+    ap.add_argument("--only", choices=["kernel", "imputed", "epoch"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("device_windows_bench.py needs the GPU: there is nothing to time without one")
     dev = torch.device("cuda:0")
     out = {"shape": SHAPE}
-    if a.only != "epoch":
+    if a.only in (None, "kernel"):
         out["kernel"] = kernel_part(dev, a.launches, max(a.repeats, 3))
         torch.cuda.empty_cache()
-    if a.only != "kernel":
+    if a.only in (None, "imputed"):
+        out["imputed"] = imputed_part(dev, a.launches, max(a.repeats, 3))
+        torch.cuda.empty_cache()
+    if a.only in (None, "epoch"):
         out["epoch"] = epoch_part(series(SHAPE["T_total"]), dev, a.steps, a.repeats)
     print(json.dumps(out))
 
