@@ -664,7 +664,13 @@ int msgat_layernorm_head_backward(const float* dout, const float* W, const float
  *       left = q_g^T Wt1_r^T, right = q_g^T Wt2_r^T [T,K] (saved in lr [G,2,T,K]),  att[g] = softmax_rows(left right^T),
  *       taps[g,1] = att[g],  taps[g,0] = att[g] shifted down by `dilation` rows (rows < dilation zero);
  *       q = pooled [G,N,T] (the alpha-weighted channel sums), Wt1 / Wt2 [R,K,N], 2 T K <= 256.  taps [G,2,T,T] is what
- *       msgat_time_mix applies (K = 2).  Backward: dpooled [G,N,T], dWt1 / dWt2 [R,K,N] from dtaps. */
+ *       msgat_time_mix applies (K = 2).  Backward: dpooled [G,N,T], dWt1 / dWt2 [R,K,N] from dtaps.
+ * The channel attention keeps its whole problem in the LDS of one workgroup, and the backward needs more of it than the
+ * forward: 4 (2 C (C+1) + 3 C T + T^2 + 2 cb C) against 4 (2 C T + T^2 + C (C+1) + cb C) bytes of 160 KiB - 1 KiB; beyond
+ * that either entry point returns MSGAT_ERR_UNSUPPORTED.  msgat_channel_attention_fused(C, cb, T) = 1 when BOTH fit (at
+ * T = 12, cb = C / 3: up to C = 114; the forward alone up to 165): a caller that differentiates asks it before the
+ * forward and evaluates the same ops elsewhere when it is 0, so that nothing fails in the middle of a backward pass. */
+int msgat_channel_attention_fused(int32_t C, int32_t cb, int32_t T);
 int msgat_channel_attention_forward(const float* pooled, const float* Wc, const float* conv, float* att, float* Mc,
                                     int32_t G, int32_t R, int32_t C, int32_t cb, int32_t T, void* stream);
 size_t msgat_channel_attention_partial_floats(int32_t G, int32_t C, int32_t cb, int32_t T);

@@ -155,6 +155,7 @@ _PROTOTYPES = {
     "msgat_layernorm_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "msgat_layernorm_partial_floats": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "msgat_layernorm_backward": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
+    "msgat_channel_attention_fused": (C.c_int, [C.c_int32] * 3),
     "msgat_channel_attention_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "msgat_channel_attention_partial_floats": (C.c_size_t, [C.c_int32] * 4),
     "msgat_channel_attention_backward": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 5 + [C.c_void_p]),

@@ -1243,6 +1243,10 @@ static int check_small(int32_t G, int32_t R, int32_t T) {
   return MSGAT_OK;
 }
 
+extern "C" int msgat_channel_attention_fused(int32_t C, int32_t cb, int32_t T) {
+  return (C > 0 && C <= kMaxC && cb > 0 && cb <= kMaxC && t_supported(T) && chanatt_fused(C, cb, T)) ? 1 : 0;
+}
+
 extern "C" int msgat_channel_attention_forward(const float* pooled, const float* Wc, const float* conv, float* att,
                                                float* Mc, int32_t G, int32_t R, int32_t C, int32_t cb, int32_t T,
                                                void* stream) {

@@ -486,6 +486,7 @@ int launch_layernorm_bwd(const float* x, const float* w, const float* dy, const 
                          float* dpw_rows = nullptr, float* dpw = nullptr);
 
 // the tiny attention matrices of a MEAM block (smallatt.hip)
+bool chanatt_fused(int C, int cb, int T);
 size_t chanatt_partial_floats(int G, int C, int cb, int T);
 int launch_chanatt_fwd(const float* pooled, const float* Wc, const float* conv, float* att, float* Mc, int G, int R,
                        int C, int cb, int T, hipStream_t s);

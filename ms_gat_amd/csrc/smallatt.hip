@@ -163,6 +163,13 @@ static size_t chanatt_bwd_lds(int C, int cb, int T) {
   return sizeof(float) * (size_t)(2 * C * (C + 1) + 3 * C * T + T * T + 2 * cb * C);
 }
 
+// both directions or neither: a forward that fits where its backward does not (C = 117 .. 165 at T = 12, cb = C / 3)
+// would fail in the middle of a training step, so callers ask this before they launch the forward
+bool chanatt_fused(int C, int cb, int T) {
+  const size_t cap = (size_t)kLdsMax - 1024;
+  return chanatt_fwd_lds(C, cb, T) <= cap && chanatt_bwd_lds(C, cb, T) <= cap;
+}
+
 size_t chanatt_partial_floats(int G, int C, int cb, int T) { return (size_t)G * ((size_t)T * T + (size_t)cb * C); }
 
 // one grant record per kernel instantiation (the template argument makes the static distinct)

@@ -185,11 +185,12 @@ class CACN(nn.Module):
 
     def channel_matrix(self, signals: torch.Tensor, pooled: torch.Tensor = None) -> torch.Tensor:
         """[B,Co,C] = conv.weight @ channel attention: node pooling in one pass (or `pooled` [B,C,T], when the caller has
-        it already: MEAM takes it out of its LayerNorm pass), the rest in one launch."""
+        it already: MEAM takes it out of its LayerNorm pass), the rest in one launch -- or, beyond the LDS budget of that
+        launch's backward (from 115 channels at T = 12), in batched torch ops: `ops.channel_matrix` decides from the shapes."""
         ca, conv = self.seq[0], self.seq[1]
         if pooled is None:
             pooled = ops.node_pool(signals, ca.alpha)
-        return ops.channel_attention_mix(pooled, ca.Wc, conv.weight.flatten(1))
+        return ops.channel_matrix(pooled, ca.Wc, conv.weight.flatten(1))
 
     def forward(self, signals: torch.Tensor, pooled: torch.Tensor = None) -> torch.Tensor:
         return ops.mix(signals, self.channel_matrix(signals, pooled), self.seq[1].bias)

@@ -1656,9 +1656,16 @@ class _ChannelAttentionMixFunction(torch.autograd.Function):
         return dp, dWc, dconv
 
 
+def channel_attention_fused(C: int, cb: int, T: int) -> bool:
+    """Whether `channel_attention_mix` has its one-launch kernels for these sizes in BOTH directions (the backward keeps
+    more in LDS than the forward: include/msgat_hip.h, msgat_channel_attention_fused); else use `channel_matrix`."""
+    return bool(_lib.lib().msgat_channel_attention_fused(int(C), int(cb), int(T)))
+
+
 def channel_attention_mix(pooled: torch.Tensor, Wc: torch.Tensor, conv: torch.Tensor) -> torch.Tensor:
     """The per-sample channel matrix of CACN: conv @ softmax(pooled Wc pooled^T)  ([G,cb,C]).  pooled [G,C,T] (node-weighted
-    sums, `node_pool`), Wc [T,T] or [R,T,T], conv [cb,C] or [R,cb,C] with R dividing G."""
+    sums, `node_pool`), Wc [T,T] or [R,T,T], conv [cb,C] or [R,cb,C] with R dividing G.  Sizes whose backward has no
+    kernel (`channel_attention_fused`) are refused here, under autograd, not in the middle of `backward()`."""
     _require_device_tensor("pooled signals", pooled)
     _require_device_tensor("Wc", Wc, pooled.device)
     _require_device_tensor("conv weight", conv, pooled.device)
@@ -1667,7 +1674,26 @@ def channel_attention_mix(pooled: torch.Tensor, Wc: torch.Tensor, conv: torch.Te
     G, Cc, T = pooled.shape
     if tuple(Wc.shape[1:]) != (T, T) or conv.dim() != 3 or conv.shape[0] != Wc.shape[0] or conv.shape[2] != Cc or G % Wc.shape[0]:
         raise ValueError(f"channel_attention_mix: pooled {tuple(pooled.shape)}, Wc {tuple(Wc.shape)}, conv {tuple(conv.shape)}")
+    if torch.is_grad_enabled() and (pooled.requires_grad or Wc.requires_grad or conv.requires_grad) and \
+            not channel_attention_fused(Cc, conv.shape[1], T):
+        raise ValueError(f"channel_attention_mix: no backward kernel for C = {Cc}, cb = {conv.shape[1]}, T = {T} "
+                         "(channel_attention_fused); channel_matrix evaluates these sizes with torch ops")
     return _ChannelAttentionMixFunction.apply(pooled, Wc, conv)
+
+
+def channel_matrix(pooled: torch.Tensor, Wc: torch.Tensor, conv: torch.Tensor) -> torch.Tensor:
+    """`channel_attention_mix` where its kernels hold the problem in both directions, decided from the shapes before
+    anything is launched; beyond that (wider than 114 channels at T = 12, cb = C / 3) the same chain as batched torch ops,
+    as the temporal attention does beyond its lane budget (model.TACN.first_taps).  What CACN calls, in both schedules."""
+    if Wc.dim() == 2:
+        Wc, conv = Wc.unsqueeze(0), conv.unsqueeze(0)
+    G, Cc, T = pooled.shape
+    R, cb = Wc.shape[0], conv.shape[1]
+    if channel_attention_fused(Cc, cb, T):
+        return channel_attention_mix(pooled, Wc, conv)
+    per_r = pooled.reshape(R, G // R, Cc, T)
+    att = torch.softmax(per_r @ Wc.unsqueeze(1) @ per_r.transpose(2, 3), dim=-1)       # [R,B,C,C]
+    return (conv.unsqueeze(1) @ att).reshape(G, cb, Cc)
 
 
 class _TemporalAttentionTapsFunction(torch.autograd.Function):

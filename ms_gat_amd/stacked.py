@@ -164,9 +164,10 @@ def _meam(P, prefix: str, m0, x: torch.Tensor, adjacency, R: int, B: int, relu_i
                                                   P(prefix + "cacn.seq.0.alpha"))
 
     # CACN's per-sample channel matrix conv @ softmax(p Wc p^T) (attention.py:90-92, msgat.py:93-94): one launch
+    # (batched torch ops where the launch's backward would not fit its LDS, as model.CACN.channel_matrix)
     conv_w = P(prefix + "cacn.seq.1.weight").flatten(2)                                # [R,cb,C,1,1] -> [R,cb,C]: a view
     conv_b = P(prefix + "cacn.seq.1.bias")                                             # [R,cb]
-    Mc = ops.channel_attention_mix(pooled_c, P(prefix + "cacn.seq.0.Wc"), conv_w)
+    Mc = ops.channel_matrix(pooled_c, P(prefix + "cacn.seq.0.Wc"), conv_w)
     Wg, alpha_g, W_g = P(prefix + "gacn.gatt.Wg"), P(prefix + "gacn.gatt.alpha"), P(prefix + "gacn.W")
     alpha_t = P(prefix + "tacn.seq.0.alpha")
     d0 = m0.dilations[0] if m0.dilations else 0

@@ -8,6 +8,8 @@ import torch
 
 from conftest import record_err, rel_err
 
+from branch_edge_fixtures import channel_attention_mix_dense, temporal_attention_taps_dense
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
@@ -406,9 +408,7 @@ def test_channel_attention_mix_is_one_launch_each_way(R, Bg, C, cb, T):
     a = _leaf(p, Wc, conv)
     ours = _grads(ops.channel_attention_mix(*a), a, dM)
     p64, W64, c64 = _leaf64(p, Wc, conv)
-    pv = p64.view(R, Bg, C, T)
-    att = torch.softmax(pv @ W64.unsqueeze(1) @ pv.transpose(2, 3), dim=-1)
-    ref = (c64.unsqueeze(1) @ att).reshape(R * Bg, cb, C)
+    ref = channel_attention_mix_dense(p64, W64, c64)
     _check(ours, _grads(ref, (p64, W64, c64), dM.double()), ["Mc", "dpooled", "dWc", "dconv"])
 
 
@@ -424,11 +424,7 @@ def test_temporal_attention_taps_are_one_launch_each_way(R, Bg, N, K, T, dil):
     a = _leaf(q, W1, W2)
     ours = _grads(ops.temporal_attention_taps(*a, dil), a, dtaps)
     q64, A64, B64 = _leaf64(q, W1, W2)
-    per_t = q64.view(R, Bg, N, T).transpose(2, 3)
-    att = torch.softmax((per_t @ A64.transpose(1, 2).unsqueeze(1)) @ (per_t @ B64.transpose(1, 2).unsqueeze(1)).transpose(2, 3), dim=-1)
-    att = att.reshape(R * Bg, T, T)
-    shifted = torch.zeros_like(att) if dil >= T else torch.nn.functional.pad(att[:, : T - dil], (0, 0, dil, 0))
-    ref = torch.stack([shifted, att], dim=1)
+    ref = temporal_attention_taps_dense(q64, A64, B64, dil)
     _check(ours, _grads(ref, (q64, A64, B64), dtaps.double()), ["taps", "dpooled", "dWt1", "dWt2"])
     assert ops.causal_shift_taps(T, 2, _dev()) is ops.causal_shift_taps(T, 2, _dev())
     eye = torch.eye(T)

@@ -208,7 +208,7 @@ def test_whole_model_matches_the_dense_op_sequence(factory, cin, R, N):
     768 positions per channel slab: every width then runs its LDS-DMA one-pass backward forms (contract.hip
     MSGAT_GLDS_FORMS; below 512 positions the register-staged kernels run)."""
     from ms_gat_amd import model
-    from oracle import dense_torch
+    from branch_edge_fixtures import msgat_dense
     torch.manual_seed(7)
     T, B = 12, 3
     gen = torch.Generator().manual_seed(11)
@@ -227,17 +227,7 @@ def test_whole_model_matches_the_dense_op_sequence(factory, cin, R, N):
     # float64 restatement with the same parameters
     P = {k: v.detach().double() for k, v in net.state_dict().items()}
     leaves = {k: v.clone().requires_grad_(True) for k, v in P.items() if k != "adj"}
-    gate = (leaves["te.h_ebd.weight"][H] + leaves["te.d_ebd.weight"][D]).view(B, R, N, T)
-    out = 0
-    for r in range(R):
-        x = X[:, r].double()
-        tpc = net.tpcs[r]
-        for l, meam in enumerate(tpc.tgacns):
-            sub = {k[len(f"tpcs.{r}.tgacns.{l}."):]: v for k, v in leaves.items() if k.startswith(f"tpcs.{r}.tgacns.{l}.")}
-            x = dense_torch.meam_dense(x, P["adj"], sub, meam.dilations)
-        x = torch.nn.functional.layer_norm(x, [T], leaves[f"tpcs.{r}.ln.weight"], leaves[f"tpcs.{r}.ln.bias"], 1e-5)
-        y = torch.nn.functional.conv2d(x.transpose(1, 3), leaves[f"tpcs.{r}.fc.weight"], leaves[f"tpcs.{r}.fc.bias"])
-        out = out + y[..., 0].transpose(1, 2) * gate[:, r]
+    out = msgat_dense(leaves, P["adj"], [m.dilations for m in net.tpcs[0].tgacns], X.double(), H, D)
     assert rel_err(pred.double(), out) < TOL
     names = [n for n, p in net.named_parameters() if p.requires_grad]
     g64 = torch.autograd.grad(out, [leaves[n] for n in names], dout.double(), allow_unused=True)
