@@ -60,7 +60,8 @@ extern "C" {
  *     + msgat_gauss_{metrics,grad} and msgat_masked_gauss_{metrics,grad} (the Gauss loss in the step tail);
  *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern);
  *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends);
- *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel).
+ *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel);
+ *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -838,6 +839,41 @@ int msgat_masked_gauss_metrics(const float* pred, const float* truth, int64_t ro
                                double* sums, void* stream);
 int msgat_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid, int64_t rows,
                             int32_t T_out, float sigma, float delta, float null_value, float* dpred, void* stream);
+
+/* ---- device: quantile forecasts in the step tail (no counterpart in the reference, whose forecasts are single numbers) ----
+ * A Q-level forecast of T_out steps is a head with Q * T_out outputs: pred [rows, Q, T_out] fp32, level-major inside a
+ * row, against truth [rows, T_out], rows = B * N.  `levels` [Q] are HOST floats, strictly increasing inside (0, 1); they
+ * reach the kernels by value.  `point` in [0, Q) names the level that serves as the point forecast.  An entry of
+ * `truth` is valid exactly as in the masked tail above (not NaN and != null_value; null_value = NaN masks the NaN
+ * entries only -- there is no unmasked form).  Per valid entry and level, with u = truth - p_q in fp32:
+ *       rho_q = max(tau_q u, (tau_q - 1) u)                                                  (the pinball loss)
+ *       d rho_q / d p_q = -tau_q where truth > p_q, 1 - tau_q where truth < p_q, 1/2 - tau_q at truth == p_q
+ *                                                                   (autograd's rule for torch.maximum at a tie)
+ * msgat_quantile_metrics: one pass and a finish launch of 7 + 2Q blocks, nothing read back:
+ *       valid[0] = the number of valid entries,  loss[0] = sum_valid (1/Q) sum_q rho_q / max(valid, 1)        (fp32)
+ *       sums [T_out + 1, 7 + 2Q] fp64 running totals (the caller zeroes them per epoch; may be NULL); row t < T_out holds
+ *       horizon t, row T_out all horizons added in horizon order.  Columns:
+ *           0-3         {valid count, sum |e|, 100 sum_{truth > mask_value} |e / truth|, sum e^2},  e = p_point - truth
+ *           4           sum of (1/Q) sum_q rho_q            (the loss column, where the masked layout has it)
+ *           5           the number of valid entries with any p_q > p_{q+1}                         (crossing)
+ *           6           sum of p_{Q-1} - p_0                                  (width of the outermost interval)
+ *           7 + q       the number of valid entries with truth <= p_q                                   (hits)
+ *           7 + Q + q   sum of rho_q
+ *     A batch without a valid entry gives loss 0 and valid 0; so does rows = 0 (MSGAT_OK, nothing else is written).
+ *     `partials`: msgat_quantile_partial_doubles(rows, T_out, Q) doubles.  Fixed summation order as in the masked tail,
+ *     no floating-point atomics: bitwise reproducible.
+ * msgat_quantile_grad: dpred[r,q,t] = c_q * (dloss[0] / max(valid[0], 1)) at the valid entries, c_q the slope above
+ *     divided by Q -- formed in double, one value per level and sign case, rounded to fp32 once -- and exactly +0 at
+ *     every other entry.  valid[0] is read from device memory, so a captured launch follows the batch of every replay.
+ * Limits, checked before any launch: 1 <= Q <= 8, 1 <= T_out, Q * T_out <= 64, rows * T_out <= 2^24
+ * (MSGAT_ERR_UNSUPPORTED otherwise); levels not increasing or outside (0, 1), NaN included, point outside [0, Q) and
+ * rows < 0: MSGAT_ERR_SHAPE. */
+size_t msgat_quantile_partial_doubles(int64_t rows, int32_t T_out, int32_t Q);
+int msgat_quantile_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, int32_t Q,
+                           const float* levels, int32_t point, float null_value, float mask_value, double* partials,
+                           float* loss, float* valid, double* sums, void* stream);
+int msgat_quantile_grad(const float* pred, const float* truth, const float* dloss, const float* valid, int64_t rows,
+                        int32_t T_out, int32_t Q, const float* levels, float null_value, float* dpred, void* stream);
 
 /* ---- device: the guard on the optimizer step (off unless a caller uses msgat_grad_guard and msgat_adam_step_guarded) ----
  * The reference trains under GradScaler (engine.py:61-63), whose step() leaves the update out when a gradient is Inf or

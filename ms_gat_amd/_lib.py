@@ -187,6 +187,11 @@ _PROTOTYPES = {
                                    + [C.c_void_p] * 5),
     "msgat_masked_gauss_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float,
                                                             C.c_void_p, C.c_void_p]),
+    "msgat_quantile_partial_doubles": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "msgat_quantile_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_float_p, C.c_int32,
+                                         C.c_float, C.c_float] + [C.c_void_p] * 5),
+    "msgat_quantile_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, c_float_p, C.c_float, C.c_void_p,
+                                                        C.c_void_p]),
     "msgat_window_gather": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                                          C.c_void_p]),
     "msgat_window_gather_imputed": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32,

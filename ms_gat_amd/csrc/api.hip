@@ -1236,6 +1236,40 @@ extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int6
                                   (hipStream_t)stream);
 }
 
+// ---- quantile forecasts in the step tail: pinball loss, point metrics, coverage / width / crossing sums ----------------
+// limits first (they bound the loop over `levels`), then the levels themselves; nothing is launched on a refusal
+static int check_quantile(int64_t rows, int32_t T_out, int32_t Q, const float* levels) {
+  if (rows < 0) return MSGAT_ERR_SHAPE;
+  if (Q < 1 || Q > 8 || T_out < 1 || Q * (int64_t)T_out > 64 || rows > kMaskedMaxEntries / T_out) return MSGAT_ERR_UNSUPPORTED;
+  for (int q = 0; q < Q; ++q) {   // strictly increasing inside (0, 1); a NaN fails its comparison
+    if (!(levels[q] > (q == 0 ? 0.f : levels[q - 1]) && levels[q] < 1.f)) return MSGAT_ERR_SHAPE;
+  }
+  return MSGAT_OK;
+}
+
+extern "C" size_t msgat_quantile_partial_doubles(int64_t rows, int32_t T_out, int32_t Q) {
+  if (rows <= 0 || Q < 1 || Q > 8 || T_out < 1 || Q * (int64_t)T_out > 64 || rows > kMaskedMaxEntries / T_out) return 0;
+  return quantile_partial_doubles(rows, T_out, Q);
+}
+
+extern "C" int msgat_quantile_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, int32_t Q,
+                                      const float* levels, int32_t point, float null_value, float mask_value,
+                                      double* partials, float* loss, float* valid, double* sums, void* stream) {
+  if (!pred || !truth || !levels || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_quantile(rows, T_out, Q, levels)) return st;
+  if (point < 0 || point >= Q) return MSGAT_ERR_SHAPE;
+  return launch_quantile_metrics(pred, truth, rows, T_out, Q, levels, point, null_value, mask_value, partials, loss, valid,
+                                 sums, (hipStream_t)stream);
+}
+
+extern "C" int msgat_quantile_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
+                                   int64_t rows, int32_t T_out, int32_t Q, const float* levels, float null_value,
+                                   float* dpred, void* stream) {
+  if (!pred || !truth || !dloss || !valid || !levels || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_quantile(rows, T_out, Q, levels)) return st;
+  return launch_quantile_grad(pred, truth, dloss, valid, rows, T_out, Q, levels, null_value, dpred, (hipStream_t)stream);
+}
+
 // ---- the tiny attention matrices of a MEAM block ----------------------------------------------------------------
 static int check_small(int32_t G, int32_t R, int32_t T) {
   if (G <= 0 || R <= 0 || G % R) return MSGAT_ERR_SHAPE;

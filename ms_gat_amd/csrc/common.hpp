@@ -543,5 +543,12 @@ int launch_masked_gauss_grad(const float* pred, const float* truth, const float*
                              hipStream_t s);
 int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                              const float* scale, float* flat, long long weight_index, hipStream_t s);
+// quantile forecasts: pred [rows, Q, T], truth [rows, T], levels [Q] on the host (checked by the caller)
+size_t quantile_partial_doubles(long long rows, int T, int Q);
+int launch_quantile_metrics(const float* pred, const float* truth, long long rows, int T, int Q, const float* levels,
+                            int point, float null_value, float mask_value, double* part, float* loss, float* valid,
+                            double* sums, hipStream_t s);
+int launch_quantile_grad(const float* pred, const float* truth, const float* dloss, const float* valid, long long rows,
+                         int T, int Q, const float* levels, float null_value, float* dpred, hipStream_t s);
 
 }  // namespace msgat

@@ -630,6 +630,198 @@ int launch_masked_gauss_grad(const float* pred, const float* truth, const float*
   return launch_masked_loss_grad(pred, truth, dloss, valid, rows, T, gauss_of(sigma, delta), null_value, dpred, s);
 }
 
+// ---- quantile forecasts: pinball loss, point metrics at one level, coverage / width / crossing sums ----------------------
+// pred [rows, Q, T] (level-major inside a row: the lanes of a horizon group read consecutive addresses for every level),
+// truth [rows, T]; validity is entry_valid of the masked tail.  Per valid entry and level, u = y - p_q in fp32:
+//   rho_q = max(tau_q u, (tau_q - 1) u);  d rho_q / d p_q = -tau_q (y > p_q), 1 - tau_q (y < p_q), 1/2 - tau_q at a tie
+//   (autograd's rule for torch.maximum).  tau_q - 1 and the three slopes over Q are formed in double on the host and
+//   rounded to fp32 once; they travel by value (QuantLevels / QuantSlopes), like the policies above.
+// Columns of a record and of sums [T + 1, 7 + 2Q]:
+//   0-3 the masked tail's {count, |e|, 100 |e / y| (y > mask), e^2} with e = p_point - y;  4 sum of (1/Q) sum_q rho_q;
+//   5 entries with any p_q > p_{q+1};  6 sum of p_{Q-1} - p_0;  7 + q entries with y <= p_q;  7 + Q + q sum of rho_q.
+//   k_quantile_metrics<Q>    k_masked_loss_metrics' walk (a lane keeps ONE horizon, its 7 + 2Q sums stay in registers in
+//                            double -- Q is a template parameter so that they ARE registers) and its hand-over: one
+//                            [7 + 2Q][256] LDS image (26 KB at Q = 3, 46 KB at Q = 8: under the 64 KB static limit, and
+//                            with at most 512 blocks of this launch on 256 CUs no limit on residency), ONE barrier, the
+//                            lanes of a horizon added in lane order, part[(c T + h) nblocks + b].
+//   k_quantile_finish        k_masked_loss_finish with the column count as an argument: block c adds column c, the block of
+//                            column 4 adds the count column too and writes loss and valid.
+// One fixed order for every sum, no floating-point atomics: bitwise reproducible.
+constexpr int kQuantMaxQ = 8;
+constexpr int kQuantBase = 7;   // the columns in front of the per-level ones
+constexpr int kQuantLossCol = 4;
+
+struct QuantLevels { float tau[kQuantMaxQ], tau_m1[kQuantMaxQ]; };
+struct QuantSlopes { float above[kQuantMaxQ], below[kQuantMaxQ], tie[kQuantMaxQ]; };   // y > p_q, y < p_q, y == p_q
+
+template <int Q>
+__global__ __launch_bounds__(kTailBlock) void k_quantile_metrics(const float* __restrict__ pred,
+                                                                 const float* __restrict__ truth, int n, int T, int lanes,
+                                                                 QuantLevels lv, int point, float null_value,
+                                                                 float mask_value, double* __restrict__ part) {
+  constexpr int kCols = kQuantBase + 2 * Q;
+  __shared__ double red[kCols][kTailBlock];
+  double s[kCols];
+#pragma unroll
+  for (int c = 0; c < kCols; ++c) s[c] = 0.0;
+  if ((int)threadIdx.x < lanes) {   // lanes % T == 0: i mod T == threadIdx.x mod T on every trip
+    const int t = (int)threadIdx.x % T;
+    const int stride = (int)gridDim.x * lanes;
+    for (int i = (int)blockIdx.x * lanes + (int)threadIdx.x; i < n; i += stride) {   // n <= 2^24
+      const float y = truth[i];
+      const float* __restrict__ pr = pred + (size_t)(i / T) * (size_t)(Q * T) + t;
+      float p[Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) p[q] = pr[q * T];
+      if (!entry_valid(y, null_value)) continue;
+      float pp = p[0];
+#pragma unroll
+      for (int q = 1; q < Q; ++q) pp = q == point ? p[q] : pp;   // a select per level: p[] stays in registers
+      const float e = pp - y, a = fabsf(e);
+      s[0] += 1.0;
+      s[1] += a;
+      if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
+      s[3] += (double)e * (double)e;
+      double total = 0.0;
+      bool crossing = false;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const float u = y - p[q];
+        const float rho = fmaxf(lv.tau[q] * u, lv.tau_m1[q] * u);
+        total += (double)rho;
+        s[kQuantBase + Q + q] += (double)rho;
+        if (y <= p[q]) s[kQuantBase + q] += 1.0;
+        if (q + 1 < Q) crossing = crossing || p[q] > p[q + 1];
+      }
+      s[kQuantLossCol] += total * (1.0 / Q);
+      if (crossing) s[5] += 1.0;
+      s[6] += (double)(p[Q - 1] - p[0]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kCols; ++c) red[c][threadIdx.x] = s[c];
+  __syncthreads();
+  for (int o = threadIdx.x; o < kCols * T; o += kTailBlock) {
+    const int c = o / T, h = o - c * T;
+    double t = 0.0;
+    for (int j = h; j < lanes; j += T) t += red[c][j];
+    part[(size_t)o * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(kMaskFinishBlock) void k_quantile_finish(const double* __restrict__ part, int nblocks, int T,
+                                                                      int cols, float* __restrict__ loss,
+                                                                      float* __restrict__ valid,
+                                                                      double* __restrict__ sums) {
+  __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (loss block)
+  const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool is_loss = c == kQuantLossCol;
+  for (int q = 0; q < (is_loss ? 2 : 1); ++q) {
+    const int col = q == 0 ? c : 0;
+    for (int h = wave; h < T; h += kMaskFinishBlock / 64) {
+      const double* __restrict__ p = part + (size_t)(col * T + h) * nblocks;
+      double t = 0.0;
+      for (int b = lane; b < nblocks; b += 64) t += p[b];
+      t = wave_sum(t);
+      if (lane == 0) rows[q][h] = t;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < T && sums != nullptr) sums[(size_t)threadIdx.x * cols + c] += rows[0][threadIdx.x];
+  if (threadIdx.x != 0) return;
+  double total = 0.0, count = 0.0;
+  for (int h = 0; h < T; ++h) total += rows[0][h];
+  if (sums != nullptr) sums[(size_t)T * cols + c] += total;
+  if (!is_loss) return;
+  for (int h = 0; h < T; ++h) count += rows[1][h];
+  valid[0] = (float)count;
+  loss[0] = (float)(total / fmax(count, 1.0));
+}
+
+// dpred[r,q,t] = c_q (dloss[0] / max(valid[0], 1)) at the valid entries, c_q the slope of its sign case over Q; +0
+// elsewhere (a NaN of the truth fails both comparisons and ends in the select).  A lane takes one (r, t) and its Q levels.
+__global__ __launch_bounds__(kTailBlock) void k_quantile_grad(const float* __restrict__ pred,
+                                                              const float* __restrict__ truth,
+                                                              const float* __restrict__ dloss,
+                                                              const float* __restrict__ valid, int n, int T, int Q,
+                                                              QuantSlopes sl, float null_value,
+                                                              float* __restrict__ dpred) {
+  const int i = (int)blockIdx.x * kTailBlock + (int)threadIdx.x;
+  if (i >= n) return;
+  const float y = truth[i];
+  const int r = i / T;
+  const size_t base = (size_t)r * (size_t)(Q * T) + (size_t)(i - r * T);
+  const bool ok = entry_valid(y, null_value);
+  const float scale = dloss[0] / fmaxf(valid[0], 1.f);
+#pragma unroll
+  for (int q = 0; q < kQuantMaxQ; ++q) {
+    if (q >= Q) break;   // kernel-uniform; unrolled, so the slopes are read at constant offsets of the argument
+    const float p = pred[base + (size_t)q * T];
+    const float c = y > p ? sl.above[q] : (y < p ? sl.below[q] : sl.tie[q]);
+    dpred[base + (size_t)q * T] = ok ? c * scale : 0.f;
+  }
+}
+
+size_t quantile_partial_doubles(long long rows, int T, int Q) {
+  return (size_t)masked_huber_blocks(rows * T, T) * (size_t)(kQuantBase + 2 * Q) * T;
+}
+
+template <int Q>
+static void launch_quantile_metrics_q(const float* pred, const float* truth, int n, int T, const QuantLevels& lv, int point,
+                                      float null_value, float mask_value, double* part, int nb, hipStream_t s) {
+  hipLaunchKernelGGL(k_quantile_metrics<Q>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T, masked_huber_lanes(T), lv,
+                     point, null_value, mask_value, part);
+}
+
+int launch_quantile_metrics(const float* pred, const float* truth, long long rows, int T, int Q, const float* levels,
+                            int point, float null_value, float mask_value, double* part, float* loss, float* valid,
+                            double* sums, hipStream_t s) {
+  if (rows == 0) {   // nothing to walk: loss 0 and valid 0 (the bits of +0.f), the totals as they were
+    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(valid, 0, sizeof(float), s);
+    return e == hipSuccess ? MSGAT_OK : MSGAT_ERR_HIP_BASE - (int)e;
+  }
+  QuantLevels lv = {};
+  for (int q = 0; q < Q; ++q) {
+    lv.tau[q] = levels[q];
+    lv.tau_m1[q] = (float)((double)levels[q] - 1.0);
+  }
+  const int n = (int)(rows * T), nb = masked_huber_blocks(n, T);
+  switch (Q) {
+    case 1: launch_quantile_metrics_q<1>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 2: launch_quantile_metrics_q<2>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 3: launch_quantile_metrics_q<3>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 4: launch_quantile_metrics_q<4>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 5: launch_quantile_metrics_q<5>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 6: launch_quantile_metrics_q<6>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 7: launch_quantile_metrics_q<7>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    case 8: launch_quantile_metrics_q<8>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
+    default: return MSGAT_ERR_UNSUPPORTED;
+  }
+  MSGAT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_quantile_finish, dim3(kQuantBase + 2 * Q), dim3(kMaskFinishBlock), 0, s, part, nb, T,
+                     kQuantBase + 2 * Q, loss, valid, sums);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+int launch_quantile_grad(const float* pred, const float* truth, const float* dloss, const float* valid, long long rows,
+                         int T, int Q, const float* levels, float null_value, float* dpred, hipStream_t s) {
+  if (rows == 0) return MSGAT_OK;
+  QuantSlopes sl = {};
+  for (int q = 0; q < Q; ++q) {
+    const double tau = (double)levels[q];
+    sl.above[q] = (float)(-tau / Q);
+    sl.below[q] = (float)((1.0 - tau) / Q);
+    sl.tie[q] = (float)((0.5 - tau) / Q);
+  }
+  const int n = (int)(rows * T);
+  hipLaunchKernelGGL(k_quantile_grad, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s, pred,
+                     truth, dloss, valid, n, T, Q, sl, null_value, dpred);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
 // k_gather_scaled with the scale read from device memory: the rank's weight of a masked step is its batch's valid
 // count, which only the device knows
 __global__ __launch_bounds__(kTailBlock) void k_gather_scaled_dev(const float* const* __restrict__ chunk_src,

@@ -20,6 +20,9 @@ Differences that are the point of this build:
     (`ops.masked_huber_metrics`; the batch's valid count stays on the device, also as the rank's weight).
   * `loss=GaussLoss(sigma, delta)` (off by default: Huber) trains and evaluates with the reference's other loss, in the same
     library tail -- one pass with metrics, masked or not, the valid count on the device, captured steps.
+  * `loss=QuantileLoss(quantiles)` trains a quantile forecast -- a head of `Q * T_out` outputs against `T_out`-step truths --
+    with the pinball loss in the same tail (`ops.quantile_metrics`): the point metrics from the level nearest 0.5, and per
+    horizon what makes such a forecast checkable, coverage per level, interval width, crossing rate (`last_stats["quantiles"]`).
   * `max_grad_norm` / `skip_nonfinite` (both off by default) put a guard on the optimizer step: the global gradient norm is
     taken on the device, the gradient is clipped to `max_grad_norm` as `torch.nn.utils.clip_grad_norm_` would, and a step
     whose norm is Inf or NaN is left out whole, as the reference's `GradScaler.step` leaves it out (engine.py:61-63) --
@@ -90,6 +93,31 @@ def masked_gauss_loss(output: torch.Tensor, target: torch.Tensor, sigma: float, 
     return torch.where(valid, gauss_entry(err, sigma, delta), zero).sum() / valid.sum().clamp(min=1)
 
 
+def quantile_entries(output: torch.Tensor, target: torch.Tensor, levels, null_value: Optional[float]):
+    """-> (p [..., Q, T_out], y [..., 1, T_out] with 0 at the entries that are not valid, valid [..., T_out],
+    rho [..., Q, T_out]): the pinball loss max(tau_q u, (tau_q - 1) u), u = y - p_q, of every level at every valid entry
+    and 0 elsewhere.  `output` is [..., Q * T_out], level-major (or [..., Q, T_out])."""
+    from . import ops
+    t_out = ops.quantile_widths(output, target, len(levels))
+    p = output.reshape(*target.shape[:-1], len(levels), t_out)
+    valid = valid_entries(target, float("nan") if null_value is None else null_value)
+    zero = torch.zeros((), dtype=output.dtype, device=output.device)
+    y = torch.where(valid, target.to(output.dtype), zero).unsqueeze(-2)
+    tau = torch.tensor(levels, dtype=output.dtype, device=output.device).reshape(-1, 1)
+    u = y - p
+    rho = torch.where(valid.unsqueeze(-2), torch.maximum(tau * u, (tau - 1) * u), zero)
+    return p, y, valid, rho
+
+
+def quantile_loss(output: torch.Tensor, target: torch.Tensor, levels, null_value: Optional[float] = None) -> torch.Tensor:
+    """Pinball loss averaged over the Q levels, summed over the valid entries of `target` and divided by max(valid count,
+    1): 0 for a batch without a valid entry.  Its autograd is the rule the kernels state: -tau_q / 1 - tau_q either side
+    of p_q and, `torch.maximum` splitting a tie evenly, 1/2 - tau_q at y == p_q.  The torch restatement of
+    `ops.quantile_metrics` (what CPU tensors run)."""
+    _, _, valid, rho = quantile_entries(output, target, levels, null_value)
+    return rho.sum() / (len(levels) * valid.sum().clamp(min=1))
+
+
 class HuberLoss(nn.Module):
     """Mean Huber loss.  `null_value` (default None: every entry counts, the reference's loss) drops the entries of the
     target that are NaN or equal to it from the sum AND from the divisor."""
@@ -149,6 +177,45 @@ class GaussLoss(nn.Module):
         return ops.gauss_metrics(pred, truth, self.sigma, self.delta, mask_value, sums, loss_weight)
 
 
+class QuantileLoss(nn.Module):
+    """Pinball loss of a quantile forecast: the model's `Q * T_out` outputs per node are, level-major, the `quantiles`
+    of the next `T_out` steps (`out_timesteps = Q * T_out`), compared with ONE truth per step.  `levels` are the
+    quantiles, `point` the index of the level nearest 0.5 (the lower one on a tie): the level whose forecast feeds MAE /
+    MAPE / RMSE.  Entries of the target that are NaN or equal to `null_value` (None: NaN only) drop out, as in the masked
+    forms of the other two losses -- there is no unmasked form.  On device tensors it is `ops.quantile_metrics`."""
+
+    def __init__(self, quantiles=(0.1, 0.5, 0.9), null_value: Optional[float] = None):
+        super().__init__()
+        from . import ops
+        self.levels = ops.quantile_levels(quantiles)      # ValueError for what the kernels refuse
+        self.point = ops.quantile_point(self.levels)
+        self.null_value = null_value
+
+    def split(self, pred: torch.Tensor) -> torch.Tensor:
+        """[B, N, Q * T_out] -> [B, N, Q, T_out] (a view where `pred` allows one)."""
+        q = len(self.levels)
+        if pred.dim() == 0 or pred.shape[-1] % q:
+            raise ValueError(f"{tuple(pred.shape)}: the last axis must hold {q} levels times T_out steps")
+        return pred.reshape(*pred.shape[:-1], q, pred.shape[-1] // q)
+
+    def point_forecast(self, pred: torch.Tensor) -> torch.Tensor:
+        """[B, N, Q * T_out] -> [B, N, T_out]: the forecast of level `point`."""
+        return self.split(pred)[..., self.point, :]
+
+    def forward(self, output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if output.is_cuda:
+            return self.fused(output, target, 0.0, None)
+        return quantile_loss(output, target, self.levels, self.null_value)
+
+    def extra_repr(self) -> str:
+        return f"quantiles={self.levels}"
+
+    def fused(self, pred, truth, mask_value, sums, loss_weight=1.0, valid=None) -> torch.Tensor:
+        """The library's one pass (`loss_weight` is not used: a rank's weight is its valid count, as in every masked form)."""
+        from . import ops
+        return ops.quantile_metrics(pred, truth, self.levels, self.null_value, mask_value, sums, valid, self.point)
+
+
 class Metrics:
     """Running MAE / MAPE / RMSE with the reference's definitions (metrics.py:11-38): MAPE sums
     |err/y| over entries with y > mask_value but divides by ALL entries, like the reference.
@@ -165,10 +232,19 @@ class Metrics:
     buffer, and `loss` is the epoch's total loss sum over its total valid count -- a ratio of totals, the same number
     for any number of ranks and any sharding of the batches, which a mean of per-batch means is not once the batches'
     valid counts differ.  `per_horizon()` / `at(steps)` give the metrics per horizon; a Metrics that was told its loss
-    (`loss_fn`, here or in `update`) also gives a "loss" list there, column 4 over the valid count."""
+    (`loss_fn`, here or in `update`) also gives a "loss" list there, column 4 over the valid count.
+
+    With a `QuantileLoss` as `loss_fn` (given HERE: it sizes the buffer) the totals are always per horizon
+    (`null_value=None` runs as NaN) and the buffer is [T_out + 1, 7 + 2Q], the layout `ops.quantile_metrics` adds to:
+    columns 0-4 as above with e = p_point - y and the pinball loss averaged over the levels, 5 the number of entries whose
+    levels cross (any p_q > p_{q+1}), 6 the sum of p_{Q-1} - p_0, 7 + q the number of entries with y <= p_q and
+    7 + Q + q the sum of level q's pinball loss.  `per_horizon()` then also has "coverage" and "pinball" (Q lists of length
+    T_out) and "crossing" and "width" (lists); `quantile_summary()` gives the same over all horizons."""
 
     def __init__(self, mask_value: float = 0.0, null_value: Optional[float] = None, loss_fn: Optional[nn.Module] = None):
         self.mask_value = mask_value
+        if isinstance(loss_fn, QuantileLoss) and null_value is None:
+            null_value = float("nan") if loss_fn.null_value is None else loss_fn.null_value
         self.null_value = null_value
         self.loss_fn = loss_fn
         self.n = 0
@@ -187,13 +263,20 @@ class Metrics:
             if self._sums is None:
                 if t_out is None:
                     raise ValueError("Metrics(null_value=...): the first totals() call needs t_out")
-                self._sums = torch.zeros(int(t_out) + 1, 5, device=device, dtype=torch.float64)
+                self._sums = torch.zeros(int(t_out) + 1, self._columns(), device=device, dtype=torch.float64)
             elif t_out is not None and self._sums.shape[0] != int(t_out) + 1:
                 raise ValueError(f"Metrics holds totals for {self._sums.shape[0] - 1} horizons, got a batch with {t_out}")
             return self._sums
         if self._sums is None:
             self._sums = torch.zeros(4, device=device, dtype=torch.float64)
         return self._sums
+
+    def _quantile(self) -> Optional["QuantileLoss"]:
+        return self.loss_fn if isinstance(self.loss_fn, QuantileLoss) else None
+
+    def _columns(self) -> int:
+        ql = self._quantile()
+        return 5 if ql is None else 7 + 2 * len(ql.levels)
 
     def count(self, y_true: torch.Tensor) -> None:
         """A batch whose sums went into `totals` inside the fused loss kernel."""
@@ -209,6 +292,13 @@ class Metrics:
         them the column, and with it `loss`, stays 0)."""
         if loss_fn is not None:
             self.loss_fn = loss_fn
+            if isinstance(loss_fn, QuantileLoss) and self.null_value is None and self._sums is None:
+                self.null_value = float("nan") if loss_fn.null_value is None else loss_fn.null_value
+        if self._quantile() is not None:
+            self._update_quantile(y_pred, y_true, self.loss_fn)
+            if count:
+                self.count(y_true)
+            return
         if self.null_value is not None:
             self._update_masked(y_pred, y_true, delta, self.loss_fn)
             if count:
@@ -245,6 +335,26 @@ class Metrics:
         sums[:t_out].add_(rows)
         sums[t_out].add_(rows.sum(0))
 
+    def _update_quantile(self, y_pred: torch.Tensor, y_true: torch.Tensor, loss_fn: "QuantileLoss") -> None:
+        """What `ops.quantile_metrics` adds to the buffer, in float64 torch ops."""
+        p, y, valid, rho = quantile_entries(y_pred.detach().double(), y_true.double(), loss_fn.levels, self.null_value)
+        t_out, q = y_true.shape[-1], len(loss_fn.levels)
+        p, y, rho = p.reshape(-1, q, t_out), y.reshape(-1, 1, t_out), rho.reshape(-1, q, t_out)
+        valid = valid.reshape(-1, t_out)
+        zero = torch.zeros_like(y[:, 0])
+        err = torch.where(valid, p[:, loss_fn.point] - y[:, 0], zero)
+        mask = valid & (y[:, 0] > self.mask_value)
+        ape = torch.where(mask, (err / torch.where(mask, y[:, 0], torch.ones_like(zero))).abs(), zero)
+        crossing = valid & (p[:, :-1] > p[:, 1:]).any(dim=1)
+        width = torch.where(valid, p[:, -1] - p[:, 0], zero)
+        hits = valid.unsqueeze(1) & (y <= p)
+        cols = [valid.double().sum(0), err.abs().sum(0), 100.0 * ape.sum(0), (err * err).sum(0), rho.sum((0, 1)) / q,
+                crossing.double().sum(0), width.sum(0), *hits.double().sum(0), *rho.sum(0)]
+        rows = torch.stack(cols, dim=1)
+        sums = self.totals(y_pred.device, t_out)
+        sums[:t_out].add_(rows)
+        sums[t_out].add_(rows.sum(0))
+
     def _get(self, i: int) -> float:
         return 0.0 if self._sums is None else float(self._sums[i].item())
 
@@ -261,14 +371,42 @@ class Metrics:
         if self.null_value is None:
             raise ValueError("per-horizon metrics need Metrics(null_value=...): the unmasked totals are kept over all horizons")
         named = {} if self.loss_fn is None else {"loss": []}
+        ql = self._quantile()
+        if ql is not None:
+            named.update(coverage=[[] for _ in ql.levels], pinball=[[] for _ in ql.levels], crossing=[], width=[])
         if self._sums is None:
             return {"MAE": [], "MAPE": [], "RMSE": [], "valid": [], **named}
         rows = self._sums[:-1].cpu()
         n = rows[:, 0].clamp(min=1.0)
         if named:
             named["loss"] = (rows[:, 4] / n).tolist()
+        if ql is not None:
+            named.update(self._quantile_columns(rows, n, len(ql.levels)))
         return {"MAE": (rows[:, 1] / n).tolist(), "MAPE": (rows[:, 2] / n).tolist(),
                 "RMSE": (rows[:, 3] / n).sqrt().tolist(), "valid": rows[:, 0].tolist(), **named}
+
+    @staticmethod
+    def _quantile_columns(rows: torch.Tensor, n: torch.Tensor, q: int) -> dict:
+        """Coverage (hits over the valid count) and mean pinball loss per level, crossing rate and mean width of the rows
+        of a quantile totals buffer: [Q][len(rows)] and [len(rows)] lists."""
+        return {"coverage": (rows[:, 7:7 + q] / n[:, None]).t().tolist(),
+                "pinball": (rows[:, 7 + q:7 + 2 * q] / n[:, None]).t().tolist(),
+                "crossing": (rows[:, 5] / n).tolist(), "width": (rows[:, 6] / n).tolist()}
+
+    def quantile_summary(self) -> dict:
+        """Over all horizons: {"levels", "coverage" (per level, the share of valid entries with y <= p_q: a calibrated
+        forecast has coverage = level), "pinball" (per level), "crossing" (share of entries whose levels cross), "width"
+        (mean p_{Q-1} - p_0)}.  Needs a `QuantileLoss` as `loss_fn`."""
+        ql = self._quantile()
+        if ql is None:
+            raise ValueError("quantile_summary() needs Metrics(loss_fn=QuantileLoss(...))")
+        q = len(ql.levels)
+        if self._sums is None:
+            return {"levels": list(ql.levels), "coverage": [0.0] * q, "pinball": [0.0] * q, "crossing": 0.0, "width": 0.0}
+        last = self._sums[-1:].cpu()
+        got = self._quantile_columns(last, last[:, 0].clamp(min=1.0), q)
+        return {"levels": list(ql.levels), "coverage": [c[0] for c in got["coverage"]],
+                "pinball": [c[0] for c in got["pinball"]], "crossing": got["crossing"][0], "width": got["width"][0]}
 
     def at(self, steps) -> Dict[str, List[float]]:
         """`per_horizon()` at the 1-based horizon steps `steps`, e.g. `at([3, 6, 12])`."""
@@ -277,7 +415,8 @@ class Metrics:
         for step in steps:
             if not 1 <= int(step) <= t_out:
                 raise IndexError(f"horizon step {step} outside 1..{t_out}")
-        return {k: [v[int(step) - 1] for step in steps] for k, v in every.items()}
+        pick = lambda v: [v[int(step) - 1] for step in steps]  # noqa: E731
+        return {k: [pick(level) for level in v] if k in ("coverage", "pinball") else pick(v) for k, v in every.items()}
 
     def all_reduce(self) -> None:
         if self.null_value is not None:
@@ -699,9 +838,9 @@ class Engine:
         self._loss_given = loss is not None     # then the per-horizon statistics carry the loss too
         if loss is None:
             loss = HuberLoss(loss_delta, null_value)
-        elif not isinstance(loss, (HuberLoss, GaussLoss)):
-            raise TypeError(f"loss must be a HuberLoss or a GaussLoss (the fused step tail runs the losses it knows), "
-                            f"not {type(loss).__name__}")
+        elif not isinstance(loss, (HuberLoss, GaussLoss, QuantileLoss)):
+            raise TypeError(f"loss must be a HuberLoss, a GaussLoss or a QuantileLoss (the fused step tail runs the losses "
+                            f"it knows), not {type(loss).__name__}")
         else:
             theirs = loss.null_value
             if null_value is not None and theirs is not None and not (
@@ -709,6 +848,8 @@ class Engine:
                 raise ValueError(f"null_value = {null_value!r} but the loss was built with null_value = {theirs!r}")
             null_value = theirs if null_value is None else null_value
             loss.null_value = null_value         # one switch: the engine's, or the loss's own where the engine got none
+            if isinstance(loss, QuantileLoss) and null_value is None:
+                null_value = float("nan")        # a quantile forecast has the masked tail only: NaN masks the NaN entries
         self.null_value = null_value     # None: every entry of the truth counts (the reference's loss and metrics)
         self._valid_count = None         # [1] fp32: the valid count of the last batch (device memory on the GPU)
         self.loss_fn, self.out_dir = loss, Path(out_dir)
@@ -746,9 +887,12 @@ class Engine:
         With `null_value` set: the masked loss and the per-horizon totals; the batch's valid count stays in
         `_valid_count` (one buffer for every step, so captured kernels and the rank weight of a replay find it)."""
         mask_value = 0.0 if metrics is None else metrics.mask_value
+        if isinstance(self.loss_fn, QuantileLoss):
+            from . import ops
+            ops.quantile_widths(pred, truth, len(self.loss_fn.levels))      # ValueError that names both sizes
         if self.null_value is not None:
             if pred.is_cuda:
-                sums = None if metrics is None else metrics.totals(pred.device, pred.shape[-1])
+                sums = None if metrics is None else metrics.totals(pred.device, truth.shape[-1])
                 return self.loss_fn.fused(pred, truth, mask_value, sums, valid=self._valid_buffer(pred.device))
             self._valid_count = valid_entries(truth, self.null_value).sum().to(torch.float32).reshape(1)
             if metrics is not None:
@@ -915,6 +1059,7 @@ class Engine:
         loss_ave = metrics.loss
         stats = {"loss": loss_ave, **metrics.todict()}
         horizons = None if self.null_value is None else metrics.per_horizon()
+        quantiles = metrics.quantile_summary() if isinstance(self.loss_fn, QuantileLoss) else None
         if rank == 0:
             if mode == "evaluate":
                 self.log_to_file(self.__labels__[mode], **stats)
@@ -923,8 +1068,14 @@ class Engine:
             if horizons is not None and mode != "train":
                 per = {k: "/".join(f"{v:.6g}" for v in horizons[k]) for k in ("MAE", "MAPE", "RMSE")}
                 self.log_to_file(self.__labels__[mode], "per horizon", **({} if mode == "evaluate" else {"epoch": epoch}), **per)
+            if quantiles is not None and mode != "train":
+                per = {k: "/".join(f"{v:.6g}" for v in quantiles[k]) for k in ("levels", "coverage", "pinball")}
+                self.log_to_file(self.__labels__[mode], "quantiles", **({} if mode == "evaluate" else {"epoch": epoch}), **per,
+                                 crossing=f"{quantiles['crossing']:.6g}", width=f"{quantiles['width']:.6g}")
         if horizons is not None:
             stats["horizons"] = horizons
+        if quantiles is not None:
+            stats["quantiles"] = quantiles
         if guarded:      # the epoch's one read of the guard state; every rank took the same decisions
             seen = self.guard_stats()
             stats["skipped_steps"] = seen["skipped_steps"] - self._skipped_reported
@@ -964,7 +1115,11 @@ class Trainer(Engine):
         `GaussLoss` instance to train with instead; `loss_delta` is then not read.  It runs in the same step tail -- one
         library pass with the metrics, masked or not, captured or not -- and takes the engine's `null_value` (or gives the
         engine its own where the engine got none; two different ones: ValueError).  `last_stats["horizons"]` then also has
-        a "loss" list.  Anything else is a TypeError: the fused tail runs the losses it knows.
+        a "loss" list.  A `QuantileLoss(quantiles)` trains a quantile forecast: the model has `out_timesteps = Q * T_out`
+        outputs against `T_out`-step truths (another width: ValueError), the totals are always per horizon (without a
+        `null_value` only NaN truths are masked, and `self.null_value` reads NaN), `last_stats["horizons"]` gains
+        "coverage", "pinball", "crossing" and "width", and `last_stats["quantiles"]` holds `Metrics.quantile_summary()`.
+        Anything else is a TypeError: the fused tail runs the losses it knows.
         `max_grad_norm`, `skip_nonfinite` (default None / False: the step as the reference's optimizer takes it): a guard on
         the optimizer step, active when either is set.  The global L2 norm of the gradient -- of the global batch's mean
         gradient under a process group -- is taken before the update; the gradient is scaled by

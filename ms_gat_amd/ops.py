@@ -1977,6 +1977,128 @@ def masked_gauss_metrics(pred: torch.Tensor, truth: torch.Tensor, sigma: float, 
     return _masked_loss_metrics("gauss", gauss_params(sigma, delta), pred, truth, null_value, mask_value, sums, valid)
 
 
+# ---- step tail: quantile forecasts (pinball loss, point metrics at one level, coverage / width / crossing sums) ------
+QUANTILE_MAX_LEVELS = 8
+QUANTILE_BASE_COLUMNS = 7     # columns of the totals in front of the per-level ones: [T_out + 1, 7 + 2Q]
+
+
+def quantile_levels(quantiles) -> tuple:
+    """The levels as floats, or ValueError: 1 to 8 of them, strictly increasing inside (0, 1) -- judged on the fp32 values
+    the kernels receive (0.99999999 is 1.0f)."""
+    try:
+        levels = tuple(float(q) for q in quantiles)
+    except TypeError:
+        raise ValueError(f"quantiles must be a sequence of numbers, not {quantiles!r}") from None
+    if not 1 <= len(levels) <= QUANTILE_MAX_LEVELS:
+        raise ValueError(f"between 1 and {QUANTILE_MAX_LEVELS} quantile levels, not {len(levels)}")
+    seen = 0.0
+    for q in levels:
+        q32 = C.c_float(q).value
+        if not (q32 > seen and q32 < 1.0):        # NaN fails both
+            raise ValueError(f"quantile levels must be strictly increasing inside (0, 1), not {levels!r}")
+        seen = q32
+    return levels
+
+
+def quantile_point(levels) -> int:
+    """The index of the level nearest 0.5 (the lower one on a tie): the level that serves as the point forecast."""
+    return min(range(len(levels)), key=lambda i: (abs(levels[i] - 0.5), i))
+
+
+def quantile_slopes(levels, dtype=torch.float32) -> torch.Tensor:
+    """[3, Q]: the slope of (1/Q) rho_q with respect to p_q where y > p_q, y < p_q and y == p_q, formed in double from the
+    fp32 levels and rounded once -- the constants `msgat_quantile_grad` multiplies with."""
+    tau = torch.tensor([C.c_float(q).value for q in levels], dtype=torch.float64)
+    n = float(len(levels))
+    return torch.stack([-tau / n, (1.0 - tau) / n, (0.5 - tau) / n]).to(dtype)
+
+
+class _QuantileMetricsFunction(torch.autograd.Function):
+    """pred [..., Q * T_out] (level-major: [..., Q, T_out]), truth [..., T_out] -> the pinball loss averaged over the levels
+    and the VALID entries of truth; adds the totals of `quantile_metrics` to `sums` and leaves the batch's valid count in
+    `valid` [1], both on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, truth, levels: tuple, point: int, null_value: float, mask_value: float, sums, valid):
+        L = _lib.lib()
+        pred_c, truth_c = pred.contiguous(), truth.contiguous()
+        t_out, n_levels = truth_c.shape[-1], len(levels)
+        rows = truth_c.numel() // t_out
+        n_part = int(L.msgat_quantile_partial_doubles(rows, t_out, n_levels))
+        part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        host_levels = (C.c_float * n_levels)(*levels)
+        st = L.msgat_quantile_metrics(_ptr(pred_c), _ptr(truth_c), rows, t_out, n_levels, host_levels, int(point),
+                                      float(null_value), float(mask_value), _ptr(part), _ptr(loss), _ptr(valid),
+                                      _ptr(sums), _stream_handle(pred.device))
+        _lib.check(st, "msgat_quantile_metrics")
+        ctx.host_levels, ctx.null_value, ctx.dims = host_levels, float(null_value), (rows, t_out, n_levels)
+        ctx.save_for_backward(pred_c, truth_c, valid)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, truth, valid = ctx.saved_tensors
+        dpred = torch.empty_like(pred)
+        rows, t_out, n_levels = ctx.dims
+        st = _lib.lib().msgat_quantile_grad(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid), rows, t_out,
+                                            n_levels, ctx.host_levels, ctx.null_value, _ptr(dpred),
+                                            _stream_handle(pred.device))
+        _lib.check(st, "msgat_quantile_grad")
+        return dpred, None, None, None, None, None, None, None
+
+
+def quantile_widths(pred: torch.Tensor, truth: torch.Tensor, n_levels: int) -> int:
+    """T_out of a quantile batch, or ValueError: pred [..., Q * T_out] (or [..., Q, T_out]) against truth [..., T_out]."""
+    t_out = truth.shape[-1] if truth.dim() else 0
+    if pred.dim() == truth.dim() + 1 and pred.dim() >= 2 and tuple(pred.shape[-2:]) == (n_levels, t_out) \
+            and pred.shape[:-2] == truth.shape[:-1]:
+        return t_out
+    if pred.dim() != truth.dim() or pred.dim() == 0 or pred.shape[:-1] != truth.shape[:-1] or pred.shape[-1] != n_levels * t_out:
+        raise ValueError(f"a forecast of {n_levels} quantile levels needs {n_levels} x {t_out} = {n_levels * t_out} outputs "
+                         f"for a target of {t_out} steps, got {pred.shape[-1] if pred.dim() else 0}: prediction "
+                         f"{tuple(pred.shape)}, target {tuple(truth.shape)}")
+    return t_out
+
+
+def quantile_metrics(pred: torch.Tensor, truth: torch.Tensor, levels, null_value: Optional[float] = None,
+                     mask_value: float = 0.0, sums: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                     point: Optional[int] = None) -> torch.Tensor:
+    """Pinball loss of a quantile forecast in one pass that also feeds the epoch's totals (`msgat_quantile_metrics`;
+    the backward is `msgat_quantile_grad`).
+
+    `pred` [..., Q * T_out] holds, level-major, the `Q = len(levels)` quantile forecasts of `truth` [..., T_out]
+    (e.g. [B, N, Q * T_out] against [B, N, T_out]; [..., Q, T_out] is accepted too); `levels` strictly increasing inside
+    (0, 1).  The loss is sum_valid (1/Q) sum_q max(tau_q u, (tau_q - 1) u), u = truth - p_q, over max(valid count, 1),
+    the valid entries being those whose truth is neither NaN nor `null_value` (None: NaN only).  `sums` (float64
+    [T_out + 1, 7 + 2Q], optional; see `engine.Metrics`) receives per horizon and over all horizons the masked tail's
+    {count, |e|, 100 |e / y| (y > mask_value), e^2} with e = p_point - y, the loss sum, the crossing count, the width sum
+    p_{Q-1} - p_0, the Q hit counts y <= p_q and the Q sums of rho_q.  `point` (default: the level nearest 0.5) names the
+    level of the point forecast.  `valid` as in `masked_huber_metrics`."""
+    levels = quantile_levels(levels)
+    n_levels = len(levels)
+    _require_device_tensor("prediction", pred)
+    _require_device_tensor("target", truth, pred.device)
+    if truth.dim() == 0 or truth.numel() == 0:
+        raise ValueError(f"target {tuple(truth.shape)} must be non-empty")
+    t_out = quantile_widths(pred, truth, n_levels)
+    if n_levels * t_out > 64:
+        raise ValueError(f"Q * T_out = {n_levels} * {t_out}: the quantile step tail supports up to 64 outputs per node")
+    point = quantile_point(levels) if point is None else int(point)
+    if not 0 <= point < n_levels:
+        raise ValueError(f"point = {point} outside the {n_levels} levels")
+    cols = QUANTILE_BASE_COLUMNS + 2 * n_levels
+    if sums is not None and (sums.dtype != torch.float64 or tuple(sums.shape) != (t_out + 1, cols) or sums.device != pred.device
+                             or not sums.is_contiguous()):
+        raise ValueError(f"sums must be a contiguous float64 [{t_out + 1}, {cols}] tensor on the prediction's device")
+    if valid is None:
+        valid = torch.empty(1, device=pred.device, dtype=torch.float32)
+    elif valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != pred.device:
+        raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
+    null_value = float("nan") if null_value is None else float(null_value)
+    return _QuantileMetricsFunction.apply(pred, truth, levels, point, null_value, mask_value, sums, valid)
+
+
 # ---- input windows of a batch from a series resident in device memory ---------------------------------------------
 def window_offsets(hours, tau: int, device) -> torch.Tensor:
     """`hours[r] * tau` as the int64 device array `window_gather` reads; a loader builds it once and passes it on."""
