@@ -602,9 +602,32 @@ __global__ __launch_bounds__(kBlock) void k_sddmm(
 // this reads dv once instead of twice: 3 slab units of HBM traffic instead of 4.  The T/4 lanes of a column leave
 // their shares of an edge's dot in LDS (lane-private entries, no atomics); after a barrier lane k adds them in a
 // fixed order and stores the chunk's partial in CSC order (k_edge_grad_csc maps it back through cperm).
+
+// The first eight edge slots of a column: sources and coefficients, two 16-byte loads each.  They depend on the
+// column's colptr entry only -- not on the slab -- so the caller asks for them ahead of the gather that reads them.
+struct EdgeWindow {
+  int b0;
+  int4u m0, m1;
+  float4u w0, w1;
+};
+__device__ __forceinline__ EdgeWindow load_edge_window(const int* __restrict__ idx, const float* __restrict__ Eg,
+                                                       int e0, int nnz) {
+  EdgeWindow w;
+  w.b0 = min(e0, nnz - 8);  // nnz >= 8 (launch condition)
+  w.m0 = *reinterpret_cast<const int4u*>(idx + w.b0);
+  w.m1 = *reinterpret_cast<const int4u*>(idx + w.b0 + 4);
+  w.w0 = *reinterpret_cast<const float4u*>(Eg + w.b0);
+  w.w1 = *reinterpret_cast<const float4u*>(Eg + w.b0 + 4);
+  return w;
+}
+
+// LDS rows in flight at a time in the gather: eight cost the second resident block its registers
+constexpr int kAgsRows = 4;
+
 template <int T4, bool FIRST>
-__device__ __forceinline__ float4 gather_row_dot(const int* __restrict__ idx, const float* __restrict__ Eg, int e0,
-                                                 int e1, int nnz, const float4* rows, int j, const float4& own,
+__device__ __forceinline__ float4 gather_row_dot(const EdgeWindow& win, const int* __restrict__ idx,
+                                                 const float* __restrict__ Eg, int e0, int e1, int nnz,
+                                                 const float4* rows, int j, const float4& own,
                                                  float* __restrict__ pd, int dummy) {
   float4 acc = f4zero();
   // branch-free: an edge slot outside the column's range multiplies by 0 and parks its dot in the lane's dummy
@@ -615,25 +638,22 @@ __device__ __forceinline__ float4 gather_row_dot(const int* __restrict__ idx, co
     const int a = valid ? k * T4 + j : dummy;
     pd[a] = FIRST ? d : pd[a] + d;
   };
-  const int b0 = min(e0, nnz - 8);  // nnz >= 8 (launch condition)
-  const int4u m0 = *reinterpret_cast<const int4u*>(idx + b0);
-  const int4u m1 = *reinterpret_cast<const int4u*>(idx + b0 + 4);
-  const float4u w0 = *reinterpret_cast<const float4u*>(Eg + b0);
-  const float4u w1 = *reinterpret_cast<const float4u*>(Eg + b0 + 4);
-  {  // four LDS rows in flight at a time: eight cost the second resident block its registers
-    float4 ra[4];
+  const int b0 = win.b0;
+  const int4u &m0 = win.m0, &m1 = win.m1;
+  const float4u &w0 = win.w0, &w1 = win.w1;
+  // in groups of kAgsRows rows, each closed by a scheduling barrier: nothing of what follows (the caller's next
+  // requests, the long columns' loop) is scheduled beside a group's rows.  The register count hangs on this form:
+  // 72 in k_agg_sddmm as written, 84 -- one resident block -- with the two groups written out one after the other
+  // (profiles/backward_load_hoisting/regs_parent_vs_tree.txt; tests/test_no_register_spills.py sees spills only).
 #pragma unroll
-    for (int k = 0; k < 4; ++k) ra[k] = rows[m0.v[k] * T4 + j];
+  for (int h = 0; h < 8; h += kAgsRows) {
+    float4 r[kAgsRows];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) edge(b0 + k, b0 + k >= e0 && b0 + k < e1, w0.v[k], ra[k]);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  {
-    float4 rb[4];
+    for (int k = 0; k < kAgsRows; ++k) r[k] = rows[(h + k < 4 ? m0.v[(h + k) & 3] : m1.v[(h + k) & 3]) * T4 + j];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) rb[k] = rows[m1.v[k] * T4 + j];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) edge(b0 + 4 + k, b0 + 4 + k >= e0 && b0 + 4 + k < e1, w1.v[k], rb[k]);
+    for (int k = 0; k < kAgsRows; ++k)
+      edge(b0 + h + k, b0 + h + k >= e0 && b0 + h + k < e1, h + k < 4 ? w0.v[(h + k) & 3] : w1.v[(h + k) & 3], r[k]);
+    __builtin_amdgcn_sched_barrier(0);
   }
   for (int e = b0 + 8; e < e1; e += 4) {  // columns with more than 8 edges
     const int b = min(e, nnz - 4);
@@ -646,13 +666,19 @@ __device__ __forceinline__ float4 gather_row_dot(const int* __restrict__ idx, co
 }
 
 // 768 lanes: the branch-free gather needs 72 registers, and 12 waves per block keep TWO blocks resident per CU
-// (one streams its slab while the other gathers): 67.8 us against 77.4 us with 1024 lanes (one resident block)
+// (one streams its slab while the other gathers): 67.8 us against 77.4 us with 1024 lanes (one resident block).
+// Two blocks of 12 waves are 6 waves per SIMD: the kernel may not take more than 80 registers.
 constexpr int kAgsBlock = 768;
+// slot iterations of a lane whose loads are asked for ahead: N T/4 <= 3072 slots (all of a PEMSD7 slab, 2649) are covered
+constexpr int kAgsAhead = 4;
 
+// The read-only arguments are not __restrict__ on purpose: loads from a read-only no-alias argument count as loads
+// from constant memory, and the compiler moves them to their first use -- across the barrier, and behind the wait for
+// the first colptr pair: the requests in front of them would be issued behind them.
 template <int T4>
 __global__ __launch_bounds__(kAgsBlock) void k_agg_sddmm(
-    const int* __restrict__ ptr, const int* __restrict__ idx, const float4* __restrict__ dv4,
-    const float* __restrict__ Ec, const float4* __restrict__ u4, float4* __restrict__ du4,
+    const int* ptr, const int* idx, const float4* dv4,
+    const float* Ec, const float4* u4, float4* __restrict__ du4,
     float* __restrict__ dEp, int Cu, int N, int nnz, int CH, int nchunks, int dvgs) {
   extern __shared__ float4 slab[];  // [CH][N][T4] of dv, then nnz * T4 floats of per-edge shares + a dummy per lane
   const int g = blockIdx.y;
@@ -666,18 +692,69 @@ __global__ __launch_bounds__(kAgsBlock) void k_agg_sddmm(
   const int dummy = nnz * T4 + threadIdx.x;
 
   const size_t vbase = ((size_t)g * dvgs + c0) * NT4;  // dv may be a channel slice of a wider tensor (dvgs channels per group)
-  for (int i = threadIdx.x; i < total; i += kAgsBlock) slab[i] = dv4[vbase + i];
+  const float* Eg = Ec + (size_t)g * nnz;
+  const int tid = threadIdx.x;
+  // Of a slot's chain -- colptr pair -> edge window -> LDS gathers -> own u -> du -- only the gathers need the slab.
+  // So the colptr pairs of the lane's first two slots are asked for in front of the slab, and the first slot's window
+  // and own u go out while the slab is still on its way and stay in flight across the barrier (plain loads do).  Every
+  // slot asks for the own u of the slot behind it (from memory: the long one of a slot's loads) and every later slot
+  // for that slot's colptr pair too, so that a slot starts with its pair and its own u in hand and is one exposed
+  // round trip, the window's, which comes from the L2.  As load -> barrier -> (colptr and own u, then window, then
+  // gathers) per slot a block went through nine dependent round trips: 72 -> 62 us at PEMSD7 size.  The next
+  // slot's window as well would take 17 more registers -- 96 in all, and the second resident block is gone.
+  // All of these loads are clamped and unconditional; what a lane without the slot gets is not used.
+  auto colptr_pair = [&](int s, int& a, int& b) {
+    const int n = min(s, NT4 - 1) / T4;
+    a = ptr[n];
+    b = ptr[n + 1];
+  };
+  int e0, e1, f0, f1;  // the pairs of the current slot and of the one behind it
+  colptr_pair(tid, e0, e1);
+  colptr_pair(tid + kAgsBlock, f0, f1);
+  // the slab: what lies beyond kAgsAhead trips of the block first (several channels per slab), then those trips
+  // through registers, so that the window can be asked for between their loads and their LDS stores.  A lane past the
+  // end loads and stores the slab's last element once more: a store behind a branch takes its load along, one round
+  // trip per trip.
+  for (int i = tid + kAgsAhead * kAgsBlock; i < total; i += kAgsBlock) slab[i] = dv4[vbase + i];
+  float4 stage[kAgsAhead];
+#pragma unroll
+  for (int k = 0; k < kAgsAhead; ++k) stage[k] = dv4[vbase + min(tid + k * kAgsBlock, total - 1)];
+  float4 own = u4[base + min(tid, NT4 - 1)];
+  EdgeWindow win = load_edge_window(idx, Eg, e0, nnz);
+#pragma unroll
+  for (int k = 0; k < kAgsAhead; ++k) slab[min(tid + k * kAgsBlock, total - 1)] = stage[k];
   __syncthreads();
 
-  const float* Eg = Ec + (size_t)g * nnz;
-  for (int s = threadIdx.x; s < NT4; s += kAgsBlock) {
+  float4 nown = own;  // the next slot's own u
+#pragma unroll
+  for (int k = 0; k < kAgsAhead; ++k) {
+    const int s = tid + k * kAgsBlock;
+    if (s >= NT4) break;
+    const int n = s / T4;
+    const int j = s - n * T4;
+    if (k > 0) {
+      win = load_edge_window(idx, Eg, e0, nnz);
+      own = nown;
+      if (k + 1 < kAgsAhead) colptr_pair(s + kAgsBlock, f0, f1);
+    }
+    if (k + 1 < kAgsAhead) nown = u4[base + min(s + kAgsBlock, NT4 - 1)];
+    du4[base + s] = gather_row_dot<T4, true>(win, idx, Eg, e0, e1, nnz, slab, j, own, pd, dummy);
+    for (int c = 1; c < ch; ++c) {
+      const float4 ownc = u4[base + (size_t)c * NT4 + s];
+      const EdgeWindow wc = load_edge_window(idx, Eg, e0, nnz);  // again: kept, it would be live across the long columns' loop
+      du4[base + (size_t)c * NT4 + s] = gather_row_dot<T4, false>(wc, idx, Eg, e0, e1, nnz, slab + c * NT4, j, ownc, pd, dummy);
+    }
+    e0 = f0, e1 = f1;
+  }
+  for (int s = tid + kAgsAhead * kAgsBlock; s < NT4; s += kAgsBlock) {  // slabs of more than kAgsAhead * 768 slots
     const int n = s / T4;
     const int j = s - n * T4;
     const int e0 = ptr[n], e1 = ptr[n + 1];
-    du4[base + s] = gather_row_dot<T4, true>(idx, Eg, e0, e1, nnz, slab, j, u4[base + s], pd, dummy);
+    const EdgeWindow w = load_edge_window(idx, Eg, e0, nnz);
+    du4[base + s] = gather_row_dot<T4, true>(w, idx, Eg, e0, e1, nnz, slab, j, u4[base + s], pd, dummy);
     for (int c = 1; c < ch; ++c) {
-      const float4 own = u4[base + (size_t)c * NT4 + s];
-      du4[base + (size_t)c * NT4 + s] = gather_row_dot<T4, false>(idx, Eg, e0, e1, nnz, slab + c * NT4, j, own, pd, dummy);
+      const float4 ownc = u4[base + (size_t)c * NT4 + s];
+      du4[base + (size_t)c * NT4 + s] = gather_row_dot<T4, false>(w, idx, Eg, e0, e1, nnz, slab + c * NT4, j, ownc, pd, dummy);
     }
   }
   __syncthreads();
