@@ -61,7 +61,8 @@ extern "C" {
  *     + msgat_edge_time_weights{,_backward} (hour- and day-dependent edge weights on one shared sparse pattern);
  *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends);
  *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel);
- *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail).
+ *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail);
+ *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -771,6 +772,35 @@ int msgat_edge_signal_weights(const msgat_graph_t* graph, const float* base, con
                               float* out, void* stream);
 int msgat_edge_signal_weights_backward(const msgat_graph_t* graph, const float* dout, const float* ab, int32_t B, int32_t d,
                                        float* dbase, float* dab, void* stream);
+/* msgat_edge_dropout: dropout on the stored edges of one sparse pattern (DropEdge with inverted scaling), the mask drawn from
+ *     a counter-based generator whose state lives in device memory.  Philox4x32-10 with the Random123 constants
+ *     (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85): edge e of global sample s at step t under
+ *     seed k reads word e & 3 of philox(counter = (e >> 2, s, t & 0xffffffff, t >> 32), key = (k & 0xffffffff, k >> 32)) and
+ *     is DROPPED iff that word < thr -- an integer compare; the caller passes thr = (uint32) floor(p * 2^32) and
+ *     scale = (float)(1 / (1 - p)), both computed in double.  s = sample_offset + v for row v of the output.
+ *       out[v,e] = exempt[e] ? w : (dropped ? +0.0f : w * scale)      -- w * scale is one fp32 multiply
+ *     w [nnz] (w_sets = 0: shared by the V samples) or [V,nnz] (w_sets != 0); exempt uint8 [nnz] or NULL (no edge is exempt);
+ *     out [V,nnz] contiguous in the order of (crow, col), which msgat_graph_t.val with val_sets = V reads where it is.
+ *     state int64 [2] = {seed, step} and used int64 [1] are device memory: the launch reads seed and step, writes the step it
+ *     drew from into used[0], and -- advance != 0 -- a one-thread launch behind it in stream order sets step + 1, after every
+ *     block has read the old one.  Nothing is read back (capturable: every replay draws the next step).  advance = 0 draws
+ *     without moving the stream.
+ * msgat_edge_dropout_backward: re-creates the draw from state[0] (the seed) and used[0] -- it does not read the step, so
+ *     several forwards followed by their backwards each see their own masks -- and writes, m = 0 / scale / 1 as above,
+ *       w_sets != 0:  dw[v,e] = dout[v,e] * m[v,e]              (one multiply: the bits of the torch expression)
+ *       w_sets == 0:  dw[e]   = sum_v dout[v,e] * m[v,e]        (rounded products added from +0 in ascending v)
+ *     Every entry is written, nothing is atomic; one launch.  dw = NULL: nothing is written, MSGAT_OK.
+ *     Both: V < 0, nnz < 0 or sample_offset < 0: MSGAT_ERR_SHAPE; nnz >= 2^34 or sample_offset + V > 2^32 (the counter's
+ *     words are 32 bits): MSGAT_ERR_UNSUPPORTED; V = 0 or nnz = 0: MSGAT_OK and nothing is launched -- an empty forward draws
+ *     nothing, so it neither writes `used` nor advances the step; a required pointer NULL with work to do: MSGAT_ERR_NULL.
+ *     The torch ops this replaces: a uniform draw, a compare, a select and a multiply forward, a multiply and a batch sum
+ *     backward, with a mask tensor kept in between. */
+int msgat_edge_dropout(const float* w, const uint8_t* exempt, int64_t* state, int64_t* used, float* out, int32_t V,
+                       int64_t nnz, int32_t w_sets, int64_t sample_offset, uint32_t thr, float scale, int32_t advance,
+                       void* stream);
+int msgat_edge_dropout_backward(const float* dout, const uint8_t* exempt, const int64_t* state, const int64_t* used,
+                                float* dw, int32_t V, int64_t nnz, int32_t w_sets, int64_t sample_offset, uint32_t thr,
+                                float scale, void* stream);
 size_t msgat_huber_partial_doubles(int64_t n);
 int msgat_huber_metrics(const float* pred, const float* truth, int64_t n, float delta, float mask_value,
                         double* partials, float* loss, double* sums, float loss_weight, void* stream);

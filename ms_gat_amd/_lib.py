@@ -200,6 +200,10 @@ _PROTOTYPES = {
     "msgat_edge_time_weights_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "msgat_edge_signal_weights": (C.c_int, [C.POINTER(Graph), C.c_void_p, C.c_void_p] + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "msgat_edge_signal_weights_backward": (C.c_int, [C.POINTER(Graph), C.c_void_p, C.c_void_p] + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "msgat_edge_dropout": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_uint32, C.c_float,
+                                                       C.c_int32, C.c_void_p]),
+    "msgat_edge_dropout_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_uint32,
+                                                                C.c_float, C.c_void_p]),
 }
 
 _lock = threading.Lock()

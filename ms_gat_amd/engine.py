@@ -753,6 +753,18 @@ class FlatAdam(optim.Optimizer):
         self._host_steps = [int(t) for t in snapshot[0].tolist()]
 
 
+def _edge_dropout_streams(model: nn.Module) -> List[torch.Tensor]:
+    """The {seed, step} buffers of every edge-dropout mask stream under `model` (`MSGAT(edge_dropout=p)`,
+    `model.EdgeDropout`): device memory that a training forward advances."""
+    return [m.edge_drop_state for m in model.modules() if isinstance(getattr(m, "edge_drop_state", None), torch.Tensor)]
+
+
+def _edge_dropout_owner(model: nn.Module):
+    """The module under `model` (itself, or what a data-parallel wrapper holds) that draws edge-dropout masks, or None."""
+    inner = getattr(model, "module", model)
+    return inner if getattr(inner, "edge_dropout", 0) and hasattr(inner, "edge_dropout_state") else None
+
+
 class _GraphedStep:
     """One captured step for one batch shape: static input buffers, `replay()` per batch.
 
@@ -776,6 +788,9 @@ class _GraphedStep:
                            for group in opt.param_groups for p in group["params"]}
             saved_steps = list(getattr(opt, "_host_steps", []))
             saved_guard = opt.guard_snapshot() if isinstance(opt, FlatAdam) else None
+            # the warm-up forwards draw edge-dropout masks and move their stream on: put it back with the parameters, so
+            # that the first replay (the capture itself executes nothing) draws the step an eager run would have drawn
+            saved_drop = [(s, s.clone()) for s in _edge_dropout_streams(model)]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -801,6 +816,8 @@ class _GraphedStep:
                 if isinstance(opt, FlatAdam) and step_in_graph:
                     opt.set_steps(saved_steps if saved_steps else [0] * len(opt._host_steps))
                     opt.guard_restore(saved_guard)   # a warm-up batch the guard left out counts once: at its replay
+                for s, old in saved_drop:
+                    s.copy_(old)
             opt.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -1006,6 +1023,7 @@ class Engine:
         guarded = training and self._guarded()
         if guarded:
             self._reset_guard_max()
+        dropper = _edge_dropout_owner(self.model) if training and world > 1 else None
         with guard, torch.set_grad_enabled(training):
             for batch in data:
                 n_global = batch[0].shape[0]
@@ -1015,6 +1033,10 @@ class Engine:
                     batch = parallel.shard_batch(batch, rank, world)
                 elif world > 1:
                     n_global = next(global_sizes) if global_sizes is not None else n_global * world
+                if dropper is not None:
+                    # this rank's samples draw the masks they have in the global batch (shard_batch and the sharded
+                    # sampler cut by the same bounds); n_global keys the captured graphs, so the offset is a constant of each
+                    dropper.edge_dropout_sample_offset = parallel.shard_bounds(n_global, rank, world)[0]
                 loss_weight = batch[0].shape[0] / n_global
                 batch = [t.to(device, non_blocking=True) for t in batch]
                 *inputs, truth = batch
@@ -1183,10 +1205,16 @@ class Trainer(Engine):
     def save(self, ckpt) -> None:
         """The reference's five keys (engine.py:135-146).  `grad_scaler` holds the state of a default-constructed,
         enabled GradScaler -- this build trains in fp32 and never scales, but the reference's `load` feeds that entry
-        to `GradScaler.load_state_dict`, which rejects an empty dict (engine.py:155)."""
-        torch.save(dict(best=self.best, epoch=self.epoch, model=self.model.state_dict(),
-                        optimizer=self.optimizer.state_dict(), scheduler=self.scheduler.state_dict(),
-                        grad_scaler=default_grad_scaler_state()), ckpt)
+        to `GradScaler.load_state_dict`, which rejects an empty dict (engine.py:155).  A model that drops edges
+        (`MSGAT(edge_dropout=p)`) adds a sixth key, `edge_dropout` = {seed, step} of its mask stream, which is no
+        `state_dict` entry; every other model's checkpoint keeps the five."""
+        states = dict(best=self.best, epoch=self.epoch, model=self.model.state_dict(),
+                      optimizer=self.optimizer.state_dict(), scheduler=self.scheduler.state_dict(),
+                      grad_scaler=default_grad_scaler_state())
+        dropper = _edge_dropout_owner(self.model)
+        if dropper is not None:
+            states["edge_dropout"] = dropper.edge_dropout_state()
+        torch.save(states, ckpt)
 
     def load(self, ckpt) -> None:
         states = torch.load(ckpt, map_location=next(self.model.parameters()).device, weights_only=False)
@@ -1196,6 +1224,9 @@ class Trainer(Engine):
         self.model.load_state_dict(strip_data_parallel_prefix(states["model"]))
         self.optimizer.load_state_dict(states["optimizer"])
         self.scheduler.load_state_dict(states["scheduler"])
+        dropper = _edge_dropout_owner(self.model)
+        if dropper is not None and states.get("edge_dropout") is not None:
+            dropper.set_edge_dropout_state(states["edge_dropout"])      # in place: captured steps read the same words
         self._sync_lr()
         if isinstance(self.optimizer, FlatAdam) and token and token != self.optimizer.buffer_token():
             self._graphs.clear()            # the optimizer's buffers moved: captured steps point at the old ones

@@ -14,7 +14,7 @@ Parameter names and shapes are the reference's (`tpcs.{r}.tgacns.{l}.gacn.gatt.W
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 from torch import nn
@@ -371,6 +371,60 @@ class EdgeSignalWeights(nn.Module):
         return ops.edge_adjacency(self.crow, self.col, self.weights(f))
 
 
+def _check_edge_dropout(p) -> float:
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
+        raise ValueError(f"edge_dropout must be a number in [0, 1), got {p!r}")
+    return float(p)
+
+
+def _read_edge_dropout_state(state: torch.Tensor) -> Dict[str, int]:
+    seed, step = (int(v) for v in state.tolist())
+    return {"seed": seed, "step": step}
+
+
+def _write_edge_dropout_state(state: torch.Tensor, value) -> None:
+    """In place: captured steps keep reading the same two words."""
+    with torch.no_grad():
+        state.copy_(torch.tensor([int(value["seed"]), int(value["step"])], dtype=torch.int64))
+
+
+class EdgeDropout(nn.Module):
+    """Dropout on the stored edges of a sparse pattern for callers of `GraphAttention`, `GACN` and `StackedGACN`:
+    `forward(weights, samples=None)` takes `weights` [nnz] (shared by `samples` samples) or [V,nnz] in the order of
+    (crow, col) and, in training mode, returns the [V,nnz] weights with each edge of each sample dropped with probability
+    `p` and the kept ones multiplied by `1 / (1 - p)` -- ready for `ops.edge_adjacency(crow, col, ·)`; in eval mode it
+    returns `weights` unchanged.  `exempt` (bool or uint8 [nnz]): edges that are never dropped or scaled, a stored diagonal
+    for instance.  `sample_offset`: the index of this process's first sample in the global batch (`ops.edge_dropout`).
+
+    The stream {seed, step} is a NON-persistent buffer (`edge_drop_state`, int64 [2]): it moves with the module, is copied
+    by `copy.deepcopy`, advances on the device by one per training forward -- inside a captured step too -- and adds no
+    `state_dict` key; `state()` / `set_state()` snapshot and restore it."""
+
+    def __init__(self, p: float, seed: int = 0, exempt: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.p = _check_edge_dropout(p)
+        self.sample_offset = 0
+        self.register_buffer("edge_drop_state", ops.edge_dropout_state(seed, "cpu"), persistent=False)
+        self.register_buffer("edge_drop_exempt", None if exempt is None else exempt.detach().to(torch.uint8).clone(),
+                             persistent=False)
+
+    def forward(self, weights: torch.Tensor, samples: Optional[int] = None) -> torch.Tensor:
+        if not self.training:
+            return weights
+        return ops.edge_dropout(weights, self.p, self.edge_drop_state, sample_offset=self.sample_offset,
+                                exempt=self.edge_drop_exempt, samples=samples)
+
+    def state(self) -> Dict[str, int]:
+        """{"seed", "step"}: reads the two words back from the device."""
+        return _read_edge_dropout_state(self.edge_drop_state)
+
+    def set_state(self, state) -> None:
+        _write_edge_dropout_state(self.edge_drop_state, state)
+
+    def extra_repr(self) -> str:
+        return f"p={self.p}"
+
+
 def _check_edge_rank(rank) -> None:
     if isinstance(rank, bool) or not isinstance(rank, int) or rank < 4 or rank > 32 or rank % 4:
         raise ValueError(f"the edge rank must be one of 4, 8, ..., 32 (rows are read as 16-byte pieces), got {rank!r}")
@@ -399,15 +453,29 @@ class MSGAT(nn.Module):
     i -> j is `edge_weight` plus the dot product of i's row side and j's column side.  The column half of `edge_proj.weight`
     starts at zero, so a fresh model computes what a `True` model computes and a `True` model's checkpoint loads with
     `strict=False`.  Built once per forward (`ops.edge_signal_weights`), shared by the R components and by every block.
+
+    `edge_dropout=p` in (0,1) regularises the graph, with any `learn_edge_weights`: the layer is `(softmax(S) * A) x`, linear
+    in `A`, so dropout on the masked attention is dropout on the stored edge weights.  In training mode one [B,nnz] mask per
+    forward -- each edge of each sample dropped with probability p, the kept ones scaled by 1 / (1 - p), the stored
+    diagonal left alone unless `edge_dropout_keep_self=False` -- is applied to the weights once they are formed
+    (`ops.edge_dropout`) and shared by the R components and by every block; the frozen graph takes the per-sample sparse
+    path on the pattern of `adj != 0`, without a weight gradient.  The masks come from a counter-based stream
+    {`edge_dropout_seed`, step} in device memory (a non-persistent buffer: no `state_dict` key) that advances by one per
+    training forward, inside a captured step too; sample b of the batch draws as global sample
+    `edge_dropout_sample_offset + b`, so a sharded batch sees the masks of the whole one.  `eval()`, `attention_maps` and
+    `torch.no_grad()` draw nothing.  `edge_dropout_state()` / `set_edge_dropout_state()` snapshot and restore the stream.
+    The default 0 adds no buffer, key or launch.
     """
 
     def __init__(self, components: Sequence[Dict], in_timesteps: int, out_timesteps: int, use_te: bool,
-                 adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False, edge_rank: int = 8):
+                 adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False, edge_rank: int = 8,
+                 edge_dropout: float = 0.0, edge_dropout_seed: int = 0, edge_dropout_keep_self: bool = True):
         if not (isinstance(learn_edge_weights, bool)
                 or (isinstance(learn_edge_weights, str) and learn_edge_weights in ("time", "signal"))):
             raise ValueError(f'learn_edge_weights must be False, True, "time" or "signal", got {learn_edge_weights!r}')
         if learn_edge_weights == "signal":
             _check_edge_rank(edge_rank)
+        edge_dropout = _check_edge_dropout(edge_dropout)
         super().__init__()
         n_nodes = len(adj)
         if use_te:
@@ -442,6 +510,39 @@ class MSGAT(nn.Module):
                     self.edge_d_ebd.weight.zero_()
                 if self.learn_edge_weights == "signal":      # the row half keeps its Xavier values
                     self.edge_proj.weight[self.edge_rank:].zero_()
+        self.edge_dropout = edge_dropout
+        self.edge_dropout_sample_offset = 0    # this process's first sample in the global batch (the engine sets it)
+        if self.edge_dropout > 0:
+            # non-persistent: the state_dict keeps the reference's keys (and those of learn_edge_weights)
+            pattern = self.adj.detach().cpu().to_sparse_csr()
+            crow, col = pattern.crow_indices(), pattern.col_indices()
+            rows = torch.repeat_interleave(torch.arange(n_nodes), crow[1:] - crow[:-1])
+            self.register_buffer("edge_drop_state", ops.edge_dropout_state(edge_dropout_seed, "cpu"), persistent=False)
+            self.register_buffer("edge_drop_exempt", (rows == col).to(torch.uint8) if edge_dropout_keep_self else None,
+                                 persistent=False)
+            if not self.learn_edge_weights:      # the frozen graph's pattern, and where its values sit in `adj`
+                self.register_buffer("edge_drop_crow", crow.clone(), persistent=False)
+                self.register_buffer("edge_drop_col", col.clone(), persistent=False)
+                self.register_buffer("edge_drop_index", rows * n_nodes + col, persistent=False)
+
+    def _drops_edges(self) -> bool:
+        """Masks are drawn in training mode with gradients enabled only: `eval()`, `attention_maps` and any evaluation under
+        `torch.no_grad()` draw nothing and leave the stream where it is."""
+        return self.edge_dropout > 0 and self.training and torch.is_grad_enabled()
+
+    def _drop_edges(self, weights: torch.Tensor, samples: int) -> torch.Tensor:
+        return ops.edge_dropout(weights, self.edge_dropout, self.edge_drop_state,
+                                sample_offset=int(self.edge_dropout_sample_offset), exempt=self.edge_drop_exempt,
+                                samples=samples if weights.dim() == 1 else None)
+
+    def edge_dropout_state(self) -> Optional[Dict[str, int]]:
+        """{"seed", "step"} of the mask stream (reads two words back from the device); None for a model that drops nothing."""
+        return _read_edge_dropout_state(self.edge_drop_state) if self.edge_dropout > 0 else None
+
+    def set_edge_dropout_state(self, state) -> None:
+        if self.edge_dropout <= 0:
+            raise ValueError("set_edge_dropout_state: this model was built with edge_dropout=0 and has no mask stream")
+        _write_edge_dropout_state(self.edge_drop_state, state)
 
     @staticmethod
     def edge_features(X: torch.Tensor) -> torch.Tensor:
@@ -451,21 +552,36 @@ class MSGAT(nn.Module):
 
     def adjacency(self, H: torch.Tensor = None, D: torch.Tensor = None, X: torch.Tensor = None):
         """What the blocks get: the frozen dense `adj`, the sparse CSR adjacency of the learned edge weights, or the batched
-        CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D` ("time") or of its inputs `X` ("signal")."""
+        CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D` ("time") or of its inputs `X` ("signal").
+        With `edge_dropout > 0`, in training mode with gradients enabled, always the batched form: one [B,nnz] draw on the
+        weights once they are formed (`ops.edge_dropout`), shared by the R components and by every block; B is read from H
+        (or X)."""
+        drop = self._drops_edges()
+        samples = None
+        if drop:
+            batch = H if H is not None else X
+            if batch is None:
+                raise ValueError("edge_dropout: the masks are drawn per sample, pass the batch's H and D (or its inputs X)")
+            samples = batch.shape[0]
         if not self.learn_edge_weights:
-            return self.adj
+            if not drop:
+                return self.adj
+            weights = self.adj.detach().reshape(-1).index_select(0, self.edge_drop_index)
+            return ops.edge_adjacency(self.edge_drop_crow, self.edge_drop_col, self._drop_edges(weights, samples))
         if self.learn_edge_weights == "signal":
             if X is None:
                 raise ValueError('learn_edge_weights="signal": the adjacency depends on the batch, pass its inputs X')
             weights = ops.edge_signal_weights(self.edge_weight, self.edge_proj(self.edge_features(X)), self.edge_crow,
                                               self.edge_col)
-            return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
-        if self.learn_edge_weights == "time":
+        elif self.learn_edge_weights == "time":
             if H is None or D is None:
                 raise ValueError('learn_edge_weights="time": the adjacency depends on the batch, pass its H and D')
             weights = ops.edge_time_weights(self.edge_weight, self.edge_h_ebd.weight, self.edge_d_ebd.weight, H, D)
-            return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
-        return ops.edge_adjacency(self.edge_crow, self.edge_col, self.edge_weight)
+        else:
+            weights = self.edge_weight
+        if drop:
+            weights = self._drop_edges(weights, samples)
+        return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
 
     def batch_adjacency(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor):
         """`adjacency` for one batch of `forward`'s inputs; only "signal" is handed X."""

@@ -1367,6 +1367,114 @@ def edge_signal_weights(base: torch.Tensor, ab: torch.Tensor, crow: torch.Tensor
     return _EdgeSignalWeightsFunction.apply(base, ab, edge_pattern_of(crow, col))
 
 
+def edge_dropout_constants(p: float) -> tuple:
+    """(thr, scale) of a drop probability p in [0,1): an edge is dropped iff its 32-bit draw is `< thr`,
+    `thr = floor(p * 2^32)`, and a kept one is multiplied by `scale = 1 / (1 - p)` -- both computed in double, the scale then
+    rounded once to fp32 (by the call)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
+        raise ValueError(f"edge_dropout: p must be a number in [0, 1), got {p!r}")
+    p = float(p)
+    return int(math.floor(p * 4294967296.0)), 1.0 / (1.0 - p)
+
+
+def edge_dropout_state(seed: int, device) -> torch.Tensor:
+    """`tensor([seed, 0])` int64 on `device`: the state {seed, step} of a fresh mask stream for `edge_dropout`."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise ValueError(f"edge_dropout: the seed must fit 64 bits, got {seed}")
+    if seed >= (1 << 63):
+        seed -= 1 << 64                                    # the same 64 bits in torch's signed type
+    return torch.tensor([seed, 0], dtype=torch.int64, device=device)
+
+
+class _EdgeDropoutFunction(torch.autograd.Function):
+    """w [nnz] or [V,nnz] -> w * m [V,nnz], m drawn from `state` {seed, step} (msgat_edge_dropout); backward re-creates m
+    from the seed and the step the forward left in `used`, a fresh int64 [1] per call."""
+
+    @staticmethod
+    def forward(ctx, w, exempt, state, V, sample_offset, thr, scale):
+        L = _lib.lib()
+        w = w.contiguous()
+        nnz = w.shape[-1]
+        sets = int(w.dim() == 2)
+        out = _new(w, V, nnz)
+        used = torch.empty(1, device=w.device, dtype=torch.int64)
+        st = L.msgat_edge_dropout(_ptr(w), _ptr(exempt), _ptr(state), _ptr(used), _ptr(out), V, nnz, sets, sample_offset, thr,
+                                  scale, 1, _stream_handle(w.device))
+        _lib.check(st, "msgat_edge_dropout")
+        ctx.call = (V, nnz, sets, sample_offset, thr, scale)
+        ctx.operands = (exempt, state, used)               # integer tensors the launch reads by address: nothing to version
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        exempt, state, used = ctx.operands
+        V, nnz, sets, sample_offset, thr, scale = ctx.call
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        dout = dout.contiguous()
+        if V == 0 or nnz == 0:                             # nothing was drawn: the empty sum
+            return (torch.zeros((V, nnz) if sets else (nnz,), device=dout.device, dtype=dout.dtype),) + (None,) * 6
+        dw = _new(dout, V, nnz) if sets else _new(dout, nnz)
+        st = L.msgat_edge_dropout_backward(_ptr(dout), _ptr(exempt), _ptr(state), _ptr(used), _ptr(dw), V, nnz, sets,
+                                           sample_offset, thr, scale, _stream_handle(dout.device))
+        _lib.check(st, "msgat_edge_dropout_backward")
+        return (dw,) + (None,) * 6
+
+
+def edge_dropout(weight: torch.Tensor, p: float, state: torch.Tensor, *, sample_offset: int = 0,
+                 exempt: Optional[torch.Tensor] = None, samples: Optional[int] = None) -> torch.Tensor:
+    """Dropout on the stored edges of one sparse pattern (DropEdge with inverted scaling; the layer is linear in the
+    adjacency, so this is dropout on the masked attention coefficients): `weight` [nnz] -- shared by `samples` = V samples --
+    or [V,nnz] -> [V,nnz], an edge of a sample dropped (+0) with probability `p` and multiplied by `1 / (1 - p)` otherwise,
+    contiguous in the order of (crow, col): `edge_adjacency(crow, col, ·)` reads it where it is.  Edges flagged in `exempt`
+    (bool or uint8 [nnz]) pass through unchanged.
+
+    The mask of sample v is a pure function of (`state` = int64 [2] {seed, step} in device memory, `sample_offset` + v,
+    the edge): Philox4x32-10, see msgat_edge_dropout.  The call draws at the current step and moves `state` one step on, on
+    the device -- inside a captured HIP graph every replay draws fresh masks -- and rows
+    [lo, hi) of a V-row draw are the (hi - lo)-row draw at `sample_offset=lo`, whichever process draws them.  Backward
+    re-creates the mask instead of storing it: `weight` [V,nnz] gets `dout * m`, `weight` [nnz] the sum over the samples in
+    ascending order, one launch.  `p == 0` still runs (nothing is dropped, the step advances)."""
+    if not torch.is_tensor(weight) or not weight.is_cuda:
+        raise ValueError(f"edge_dropout: weight is on {getattr(weight, 'device', type(weight).__name__)}: the op runs on the GPU "
+                         "only, there is no CPU path")
+    if weight.dtype != torch.float32:
+        raise TypeError(f"edge_dropout: weight must be float32, got {weight.dtype}")
+    thr, scale = edge_dropout_constants(p)
+    if weight.dim() == 1:
+        if samples is None or isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
+            raise ValueError(f"edge_dropout: weight {tuple(weight.shape)} is shared by the samples, pass their number as "
+                             f"samples=V (got {samples!r})")
+        V = samples
+    elif weight.dim() == 2:
+        V = weight.shape[0]
+        if samples is not None and samples != V:
+            raise ValueError(f"edge_dropout: weight {tuple(weight.shape)} has {V} samples, samples={samples!r}")
+    else:
+        raise ValueError(f"edge_dropout: weight must be [nnz] or [V, nnz], got {tuple(weight.shape)}")
+    nnz = weight.shape[-1]
+    if (not torch.is_tensor(state) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or state.device != weight.device
+            or not state.is_contiguous()):
+        raise ValueError(f"edge_dropout: state must be int64 [2] {{seed, step}} on {weight.device} (edge_dropout_state), got "
+                         f"{getattr(state, 'dtype', type(state).__name__)} {tuple(getattr(state, 'shape', ()))} on "
+                         f"{getattr(state, 'device', None)}")
+    if isinstance(sample_offset, bool) or not isinstance(sample_offset, int) or sample_offset < 0 or sample_offset + V > 1 << 32:
+        raise ValueError(f"edge_dropout: sample_offset = {sample_offset!r} with {V} samples: global sample indices are 32 bits")
+    if nnz >= 1 << 34:
+        raise ValueError(f"edge_dropout: {nnz} stored edges, at most 2^34 - 1 are supported")
+    if exempt is not None:
+        if (not torch.is_tensor(exempt) or exempt.dtype not in (torch.uint8, torch.bool) or tuple(exempt.shape) != (nnz,)
+                or exempt.device != weight.device):
+            raise ValueError(f"edge_dropout: exempt must be uint8 or bool [{nnz}] on {weight.device}, got "
+                             f"{getattr(exempt, 'dtype', type(exempt).__name__)} {tuple(getattr(exempt, 'shape', ()))}")
+        exempt = exempt.contiguous()
+        if exempt.dtype == torch.bool:
+            exempt = exempt.view(torch.uint8)
+    return _EdgeDropoutFunction.apply(weight, exempt, state, V, sample_offset, thr, scale)
+
+
 # ---- channel axes assembled from several tensors: one pass instead of cat / several mixes -------------------
 
 def _sliced_grad(dz: torch.Tensor, accepts):
