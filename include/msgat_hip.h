@@ -62,7 +62,8 @@ extern "C" {
  *     + msgat_edge_signal_weights{,_backward} (edge weights from the per-sample node signals at the edge's two ends);
  *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel);
  *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail);
- *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory).
+ *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory);
+ *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -938,6 +939,33 @@ int msgat_adam_step_guarded(float* const* chunk_param, const int64_t* chunk_off,
                             int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq, float* steps,
                             const float* lr, double beta1, double beta2, double eps, double weight_decay,
                             const float* grad_divisor, const float* guard, void* stream);
+
+/* ---- device: averaged weights (off unless a caller uses msgat_adam_step_averaged) ---------------------------------------
+ * An exponential moving average (EMA) of the parameters, kept by the launch that forms them: it cannot be added from
+ * outside a captured step (the update is inside the graph), beside the guard (the host does not know which steps were left
+ * out) or across ranks (only the same launch gives every rank the same bits).
+ * msgat_adam_step_averaged: msgat_adam_step (guard == NULL) or msgat_adam_step_guarded (guard given) -- the same two
+ *     launches, and parameters, moments and step counts with the bits those leave -- that also moves `shadow`, a flat fp32
+ *     buffer in the layout of exp_avg.  For every element of every chunk of the table, after w_new is formed:
+ *         t   = steps[chunk_tensor[c]]                  (already advanced: 1 at a tensor's first update; exact up to 2^24)
+ *         d   = min((float)decay, (1 + t) / (10 + t))   (the warm-up of the average, per tensor)
+ *         omd = 1 - d
+ *         e   = e + omd * (w_new - e)                   (e = shadow[chunk_off[c] + i])
+ *     every operation of these lines rounded on its own in fp32 (no fma, no contraction): a float32 restatement gives the
+ *     same bits.  The tensor's step count is the only clock.  A tensor without a gradient has no chunk and its shadow is
+ *     not touched, as its parameter is not; with `guard` given a non-finite step writes nothing, the shadow included.
+ *     decay outside [0, 1) or NaN: MSGAT_ERR_SHAPE; shadow NULL: MSGAT_ERR_NULL.
+ * msgat_param_swap: one launch, one block per chunk, exchanges chunk_param[c][i] with flat[chunk_off[c] + i] as 32-bit
+ *     words (NaNs keep their bits): two calls are the identity.  With flat = shadow, whoever holds the parameters'
+ *     addresses (a captured validation graph) reads the averaged weights.  n_chunks == 0: MSGAT_OK, nothing launched;
+ *     n_chunks < 0: MSGAT_ERR_SHAPE. */
+int msgat_adam_step_averaged(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                             const int32_t* chunk_tensor, int32_t n_chunks, const int32_t* active_tensors,
+                             int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq, float* steps,
+                             const float* lr, double beta1, double beta2, double eps, double weight_decay,
+                             const float* grad_divisor, const float* guard, float* shadow, double decay, void* stream);
+int msgat_param_swap(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
+                     float* flat, void* stream);
 
 /* ---- device: the input windows of a batch (replaces data_loader.py:92-115, TimeSeriesSlice, and the host collate) ----
  * msgat_window_gather: one launch builds the batch of B forecast origins from a series that stays in device memory.

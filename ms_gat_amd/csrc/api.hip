@@ -1169,6 +1169,32 @@ extern "C" int msgat_adam_step_guarded(float* const* chunk_param, const int64_t*
                              guard, (hipStream_t)stream);
 }
 
+// ---- averaged weights: the update that also moves the shadow, and the in-place exchange ------------------------------
+extern "C" int msgat_adam_step_averaged(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                                        const int32_t* chunk_tensor, int32_t n_chunks, const int32_t* active_tensors,
+                                        int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                        float* steps, const float* lr, double beta1, double beta2, double eps,
+                                        double weight_decay, const float* grad_divisor, const float* guard, float* shadow,
+                                        double decay, void* stream) {
+  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
+  if (!steps || !lr || !shadow) return MSGAT_ERR_NULL;   // guard may be NULL: the unguarded update
+  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
+  if (n_chunks > 0 && (!chunk_param || !chunk_off || !chunk_len || !chunk_tensor || !grad || !exp_avg || !exp_avg_sq)) return MSGAT_ERR_NULL;
+  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
+  if (!(decay >= 0. && decay < 1.)) return MSGAT_ERR_SHAPE;   // also NaN
+  return launch_adam_averaged(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors,
+                              n_active, grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor,
+                              guard, shadow, decay, (hipStream_t)stream);
+}
+
+extern "C" int msgat_param_swap(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                                int32_t n_chunks, float* flat, void* stream) {
+  if (n_chunks < 0) return MSGAT_ERR_SHAPE;
+  if (n_chunks == 0) return MSGAT_OK;
+  if (!chunk_param || !chunk_off || !chunk_len || !flat) return MSGAT_ERR_NULL;
+  return launch_param_swap(chunk_param, (const long long*)chunk_off, chunk_len, n_chunks, flat, (hipStream_t)stream);
+}
+
 extern "C" int msgat_gather_scaled(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                                    int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
   if (n_chunks <= 0) return MSGAT_ERR_SHAPE;

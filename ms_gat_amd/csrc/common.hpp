@@ -527,6 +527,14 @@ int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, c
                         const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
                         float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
                         double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s);
+// the update that also moves the flat shadow (the averaged weights); guard == nullptr: the unguarded update
+int launch_adam_averaged(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                         const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
+                         float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
+                         double weight_decay, const float* grad_divisor, const float* guard, float* shadow, double decay,
+                         hipStream_t s);
+int launch_param_swap(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, int nchunks,
+                      float* flat, hipStream_t s);
 int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                          float scale, float* flat, long long weight_index, hipStream_t s);
 size_t masked_huber_partial_doubles(long long rows, int T);

@@ -17,6 +17,9 @@
 //                        (torch.nn.utils.clip_grad_norm_'s) and whether it is finite, left in device memory; the guarded
 //                        forms of k_adam_advance / k_adam read them there and scale the gradient or -- like
 //                        GradScaler.step (reference engine.py:61-63) -- leave a non-finite step out altogether.
+//   average (optional)   k_adam<., Shadow>: k_adam that also moves a flat shadow of the parameters towards w_new (an
+//                        exponential moving average, warmed up by the tensor's step count); k_param_swap exchanges
+//                        parameters and shadow in place, so validation reads the average at the addresses it holds.
 #include "common.hpp"
 
 namespace msgat {
@@ -368,7 +371,34 @@ __global__ void k_adam_advance(float* __restrict__ steps, const int* __restrict_
   if (i < n_active) steps[active[i]] += 1.0f;
 }
 
-template <bool kGuard>
+// The average of the weights (optional: msgat_adam_step_averaged).  After w_new is formed, the shadow e of the element moves
+// towards it by 1 - d, d = min(decay, (1 + t) / (10 + t)) with t the tensor's own step count (already advanced): the
+// warm-up of the average per tensor, on the only clock the update has.  Every operation is rounded on its own, in fp32 --
+// a numpy float32 restatement gives the same bits.  Contraction is switched off in these functions: the __f*_rn spellings
+// of this toolchain are plain operators, which the default (-ffp-contract=fast) would fuse into an fma after inlining.
+// k_adam takes the shadow as a trailing argument pack: empty for the two kernels that existed before the average (their
+// signature, and their code, are what they were), one Shadow for the averaged ones.
+struct Shadow {
+  float* e;      // flat, in the layout of the moments
+  float decay;
+};
+__device__ __forceinline__ float average_rate(float) { return 0.f; }            // no shadow: nothing is averaged
+__device__ __forceinline__ float average_load(long long) { return 0.f; }
+__device__ __forceinline__ void average_move(long long, float, float, float) {}
+__device__ __forceinline__ float average_rate(float t, Shadow s) {
+#pragma clang fp contract(off)
+  const float d = fminf(s.decay, (1.f + t) / (10.f + t));
+  return 1.f - d;
+}
+__device__ __forceinline__ float average_load(long long at, Shadow s) { return s.e[at]; }
+__device__ __forceinline__ void average_move(long long at, float e, float w_new, float omd, Shadow s) {
+#pragma clang fp contract(off)
+  const float diff = w_new - e;
+  const float step = omd * diff;
+  s.e[at] = e + step;
+}
+
+template <bool kGuard, class... Average>
 __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ chunk_param,
                                                      const long long* __restrict__ chunk_off,
                                                      const int* __restrict__ chunk_len,
@@ -378,7 +408,7 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
                                                      const float* __restrict__ lrp, double beta1d, double beta2d,
                                                      float eps, float weight_decay,
                                                      const float* __restrict__ grad_divisor,
-                                                     const float* __restrict__ guard) {
+                                                     const float* __restrict__ guard, Average... shadow) {
   if (kGuard && guard[kGuardFinite] == 0.f) return;   // kernel-uniform
   // clip_grad_norm_ scales the raw gradient, optim.Adam then adds the L2 term: coef acts before weight_decay * w
   const float coef = kGuard ? guard[kGuardCoef] : 1.f;
@@ -397,18 +427,22 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
   const double bc1 = 1.0 - pow(beta1d, (double)t), bc2 = 1.0 - pow(beta2d, (double)t);
   const float beta2 = (float)beta2d, omb1 = (float)(1.0 - beta1d), omb2 = (float)(1.0 - beta2d);  // 1 - beta rounded once
   const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  const float omd = average_rate(t, shadow...);       // 1 - d of this tensor
   for (int i = threadIdx.x; i < len; i += kTailBlock) {
     const float w = p[i];
     float gin = scaled ? grad[off + i] / div : grad[off + i];
     if (kGuard) gin = coef * gin;                     // coef == 1: the same bits as the unguarded kernel
     const float g = fmaf(weight_decay, w, gin);
     float mi = m[off + i], vi = v[off + i];
+    const float e = average_load(off + i, shadow...);  // ahead of the parameter's store, which it cannot be moved across
     mi = fmaf(g - mi, omb1, mi);                      // exp_avg.lerp_(grad, 1 - beta1)
     vi = fmaf(g * g, omb2, vi * beta2);               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     m[off + i] = mi;
     v[off + i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = w - step_size * (mi / denom);
+    const float w_new = w - step_size * (mi / denom);
+    p[i] = w_new;
+    average_move(off + i, e, w_new, omd, shadow...);
   }
 }
 
@@ -445,6 +479,68 @@ int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, c
                         double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s) {
   return launch_adam_form<true>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad, m, v,
                                 steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard, s);
+}
+
+template <bool kGuard>
+static int launch_adam_averaged_form(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                                     const int* chunk_tensor, int nchunks, const int* active, int n_active,
+                                     const float* grad, float* m, float* v, float* steps, const float* lr, double beta1,
+                                     double beta2, double eps, double weight_decay, const float* grad_divisor,
+                                     const float* guard, float* shadow, double decay, hipStream_t s) {
+  if (n_active > 0) {
+    hipLaunchKernelGGL(k_adam_advance<kGuard>, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active,
+                       n_active, guard);
+    MSGAT_CHECK_LAUNCH();
+  }
+  if (nchunks > 0) {
+    hipLaunchKernelGGL((k_adam<kGuard, Shadow>), dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len,
+                       chunk_tensor, grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor,
+                       guard, Shadow{shadow, (float)decay});
+    MSGAT_CHECK_LAUNCH();
+  }
+  return MSGAT_OK;
+}
+
+// guard == nullptr: the unguarded update
+int launch_adam_averaged(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
+                         const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
+                         float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
+                         double weight_decay, const float* grad_divisor, const float* guard, float* shadow, double decay,
+                         hipStream_t s) {
+  if (guard)
+    return launch_adam_averaged_form<true>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active,
+                                           grad, m, v, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard,
+                                           shadow, decay, s);
+  return launch_adam_averaged_form<false>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad,
+                                          m, v, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, nullptr, shadow,
+                                          decay, s);
+}
+
+// ---- parameters <-> a flat buffer, exchanged in place --------------------------------------------------------------
+// Block c swaps chunk_param[c][i] with flat[chunk_off[c] + i] as 32-bit words (NaNs keep their bits; two calls are the
+// identity).  With flat = the shadow, whatever holds the parameters' addresses -- a captured validation graph -- reads
+// the averaged weights.  Parameter views are 4-byte aligned only: scalar accesses, as in k_adam.
+__global__ __launch_bounds__(kTailBlock) void k_param_swap(unsigned* const* __restrict__ chunk_param,
+                                                           const long long* __restrict__ chunk_off,
+                                                           const int* __restrict__ chunk_len,
+                                                           unsigned* __restrict__ flat) {
+  const int c = blockIdx.x;
+  unsigned* p = chunk_param[c];
+  unsigned* __restrict__ f = flat + chunk_off[c];
+  const int len = chunk_len[c];
+  for (int i = threadIdx.x; i < len; i += kTailBlock) {
+    const unsigned a = p[i], b = f[i];
+    p[i] = b;
+    f[i] = a;
+  }
+}
+
+int launch_param_swap(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, int nchunks,
+                      float* flat, hipStream_t s) {
+  hipLaunchKernelGGL(k_param_swap, dim3(nchunks), dim3(kTailBlock), 0, s, (unsigned* const*)chunk_param, chunk_off,
+                     chunk_len, (unsigned*)flat);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
 }
 
 int adam_chunk_elems() { return kAdamChunk; }

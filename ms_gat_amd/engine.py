@@ -27,12 +27,18 @@ Differences that are the point of this build:
     taken on the device, the gradient is clipped to `max_grad_norm` as `torch.nn.utils.clip_grad_norm_` would, and a step
     whose norm is Inf or NaN is left out whole, as the reference's `GradScaler.step` leaves it out (engine.py:61-63) --
     inside a captured step and after the one all-reduce of a multi-rank step, with nothing read back (`FlatAdam`).
+  * `ema_decay` (off by default) keeps an exponential moving average of the parameters inside the same update launch
+    (`msgat_adam_step_averaged`): one more flat buffer, warmed up by each tensor's own step count, untouched by a step the
+    guard leaves out, bit-identical across ranks.  `fit` validates -- and so picks its best checkpoint -- on the averaged
+    weights, exchanged with the parameters in place by one launch (`msgat_param_swap`), so captured validation graphs read
+    them at the addresses they hold; checkpoints gain an `ema` key and `Evaluator(weights=...)` chooses which set to load.
   * `hip_graph="auto"` (the default on the GPU) captures a step in a HIP graph once its batch shape recurs and replays it.
 CPU tensors (the host-logic tests run a small CPU `nn.Module` through this loop) take plain PyTorch
 ops for loss and optimizer; the library has no CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from pathlib import Path
@@ -465,6 +471,21 @@ def check_max_grad_norm(max_grad_norm) -> None:
         raise ValueError(f"max_grad_norm must be a positive number or None, not {max_grad_norm!r}")
 
 
+def check_ema_decay(ema_decay) -> None:
+    if ema_decay is None:
+        return
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) < 1.0:   # also NaN
+        raise ValueError(f"ema_decay must be a float in [0, 1) or None, not {ema_decay!r}")
+
+
+def average_rate(decay: float, step) -> torch.Tensor:
+    """1 - d of the averaged weights, d = min(decay, (1 + t) / (10 + t)) at the (already advanced) step count t: three
+    separately rounded fp32 operations, as `k_adam` takes them (csrc/tail.hip)."""
+    t = torch.as_tensor(float(step), dtype=torch.float32)
+    d = torch.minimum(torch.tensor(float(decay), dtype=torch.float32), (1.0 + t) / (10.0 + t))
+    return 1.0 - d
+
+
 class FlatAdam(optim.Optimizer):
     """`torch.optim.Adam` (engine.py:106; L2 weight decay on the gradient, bias correction, eps outside the
     square root) as ONE launch over flat state buffers (`msgat_adam_step`, csrc/tail.hip).
@@ -486,10 +507,20 @@ class FlatAdam(optim.Optimizer):
     moves -- which is `GradScaler.step`'s behaviour and on purpose NOT `clip_grad_norm_`'s (it would scale every gradient
     by NaN).  Nothing is read back: `guard_stats()` is the only call that synchronises.  The host cannot know which
     steps were left out, so with the guard on the step counts in device memory are the truth and `state_dict()` reads
-    them back."""
+    them back.
+
+    The average (`ema_decay`, a float in [0, 1); None, the default, changes nothing here): `shadow`, one more flat buffer
+    next to the moments, starts as a copy of the parameters and is moved by the update launch itself
+    (`msgat_adam_step_averaged`, guarded or not): `e += (1 - d) * (w_new - e)` with `d = min(ema_decay, (1 + t) / (10 + t))`
+    and t the tensor's own step count -- so a tensor without a gradient keeps its shadow, a step the guard leaves out moves
+    none, and after the all-reduce every rank holds the same bits.  `swap_averaged()` exchanges parameters and shadow in
+    place (one launch, `msgat_param_swap`; twice = the identity) and `averaged_parameters()` does so around a block: whoever
+    holds the parameters' addresses -- a captured validation graph -- then reads the averaged weights.  While they are
+    swapped in, `step()`, `state_dict()` and `averaged_state()` raise: the parameters are not the trained ones.
+    `averaged_state()` / `load_averaged_state()` carry the shadow to and from checkpoints, in place."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             raise ValueError("FlatAdam takes one parameter group (the reference trains with one, engine.py:106)")
@@ -499,6 +530,10 @@ class FlatAdam(optim.Optimizer):
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self._guard = None            # [GUARD_FLOATS] fp32 on the device: norm, coef, skipped steps, largest norm, finite
         self._guard_partials = None   # one double per chunk of the whole layout
+        check_ema_decay(ema_decay)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.shadow = None            # [numel] fp32: the averaged weights (with ema_decay), in the layout of the moments
+        self.swapped = False          # True while the parameters hold the averaged weights and `shadow` the trained ones
         self._params: List[nn.Parameter] = []
         self._loaded_steps: Dict[int, float] = {}    # steps that arrived through load_state_dict, by id(param)
         self._host_steps: List[int] = []             # host mirror of the per-parameter step counts
@@ -538,6 +573,9 @@ class FlatAdam(optim.Optimizer):
             self.exp_avg_sq = torch.zeros(off, device=dev, dtype=torch.float32)
             self._dev_steps = steps.to(dev)
             self._dev_lr = torch.tensor([float(self.param_groups[0]["lr"])], device=dev)
+            if self.ema_decay is not None:
+                self.shadow = torch.empty(off, device=dev, dtype=torch.float32)
+                self.reset_average()
             self._tables.clear()
             self._gather_tables.clear()
             if self.guarded:          # here, not at the first guarded step: they exist before any capture
@@ -572,6 +610,8 @@ class FlatAdam(optim.Optimizer):
                  self._dev_steps.data_ptr(), self._dev_lr.data_ptr())
         if self.guarded:
             token += (self._guard.data_ptr(), self._guard_partials.data_ptr())
+        if self.shadow is not None:
+            token += (self.shadow.data_ptr(),)
         return token
 
     def _table(self, active: tuple):
@@ -626,6 +666,7 @@ class FlatAdam(optim.Optimizer):
         the device, and the summed weight is clamped to at least 1 before it divides -- counts are integers, so the
         clamp is exact whenever anything was valid, and a global batch without a valid entry gives a zero gradient."""
         from . import _lib
+        self._refuse_while_swapped("step()")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -658,6 +699,10 @@ class FlatAdam(optim.Optimizer):
         ptrs, offs, lens, tens, act, n, n_act = self._table(active)
         g = self.param_groups[0]
         stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
+        adam = (ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n, act.data_ptr(), n_act,
+                self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._dev_steps.data_ptr(),
+                self._dev_lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                divisor)
         if self.guarded:
             # the norm of what the update is about to consume: the flat views (one GPU) or the all-reduced sum over
             # its clamped divisor (several ranks: the same bits, hence the same decision, on every rank)
@@ -665,18 +710,15 @@ class FlatAdam(optim.Optimizer):
             st = _lib.lib().msgat_grad_guard(offs.data_ptr(), lens.data_ptr(), n, self.flat_grad.data_ptr(), divisor, max_norm,
                                              self._guard_partials.data_ptr(), self._guard.data_ptr(), stream)
             _lib.check(st, "msgat_grad_guard")
-            st = _lib.lib().msgat_adam_step_guarded(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n,
-                                                    act.data_ptr(), n_act, self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                    self.exp_avg_sq.data_ptr(), self._dev_steps.data_ptr(),
-                                                    self._dev_lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]),
-                                                    float(g["eps"]), float(g["weight_decay"]), divisor,
-                                                    self._guard.data_ptr(), stream)
+        if self.shadow is not None:       # the guarded or the plain update, and the average, in the same launch
+            st = _lib.lib().msgat_adam_step_averaged(*adam, self._guard.data_ptr() if self.guarded else 0,
+                                                     self.shadow.data_ptr(), self.ema_decay, stream)
+            _lib.check(st, "msgat_adam_step_averaged")
+        elif self.guarded:
+            st = _lib.lib().msgat_adam_step_guarded(*adam, self._guard.data_ptr(), stream)
             _lib.check(st, "msgat_adam_step_guarded")
         else:
-            st = _lib.lib().msgat_adam_step(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), tens.data_ptr(), n, act.data_ptr(),
-                                            n_act, self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                            self._dev_steps.data_ptr(), self._dev_lr.data_ptr(), float(g["betas"][0]),
-                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), divisor, stream)
+            st = _lib.lib().msgat_adam_step(*adam, stream)
             _lib.check(st, "msgat_adam_step")
         if torch.cuda.is_current_stream_capturing():
             self._captured_active = active
@@ -693,6 +735,7 @@ class FlatAdam(optim.Optimizer):
 
     # -- torch.optim.Adam's checkpoint format ------------------------------------------------------------------
     def state_dict(self):
+        self._refuse_while_swapped("state_dict()")
         if self.guarded and self._params and self.flat_grad is not None:
             # the host mirror counted every launch, the device only the steps that were not left out
             self._host_steps = [int(t) for t in self._dev_steps.tolist()]
@@ -719,6 +762,80 @@ class FlatAdam(optim.Optimizer):
         """Put the step counts (host mirror and device) back, e.g. after the warm-up iterations of a graph capture."""
         self._host_steps = list(steps)
         self._dev_steps.copy_(torch.tensor([float(t) for t in steps]))
+
+    # -- the averaged weights ------------------------------------------------------------------------------------
+    def _refuse_while_swapped(self, what: str) -> None:
+        if self.swapped:
+            raise RuntimeError(f"FlatAdam.{what} while the averaged weights are swapped in: the parameters are not the trained "
+                               f"ones (leave averaged_parameters(), or call swap_averaged() again)")
+
+    def _need_average(self) -> None:
+        if self.ema_decay is None:
+            raise RuntimeError("FlatAdam was built without ema_decay: there are no averaged weights")
+        if not self._params or self.flat_grad is None:
+            self._build()
+
+    def _shadow_views(self) -> List[torch.Tensor]:
+        return [self.shadow[o:o + p.numel()].view_as(p) for p, o in zip(self._params, self._offsets)]
+
+    @torch.no_grad()
+    def reset_average(self) -> None:
+        """Start the average at the current parameters, in place."""
+        torch._foreach_copy_(self._shadow_views(), [p.detach() for p in self._params])
+
+    def swap_averaged(self) -> None:
+        """Exchange parameters and shadow in place, bit for bit: one launch over the table of all trainable parameters."""
+        from . import _lib
+        self._need_average()
+        ptrs, offs, lens, _, _, n, _ = self._table((True,) * len(self._params))
+        stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
+        st = _lib.lib().msgat_param_swap(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, self.shadow.data_ptr(), stream)
+        _lib.check(st, "msgat_param_swap")
+        self.swapped = not self.swapped
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """`with opt.averaged_parameters():` the model computes with the averaged weights; the trained ones come back
+        when the block ends, also when it raises."""
+        self.swap_averaged()
+        try:
+            yield
+        finally:
+            self.swap_averaged()
+
+    def averaged_state(self) -> dict:
+        """{"decay": ema_decay, "shadow": {index: tensor}}: a copy of the shadow of every trainable parameter, by its index
+        in the parameter group (the indices of `state_dict()["state"]`)."""
+        self._need_average()
+        self._refuse_while_swapped("averaged_state()")
+        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        return {"decay": self.ema_decay,
+                "shadow": {index[id(p)]: e.clone() for p, e in zip(self._params, self._shadow_views())}}
+
+    @torch.no_grad()
+    def load_averaged_state(self, state: dict) -> None:
+        """Write the shadows of `state` (from `averaged_state()`) into the flat buffer, in place: captured steps keep
+        reading the same words.  Parameters that `state` does not name keep their shadow; the decay stays this optimizer's."""
+        self._need_average()
+        self._refuse_while_swapped("load_averaged_state()")
+        views = {id(p): e for p, e in zip(self._params, self._shadow_views())}
+        group = self.param_groups[0]["params"]
+        for i, tensor in state["shadow"].items():
+            views[id(group[int(i)])].copy_(tensor)
+
+    def shadow_snapshot(self):
+        """A copy of the shadow, for `shadow_restore` (None: no average, or nothing built yet)."""
+        return None if self.shadow is None else self.shadow.clone()
+
+    def shadow_restore(self, snapshot) -> None:
+        """Undo what the warm-up of a graph capture did to the shadow; without a snapshot (the warm-up built the buffers)
+        the average starts at the parameters, which the caller has put back."""
+        if self.shadow is None:
+            return
+        if snapshot is None:
+            self.reset_average()
+        else:
+            self.shadow.copy_(snapshot)
 
     # -- the guard ---------------------------------------------------------------------------------------------
     def guard_stats(self) -> Dict[str, float]:
@@ -788,6 +905,7 @@ class _GraphedStep:
                            for group in opt.param_groups for p in group["params"]}
             saved_steps = list(getattr(opt, "_host_steps", []))
             saved_guard = opt.guard_snapshot() if isinstance(opt, FlatAdam) else None
+            saved_shadow = opt.shadow_snapshot() if isinstance(opt, FlatAdam) else None
             # the warm-up forwards draw edge-dropout masks and move their stream on: put it back with the parameters, so
             # that the first replay (the capture itself executes nothing) draws the step an eager run would have drawn
             saved_drop = [(s, s.clone()) for s in _edge_dropout_streams(model)]
@@ -816,6 +934,7 @@ class _GraphedStep:
                 if isinstance(opt, FlatAdam) and step_in_graph:
                     opt.set_steps(saved_steps if saved_steps else [0] * len(opt._host_steps))
                     opt.guard_restore(saved_guard)   # a warm-up batch the guard left out counts once: at its replay
+                    opt.shadow_restore(saved_shadow)  # the parameters are back: the average the warm-up moved goes back too
                 for s, old in saved_drop:
                     s.copy_(old)
             opt.zero_grad(set_to_none=True)
@@ -883,6 +1002,9 @@ class Engine:
         self.skip_nonfinite = False
         self._cpu_guard = {"grad_norm": 0.0, "clip_coef": 1.0, "skipped_steps": 0, "grad_norm_max": 0.0}
         self._skipped_reported = 0   # the cumulative skipped count at the last end of a training epoch
+        self.ema_decay: Optional[float] = None       # the averaged weights (see Trainer); off by default
+        self._cpu_shadow: Optional[List[torch.Tensor]] = None   # the average of CPU parameters under torch.optim.Adam
+        self._cpu_swapped = False
 
     # -- helpers -------------------------------------------------------------------------
     def _device(self, gpu_id):
@@ -951,9 +1073,28 @@ class Engine:
             if self._grad_sync is None:
                 self._grad_sync = parallel.FlatGradAllReduce(self.model.parameters())
             self._grad_sync(weight=weight)
+        if self._cpu_swapped:
+            raise RuntimeError("an optimizer step while the averaged weights are swapped in: the parameters are not the trained ones")
         if self._guarded() and not self._cpu_guard_passes():
-            return
+            return                      # left out whole: the average does not move either
         self.optimizer.step()
+        if self._cpu_shadow is not None:
+            self._cpu_average()
+
+    def _trained(self) -> List[nn.Parameter]:
+        return [p for group in self.optimizer.param_groups for p in group["params"] if p.requires_grad]
+
+    @torch.no_grad()
+    def _cpu_average(self) -> None:
+        """The average in torch fp32 ops (CPU parameters under torch.optim.Adam), after the step: what `k_adam` does on the
+        GPU -- every operation rounded on its own, the clock each parameter's own step count, a parameter without a
+        gradient (which Adam skipped) left alone."""
+        for p, e in zip(self._trained(), self._cpu_shadow):
+            if p.grad is None:
+                continue
+            omd = average_rate(self.ema_decay, self.optimizer.state[p]["step"])
+            diff = p.detach() - e
+            e.copy_(e + omd * diff)
 
     def _guarded(self) -> bool:
         return self.max_grad_norm is not None or self.skip_nonfinite
@@ -1132,7 +1273,7 @@ class Trainer(Engine):
 
     def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto",
                  null_value: Optional[float] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, loss: Optional[nn.Module] = None):
+                 skip_nonfinite: bool = False, loss: Optional[nn.Module] = None, ema_decay: Optional[float] = None):
         """`loss` (default None: `HuberLoss(loss_delta, null_value)`, the reference's training loss): a `HuberLoss` or a
         `GaussLoss` instance to train with instead; `loss_delta` is then not read.  It runs in the same step tail -- one
         library pass with the metrics, masked or not, captured or not -- and takes the engine's `null_value` (or gives the
@@ -1151,6 +1292,14 @@ class Trainer(Engine):
         every gradient by NaN instead.  On the GPU all of it happens in the library, inside a captured step too
         (`FlatAdam`).  A training epoch then adds `skipped_steps` (this epoch's) and `grad_norm_max` to `last_stats` and one
         `guard` line to run.log.
+        `ema_decay` (default None: off, and then no launch, bit, key or checkpoint changes; a float in [0, 1), e.g. 0.999):
+        an exponential moving average of every trainable parameter, kept by the update itself: after a parameter's step,
+        `e += (1 - d) (w - e)`, `d = min(ema_decay, (1 + t) / (10 + t))` with t that parameter's step count.  A parameter
+        without a gradient, and every parameter in a step the guard leaves out, keeps its average.  `fit` validates on the
+        averaged weights (`averaged_parameters()`), so the best checkpoint and the logged validation loss are theirs, with
+        one more `average` log line per validation epoch; `save` adds the key `ema` = {"decay", "shadow": {name: tensor}}
+        beside the raw weights under `model`, `load` restores it in place (a checkpoint without it: the average starts at the
+        loaded parameters) and `Evaluator(weights="auto" | "raw" | "averaged")` picks the set to evaluate.
         `null_value` (default None: the reference's loss and metrics over every entry): entries of the truth that are
         NaN or equal to it are missing readings -- they drop out of the loss, its gradient and the metrics, the metrics are
         kept per forecast horizon (`last_stats["horizons"]`, one more log line per validation epoch), and under a process
@@ -1171,11 +1320,15 @@ class Trainer(Engine):
         check_max_grad_norm(max_grad_norm)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
+        check_ema_decay(ema_decay)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
         if on_gpu:
             self.optimizer = FlatAdam(model.parameters(), lr=1e-3, weight_decay=5e-4, max_grad_norm=self.max_grad_norm,
-                                      skip_nonfinite=self.skip_nonfinite)
+                                      skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay)
         else:
             self.optimizer = optim.Adam(model.parameters(), lr=1e-3, weight_decay=5e-4)
+            if self.ema_decay is not None:
+                self._cpu_shadow = [p.detach().clone() for p in self._trained()]
         self.scheduler = lr_scheduler.StepLR(self.optimizer, step_size=30, gamma=0.1)
         self.best = {"epoch": 0, "loss": float("inf"), "ckpt": ""}
         self.epoch = 1
@@ -1186,7 +1339,13 @@ class Trainer(Engine):
         train, val = data_loaders
         while self.epoch <= self.max_epochs:
             self.run_epoch(train, gpu_id=gpu_id, epoch=self.epoch, mode="train")
-            loss = self.run_epoch(val, gpu_id=gpu_id, epoch=self.epoch, mode="validate")
+            if self.ema_decay is None:
+                loss = self.run_epoch(val, gpu_id=gpu_id, epoch=self.epoch, mode="validate")
+            else:       # the validation loss, and with it the best checkpoint, are those of the averaged weights
+                with self.averaged_parameters():
+                    loss = self.run_epoch(val, gpu_id=gpu_id, epoch=self.epoch, mode="validate")
+                if self._world()[0] == 0:
+                    self.log_to_file(self.__labels__["validate"], "average", epoch=self.epoch, decay=self.ema_decay)
             self.scheduler.step()
             self._sync_lr()
             if self.epoch > self.min_epochs:
@@ -1202,18 +1361,84 @@ class Trainer(Engine):
         if isinstance(self.optimizer, FlatAdam):
             self.optimizer.sync_lr()   # a captured update reads the rate from device memory
 
+    # -- the averaged weights ------------------------------------------------------------------------------------
+    def _need_average(self) -> None:
+        if self.ema_decay is None:
+            raise RuntimeError("Trainer was built without ema_decay: there are no averaged weights")
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """`with trainer.averaged_parameters():` the model holds the averaged weights, exchanged with the trained ones in
+        place -- on the GPU by `FlatAdam.swap_averaged()`, so captured validation graphs need no recapture -- and gets the
+        trained ones back when the block ends, also when it raises.  No optimizer step inside."""
+        self._need_average()
+        if isinstance(self.optimizer, FlatAdam):
+            with self.optimizer.averaged_parameters():
+                yield
+            return
+        self._cpu_swap()
+        try:
+            yield
+        finally:
+            self._cpu_swap()
+
+    @torch.no_grad()
+    def _cpu_swap(self) -> None:
+        for p, e in zip(self._trained(), self._cpu_shadow):
+            kept = p.detach().clone()
+            p.copy_(e)
+            e.copy_(kept)
+        self._cpu_swapped = not self._cpu_swapped
+
+    def _named_trained(self) -> List[Tuple[str, int]]:
+        """(name in the model, index in the optimizer's group) of every trainable parameter, in the optimizer's order."""
+        names = {id(p): name for name, p in self.model.named_parameters()}
+        group = self.optimizer.param_groups[0]["params"]
+        return [(names[id(p)], i) for i, p in enumerate(group) if p.requires_grad]
+
+    def averaged_state(self) -> dict:
+        """{"decay": ema_decay, "shadow": {parameter name: tensor}}: what `save` writes under `ema`."""
+        self._need_average()
+        if isinstance(self.optimizer, FlatAdam):
+            shadow = self.optimizer.averaged_state()["shadow"]
+            return {"decay": self.ema_decay, "shadow": {name: shadow[i] for name, i in self._named_trained()}}
+        if self._cpu_swapped:
+            raise RuntimeError("averaged_state() while the averaged weights are swapped in")
+        return {"decay": self.ema_decay,
+                "shadow": {name: e.clone() for (name, _), e in zip(self._named_trained(), self._cpu_shadow)}}
+
+    @torch.no_grad()
+    def _load_average(self, state: Optional[dict]) -> None:
+        """The shadow from a checkpoint's `ema` entry, in place; None (a checkpoint of a run without the average): the
+        average starts at the parameters just loaded."""
+        named = self._named_trained()
+        if isinstance(self.optimizer, FlatAdam):
+            if state is None:
+                self.optimizer._need_average()
+                self.optimizer.reset_average()
+            else:
+                shadow = strip_data_parallel_prefix(state["shadow"])
+                self.optimizer.load_averaged_state({"shadow": {i: shadow[strip_prefix(name)] for name, i in named}})
+            return
+        for (name, _), p, e in zip(named, self._trained(), self._cpu_shadow):
+            e.copy_(p.detach() if state is None else strip_data_parallel_prefix(state["shadow"])[strip_prefix(name)])
+
     def save(self, ckpt) -> None:
         """The reference's five keys (engine.py:135-146).  `grad_scaler` holds the state of a default-constructed,
         enabled GradScaler -- this build trains in fp32 and never scales, but the reference's `load` feeds that entry
         to `GradScaler.load_state_dict`, which rejects an empty dict (engine.py:155).  A model that drops edges
         (`MSGAT(edge_dropout=p)`) adds a sixth key, `edge_dropout` = {seed, step} of its mask stream, which is no
-        `state_dict` entry; every other model's checkpoint keeps the five."""
+        `state_dict` entry; every other model's checkpoint keeps the five.  With `ema_decay` set one more key, `ema` =
+        {"decay", "shadow": {parameter name: tensor}}, holds the averaged weights; `model` stays the raw ones, which
+        resuming needs and the reference's loader reads."""
         states = dict(best=self.best, epoch=self.epoch, model=self.model.state_dict(),
                       optimizer=self.optimizer.state_dict(), scheduler=self.scheduler.state_dict(),
                       grad_scaler=default_grad_scaler_state())
         dropper = _edge_dropout_owner(self.model)
         if dropper is not None:
             states["edge_dropout"] = dropper.edge_dropout_state()
+        if self.ema_decay is not None:
+            states["ema"] = self.averaged_state()
         torch.save(states, ckpt)
 
     def load(self, ckpt) -> None:
@@ -1227,6 +1452,8 @@ class Trainer(Engine):
         dropper = _edge_dropout_owner(self.model)
         if dropper is not None and states.get("edge_dropout") is not None:
             dropper.set_edge_dropout_state(states["edge_dropout"])      # in place: captured steps read the same words
+        if self.ema_decay is not None:
+            self._load_average(states.get("ema"))
         self._sync_lr()
         if isinstance(self.optimizer, FlatAdam) and token and token != self.optimizer.buffer_token():
             self._graphs.clear()            # the optimizer's buffers moved: captured steps point at the old ones
@@ -1240,15 +1467,30 @@ def default_grad_scaler_state() -> dict:
 
 class Evaluator(Engine):
     def __init__(self, model: nn.Module, delta: float, out_dir: str, ckpt, hip_graph="auto",
-                 null_value: Optional[float] = None, loss: Optional[nn.Module] = None):
+                 null_value: Optional[float] = None, loss: Optional[nn.Module] = None, weights: str = "auto"):
         # null_value, loss: see Trainer (with `loss` given, `delta` is not read)
+        # weights: "auto" -- the averaged weights where the checkpoint has them (its `ema` key, Trainer(ema_decay=...)),
+        # else the raw ones; "raw" -- always `model`; "averaged" -- KeyError without the `ema` key
+        if weights not in ("auto", "raw", "averaged"):
+            raise ValueError(f"weights must be 'auto', 'raw' or 'averaged', not {weights!r}")
         super().__init__(model, loss_delta=delta, out_dir=out_dir, null_value=null_value, loss=loss)
         states = torch.load(ckpt, map_location=next(model.parameters()).device, weights_only=False)
-        model.load_state_dict(strip_data_parallel_prefix(states["model"]))
+        if weights == "averaged" and states.get("ema") is None:
+            raise KeyError(f"{ckpt}: no 'ema' key -- the checkpoint was written without averaged weights (Trainer(ema_decay=...))")
+        state = dict(states["model"])
+        self.weights = "raw"
+        if weights != "raw" and states.get("ema") is not None:
+            state.update(states["ema"]["shadow"])       # the trainable parameters; buffers and frozen ones stay
+            self.weights = "averaged"
+        model.load_state_dict(strip_data_parallel_prefix(state))
         self.hip_graph = hip_graph if next(model.parameters()).is_cuda else False   # see Trainer
 
     def eval(self, data_loader, gpu_id=None) -> float:
         return self.run_epoch(data_loader, gpu_id=gpu_id, mode="evaluate")
+
+
+def strip_prefix(name: str) -> str:
+    return name[len("module."):] if name.startswith("module.") else name
 
 
 def strip_data_parallel_prefix(state_dict):
