@@ -63,7 +63,8 @@ extern "C" {
  *     + msgat_window_gather_imputed (the input windows with missing readings filled in and a validity channel);
  *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail);
  *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory);
- *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update).
+ *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update);
+ *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -966,6 +967,24 @@ int msgat_adam_step_averaged(float* const* chunk_param, const int64_t* chunk_off
                              const float* grad_divisor, const float* guard, float* shadow, double decay, void* stream);
 int msgat_param_swap(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
                      float* flat, void* stream);
+
+/* ---- device: gradient accumulation (off unless a caller uses these two) -------------------------------------------------
+ * A window of k micro-batches is one optimizer step on their union: the first micro-batch enters the flat buffer through
+ * msgat_gather_scaled{,_dev} (which overwrites: no zeroing pass), every later one through
+ * msgat_gather_accumulate: one launch, one block per chunk of the same chunk table,
+ *         flat[chunk_off[c] + i] = flat[chunk_off[c] + i] + scale * chunk_src[c][i]
+ *         flat[weight_index]     = flat[weight_index] + scale                              (block 0; weight_index >= 0)
+ *     with the product and the sum each rounded on its own in fp32 (no fma, no contraction): the buffer after two
+ *     micro-batches has the bits of a two-rank all-reduce sum of the same two scaled gradients, and a float32 restatement
+ *     gives them too.  No atomics, one fixed order; elements outside the table's chunks are neither read nor written.
+ *     The update then divides by flat[weight_index] on the way in (grad_divisor of msgat_adam_step*).
+ * msgat_gather_accumulate_dev: the same with the scale read from device memory (scale[0]: the valid count of a masked
+ *     micro-batch, never read back).
+ * Arguments, NULL and shape checks (before anything is enqueued) as msgat_gather_scaled / msgat_gather_scaled_dev. */
+int msgat_gather_accumulate(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                            int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream);
+int msgat_gather_accumulate_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                                int32_t n_chunks, const float* scale, float* flat, int64_t weight_index, void* stream);
 
 /* ---- device: the input windows of a batch (replaces data_loader.py:92-115, TimeSeriesSlice, and the host collate) ----
  * msgat_window_gather: one launch builds the batch of B forecast origins from a series that stays in device memory.

@@ -183,6 +183,8 @@ _PROTOTYPES = {
     "msgat_adam_step_averaged": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
                                  + [C.c_double] * 4 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p]),
     "msgat_param_swap": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "msgat_gather_accumulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "msgat_gather_accumulate_dev": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msgat_gauss_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 3
                             + [C.c_float, C.c_void_p]),
     "msgat_gauss_grad": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),

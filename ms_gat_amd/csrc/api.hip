@@ -1262,6 +1262,24 @@ extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int6
                                   (hipStream_t)stream);
 }
 
+// ---- gradient accumulation: a later micro-batch of a window, added into the flat buffer (the siblings' checks) ---------
+extern "C" int msgat_gather_accumulate(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                                       int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
+  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
+  if (!chunk_src || !chunk_off || !chunk_len || !flat) return MSGAT_ERR_NULL;
+  return launch_gather_accumulate(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat, weight_index,
+                                  (hipStream_t)stream);
+}
+
+extern "C" int msgat_gather_accumulate_dev(const float* const* chunk_src, const int64_t* chunk_off,
+                                           const int32_t* chunk_len, int32_t n_chunks, const float* scale, float* flat,
+                                           int64_t weight_index, void* stream) {
+  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
+  if (!chunk_src || !chunk_off || !chunk_len || !scale || !flat) return MSGAT_ERR_NULL;
+  return launch_gather_accumulate_dev(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat,
+                                      weight_index, (hipStream_t)stream);
+}
+
 // ---- quantile forecasts in the step tail: pinball loss, point metrics, coverage / width / crossing sums ----------------
 // limits first (they bound the loop over `levels`), then the levels themselves; nothing is launched on a refusal
 static int check_quantile(int64_t rows, int32_t T_out, int32_t Q, const float* levels) {

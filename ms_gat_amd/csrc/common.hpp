@@ -551,6 +551,11 @@ int launch_masked_gauss_grad(const float* pred, const float* truth, const float*
                              hipStream_t s);
 int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
                              const float* scale, float* flat, long long weight_index, hipStream_t s);
+// gradient accumulation: flat += scale * src on the same chunk tables, flat[weight_index] += scale
+int launch_gather_accumulate(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
+                             float scale, float* flat, long long weight_index, hipStream_t s);
+int launch_gather_accumulate_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len,
+                                 int nchunks, const float* scale, float* flat, long long weight_index, hipStream_t s);
 // quantile forecasts: pred [rows, Q, T], truth [rows, T], levels [Q] on the host (checked by the caller)
 size_t quantile_partial_doubles(long long rows, int T, int Q);
 int launch_quantile_metrics(const float* pred, const float* truth, long long rows, int T, int Q, const float* levels,

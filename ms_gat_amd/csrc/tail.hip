@@ -942,4 +942,59 @@ int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chu
   return MSGAT_OK;
 }
 
+// ---- gradient accumulation: a later micro-batch of a window is added into the flat buffer ----------------------------
+// flat[chunk_off[c] + i] = flat[chunk_off[c] + i] + scale * chunk_src[c][i]; block 0 also does flat[weight_index] +=
+// scale.  The first micro-batch of a window is k_gather_scaled (it overwrites: no zeroing pass), every later one comes
+// through here, so after k micro-batches the buffer holds sum(w g) and sum(w) in call order -- what the all-reduce of
+// k ranks would have summed.  The product and the sum are rounded one after the other in fp32 (contraction off, as in
+// average_move: an fma would round once), which is what makes two accumulated micro-batches bit-equal to the two-rank
+// all-reduce sum of the same two gradients, and a numpy float32 restatement bit-equal to both.  Every element is read
+// and written by one lane of one block, block 0's lane 0 alone touches the weight: no atomics, one fixed order.
+// Parameter views and flat offsets are 4-byte aligned only: scalar accesses, as in k_gather_scaled.
+__device__ __forceinline__ void accumulate_chunk(const float* __restrict__ src, float* __restrict__ dst, int len,
+                                                 float scale) {
+#pragma clang fp contract(off)
+  for (int i = threadIdx.x; i < len; i += kTailBlock) {
+    const float term = scale * src[i];
+    dst[i] = dst[i] + term;
+  }
+}
+
+__global__ __launch_bounds__(kTailBlock) void k_gather_accumulate(const float* const* __restrict__ chunk_src,
+                                                                  const long long* __restrict__ chunk_off,
+                                                                  const int* __restrict__ chunk_len, float scale,
+                                                                  float* __restrict__ flat, long long weight_index) {
+  const int c = blockIdx.x;
+  accumulate_chunk(chunk_src[c], flat + chunk_off[c], chunk_len[c], scale);
+  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] += scale;
+}
+
+// the scale read from device memory: the valid count of a masked micro-batch is never read back
+__global__ __launch_bounds__(kTailBlock) void k_gather_accumulate_dev(const float* const* __restrict__ chunk_src,
+                                                                      const long long* __restrict__ chunk_off,
+                                                                      const int* __restrict__ chunk_len,
+                                                                      const float* __restrict__ scale,
+                                                                      float* __restrict__ flat, long long weight_index) {
+  const int c = blockIdx.x;
+  const float sc = scale[0];
+  accumulate_chunk(chunk_src[c], flat + chunk_off[c], chunk_len[c], sc);
+  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] += sc;
+}
+
+int launch_gather_accumulate(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
+                             float scale, float* flat, long long weight_index, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_accumulate, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
+                     flat, weight_index);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
+int launch_gather_accumulate_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len,
+                                 int nchunks, const float* scale, float* flat, long long weight_index, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_accumulate_dev, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
+                     flat, weight_index);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+
 }  // namespace msgat

@@ -32,6 +32,9 @@ Differences that are the point of this build:
     guard leaves out, bit-identical across ranks.  `fit` validates -- and so picks its best checkpoint -- on the averaged
     weights, exchanged with the parameters in place by one launch (`msgat_param_swap`), so captured validation graphs read
     them at the addresses they hold; checkpoints gain an `ema` key and `Evaluator(weights=...)` chooses which set to load.
+  * `accumulate_steps=k` (1, off, by default) takes one optimizer step per window of k batches: every micro-batch is added
+    into the flat gradient buffer with the weight a rank would have (`msgat_gather_accumulate`), the last one's step
+    divides by the summed weight -- one step on the union of the window, one collective per window under a process group.
   * `hip_graph="auto"` (the default on the GPU) captures a step in a HIP graph once its batch shape recurs and replays it.
 CPU tensors (the host-logic tests run a small CPU `nn.Module` through this loop) take plain PyTorch
 ops for loss and optimizer; the library has no CPU path.
@@ -478,6 +481,11 @@ def check_ema_decay(ema_decay) -> None:
         raise ValueError(f"ema_decay must be a float in [0, 1) or None, not {ema_decay!r}")
 
 
+def check_accumulate_steps(accumulate_steps) -> None:
+    if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, int) or accumulate_steps < 1:
+        raise ValueError(f"accumulate_steps must be an int >= 1, not {accumulate_steps!r}")
+
+
 def average_rate(decay: float, step) -> torch.Tensor:
     """1 - d of the averaged weights, d = min(decay, (1 + t) / (10 + t)) at the (already advanced) step count t: three
     separately rounded fp32 operations, as `k_adam` takes them (csrc/tail.hip)."""
@@ -517,7 +525,17 @@ class FlatAdam(optim.Optimizer):
     place (one launch, `msgat_param_swap`; twice = the identity) and `averaged_parameters()` does so around a block: whoever
     holds the parameters' addresses -- a captured validation graph -- then reads the averaged weights.  While they are
     swapped in, `step()`, `state_dict()` and `averaged_state()` raise: the parameters are not the trained ones.
-    `averaged_state()` / `load_averaged_state()` carry the shadow to and from checkpoints, in place."""
+    `averaged_state()` / `load_averaged_state()` carry the shadow to and from checkpoints, in place.
+
+    Gradient accumulation (`accumulate(weight)`; never called: nothing here changes): a window of k micro-batches is ONE
+    step on their union.  `accumulate(w)` adds `w * p.grad` into the flat buffer and `w` into its last element -- the first
+    micro-batch of a window through the overwriting gather, later ones through `msgat_gather_accumulate{,_dev}` (product
+    and sum rounded one after the other: the bits of an all-reduce sum over as many ranks) -- and `step(rank_weight=w)`
+    adds the last one and closes the window: the all-reduce (several ranks: one collective per window), the clamp of the
+    summed weight (device counts), then guard, update and average as the data-parallel step has them, dividing by the
+    summed weight on the way in.  Step counts, the average and the guard move once per window; the guard sees the norm of
+    the window's mean gradient, so one non-finite micro-batch leaves the whole window out.  `pending` counts the open
+    window's micro-batches; while it is not 0, `state_dict()`, `swap_averaged()` and `averaged_state()` raise."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None):
@@ -544,6 +562,10 @@ class FlatAdam(optim.Optimizer):
         self._last_active: Optional[tuple] = None
         self.flat_grad = None
         self.numel = -1
+        self._pending = 0                            # micro-batches in the open accumulation window
+        self._window_active: Optional[tuple] = None  # the active set of the window's first micro-batch
+        self._window_on_device = False               # the window's weights are device counts (clamped when it closes)
+        self.param_names: Dict[int, str] = {}        # id(param) -> name, for messages (Trainer fills it in)
 
     # -- flat buffers ----------------------------------------------------------------------------------------
     def _build(self) -> None:
@@ -640,10 +662,73 @@ class FlatAdam(optim.Optimizer):
             self._tables[key] = hit       # never evicted: a captured step may hold the addresses of an older table
         return hit
 
-    def _gather(self, grads: List[torch.Tensor], active: tuple, weight) -> None:
-        """flat = weight * gradients, flat[-1] = weight, in ONE launch (`parallel.gather_scaled`)."""
+    def _gather(self, grads: List[torch.Tensor], active: tuple, weight, accumulate: bool = False) -> None:
+        """flat = weight * gradients, flat[-1] = weight, in ONE launch (`parallel.gather_scaled`); `accumulate`: added to
+        what the buffer holds instead (a later micro-batch of a window)."""
         offsets = [o for o, on in zip(self._offsets, active) if on]
-        parallel.gather_scaled(self.flat_grad, grads, offsets, weight, self.numel, self._gather_tables)
+        parallel.gather_scaled(self.flat_grad, grads, offsets, weight, self.numel, self._gather_tables, accumulate=accumulate)
+
+    # -- gradient accumulation ---------------------------------------------------------------------------------
+    @property
+    def pending(self) -> int:
+        """The number of micro-batches in the open accumulation window (0: none is open)."""
+        return self._pending
+
+    def _refuse_while_pending(self, what: str) -> None:
+        if self._pending:
+            raise RuntimeError(f"FlatAdam.{what} while an accumulation window is open ({self._pending} micro-batch(es) "
+                               f"pending): close it with step() first")
+
+    def _name(self, i: int) -> str:
+        p = self._params[i]
+        return self.param_names.get(id(p), f"parameter {i} of shape {tuple(p.shape)}")
+
+    def _add_micro_batch(self, weight, several_ranks: bool) -> None:
+        """The current gradients, times `weight`, into the window: the first micro-batch through the overwriting gather
+        (no zeroing pass), a later one through the accumulating gather, the weight into the buffer's last element."""
+        active = tuple(p.grad is not None for p in self._params)
+        grads = [p.grad for p in self._params if p.grad is not None]
+        on_device = torch.is_tensor(weight)
+        first = self._pending == 0
+        if first:
+            if several_ranks and active != self._last_active:
+                self.flat_grad.zero_()           # parameters without a gradient contribute zeros on every rank
+            self._window_active, self._window_on_device = active, on_device
+        else:
+            if active != self._window_active:
+                i = next(j for j, (a, b) in enumerate(zip(active, self._window_active)) if a != b)
+                raise RuntimeError(
+                    f"gradient accumulation: {self._name(i)} {'has a' if active[i] else 'has no'} gradient in micro-batch "
+                    f"{self._pending + 1} of the window but {'had none' if active[i] else 'had one'} in its first: a window's "
+                    f"set of parameters with a gradient is that of its first micro-batch")
+            if on_device != self._window_on_device:
+                raise ValueError("gradient accumulation: the weights of one window are all floats (sample counts) or all "
+                                 "one-element device tensors (valid counts)")
+        if grads:
+            self._gather(grads, active, weight if on_device else float(weight), accumulate=not first)
+        else:
+            slot = self.flat_grad[self.numel:]       # no gradient anywhere: the weight alone
+            if not first:
+                slot.add_(weight.reshape(1) if on_device else float(weight))
+            elif on_device:
+                slot.copy_(weight.reshape(1))
+            else:
+                slot.fill_(float(weight))
+        self._pending += 1
+
+    @torch.no_grad()
+    def accumulate(self, weight) -> None:
+        """Add the current `p.grad` of every trained parameter, times `weight`, into the open accumulation window (opening
+        one if none is).  `weight`: this micro-batch's sample count (a float) or its valid count (a one-element float32
+        device tensor, read where it lives).  Nothing is updated: `step()` closes the window."""
+        self._refuse_while_swapped("accumulate()")
+        if not self._params or self.flat_grad is None or self._params[0].device != self.flat_grad.device:
+            self._build()
+        self._add_micro_batch(weight, dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+
+    def drop_window(self) -> None:
+        """Forget the open window (after an error inside it): the next micro-batch opens a new one, which overwrites."""
+        self._pending, self._window_active = 0, None
 
     def sync_lr(self) -> None:
         """Write the group's learning rate (a host float the scheduler edits) into device memory when it changed."""
@@ -664,7 +749,10 @@ class FlatAdam(optim.Optimizer):
         uneven shards -- before the update, in the one collective of the step.
         A one-element float32 device tensor is accepted too (the valid count of a masked batch): the gather reads it on
         the device, and the summed weight is clamped to at least 1 before it divides -- counts are integers, so the
-        clamp is exact whenever anything was valid, and a global batch without a valid entry gives a zero gradient."""
+        clamp is exact whenever anything was valid, and a global batch without a valid entry gives a zero gradient.
+        With an accumulation window open (`accumulate`) the current gradients are its last micro-batch, weighted by
+        `rank_weight`, and the window closes: one step on the union of its micro-batches.  `rank_weight=None` then
+        closes the window as it stands, without adding anything."""
         from . import _lib
         self._refuse_while_swapped("step()")
         loss = None
@@ -676,7 +764,21 @@ class FlatAdam(optim.Optimizer):
         active = tuple(p.grad is not None for p in self._params)
         grads = [p.grad for p in self._params if p.grad is not None]
         divisor = 0
-        if rank_weight is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        several_ranks = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if self._pending:
+            # an accumulation window is open: the current gradients are its last micro-batch (rank_weight None: nothing
+            # is added, the window closes as it stands -- the shorter last window of an epoch).  Then the collective,
+            # the clamp and the divisor exactly as the data-parallel step below has them: flat = sum(w g), last = sum(w)
+            if rank_weight is not None:
+                self._add_micro_batch(rank_weight, several_ranks)
+            active = self._window_active
+            if several_ranks:
+                parallel.all_reduce_flat(self.flat_grad)
+            if self._window_on_device:
+                self.flat_grad[self.numel:].clamp_(min=1.0)
+            divisor = self.flat_grad.data_ptr() + 4 * self.numel
+            self._pending, self._window_active = 0, None
+        elif rank_weight is not None and several_ranks:
             # one launch before the collective (gather, scaled by the rank's weight, which also rides in the last
             # element) and one after it (the update divides by the summed weight on the way in)
             if active != self._last_active:
@@ -736,6 +838,7 @@ class FlatAdam(optim.Optimizer):
     # -- torch.optim.Adam's checkpoint format ------------------------------------------------------------------
     def state_dict(self):
         self._refuse_while_swapped("state_dict()")
+        self._refuse_while_pending("state_dict()")
         if self.guarded and self._params and self.flat_grad is not None:
             # the host mirror counted every launch, the device only the steps that were not left out
             self._host_steps = [int(t) for t in self._dev_steps.tolist()]
@@ -787,6 +890,7 @@ class FlatAdam(optim.Optimizer):
         """Exchange parameters and shadow in place, bit for bit: one launch over the table of all trainable parameters."""
         from . import _lib
         self._need_average()
+        self._refuse_while_pending("swap_averaged()")
         ptrs, offs, lens, _, _, n, _ = self._table((True,) * len(self._params))
         stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
         st = _lib.lib().msgat_param_swap(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, self.shadow.data_ptr(), stream)
@@ -808,6 +912,7 @@ class FlatAdam(optim.Optimizer):
         in the parameter group (the indices of `state_dict()["state"]`)."""
         self._need_average()
         self._refuse_while_swapped("averaged_state()")
+        self._refuse_while_pending("averaged_state()")
         index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
         return {"decay": self.ema_decay,
                 "shadow": {index[id(p)]: e.clone() for p, e in zip(self._params, self._shadow_views())}}
@@ -1005,6 +1110,8 @@ class Engine:
         self.ema_decay: Optional[float] = None       # the averaged weights (see Trainer); off by default
         self._cpu_shadow: Optional[List[torch.Tensor]] = None   # the average of CPU parameters under torch.optim.Adam
         self._cpu_swapped = False
+        self.accumulate_steps = 1    # micro-batches per optimizer step (see Trainer); 1: every batch is a step
+        self._cpu_window: Optional[list] = None      # [accumulators sum(w g) per trained parameter, sum(w), count]
 
     # -- helpers -------------------------------------------------------------------------
     def _device(self, gpu_id):
@@ -1061,14 +1168,70 @@ class Engine:
             self._valid_count = torch.zeros(1, device=device, dtype=torch.float32)
         return self._valid_count
 
-    def _optimizer_step(self, n_samples: int, world: int) -> None:
+    def _step_weight(self, n_samples: int):
         # a rank's weight in the gradient mean: its sample count, or -- entries dropping out of a masked loss -- its
         # batch's valid count, which is in device memory: sum_r v_r g_r / sum_r v_r is the gradient of the global
         # masked mean for any split
-        weight = float(n_samples) if self.null_value is None else self._valid_count
+        return float(n_samples) if self.null_value is None else self._valid_count
+
+    def _optimizer_step(self, n_samples: int, world: int) -> None:
+        weight = self._step_weight(n_samples)
         if isinstance(self.optimizer, FlatAdam):
             self.optimizer.step(rank_weight=weight if world > 1 else None)
             return
+        self._cpu_step(weight, world)
+
+    def _window_step(self, n_samples: Optional[int], world: int, close: bool) -> None:
+        """One micro-batch of an accumulation window (`accumulate_steps` > 1), weighted like a rank of a data-parallel
+        step; `close`: it is the window's last, the optimizer steps.  `n_samples` None: no micro-batch, only the closing
+        of the shorter window an epoch ends with."""
+        weight = None if n_samples is None else self._step_weight(n_samples)
+        if isinstance(self.optimizer, FlatAdam):
+            if close:
+                self.optimizer.step(rank_weight=weight)
+            else:
+                self.optimizer.accumulate(weight)
+            return
+        if weight is not None:
+            self._cpu_accumulate(weight)
+        if close:
+            total = self._cpu_close_window()
+            self._cpu_step(total, world)
+
+    @torch.no_grad()
+    def _cpu_accumulate(self, weight) -> None:
+        """The window in torch fp32 ops (CPU parameters under torch.optim.Adam): one accumulator per trained parameter,
+        acc = acc + w * g with the product and the sum rounded one after the other, as the library's gather does."""
+        params = self._trained()
+        if self._cpu_window is None:
+            self._cpu_window = [[None if p.grad is None else weight * p.grad for p in params], weight, 1]
+            return
+        accs = self._cpu_window[0]
+        names = {id(p): name for name, p in self.model.named_parameters()}
+        for i, p in enumerate(params):
+            if (p.grad is None) != (accs[i] is None):
+                raise RuntimeError(
+                    f"gradient accumulation: {names.get(id(p), i)} {'has no' if p.grad is None else 'has a'} gradient in "
+                    f"micro-batch {self._cpu_window[2] + 1} of the window, unlike in its first: a window's set of parameters "
+                    f"with a gradient is that of its first micro-batch")
+        for i, p in enumerate(params):
+            if accs[i] is not None:
+                accs[i] = accs[i] + weight * p.grad
+        self._cpu_window[1] = self._cpu_window[1] + weight
+        self._cpu_window[2] += 1
+
+    @torch.no_grad()
+    def _cpu_close_window(self):
+        """p.grad = sum(w g) / max(sum w, 1): the window's mean gradient, in front of the all-reduce, the guard and
+        `optimizer.step()`.  Returns sum w, this rank's weight in the gradient mean over ranks."""
+        accs, total, _ = self._cpu_window
+        self._cpu_window = None
+        divisor = total.clamp(min=1.0) if torch.is_tensor(total) else max(total, 1.0)
+        for p, a in zip(self._trained(), accs):
+            p.grad = None if a is None else a / divisor
+        return total
+
+    def _cpu_step(self, weight, world: int) -> None:
         if world > 1:
             if self._grad_sync is None:
                 self._grad_sync = parallel.FlatGradAllReduce(self.model.parameters())
@@ -1165,6 +1328,11 @@ class Engine:
         if guarded:
             self._reset_guard_max()
         dropper = _edge_dropout_owner(self.model) if training and world > 1 else None
+        # gradient accumulation: micro-batches 1 .. k-1 of a window are accumulated, the k-th steps; the update then stays
+        # outside a captured step, as with several ranks (the graph ends after backward)
+        window = self.accumulate_steps if training else 1
+        step_in_graph = world == 1 and window == 1
+        in_window = optimizer_steps = 0
         with guard, torch.set_grad_enabled(training):
             for batch in data:
                 n_global = batch[0].shape[0]
@@ -1200,11 +1368,11 @@ class Engine:
                         # capture (hipStreamEndCapture crashes) -- the previous iteration's `loss` / `pred` do exactly that
                         pred = loss = None
                         with torch.enable_grad():
-                            graphed = self._graphs[key] = _GraphedStep(self, batch, training, step_in_graph=world == 1,
+                            graphed = self._graphs[key] = _GraphedStep(self, batch, training, step_in_graph=step_in_graph,
                                                                        loss_weight=loss_weight)
                 if graphed is not None:
                     pred, loss, truth = graphed.replay(batch)
-                    if training and world == 1 and isinstance(self.optimizer, FlatAdam):
+                    if training and step_in_graph and isinstance(self.optimizer, FlatAdam):
                         self.optimizer.note_replayed_step()
                 else:
                     pred = self.model(*inputs)
@@ -1212,15 +1380,25 @@ class Engine:
                     if training:
                         self.optimizer.zero_grad(set_to_none=True)
                         loss.backward()
-                if training and (world > 1 or graphed is None):
+                if training and window > 1:
+                    in_window += 1
+                    self._window_step(truth.shape[0], world, close=in_window == window)
+                    if in_window == window:
+                        in_window, optimizer_steps = 0, optimizer_steps + 1
+                elif training and (not step_in_graph or graphed is None):
                     self._optimizer_step(truth.shape[0], world)
                 metrics.count(truth)
+            if in_window:       # the batch count was no multiple of the window: no gradient outlives the epoch
+                self._window_step(None, world, close=True)
+                optimizer_steps += 1
         if world > 1:
             if metrics._sums is None and self.null_value is None:
                 metrics.totals(device)
             metrics.all_reduce()
         loss_ave = metrics.loss
         stats = {"loss": loss_ave, **metrics.todict()}
+        if window > 1:
+            stats["optimizer_steps"] = optimizer_steps
         horizons = None if self.null_value is None else metrics.per_horizon()
         quantiles = metrics.quantile_summary() if isinstance(self.loss_fn, QuantileLoss) else None
         if rank == 0:
@@ -1273,7 +1451,8 @@ class Trainer(Engine):
 
     def __init__(self, model: nn.Module, loss_delta: float, out_dir: str, hip_graph="auto",
                  null_value: Optional[float] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, loss: Optional[nn.Module] = None, ema_decay: Optional[float] = None):
+                 skip_nonfinite: bool = False, loss: Optional[nn.Module] = None, ema_decay: Optional[float] = None,
+                 accumulate_steps: int = 1):
         """`loss` (default None: `HuberLoss(loss_delta, null_value)`, the reference's training loss): a `HuberLoss` or a
         `GaussLoss` instance to train with instead; `loss_delta` is then not read.  It runs in the same step tail -- one
         library pass with the metrics, masked or not, captured or not -- and takes the engine's `null_value` (or gives the
@@ -1300,6 +1479,17 @@ class Trainer(Engine):
         one more `average` log line per validation epoch; `save` adds the key `ema` = {"decay", "shadow": {name: tensor}}
         beside the raw weights under `model`, `load` restores it in place (a checkpoint without it: the average starts at the
         loaded parameters) and `Evaluator(weights="auto" | "raw" | "averaged")` picks the set to evaluate.
+        `accumulate_steps` (default 1: every batch is a step, and no launch, bit, key or log line changes; an int >= 1):
+        gradient accumulation -- k consecutive batches of a training epoch are the micro-batches of one window and ONE
+        optimizer step on their union: each is weighted like a rank of a data-parallel step (its sample count, or its valid
+        count under `null_value`), micro-batches 1 to k-1 are added into the optimizer's flat buffer
+        (`FlatAdam.accumulate`), the k-th steps (`FlatAdam.step`), which divides by the summed weight.  The model has no
+        batch statistics, so this is the step of a k times larger batch at the activation memory of one.  Step counts, the
+        guard (one non-finite micro-batch leaves the whole window out) and the averaged weights move once per window, and
+        under a process group the collective runs once per window.  An epoch whose batch count is no multiple of k closes
+        its last, shorter window at its end: no gradient crosses validation, an epoch boundary or `save`.  Captured steps end
+        after backward, as with several ranks, and the window's tail is launched eagerly.  `last_stats` and the train log
+        line gain `optimizer_steps`.  CPU parameters get the same semantics in torch ops.
         `null_value` (default None: the reference's loss and metrics over every entry): entries of the truth that are
         NaN or equal to it are missing readings -- they drop out of the loss, its gradient and the metrics, the metrics are
         kept per forecast horizon (`last_stats["horizons"]`, one more log line per validation epoch), and under a process
@@ -1322,9 +1512,12 @@ class Trainer(Engine):
         self.skip_nonfinite = bool(skip_nonfinite)
         check_ema_decay(ema_decay)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
+        check_accumulate_steps(accumulate_steps)
+        self.accumulate_steps = accumulate_steps
         if on_gpu:
             self.optimizer = FlatAdam(model.parameters(), lr=1e-3, weight_decay=5e-4, max_grad_norm=self.max_grad_norm,
                                       skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay)
+            self.optimizer.param_names = {id(p): name for name, p in model.named_parameters()}
         else:
             self.optimizer = optim.Adam(model.parameters(), lr=1e-3, weight_decay=5e-4)
             if self.ema_decay is not None:

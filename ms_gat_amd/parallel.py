@@ -147,12 +147,15 @@ def _device_weight(weight: torch.Tensor, device) -> torch.Tensor:
 
 
 def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Sequence[int], weight,
-                  weight_index: int, cache: dict) -> None:
+                  weight_index: int, cache: dict, accumulate: bool = False) -> None:
     """flat[offsets[i] : ...] = weight * grads[i] for every gradient and flat[weight_index] = weight, in ONE launch
     (`msgat_gather_scaled`, csrc/tail.hip).  `cache` keeps one persistent device table per gradient layout
     (`_GatherTable`): a replayed HIP graph or a warm caching allocator hands out the same pointers step after step and
     nothing is uploaded; new pointers cost one asynchronous copy from pinned memory.
-    `weight`: a float, or a one-element float32 device tensor that the launch reads (`msgat_gather_scaled_dev`)."""
+    `weight`: a float, or a one-element float32 device tensor that the launch reads (`msgat_gather_scaled_dev`).
+    `accumulate=True`: a later micro-batch of an accumulation window -- the same table, the same re-pointing rules, but
+    the launch (`msgat_gather_accumulate{,_dev}`) ADDS: flat[...] = flat[...] + weight * grads[i] (product and sum rounded
+    one after the other) and flat[weight_index] += weight."""
     from . import _lib
     keep = [g if g.is_contiguous() else g.contiguous() for g in grads]
     key = (tuple(g.numel() for g in keep), tuple(offsets))
@@ -160,16 +163,19 @@ def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Se
     if table is None:
         table = cache[key] = _GatherTable(key[0], key[1], flat.device)
     table.point_at(tuple(g.data_ptr() for g in keep))
+    L = _lib.lib()
+    stream = torch.cuda.current_stream(flat.device).cuda_stream
     if torch.is_tensor(weight):
-        st = _lib.lib().msgat_gather_scaled_dev(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
-                                                _device_weight(weight, flat.device).data_ptr(), flat.data_ptr(),
-                                                int(weight_index), torch.cuda.current_stream(flat.device).cuda_stream)
-        _lib.check(st, "msgat_gather_scaled_dev")
-        return
-    st = _lib.lib().msgat_gather_scaled(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
-                                        float(weight), flat.data_ptr(), int(weight_index),
-                                        torch.cuda.current_stream(flat.device).cuda_stream)
-    _lib.check(st, "msgat_gather_scaled")
+        launch, what = ((L.msgat_gather_accumulate_dev, "msgat_gather_accumulate_dev") if accumulate else
+                        (L.msgat_gather_scaled_dev, "msgat_gather_scaled_dev"))
+        st = launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
+                    _device_weight(weight, flat.device).data_ptr(), flat.data_ptr(), int(weight_index), stream)
+    else:
+        launch, what = ((L.msgat_gather_accumulate, "msgat_gather_accumulate") if accumulate else
+                        (L.msgat_gather_scaled, "msgat_gather_scaled"))
+        st = launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n, float(weight),
+                    flat.data_ptr(), int(weight_index), stream)
+    _lib.check(st, what)
 
 
 class FlatGradAllReduce:
