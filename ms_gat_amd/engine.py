@@ -505,6 +505,13 @@ class FlatAdam(optim.Optimizer):
     `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format (per-parameter `step`, `exp_avg`,
     `exp_avg_sq`), so checkpoints interchange with the reference's optimizer.
 
+    Who writes a parameter: the update kernels (`msgat_adam_step` and its guarded and averaged forms) and
+    `msgat_param_swap` write it through its device address.  No tensor's version counter moves, and inside a captured
+    step no Python runs at all, so nothing derived from a trained parameter may be cached on its identity or version.
+    The library's own caches follow that: a dense adjacency that requires grad has its values re-read from the tensor at
+    every call (`graph.graph_of`, `graph.batched_graph_of`), a sparse one's are read where they sit.  Anything a caller
+    derives from a parameter on the host must be derived again after a step, a replay or a swap.
+
     The guard (`max_grad_norm`, `skip_nonfinite`; off unless one is set, and then nothing here changes): two more launches
     (`msgat_grad_guard`) take the global L2 norm of the flat gradient -- on one GPU after the copy into the flat views, with
     several ranks after the all-reduce and the clamp of the divisor, so every rank decides from the same bits and the norm
@@ -1174,6 +1181,28 @@ class Engine:
         # masked mean for any split
         return float(n_samples) if self.null_value is None else self._valid_count
 
+    # -- a learned dense adjacency under captured steps (graph._learned_graph_of) ----------------------------------
+    # A captured step refills the adjacency's values on the pattern it was captured with.  Where the optimizer runs
+    # inside the step, the warm-up's eager steps grow the pattern before the capture.  Where it runs outside (several
+    # ranks, gradient accumulation), the first update after a capture fills every zero of a sparse-start graph: the
+    # pattern is rebuilt right after that update and the captured steps are dropped, so the next batch captures anew.
+    # Whatever still slips through -- a step captured before the pattern grew and replayed after -- is counted on the
+    # device and raised at the end of the epoch, since no eager call on the tensor may ever come.
+    def _recapture_outgrown(self) -> None:
+        from . import graph
+        if graph._CAPTURED and graph.learned_patterns_grew(list(self.model.parameters())):     # empty: no such adjacency
+            self._graphs.clear()
+
+    def _check_captured_patterns(self) -> None:
+        from . import _lib, graph
+        if not graph._CAPTURED:
+            return
+        try:
+            graph.check_captured_patterns(list(self.model.parameters()))
+        except _lib.MsgatError:
+            self._graphs.clear()      # they hold the outgrown pattern: the next epoch captures anew
+            raise
+
     def _optimizer_step(self, n_samples: int, world: int) -> None:
         weight = self._step_weight(n_samples)
         if isinstance(self.optimizer, FlatAdam):
@@ -1387,10 +1416,14 @@ class Engine:
                         in_window, optimizer_steps = 0, optimizer_steps + 1
                 elif training and (not step_in_graph or graphed is None):
                     self._optimizer_step(truth.shape[0], world)
+                if training and graphed is not None and not step_in_graph:
+                    self._recapture_outgrown()
                 metrics.count(truth)
             if in_window:       # the batch count was no multiple of the window: no gradient outlives the epoch
                 self._window_step(None, world, close=True)
                 optimizer_steps += 1
+        if self._graphs:
+            self._check_captured_patterns()
         if world > 1:
             if metrics._sums is None and self.null_value is None:
                 metrics.totals(device)

@@ -292,8 +292,9 @@ class _TensorCache(_Lru):
 
 
 _CACHE_MAX = 16
-_GRAPHS = _TensorCache(_CACHE_MAX)     # dense [N,N] / [1,N,N] -> (SparseGraph, a copy of the contents)
-_BATCHED = _TensorCache(_CACHE_MAX)    # dense [V,N,N], sell -> BatchedGraph
+_GRAPHS = _TensorCache(_CACHE_MAX)     # frozen dense [N,N] / [1,N,N] -> (SparseGraph, a copy of the contents)
+_BATCHED = _TensorCache(_CACHE_MAX)    # frozen dense [V,N,N], sell -> BatchedGraph
+_LEARNED = _Lru(_CACHE_MAX)            # a dense adjacency that requires grad: address, shape, strides, device, sell -> BatchedGraph
 _SPARSE = _TensorCache(_CACHE_MAX)     # index tensors of a sparse adjacency, layout, N, sell -> (SparsePattern | SparseSets, indices)
 _PATTERNS = _Lru(8)                    # CSR content (N, sell, rowptr, col) -> SparsePattern
 
@@ -308,13 +309,129 @@ def _not_cached(what: str) -> _lib.MsgatError:
                            "its warm-up)")
 
 
-def graph_of(adjacency: torch.Tensor) -> SparseGraph:
-    """Cached `SparseGraph` of a dense adjacency tensor [N,N] (or [1,N,N], its one matrix).
+def _learned_graph_of(adjacency: torch.Tensor, sets: torch.Tensor, sell: str) -> "BatchedGraph":
+    """The graph of a dense adjacency that requires grad; `sets` is `adjacency.detach()` as [V,N,N].
 
-    The adjacency is a frozen parameter (msgat.py:190): one CSR build per tensor version.  Keyed on (storage address,
+    Whoever trains a tensor writes it, and most writers leave no trace: `FlatAdam` and its kernels (`msgat_adam_step` and
+    its guarded and averaged forms, `msgat_param_swap`) write through the address, a replay of a captured step runs no
+    Python, `.data` skips the version counter.  So neither identity nor version proves anything about the contents, and
+    the cache keeps only what a write cannot change cheaply -- the pattern: a `BatchedGraph` (one value set for [N,N]
+    and [1,N,N]) keyed on (storage address, shape, strides, device, sell) and good while the tensor it was made for
+    lives (a weakref), whose values are refilled from the tensor on
+    EVERY call by `msgat_graph_edge_values` (one launch that reads the V N^2 floats and writes V nnz).  The launch
+    counts the non-zeros outside the pattern.  Eagerly the two counters are read back (8 bytes) and a non-zero eager
+    count rebuilds the pattern from the tensor (N^2 mask bytes to the host; one optimizer step on a learned graph makes
+    every entry an edge).  Inside a HIP-graph capture nothing is read back and the pattern cannot grow: the count
+    accumulates at every replay, and if a replay dropped edges the next eager call on the tensor raises `MsgatError`
+    -- or `check_captured_patterns()`, which `engine.Trainer` calls at the end of every epoch, where no eager call may
+    come; what was reported is cleared.  A graph that a captured step refills is pinned (`_CAPTURED`) while its tensor
+    lives: the step holds its addresses, so the LRU must not free it."""
+    key = (adjacency.data_ptr(), tuple(adjacency.shape), tuple(adjacency.stride()), str(adjacency.device), sell)
+    g = _LEARNED.hit(key)
+    capturing = _capturing(adjacency)
+    if g is not None and g.owner() is None:
+        # the tensor this entry was made for is gone: the allocator recycled its address, or the adjacency is computed
+        # anew at every call.  Neither the entry's counters and captured steps nor its pattern (a superset would do, but
+        # a full one would make a sparse graph pay for N^2 edges from then on) are this tensor's: built anew
+        g = None
+    if g is None:
+        if capturing:
+            raise _not_cached("the pattern of this learned adjacency is not known yet")
+        g = BatchedGraph(sets, sell)
+        g.owner, g.sell = weakref.ref(adjacency), sell
+        return _LEARNED.put(key, g)
+    # (another live object at this address is a view of the owner's memory: the same contents, refilled all the same)
+    g.update_(sets)
+    if capturing:
+        if not g.in_capture:
+            g.in_capture = True
+            _CAPTURED.append(g)      # the captured step holds its addresses: it outlives the LRU
+        return g
+    captured, eager = g.outside_counts()
+    # a graph that a captured step refills and that the tensor outgrew eagerly: the step keeps its addresses and its
+    # pattern, so it stays alive behind its successor and its replays stay checked (one more read-back each, only then)
+    _refuse_dropped(g, captured)
+    if eager:
+        new = BatchedGraph(sets, sell)
+        new.owner, new.sell = g.owner, sell
+        new.retired = g.retired + [g] if g.in_capture else g.retired
+        g = _LEARNED.put(key, new)
+    return g
+
+
+_CAPTURED = []     # the learned graphs that captured steps refill, while their tensors live (pruned by check_captured_patterns)
+
+
+def _refuse_dropped(g: "BatchedGraph", captured: int) -> None:
+    """Raise if replays of captured steps dropped entries of the learned adjacency behind `g` (`captured`: the count of
+    `g` itself, already read; its retired predecessors are read here).  What is reported is cleared: the error comes
+    back only if a step captured on an outgrown pattern is replayed again."""
+    stale = [old for old in g.retired if old.outside_counts()[0]]
+    if not captured and not stale:
+        return
+    total = captured + sum(old.outside_counts()[0] for old in stale)
+    for each in stale + ([g] if captured else []):
+        each._outside[0] = 0
+    owner = g.owner()
+    raise _lib.MsgatError(
+        f"the pattern of the learned dense adjacency{'' if owner is None else ' ' + str(tuple(owner.shape))} grew under a "
+        f"captured step: replays found {total} non-zero entries outside the pattern the step was captured with and "
+        "dropped them (a captured step cannot rebuild the pattern; the results of those replays are wrong).  Capture the "
+        "step again after the pattern has grown -- one eager optimizer step fills every zero of a dense learned "
+        "adjacency; engine.Trainer does both by itself -- or start from values without a zero entry, or keep the pattern "
+        "fixed with ops.edge_adjacency")
+
+
+def _owned(g: "BatchedGraph", tensors) -> bool:
+    owner = g.owner()
+    return owner is not None and (tensors is None or any(owner is t for t in tensors))
+
+
+def check_captured_patterns(tensors=None) -> None:
+    """Raise `MsgatError` if a replay of a captured step dropped entries of a learned dense adjacency (one of `tensors`;
+    None: any): 8 bytes read back per learned graph that a captured step refills.  `engine.Trainer` calls it at the
+    end of `run_epoch` for the model's parameters, where no eager call on the tensor may ever come."""
+    _CAPTURED[:] = [g for g in _CAPTURED if g.owner() is not None]       # a dead tensor's capture cannot be replayed
+    for g in _CAPTURED:
+        if _owned(g, tensors):
+            _refuse_dropped(g, g.outside_counts()[0])
+
+
+def learned_patterns_grew(tensors=None) -> bool:
+    """After an eager write (an optimizer step outside the captured step): whether a learned dense adjacency (one of
+    `tensors`; None: any) that a captured step refills has outgrown the pattern the step was captured with.  The pattern
+    is rebuilt here, and the caller must drop its captured steps: they hold the old one.  A pattern that is full
+    cannot grow and costs nothing; any other costs the launch and the 8-byte read-back of an eager call."""
+    grew = False
+    for g in list(_LEARNED.values()):
+        n = g.n_nodes
+        if g.in_capture and g.nnz < n * n and _owned(g, tensors):
+            t = g.owner()
+            now = batched_graph_of(t, g.sell) if t.dim() == 3 and t.shape[0] != 1 else graph_of(t)
+            grew = grew or now is not g
+    return grew
+
+
+def graph_of(adjacency: torch.Tensor) -> "SparseGraph | BatchedGraph":
+    """Cached graph of a dense adjacency tensor [N,N] (or [1,N,N], its one matrix).
+
+    A tensor that requires grad is somebody's to train: its values are re-read from the tensor on every call, whoever
+    wrote them and however (`_learned_graph_of`; the graph is then a one-set `BatchedGraph`, which runs the same
+    kernels).
+
+    A frozen tensor (msgat.py:190) gets a `SparseGraph`: one CSR build per tensor version.  Keyed on (storage address,
     shape, device, version).  A hit on the very same tensor object is free; a hit through a different object (a view,
     or a new tensor the allocator placed at a recycled address) is confirmed by comparing contents before it is trusted.
+    What a frozen tensor promises: every write that moves its version counter (an in-place torch op, directly or
+    through a view) is seen; a write that does not (`.data`, a kernel or a NumPy alias that writes through the address)
+    is NOT seen while the same object is passed again -- the price of a free hit.  Who writes a frozen adjacency that way
+    passes `adjacency.detach()` (a new object: compared by content), bumps the version (`adjacency.add_(0)`), or lets
+    the tensor require grad.
     """
+    if adjacency.requires_grad and adjacency.dim() in (2, 3) and adjacency.shape[-1] == adjacency.shape[-2] \
+            and (adjacency.dim() == 2 or adjacency.shape[0] == 1):
+        n = adjacency.shape[-1]
+        return _learned_graph_of(adjacency, adjacency.detach().reshape(1, n, n), "auto")
     key = _tensor_key(adjacency)
     hit, same = _GRAPHS.lookup(key, adjacency)
     if same:
@@ -359,7 +476,9 @@ class BatchedGraph(ValuedGraph):
     `update_(adj)` refills the values in place from a device tensor with the `msgat_graph_edge_values` kernel, which also
     adds the non-zeros it finds outside the structure to a device counter; nothing is read back, so it may sit inside a
     HIP-graph capture.  `check()` reads the counter and raises if any sample had an edge the structure lacks (those edges
-    would be silently dropped).  A CPU tensor is gathered on the host by indexing (no GPU needed)."""
+    would be silently dropped).  A CPU tensor is gathered on the host by indexing (no GPU needed).  There are two
+    counters, one for refreshes enqueued inside a HIP-graph capture (every replay adds to it) and one for eager ones:
+    `outside_counts()` reads both in one read-back, `outside()` is their sum."""
 
     def __init__(self, adjacency: torch.Tensor, sell: str = "auto", structure: SparseGraph = None):
         _check_batched(adjacency)
@@ -371,7 +490,11 @@ class BatchedGraph(ValuedGraph):
             raise ValueError(f"structure has {structure.n_nodes} nodes, the adjacency {N}")
         self.device = adjacency.device
         super().__init__(structure, torch.zeros((V, max(structure.nnz, 1)), dtype=torch.float32, device=self.device), V)
-        self._outside = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._outside = torch.zeros(2, dtype=torch.int32, device=self.device)   # [inside a capture, eager]
+        self.in_capture = False          # a captured step refills this graph (`_learned_graph_of`) ...
+        self.retired = []                # ... and these, its predecessors, which the tensor has outgrown
+        self.owner = lambda: None        # weakref to the learned tensor this graph is cached for
+        self.sell = sell
         self.update_(adjacency)
 
     def update_(self, adjacency: torch.Tensor) -> "BatchedGraph":
@@ -393,17 +516,24 @@ class BatchedGraph(ValuedGraph):
             if self.nnz:
                 self.val[:, : self.nnz] = a[:, s.erow[: self.nnz].long(), s.col[: self.nnz].long()]
             inside = int((self.val[:, : self.nnz] != 0).sum())
-            self._outside += int((a != 0).sum()) - inside
+            self._outside[0 if _capturing(a) else 1] += int((a != 0).sum()) - inside
             return self
         gstruct, _ = s.on(a.device)
+        counter = self._outside.data_ptr() + (0 if _capturing(a) else 4)
         _lib.check(_lib.lib().msgat_graph_edge_values(C.byref(gstruct), a.data_ptr(), self.n_sets, self.val.data_ptr(),
-                                                      self._outside.data_ptr(), _lib.stream_handle(a.device)),
+                                                      counter, _lib.stream_handle(a.device)),
                    "msgat_graph_edge_values")
         return self
 
+    def outside_counts(self) -> Tuple[int, int]:
+        """Non-zeros found outside the structure by every refresh so far: (by those enqueued inside a HIP-graph capture,
+        once per replay; by the eager ones).  One read-back of 8 bytes."""
+        captured, eager = self._outside.tolist()
+        return int(captured), int(eager)
+
     def outside(self) -> int:
         """Non-zeros found outside the structure by every refresh so far (a read-back)."""
-        return int(self._outside.item())
+        return sum(self.outside_counts())
 
     def check(self) -> "BatchedGraph":
         n = self.outside()
@@ -421,8 +551,15 @@ def batched_graph_of(adjacency: torch.Tensor, sell: str = "auto") -> BatchedGrap
     last for this N when there is one: the values are filled by the kernel and the 4-byte outside count is read back;
     a non-zero count rebuilds the union pattern (N^2 mask bytes to the host) and fills again.  Under capture nothing is
     read back: the known pattern is used and the count only accumulates (`check()` reads it later); with no known
-    pattern it raises, as graph_of does."""
+    pattern it raises, as graph_of does.
+
+    All of that is the frozen tensor's path, with graph_of's promise: a write that moves the version counter is seen, one
+    that does not (`.data`, a kernel or an alias writing through the address) is not while the same object is passed
+    eagerly again.  A tensor that requires grad has its values refilled from the tensor on every call, eager or captured,
+    and its pattern rebuilt when they outgrow it (`_learned_graph_of`)."""
     _check_batched(adjacency)
+    if adjacency.requires_grad:
+        return _learned_graph_of(adjacency, adjacency.detach(), sell)
     capturing = _capturing(adjacency)
     key = _tensor_key(adjacency) + (sell,)
     hit, same = _BATCHED.lookup(key, adjacency)

@@ -96,9 +96,13 @@ def _gacn_plan(graph, dev, R, Bg, Cin, Co, N, T, need_bwd, own_q=True) -> _GacnP
 
 # ---- an adjacency that requires grad ----------------------------------------------------------------------------------
 # The adjacency tensor rides into the autograd Function as a last input, so that its gradient has somewhere to go; the
-# graph is built from the tensor itself (the caches hit it by identity, inside a HIP-graph capture too, and an in-place
-# update bumps its version and rebuilds the graph).  A frozen adjacency -- every caller of the reference's models -- costs
-# one `requires_grad` check; a prebuilt SparseGraph / BatchedGraph is not a tensor and gets no gradient.
+# graph is built from the tensor itself.  Whoever uses that gradient writes the tensor, and the writers that matter leave
+# no trace on it: FlatAdam's kernels write through the address, a replay of a captured step runs no Python, `.data` skips
+# the version counter.  So for a dense adjacency that requires grad the caches keep the pattern only, and every call --
+# eager or captured -- refills the values from the tensor with one launch (graph._learned_graph_of); a sparse adjacency's
+# values are read where they sit.  A frozen adjacency -- every caller of the reference's models -- costs one
+# `requires_grad` check and is trusted by identity and version; a prebuilt SparseGraph / BatchedGraph is not a tensor
+# and gets no gradient.
 
 def edge_adjacency(crow: torch.Tensor, col: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """The sparse CSR adjacency [N,N] (N = crow.numel() - 1) with a learned weight per stored edge: `weight` [nnz] in
