@@ -64,7 +64,8 @@ extern "C" {
  *     + msgat_quantile_{partial_doubles,metrics,grad} (quantile forecasts: pinball loss and coverage in the step tail);
  *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory);
  *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update);
- *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window).
+ *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window);
+ *     + msgat_edge_validity{,_backward} (edges gated by the validity of their source node's input window, per sample).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -803,6 +804,35 @@ int msgat_edge_dropout(const float* w, const uint8_t* exempt, int64_t* state, in
 int msgat_edge_dropout_backward(const float* dout, const uint8_t* exempt, const int64_t* state, const int64_t* used,
                                 float* dw, int32_t V, int64_t nnz, int32_t w_sets, int64_t sample_offset, uint32_t thr,
                                 float scale, void* stream);
+/* msgat_edge_validity: validity-gated edges on the pattern of `graph` -- a sensor whose input window holds missing readings
+ *     sends weaker messages, or none.  val [V,N,T] fp32 is the validity channel of the samples' input windows (1 = measured,
+ *     0 = imputed): its last two dimensions are contiguous and sample v starts val_stride ELEMENTS after sample v - 1, so the
+ *     strided view X[:, 0, -1] of a contiguous X [B,R,C,N,T] is read where it is.  With
+ *       count[v,n] = the number of t with val[v,n,t] > 0.5f            -- a NaN is not counted
+ *       g[v,n]     = table[count[v,n]]                                 -- table: T + 1 HOST floats, passed on by value
+ *     edge e of the pattern in the graph's CSR edge order, with source node col(e), gets
+ *       out[v,e] = exempt[e] ? w : (g[v,col(e)] == 0 ? +0.0f : w * g[v,col(e)])     -- w * g is one fp32 multiply
+ *     so a fully gated edge is +0 whatever w holds (a NaN too).  w [nnz] (w_sets = 0: shared by the V samples) or [V,nnz]
+ *     (w_sets != 0); exempt uint8 [nnz] or NULL (no edge is exempt); out [V,nnz] contiguous, which msgat_graph_t.val with
+ *     val_sets = V reads where it is.  Reads graph->col, graph->nnz and graph->n_nodes only; graph->val is not read.
+ *     One launch.  An aligned val (base and val_stride * 4 multiples of 16 bytes) is read as 16-byte pieces, any other with
+ *     single loads: the same result.
+ * msgat_edge_validity_backward: re-creates the gate from val -- nothing is kept between the two calls -- and writes
+ *       w_sets != 0:  dw[v,e] = exempt[e] ? dout[v,e] : (g == 0 ? +0.0f : dout[v,e] * g)
+ *       w_sets == 0:  dw[e]   = the sum over v of those rounded terms, from +0 in ascending v
+ *     Every entry is written, nothing is atomic; one launch.  dw = NULL: nothing is written, MSGAT_OK.  val gets no gradient:
+ *     it is data.
+ *     Both: graph = NULL: MSGAT_ERR_NULL; V < 0, T < 0, val_stride < 0 or a negative size in graph: MSGAT_ERR_SHAPE; T not in
+ *     {4, 8, 12, 16}: MSGAT_ERR_UNSUPPORTED; V = 0 or nnz = 0: MSGAT_OK and nothing is launched; a required pointer NULL with
+ *     work to do: MSGAT_ERR_NULL -- all decided on the host before any launch.  Nothing is read back (capturable).
+ *     The torch ops this replaces: a compare, a sum, two gathers, a compare, two selects and a multiply forward; the same
+ *     gate again, a multiply and a batch sum backward. */
+int msgat_edge_validity(const msgat_graph_t* graph, const float* w, const uint8_t* exempt, const float* val,
+                        int64_t val_stride, const float* table, float* out, int32_t V, int32_t T, int32_t w_sets,
+                        void* stream);
+int msgat_edge_validity_backward(const msgat_graph_t* graph, const float* dout, const uint8_t* exempt, const float* val,
+                                 int64_t val_stride, const float* table, float* dw, int32_t V, int32_t T, int32_t w_sets,
+                                 void* stream);
 size_t msgat_huber_partial_doubles(int64_t n);
 int msgat_huber_metrics(const float* pred, const float* truth, int64_t n, float delta, float mask_value,
                         double* partials, float* loss, double* sums, float loss_weight, void* stream);

@@ -10,9 +10,10 @@ parallelism (`parallel.py`).
 from .attention import GACN, GraphAttention, StackedGACN  # noqa: F401
 from .graph import BatchedGraph, SparseGraph, batched_graph_of, graph_of, random_edges, sym_norm_adjacency, synthetic_adjacency  # noqa: F401
 from .ops import edge_adjacency, gacn, graph_attention  # noqa: F401
-from .model import MEAM, MSGAT, TPC, msgat48, msgat72, msgat96  # noqa: F401
+from .model import MEAM, MSGAT, TPC, EdgeValidity, msgat48, msgat72, msgat96  # noqa: F401
 from .engine import Evaluator, GaussLoss, HuberLoss, Metrics, QuantileLoss, Trainer  # noqa: F401
 
 __all__ = ["GACN", "GraphAttention", "StackedGACN", "SparseGraph", "graph_of", "BatchedGraph", "batched_graph_of", "random_edges",
            "sym_norm_adjacency", "synthetic_adjacency", "gacn", "graph_attention", "edge_adjacency", "MEAM", "TPC", "MSGAT",
-           "msgat48", "msgat72", "msgat96", "Trainer", "Evaluator", "HuberLoss", "GaussLoss", "QuantileLoss", "Metrics"]
+           "msgat48", "msgat72", "msgat96", "Trainer", "Evaluator", "HuberLoss", "GaussLoss", "QuantileLoss", "Metrics",
+           "EdgeValidity"]

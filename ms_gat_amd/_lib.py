@@ -209,6 +209,11 @@ _PROTOTYPES = {
                                                        C.c_int32, C.c_void_p]),
     "msgat_edge_dropout_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_uint32,
                                                                 C.c_float, C.c_void_p]),
+    "msgat_edge_validity": (C.c_int, [C.POINTER(Graph)] + [C.c_void_p] * 3 + [C.c_int64, c_float_p, C.c_void_p, C.c_int32,
+                                                                             C.c_int32, C.c_int32, C.c_void_p]),
+    "msgat_edge_validity_backward": (C.c_int, [C.POINTER(Graph)] + [C.c_void_p] * 3 + [C.c_int64, c_float_p, C.c_void_p,
+                                                                                      C.c_int32, C.c_int32, C.c_int32,
+                                                                                      C.c_void_p]),
 }
 
 _lock = threading.Lock()

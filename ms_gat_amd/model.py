@@ -425,6 +425,45 @@ class EdgeDropout(nn.Module):
         return f"p={self.p}"
 
 
+def _check_missing_edges(mode, T: int):
+    if mode is not None:
+        ops.edge_validity_table(mode, T)                   # raises on anything but "scale", "drop" or an int in 1..T
+    return mode
+
+
+def _self_loops(crow: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+    """uint8 [nnz]: 1 at the stored diagonal of the CSR pattern (crow, col)."""
+    rows = torch.repeat_interleave(torch.arange(crow.numel() - 1, device=crow.device), crow[1:] - crow[:-1])
+    return (rows == col).to(torch.uint8)
+
+
+class EdgeValidity(nn.Module):
+    """Validity-gated edges of a sparse pattern for callers of `GraphAttention`, `GACN` and `StackedGACN`:
+    `forward(weights, validity)` takes `weights` [nnz] or [V,nnz] in the order of (crow, col) and the validity windows
+    `validity` [V,N,T] of the samples (1 = measured, 0 = imputed) and returns the [V,nnz] weights with the edges OUT OF
+    each node multiplied by `ops.edge_validity_table(mode, T)[its number of valid readings]` -- ready for
+    `ops.edge_adjacency(crow, col, ·)`.  `mode`: "scale" (c / T), "drop" (any missing reading silences the node) or an int m
+    (at least m readings keep the edges).  `keep_self=True` leaves the stored diagonal alone.  It is a function of the
+    input, not noise: training and eval mode compute the same.  No parameter, no `state_dict` key (`ops.edge_validity`)."""
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, mode="scale", keep_self: bool = True):
+        super().__init__()
+        if crow.dim() != 1 or col.dim() != 1 or crow.numel() < 1:
+            raise ValueError(f"EdgeValidity: crow {tuple(crow.shape)} and col {tuple(col.shape)} must be [N+1] and [nnz]")
+        if not (mode in ("scale", "drop") or (isinstance(mode, int) and not isinstance(mode, bool) and mode >= 1)):
+            raise ValueError(f'EdgeValidity: mode must be "scale", "drop" or a positive int, got {mode!r}')
+        self.mode = mode
+        self.register_buffer("crow", crow.detach().clone(), persistent=False)
+        self.register_buffer("col", col.detach().clone(), persistent=False)
+        self.register_buffer("exempt", _self_loops(self.crow, self.col) if keep_self else None, persistent=False)
+
+    def forward(self, weights: torch.Tensor, validity: torch.Tensor) -> torch.Tensor:
+        return ops.edge_validity(weights, validity, self.crow, self.col, mode=self.mode, exempt=self.exempt)
+
+    def extra_repr(self) -> str:
+        return f"mode={self.mode!r}, keep_self={self.exempt is not None}"
+
+
 def _check_edge_rank(rank) -> None:
     if isinstance(rank, bool) or not isinstance(rank, int) or rank < 4 or rank > 32 or rank % 4:
         raise ValueError(f"the edge rank must be one of 4, 8, ..., 32 (rows are read as 16-byte pieces), got {rank!r}")
@@ -465,17 +504,33 @@ class MSGAT(nn.Module):
     `edge_dropout_sample_offset + b`, so a sharded batch sees the masks of the whole one.  `eval()`, `attention_maps` and
     `torch.no_grad()` draw nothing.  `edge_dropout_state()` / `set_edge_dropout_state()` snapshot and restore the stream.
     The default 0 adds no buffer, key or launch.
+
+    `missing_edges="scale" | "drop" | m` takes a sensor with missing input readings out of the graph for that sample: the
+    edges OUT OF node j are multiplied by a gate from the number c of valid readings in j's most recent input window --
+    c / T_in ("scale"), 1 only at c == T_in ("drop"), or 1 where c >= m (an int m in 1..T_in) -- so an imputed window
+    reaches the neighbours at reduced weight or not at all.  The validity windows are `X[:, 0, -1]`, the LAST input channel
+    of the most recent component: build the data with `make_loaders(..., input_null_value=..., mask_channel=True)` and the
+    model with `in_channels=data.input_channels`.  Nothing can check that without reading the batch back: on inputs without
+    a validity channel the last channel's readings are taken for one.  The [B,nnz] gate is applied once per forward, after
+    the weights are formed and after `edge_dropout`, and shared by the R components and by every block
+    (`ops.edge_validity`); with the option on the adjacency is always the batched sparse form, on the pattern of `adj != 0`
+    for the frozen graph.  Unlike dropout it is a function of the input, so `eval()`, `torch.no_grad()` and
+    `attention_maps` apply it too.  The stored diagonal is exempt unless `missing_edges_keep_self=False`.  The softmax
+    denominators still run over all nodes and the remaining edges are not rescaled.  No parameter and no `state_dict` key:
+    checkpoints interchange with and without the option.  The default None adds no buffer, key or launch.
     """
 
     def __init__(self, components: Sequence[Dict], in_timesteps: int, out_timesteps: int, use_te: bool,
                  adj: torch.Tensor, learn_edge_weights: Union[bool, str] = False, edge_rank: int = 8,
-                 edge_dropout: float = 0.0, edge_dropout_seed: int = 0, edge_dropout_keep_self: bool = True):
+                 edge_dropout: float = 0.0, edge_dropout_seed: int = 0, edge_dropout_keep_self: bool = True,
+                 missing_edges=None, missing_edges_keep_self: bool = True):
         if not (isinstance(learn_edge_weights, bool)
                 or (isinstance(learn_edge_weights, str) and learn_edge_weights in ("time", "signal"))):
             raise ValueError(f'learn_edge_weights must be False, True, "time" or "signal", got {learn_edge_weights!r}')
         if learn_edge_weights == "signal":
             _check_edge_rank(edge_rank)
         edge_dropout = _check_edge_dropout(edge_dropout)
+        missing_edges = _check_missing_edges(missing_edges, in_timesteps)
         super().__init__()
         n_nodes = len(adj)
         if use_te:
@@ -524,6 +579,18 @@ class MSGAT(nn.Module):
                 self.register_buffer("edge_drop_crow", crow.clone(), persistent=False)
                 self.register_buffer("edge_drop_col", col.clone(), persistent=False)
                 self.register_buffer("edge_drop_index", rows * n_nodes + col, persistent=False)
+        self.missing_edges = missing_edges
+        if self.missing_edges is not None:
+            # non-persistent, and no parameter: checkpoints interchange with and without the option
+            pattern = self.adj.detach().cpu().to_sparse_csr()
+            crow, col = pattern.crow_indices(), pattern.col_indices()
+            self.register_buffer("edge_valid_exempt", _self_loops(crow, col) if missing_edges_keep_self else None,
+                                 persistent=False)
+            if not self.learn_edge_weights:      # the frozen graph's pattern, and where its values sit in `adj`
+                rows = torch.repeat_interleave(torch.arange(n_nodes), crow[1:] - crow[:-1])
+                self.register_buffer("edge_valid_crow", crow.clone(), persistent=False)
+                self.register_buffer("edge_valid_col", col.clone(), persistent=False)
+                self.register_buffer("edge_valid_index", rows * n_nodes + col, persistent=False)
 
     def _drops_edges(self) -> bool:
         """Masks are drawn in training mode with gradients enabled only: `eval()`, `attention_maps` and any evaluation under
@@ -534,6 +601,10 @@ class MSGAT(nn.Module):
         return ops.edge_dropout(weights, self.edge_dropout, self.edge_drop_state,
                                 sample_offset=int(self.edge_dropout_sample_offset), exempt=self.edge_drop_exempt,
                                 samples=samples if weights.dim() == 1 else None)
+
+    def _gate_missing(self, weights: torch.Tensor, X: torch.Tensor, crow: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+        """[B,nnz]: `weights` ([nnz] or [B,nnz]) gated by the validity windows X[:, 0, -1], read where they are."""
+        return ops.edge_validity(weights, X[:, 0, -1], crow, col, mode=self.missing_edges, exempt=self.edge_valid_exempt)
 
     def edge_dropout_state(self) -> Optional[Dict[str, int]]:
         """{"seed", "step"} of the mask stream (reads two words back from the device); None for a model that drops nothing."""
@@ -555,8 +626,13 @@ class MSGAT(nn.Module):
         CSR adjacency [B,N,N] of the weights of the batch's hours `H` and days `D` ("time") or of its inputs `X` ("signal").
         With `edge_dropout > 0`, in training mode with gradients enabled, always the batched form: one [B,nnz] draw on the
         weights once they are formed (`ops.edge_dropout`), shared by the R components and by every block; B is read from H
-        (or X)."""
+        (or X).  With `missing_edges`, always -- in eval mode and under no_grad too -- the batched form, gated by the validity
+        windows of `X` (`ops.edge_validity`) after the dropout."""
         drop = self._drops_edges()
+        gate = self.missing_edges is not None
+        if gate and X is None:
+            raise ValueError("missing_edges: the gate is formed from the batch's validity windows X[:, 0, -1], pass its "
+                             "inputs X (batch_adjacency does)")
         samples = None
         if drop:
             batch = H if H is not None else X
@@ -564,10 +640,16 @@ class MSGAT(nn.Module):
                 raise ValueError("edge_dropout: the masks are drawn per sample, pass the batch's H and D (or its inputs X)")
             samples = batch.shape[0]
         if not self.learn_edge_weights:
-            if not drop:
+            if not drop and not gate:
                 return self.adj
-            weights = self.adj.detach().reshape(-1).index_select(0, self.edge_drop_index)
-            return ops.edge_adjacency(self.edge_drop_crow, self.edge_drop_col, self._drop_edges(weights, samples))
+            crow, col, index = ((self.edge_valid_crow, self.edge_valid_col, self.edge_valid_index) if gate else
+                                (self.edge_drop_crow, self.edge_drop_col, self.edge_drop_index))
+            weights = self.adj.detach().reshape(-1).index_select(0, index)
+            if drop:
+                weights = self._drop_edges(weights, samples)
+            if gate:
+                weights = self._gate_missing(weights, X, crow, col)
+            return ops.edge_adjacency(crow, col, weights)
         if self.learn_edge_weights == "signal":
             if X is None:
                 raise ValueError('learn_edge_weights="signal": the adjacency depends on the batch, pass its inputs X')
@@ -581,11 +663,14 @@ class MSGAT(nn.Module):
             weights = self.edge_weight
         if drop:
             weights = self._drop_edges(weights, samples)
+        if gate:
+            weights = self._gate_missing(weights, X, self.edge_crow, self.edge_col)
         return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
 
     def batch_adjacency(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor):
-        """`adjacency` for one batch of `forward`'s inputs; only "signal" is handed X."""
-        return self.adjacency(H, D, X) if self.learn_edge_weights == "signal" else self.adjacency(H, D)
+        """`adjacency` for one batch of `forward`'s inputs; only "signal" and `missing_edges` are handed X."""
+        needs_x = self.learn_edge_weights == "signal" or self.missing_edges is not None
+        return self.adjacency(H, D, X) if needs_x else self.adjacency(H, D)
 
     def forward(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor) -> torch.Tensor:
         if self.stack_components and stacked.can_stack(self):

@@ -1479,6 +1479,152 @@ def edge_dropout(weight: torch.Tensor, p: float, state: torch.Tensor, *, sample_
     return _EdgeDropoutFunction.apply(weight, exempt, state, V, sample_offset, thr, scale)
 
 
+EDGE_VALIDITY_T = (4, 8, 12, 16)           # the package's T_in set: what msgat_edge_validity is built for
+
+
+def edge_validity_table(mode, T: int) -> tuple:
+    """The gate of a source node by its count of valid readings: `table[c]`, c = 0..T, T + 1 floats computed in double and
+    rounded once to fp32.  `mode="scale"`: c / T; `"drop"`: 1 at c == T and 0 below; an int m in 1..T: 1 where c >= m and 0
+    below.  `table[T] == 1` in every mode: a window without a missing reading leaves its edges bit for bit as they were."""
+    if isinstance(T, bool) or not isinstance(T, int) or T not in EDGE_VALIDITY_T:
+        raise ValueError(f"edge_validity: T = {T!r} readings per window, supported are {EDGE_VALIDITY_T}")
+    if isinstance(mode, str) and mode == "scale":
+        table = [c / T for c in range(T + 1)]
+    elif isinstance(mode, str) and mode == "drop":
+        table = [1.0 if c == T else 0.0 for c in range(T + 1)]
+    elif isinstance(mode, int) and not isinstance(mode, bool) and 1 <= mode <= T:
+        table = [1.0 if c >= mode else 0.0 for c in range(T + 1)]
+    else:
+        raise ValueError(f'edge_validity: mode must be "scale", "drop" or an int in 1..{T} (the least number of valid '
+                         f"readings that keeps the edges), got {mode!r}")
+    return tuple(C.c_float(x).value for x in table)
+
+
+def _edge_validity_operands(weight, validity, crow, col, exempt, samples):
+    """Shape and type checks shared by the op and its restatement; returns (V, N, T, nnz)."""
+    if not torch.is_tensor(weight) or not torch.is_tensor(validity):
+        raise ValueError("edge_validity: weight and validity must be tensors")
+    if weight.dtype != torch.float32 or validity.dtype != torch.float32:
+        raise TypeError(f"edge_validity: weight and validity must be float32, got {weight.dtype} and {validity.dtype}")
+    if validity.dim() != 3 or crow.dim() != 1 or col.dim() != 1 or crow.numel() != validity.shape[1] + 1:
+        raise ValueError(f"edge_validity: validity {tuple(validity.shape)}, crow {tuple(crow.shape)} and col {tuple(col.shape)} "
+                         "must be [V, N, T], [N+1] and [nnz]")
+    V, N, T = validity.shape
+    nnz = col.numel()
+    if weight.dim() not in (1, 2) or weight.shape[-1] != nnz or (weight.dim() == 2 and weight.shape[0] != V):
+        raise ValueError(f"edge_validity: weight {tuple(weight.shape)} must be [{nnz}] or [{V}, {nnz}] (validity "
+                         f"{tuple(validity.shape)}, {nnz} stored edges)")
+    if samples is not None and samples != V:
+        raise ValueError(f"edge_validity: samples={samples!r}, validity {tuple(validity.shape)} has {V}")
+    if any(t.device != weight.device for t in (validity, crow, col)):
+        raise ValueError(f"edge_validity: weight is on {weight.device}, validity on {validity.device}, crow on {crow.device} "
+                         f"and col on {col.device}")
+    if exempt is not None and (not torch.is_tensor(exempt) or exempt.dtype not in (torch.uint8, torch.bool)
+                               or tuple(exempt.shape) != (nnz,) or exempt.device != weight.device):
+        raise ValueError(f"edge_validity: exempt must be uint8 or bool [{nnz}] on {weight.device}, got "
+                         f"{getattr(exempt, 'dtype', type(exempt).__name__)} {tuple(getattr(exempt, 'shape', ()))}")
+    return V, N, T, nnz
+
+
+_EDGE_VALIDITY_TABLES = {}            # (mode, T, device) -> the table as a tensor there, for the torch restatement
+
+
+def edge_validity_reference(weight: torch.Tensor, validity: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, *,
+                            mode="scale", exempt: Optional[torch.Tensor] = None,
+                            samples: Optional[int] = None) -> torch.Tensor:
+    """`edge_validity` restated with torch ops, on whichever device the operands are: a compare and a sum for the counts, a
+    table gather, a gather by source node, a compare, a select, one fp32 multiply and the exempt edges' select.  What the op
+    runs for CPU tensors, and the torch-op formulation the measurements compare against."""
+    V, N, T, nnz = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
+    key = (mode, T, str(weight.device))
+    table = _EDGE_VALIDITY_TABLES.get(key)
+    if table is None:                  # kept per (mode, T, device): a captured step cannot copy it from the host
+        table = _EDGE_VALIDITY_TABLES[key] = torch.tensor(edge_validity_table(mode, T), dtype=torch.float32,
+                                                          device=weight.device)
+    g = table[(validity > 0.5).sum(-1)].index_select(1, col.long())          # [V,nnz]: the gate of each edge's source node
+    w = weight if weight.dim() == 2 else weight[None, :].expand(V, nnz)
+    out = torch.where(g == 0, torch.zeros((), dtype=torch.float32, device=weight.device), w * g)
+    return out if exempt is None else torch.where(exempt.bool()[None, :], w, out)
+
+
+class _EdgeValidityFunction(torch.autograd.Function):
+    """w [nnz] or [V,nnz], validity [V,N,T] -> w * g [V,nnz] on `pattern`'s structure (msgat_edge_validity); backward
+    re-creates the gate from `validity`.  Values cross in the caller's order of (crow, col), as in
+    `_EdgeSignalWeightsFunction`."""
+
+    @staticmethod
+    def forward(ctx, w, validity, exempt, pattern, table):
+        L = _lib.lib()
+        w = w.contiguous()
+        V, N, T = validity.shape
+        if validity.stride(2) != 1 or validity.stride(1) != T or (V > 1 and validity.stride(0) < 0):
+            validity = validity.contiguous()               # the kernel wants [N,T] rows contiguous; any sample stride is read
+        nnz = pattern.structure.nnz
+        sets = int(w.dim() == 2)
+        gstruct, keep = pattern.structure.on(w.device)
+        perm = None if pattern.identity else pattern._perm(w.device)         # (library edge -> input position, its inverse)
+        if perm is not None:
+            w = w.index_select(w.dim() - 1, perm[0])
+            exempt = None if exempt is None else exempt.index_select(0, perm[0])
+        stride = validity.stride(0) if V > 1 else N * T
+        ctable = (C.c_float * (T + 1))(*table)
+        out = _new(w, V, nnz)
+        st = L.msgat_edge_validity(C.byref(gstruct), _ptr(w), _ptr(exempt), _ptr(validity), stride, ctable, _ptr(out), V, T,
+                                   sets, _stream_handle(w.device))
+        _lib.check(st, "msgat_edge_validity")
+        ctx.call = (gstruct, keep, perm, V, T, nnz, sets, stride, ctable)
+        ctx.operands = (exempt,)                           # an integer tensor the launch reads by address: nothing to version
+        ctx.save_for_backward(validity)
+        return out if perm is None else out.index_select(1, perm[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        validity, = ctx.saved_tensors
+        exempt, = ctx.operands
+        gstruct, _, perm, V, T, nnz, sets, stride, ctable = ctx.call
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        dout = dout.contiguous() if perm is None else dout.index_select(1, perm[0])
+        if V == 0 or nnz == 0:                             # nothing is launched: the empty sum
+            return (torch.zeros((V, nnz) if sets else (nnz,), device=dout.device, dtype=dout.dtype),) + (None,) * 4
+        dw = _new(dout, V, nnz) if sets else _new(dout, nnz)
+        st = L.msgat_edge_validity_backward(C.byref(gstruct), _ptr(dout), _ptr(exempt), _ptr(validity), stride, ctable,
+                                            _ptr(dw), V, T, sets, _stream_handle(dout.device))
+        _lib.check(st, "msgat_edge_validity_backward")
+        if perm is not None:
+            dw = dw.index_select(dw.dim() - 1, perm[1])
+        return (dw,) + (None,) * 4
+
+
+def edge_validity(weight: torch.Tensor, validity: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, *, mode="scale",
+                  exempt: Optional[torch.Tensor] = None, samples: Optional[int] = None) -> torch.Tensor:
+    """Validity-gated edges on one sparse pattern: a sensor whose input window has missing readings sends weaker messages
+    to its neighbours, or none.  `weight` [nnz] -- shared by the V samples -- or [V,nnz] in the order of (`crow` [N+1], `col`
+    [nnz]); `validity` [V,N,T]: the validity channel of the samples' input windows (1 = measured, 0 = imputed,
+    `make_loaders(..., input_null_value=..., mask_channel=True)`), T in {4, 8, 12, 16}.  Edge e, whose SOURCE node is
+    col(e) (row i of the adjacency gathers from its columns), gets `weight * table[count]` with `count` the number of
+    readings `> 0.5` in the source node's window and `table = edge_validity_table(mode, T)`: "scale" c / T, "drop" all or
+    nothing, an int m keeps the edges of a node with at least m readings.  A gate of 0 gives +0 whatever the weight holds;
+    edges flagged in `exempt` (bool or uint8 [nnz]) pass through unchanged.  The result [V,nnz] is contiguous:
+    `edge_adjacency(crow, col, ·)` reads it where it is.
+
+    `validity` is read where it is when its last two dimensions are contiguous (the view `X[:, 0, -1]` of a contiguous
+    X [B,R,C,N,T]), aligned or not; it is data and gets no gradient.  Backward re-creates the gate instead of storing it:
+    `weight` [V,nnz] gets `dout * g`, `weight` [nnz] the sum over the samples in ascending order; one launch each way, no
+    atomics, capturable (msgat_edge_validity{,_backward}).  Row v depends on sample v alone, so rows [lo, hi) of a V-row
+    call are the call on that shard.  CPU tensors run `edge_validity_reference`, the same arithmetic in torch ops."""
+    V, N, T, nnz = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
+    table = edge_validity_table(mode, T)
+    if not weight.is_cuda:
+        return edge_validity_reference(weight, validity, crow, col, mode=mode, exempt=exempt, samples=samples)
+    if exempt is not None:
+        exempt = exempt.contiguous()
+        if exempt.dtype == torch.bool:
+            exempt = exempt.view(torch.uint8)
+    return _EdgeValidityFunction.apply(weight, validity.detach(), exempt, edge_pattern_of(crow, col), table)
+
+
 # ---- channel axes assembled from several tensors: one pass instead of cat / several mixes -------------------
 
 def _sliced_grad(dz: torch.Tensor, accepts):
