@@ -65,7 +65,8 @@ extern "C" {
  *     + msgat_edge_dropout{,_backward} (dropout on the stored edges, masks from a counter-based generator in device memory);
  *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update);
  *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window);
- *     + msgat_edge_validity{,_backward} (edges gated by the validity of their source node's input window, per sample).
+ *     + msgat_edge_validity{,_backward} (edges gated by the validity of their source node's input window, per sample);
+ *     + msgat_ring_push and msgat_ring_windows (online forecasting: a ring of readings and the windows of its newest origin).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -1054,6 +1055,44 @@ int msgat_window_gather_imputed(const float* series, const float* climatology, c
                                 const int64_t* origins, const int64_t* offsets, float* X, int64_t* H, int64_t* D,
                                 float* Y, int32_t B, int32_t R, int32_t C, int32_t N, int64_t T_total, int32_t tau,
                                 int32_t q, int64_t history, int32_t period, int32_t mask_channel, void* stream);
+
+/* ---- device: online forecasting -- a ring of readings in device memory and the windows of the origin "now" ----
+ * (data_loader.py:92-120 slices and normalises a series that exists in full; a reading that arrives after training has
+ * no path there.)  State, both in device memory and never read back:
+ *       ring  [L, C, N] fp32   the normalised history, TIME-MAJOR: the row of absolute step s is s mod L; a missing
+ *                              reading is stored as a NaN.  A new ring is filled with the canonical NaN 0x7fc00000.
+ *       clock [2] int64        clock[0]: the absolute index of the next reading = the forecast origin t;
+ *                              clock[1]: the count of readings held, saturating at L
+ * "mod" is the floor-mod into [0, L): ANY clock content (a cold ring, t smaller than an offset, a wild word) addresses
+ * rows inside the ring, so neither entry point can read or write outside its arrays.
+ *
+ * msgat_ring_push: raw [K, C, N] fp32, the readings of K consecutive steps (1 <= K <= L), go into the rows
+ *     (clock[0] + k) mod L as (raw - mean[c,n]) / std[c,n] -- one IEEE subtract and one correctly rounded divide, the bits
+ *     of the torch expression the training series was normalised with (mean, std [C, N] fp32).  has_null != 0: a reading
+ *     that is NaN or equal to null_value is stored as the word 0x7fc00000 (null_value = NaN: the NaNs only); has_null
+ *     == 0: the quotient and nothing else.  A one-thread launch that follows in stream order then sets clock[0] += K and
+ *     clock[1] = min(clock[1] + K, L): two launches, capturable.
+ *     A NULL pointer: MSGAT_ERR_NULL; K, C, N or L <= 0, or K > L: MSGAT_ERR_SHAPE; C * N above 2^31 - 256:
+ *     MSGAT_ERR_UNSUPPORTED.
+ *
+ * msgat_ring_windows: X, H, D of the ONE origin t = clock[0], read on the device, in one launch -- what
+ *     msgat_window_gather{,_imputed} gives for B = 1 over the full series:
+ *       X [1, R, C', N, tau] fp32  X[0,r,c,n,k] = ring[(t - offsets[r] + k) mod L, c, n]; with a table, where that word
+ *                                  is a NaN, climatology[(t - offsets[r] + k) mod period, c, n]; with mask_channel != 0
+ *                                  C' = C + 1 and X[0,r,C,n,k] = 1.0f where no channel of that row at node n is a NaN,
+ *                                  else 0.0f.  Every other word keeps its bits.  16-byte aligned.
+ *       H [1], D [1] int64         floor(t / tau) mod 24 and floor(t / tau / 24) mod 7
+ *     offsets [R] int64 on the device as for msgat_window_gather; the caller sees to L >= their largest and decides
+ *     whether a ring that holds fewer readings may be forecast from.  climatology_or_null [period, C, N] or NULL: NULL is
+ *     the plain form (no substitution; mask_channel must be 0, period is ignored).
+ *     A NULL pointer (other than the table): MSGAT_ERR_NULL; R, C, N, L <= 0, L not a multiple of tau, period < 1 with a
+ *     table, mask_channel without one: MSGAT_ERR_SHAPE; tau not in {4, 8, 12, 16} or (C + 1) * N above 2^31 - 256:
+ *     MSGAT_ERR_UNSUPPORTED. */
+int msgat_ring_push(const float* raw, const float* mean, const float* std, float* ring, int64_t* clock, int32_t K,
+                    int32_t C, int32_t N, int64_t L, int32_t has_null, float null_value, void* stream);
+int msgat_ring_windows(const float* ring, const float* climatology_or_null, const int64_t* clock, const int64_t* offsets,
+                       float* X, int64_t* H, int64_t* D, int32_t R, int32_t C, int32_t N, int64_t L, int32_t tau,
+                       int32_t period, int32_t mask_channel, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,8 +12,9 @@ from .graph import BatchedGraph, SparseGraph, batched_graph_of, graph_of, random
 from .ops import edge_adjacency, gacn, graph_attention  # noqa: F401
 from .model import MEAM, MSGAT, TPC, EdgeValidity, msgat48, msgat72, msgat96  # noqa: F401
 from .engine import Evaluator, GaussLoss, HuberLoss, Metrics, QuantileLoss, Trainer  # noqa: F401
+from .online import OnlineForecaster  # noqa: F401
 
 __all__ = ["GACN", "GraphAttention", "StackedGACN", "SparseGraph", "graph_of", "BatchedGraph", "batched_graph_of", "random_edges",
            "sym_norm_adjacency", "synthetic_adjacency", "gacn", "graph_attention", "edge_adjacency", "MEAM", "TPC", "MSGAT",
            "msgat48", "msgat72", "msgat96", "Trainer", "Evaluator", "HuberLoss", "GaussLoss", "QuantileLoss", "Metrics",
-           "EdgeValidity"]
+           "EdgeValidity", "OnlineForecaster"]

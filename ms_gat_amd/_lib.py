@@ -214,6 +214,8 @@ _PROTOTYPES = {
     "msgat_edge_validity_backward": (C.c_int, [C.POINTER(Graph)] + [C.c_void_p] * 3 + [C.c_int64, c_float_p, C.c_void_p,
                                                                                       C.c_int32, C.c_int32, C.c_int32,
                                                                                       C.c_void_p]),
+    "msgat_ring_push": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
+    "msgat_ring_windows": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 3 + [C.c_void_p]),
 }
 
 _lock = threading.Lock()

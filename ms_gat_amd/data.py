@@ -10,7 +10,8 @@ layout for benchmarks and tests.
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+import dataclasses
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -34,8 +35,14 @@ def load_adjacency_csv(path: str, n_nodes: int) -> torch.Tensor:
 
 def zscore(series: torch.Tensor, split: int) -> torch.Tensor:
     """Per (channel, node) z-score with statistics of the first `split` steps only (data_loader.py:118-120)."""
-    std, mean = torch.std_mean(series[..., :split], dim=-1, keepdim=True)
+    mean, std = _zscore_stats(series, split)
     return (series - mean) / std
+
+
+def _zscore_stats(series: torch.Tensor, split: int):
+    """(mean, std) [..., 1] of the first `split` steps, as `zscore` applies them (unbiased std)."""
+    std, mean = torch.std_mean(series[..., :split], dim=-1, keepdim=True)
+    return mean, std
 
 
 def missing_entries(series: torch.Tensor, input_null_value: float) -> torch.Tensor:
@@ -56,16 +63,8 @@ def prepare_missing(raw: torch.Tensor, split: int, input_null_value: float, peri
     if raw.dim() != 3 or period < 1 or not 0 <= split <= raw.shape[-1]:
         raise ValueError(f"prepare_missing: raw {tuple(raw.shape)} must be [C,N,T_total], period = {period} >= 1 and "
                          f"split = {split} within the series")
-    valid = ~missing_entries(raw, input_null_value)
-    x = torch.where(valid, raw, torch.zeros((), dtype=raw.dtype)).double()
-    head, head_valid = x[..., :split], valid[..., :split]
-    count = head_valid.sum(-1, keepdim=True)
-    mean = head.sum(-1, keepdim=True) / count.clamp(min=1)
-    dev2 = (torch.where(head_valid, head - mean, torch.zeros((), dtype=torch.float64)) ** 2).sum(-1, keepdim=True)
-    std = (dev2 / (count - 1).clamp(min=1)).sqrt()
-    std = torch.where((count < 2) | ~(std > 0), torch.ones_like(std), std)
-    mean, std = mean.float(), std.float()
-    std = torch.where(std > 0, std, torch.ones_like(std))        # a spread that rounds to 0 in float32
+    valid, mean, std = _missing_stats(raw, split, input_null_value)
+    head_valid = valid[..., :split]
     nan = torch.full((), float("nan"), dtype=torch.float32)
     normed = torch.where(valid, (raw.float() - mean) / std, nan)
     slot = torch.arange(split) % period
@@ -77,6 +76,23 @@ def prepare_missing(raw: torch.Tensor, split: int, input_null_value: float, peri
     counts.index_add_(0, slot, train_valid.double())
     climatology = torch.where(counts > 0, sums / counts.clamp(min=1), torch.zeros((), dtype=torch.float64)).float()
     return normed, climatology
+
+
+def _missing_stats(raw: torch.Tensor, split: int, input_null_value: float):
+    """(valid [C,N,T_total] bool, mean [C,N,1], std [C,N,1], both float32): the statistics `prepare_missing` normalises
+    with -- float64 over the valid entries of the first `split` steps, rounded once, with its rules for rows that have
+    fewer than two valid entries or no spread."""
+    valid = ~missing_entries(raw, input_null_value)
+    x = torch.where(valid, raw, torch.zeros((), dtype=raw.dtype)).double()
+    head, head_valid = x[..., :split], valid[..., :split]
+    count = head_valid.sum(-1, keepdim=True)
+    mean = head.sum(-1, keepdim=True) / count.clamp(min=1)
+    dev2 = (torch.where(head_valid, head - mean, torch.zeros((), dtype=torch.float64)) ** 2).sum(-1, keepdim=True)
+    std = (dev2 / (count - 1).clamp(min=1)).sqrt()
+    std = torch.where((count < 2) | ~(std > 0), torch.ones_like(std), std)
+    mean, std = mean.float(), std.float()
+    std = torch.where(std > 0, std, torch.ones_like(std))        # a spread that rounds to 0 in float32
+    return valid, mean, std
 
 
 def split_intervals(total_steps: int, in_hours: Sequence[int], out_timesteps: int, tau: int):
@@ -225,6 +241,104 @@ def _windows_torch(series_tm: torch.Tensor, target: torch.Tensor, origins: torch
     y = target[:, origins[:, None] + torch.arange(q, device=origins.device)].permute(1, 0, 2).contiguous()
     hour = origins // tau
     return x, hour % 24, (hour // 24) % 7, y
+
+
+@dataclasses.dataclass
+class SeriesStats:
+    """What training knew about the series and a reading that arrives later needs: the per-(channel, node) `mean` and
+    `std` [C,N] the inputs were normalised with, the slot table `climatology` [period,C,N] a missing reading is imputed
+    from (None for a series without missing readings), and the arguments they were made for.  `series_stats` builds it;
+    `save` / `load` keep it beside a checkpoint (`Trainer.save` does not hold it)."""
+    mean: torch.Tensor
+    std: torch.Tensor
+    climatology: Optional[torch.Tensor]
+    hours: List[int]
+    tau: int
+    period: Optional[int]
+    input_null_value: Optional[float]
+    mask_channel: bool
+    input_channels: int
+    train_end: int
+
+    @property
+    def history(self) -> int:
+        return self.tau * max(self.hours)
+
+    def normalise(self, raw: torch.Tensor) -> torch.Tensor:
+        """raw [C,N,T] -> what `make_loaders` put into its loaders for these steps: the z-score, with NaN at the missing
+        readings of a series that has an `input_null_value`."""
+        normed = (raw.float() - self.mean[..., None]) / self.std[..., None]
+        if self.input_null_value is None:
+            return normed
+        nan = torch.full((), float("nan"), dtype=torch.float32)
+        return torch.where(missing_entries(raw, self.input_null_value), nan, normed)
+
+    def save(self, path) -> None:
+        torch.save(dataclasses.asdict(self), path)
+
+    @classmethod
+    def load(cls, path) -> "SeriesStats":
+        return cls(**torch.load(path, map_location="cpu"))
+
+
+def series_stats(raw: torch.Tensor, in_hours, out_timesteps: int, tau: int, input_null_value: float | None = None,
+                 impute: str = "period", mask_channel: bool = True) -> SeriesStats:
+    """The statistics `make_loaders` uses internally for the same arguments, as an object that outlives training:
+    `stats.normalise(raw)` has the bits of the series in its loaders and `stats.climatology` those of its table."""
+    if impute not in ("period", "mean"):
+        raise ValueError(f"impute = {impute!r} must be 'period' or 'mean'")
+    if raw.dim() != 3:
+        raise ValueError(f"series_stats: raw {tuple(raw.shape)} must be [C,N,T_total]")
+    hours = [int(h) for h in in_hours]
+    _, train_end = split_intervals(raw.size(-1), hours, out_timesteps, tau)
+    table = period = None
+    if input_null_value is None:
+        mean, std = _zscore_stats(raw.float(), train_end)
+    else:
+        period = 7 * 24 * tau if impute == "period" else 1
+        _, mean, std = _missing_stats(raw, train_end, input_null_value)
+        table = prepare_missing(raw, train_end, input_null_value, period)[1]
+        if impute == "mean":
+            table.zero_()
+    with_mask = input_null_value is not None and bool(mask_channel)
+    return SeriesStats(mean=mean[..., 0].contiguous(), std=std[..., 0].contiguous(), climatology=table, hours=hours,
+                       tau=int(tau), period=period,
+                       input_null_value=None if input_null_value is None else float(input_null_value),
+                       mask_channel=with_mask, input_channels=raw.shape[0] + int(with_mask), train_end=int(train_end))
+
+
+def _ring_push_torch(raw: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, ring: torch.Tensor, clock: torch.Tensor,
+                     null_value: float | None = None) -> None:
+    """`ops.ring_push` restated with torch indexing; serves CPU tensors and states what the kernel must give.
+    raw [K,C,N], the readings of K consecutive steps starting at step clock[0], go normalised into the rows
+    (clock[0] + k) mod L of `ring` [L,C,N]; with `null_value` a reading that is NaN or equal to it is stored as the
+    canonical NaN.  Then clock[0] += K and clock[1] = min(clock[1] + K, L)."""
+    K, L = raw.shape[0], ring.shape[0]
+    value = (raw - mean) / std
+    if null_value is not None:
+        value = torch.where(missing_entries(raw, null_value), torch.full_like(value, float("nan")), value)
+    ring[(clock[0] + torch.arange(K, device=clock.device)) % L] = value       # `%` of tensors is the floor-mod
+    clock[0] += K
+    clock[1] = torch.clamp(clock[1] + K, max=L)
+
+
+def _ring_windows_torch(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int,
+                        climatology: torch.Tensor | None = None, mask_channel: bool = False):
+    """`ops.ring_windows` restated with torch indexing: `_windows_torch` for the one origin t = clock[0], the row of
+    absolute step s read at s mod L of `ring` [L,C,N] and its slot of the table at s mod period.  (X [1,R,C(+1),N,tau],
+    H [1], D [1])."""
+    t = clock[:1]
+    back = torch.tensor([h * tau for h in hours], dtype=torch.int64, device=clock.device)
+    steps = t[:, None, None] - back[None, :, None] + torch.arange(tau, device=clock.device)            # [1,R,tau]
+    x = ring[steps % ring.shape[0]]                                                                    # [1,R,tau,C,N]
+    if climatology is not None:
+        missing = torch.isnan(x)
+        x = torch.where(missing, climatology[steps % climatology.shape[0]], x)
+        if mask_channel:
+            x = torch.cat([x, (~missing.any(3, keepdim=True)).to(x.dtype)], dim=3)
+    x = x.permute(0, 1, 3, 4, 2).contiguous()
+    hour = torch.div(t, tau, rounding_mode="floor")
+    return x, hour % 24, torch.div(hour, 24, rounding_mode="floor") % 7
 
 
 class DeviceWindows:

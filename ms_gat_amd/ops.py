@@ -2445,6 +2445,104 @@ def _window_gather(what, inputs_dev, target_dev, origins, hours, tau, q, offsets
     return X, HD[0], HD[1], Y
 
 
+# ---- online forecasting: a ring of readings in device memory and the windows of its newest origin ------------------
+def _check_ring(what, ring, clock, others):
+    """`ring` float32 [L,C,N] and `clock` int64 [2] on one device with the float32 tensors `others` = [(name, tensor,
+    shape)], all contiguous; returns (L, C, N)."""
+    for name, t, _ in [("ring", ring, None)] + others:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32, got {t.dtype}")
+    if clock.dtype != torch.int64:
+        raise TypeError(f"{what}: clock must be int64, got {clock.dtype}")
+    if ring.dim() != 3 or ring.numel() == 0:
+        raise ValueError(f"{what}: ring {tuple(ring.shape)} must be a non-empty [L, C, N]")
+    if tuple(clock.shape) != (2,):
+        raise ValueError(f"{what}: clock {tuple(clock.shape)} must be [2]: the next step and the count of readings held")
+    for name, t, shape in others + [("clock", clock, None)]:
+        if t.device != ring.device:
+            raise ValueError(f"{what}: ring on {ring.device} and {name} on {t.device} must share one device")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} must be {list(shape)}")
+    if not all(t.is_contiguous() for t in [ring, clock] + [t for _, t, _ in others]):
+        raise ValueError(f"{what}: ring, clock, {', '.join(name for name, _, _ in others)} must be contiguous")
+    _require_device_tensor("ring", ring)
+    return tuple(ring.shape)
+
+
+def ring_push(raw: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, ring: torch.Tensor, clock: torch.Tensor,
+              null_value: Optional[float] = None) -> None:
+    """The readings `raw` [K,C,N] (float32, on the device) of K consecutive steps go, normalised as `(raw - mean) / std`
+    with the bits of that torch expression, into the rows `(clock[0] + k) mod L` of `ring` [L,C,N]; then `clock[0] += K`
+    and `clock[1] = min(clock[1] + K, L)`, on the device (`msgat_ring_push`: two launches, nothing read back).
+
+    `mean`, `std` [C,N] are `data.SeriesStats`'; `clock` int64 [2].  With `null_value` a reading that is NaN or equal to it
+    is stored as the canonical NaN (`null_value = nan`: the NaNs only), which `ring_windows` takes for missing.  Writes
+    `ring` and `clock` in place.  No autograd: data."""
+    if raw.dim() != 3 or raw.shape[0] < 1:
+        raise ValueError(f"ring_push: raw {tuple(raw.shape)} must be [K >= 1, C, N]")
+    L, C_, N = _check_ring("ring_push", ring, clock, [("raw", raw, (raw.shape[0], *ring.shape[1:])),
+                                                       ("mean", mean, ring.shape[1:]), ("std", std, ring.shape[1:])])
+    K = raw.shape[0]
+    if K > L:
+        raise ValueError(f"ring_push: raw holds K = {K} steps, more than the ring's L = {L}")
+    dev = ring.device
+    with torch.cuda.device(dev):
+        st = _lib.lib().msgat_ring_push(_ptr(raw), _ptr(mean), _ptr(std), _ptr(ring), _ptr(clock), K, C_, N, L,
+                                        int(null_value is not None), 0.0 if null_value is None else float(null_value),
+                                        _stream_handle(dev))
+    _lib.check(st, "msgat_ring_push")
+
+
+def ring_windows(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int, climatology: Optional[torch.Tensor] = None,
+                 mask_channel: bool = False, offsets: Optional[torch.Tensor] = None, out=None):
+    """`(X [1,R,C,N,tau], H [1], D [1])` of the forecast origin `t = clock[0]`, read on the device, in one launch
+    (`msgat_ring_windows`): what `window_gather` gives for that one origin over the full series, the row of absolute step
+    s read at `s mod L` of `ring` [L,C,N].  With `climatology` [period,C,N] it is `window_gather_imputed`: a NaN becomes
+    `climatology[s mod period]`, and `mask_channel` appends the validity channel.
+
+    L must be a multiple of `tau` and at least `tau * max(hours)`; whether the ring holds enough readings is the caller's
+    to know (`clock[1]`; `OnlineForecaster.ready`).  `offsets` as for `window_gather`.  `out=(X, H, D)`: caller-owned
+    buffers of those shapes to write into (a captured step needs them).  No autograd: data."""
+    what = "ring_windows"
+    others = [] if climatology is None else [("climatology", climatology, None)]
+    L, C_, N = _check_ring(what, ring, clock, others)
+    hours = [int(h) for h in hours]
+    if not hours or min(hours) < 1:
+        raise ValueError(f"{what}: hours {hours} must be a non-empty sequence of positive ints")
+    if tau not in (4, 8, 12, 16):
+        raise ValueError(f"{what}: tau = {tau} must be 4, 8, 12 or 16")
+    if L % tau or L < tau * max(hours):
+        raise ValueError(f"{what}: the ring's L = {L} must be a multiple of tau = {tau} and at least tau * max(hours) = "
+                         f"{tau * max(hours)}")
+    if climatology is None and mask_channel:
+        raise ValueError(f"{what}: mask_channel needs a climatology (a ring without a table has no missing readings)")
+    if climatology is not None and (climatology.dim() != 3 or climatology.shape[0] < 1
+                                    or tuple(climatology.shape[1:]) != (C_, N)):
+        raise ValueError(f"{what}: climatology {tuple(climatology.shape)} must be [period >= 1, {C_}, {N}]")
+    dev, R = ring.device, len(hours)
+    if offsets is None:
+        offsets = window_offsets(hours, tau, dev)
+    elif offsets.dtype != torch.int64 or offsets.device != dev or tuple(offsets.shape) != (R,) or not offsets.is_contiguous():
+        raise ValueError(f"{what}: offsets must be a contiguous int64 [{R}] tensor on {dev}")
+    x_shape = (1, R, C_ + int(bool(mask_channel)), N, tau)
+    if out is None:
+        X = torch.empty(x_shape, device=dev, dtype=torch.float32)
+        HD = torch.empty((2, 1), device=dev, dtype=torch.int64)
+        H, D = HD[0], HD[1]
+    else:
+        X, H, D = out
+        for name, t, shape, dtype in (("X", X, x_shape, torch.float32), ("H", H, (1,), torch.int64),
+                                      ("D", D, (1,), torch.int64)):
+            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what}: out's {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}")
+    with torch.cuda.device(dev):
+        st = _lib.lib().msgat_ring_windows(_ptr(ring), _ptr(climatology), _ptr(clock), _ptr(offsets), _ptr(X), _ptr(H),
+                                           _ptr(D), R, C_, N, L, tau, 1 if climatology is None else climatology.shape[0],
+                                           int(bool(mask_channel)), _stream_handle(dev))
+    _lib.check(st, "msgat_ring_windows")
+    return X, H, D
+
+
 # ---- boundary hygiene for every autograd.Function above -----------------------------------------------------------
 # (a) the library's launches act on the CURRENT HIP device (hipFuncSetAttribute for > 64 KB LDS, occupancy queries),
 #     while the reference's API lets the caller name any device (`run_epoch(..., gpu_id=k)`, engine.py:40,50):
