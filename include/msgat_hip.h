@@ -66,7 +66,8 @@ extern "C" {
  *     + msgat_adam_step_averaged and msgat_param_swap (an exponential moving average of the weights inside the update);
  *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window);
  *     + msgat_edge_validity{,_backward} (edges gated by the validity of their source node's input window, per sample);
- *     + msgat_ring_push and msgat_ring_windows (online forecasting: a ring of readings and the windows of its newest origin).
+ *     + msgat_ring_push and msgat_ring_windows (online forecasting: a ring of readings and the windows of its newest origin);
+ *     + msgat_forecast_store and msgat_forecast_score{,_partial_doubles} (online forecasts scored as their readings arrive).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -1093,6 +1094,52 @@ int msgat_ring_push(const float* raw, const float* mean, const float* std, float
 int msgat_ring_windows(const float* ring, const float* climatology_or_null, const int64_t* clock, const int64_t* offsets,
                        float* X, int64_t* H, int64_t* D, int32_t R, int32_t C, int32_t N, int64_t L, int32_t tau,
                        int32_t period, int32_t mask_channel, void* stream);
+
+/* ---- device: online forecasts scored as their readings arrive (no counterpart in the reference, which scores a loader
+ * over a series that exists in full: engine.py:66-70, metrics.py:20-35) ----
+ * The forecast issued at origin o (= clock[0] when it is made) predicts the steps o .. o + T_out - 1; it is due at
+ * horizon h when the reading of absolute step o + h arrives, and its truth is channel 0 of that RAW reading.  State, all
+ * in device memory and never read back during a step:
+ *       book      [P, N, out] fp32   P >= T_out; the forecast of origin o lives in row o mod P (the floor-mod of the
+ *                                    ring above); out = T_out for a point head, Q * T_out, level-major, for Q levels
+ *       issued    [P] int64          the origin each row was written for; a fresh book holds INT64_MIN = never.  A row
+ *                                    counts for origin o only if issued[row] == o and o >= 0.
+ *       sums      [T_out + 1, W] fp64  running totals, zeroed by the caller.  W = 5 for a point head (Q = 0, levels may be
+ *                                    NULL), 7 + 2Q for Q levels.  Row t < T_out: horizon t; row T_out: all horizons.
+ *                                    Columns 0-3: the masked tail's {valid count, sum |e|, 100 sum_{y > mask_value} |e / y|,
+ *                                    sum e^2} with e = p - y, p the point forecast (level `point` of a Q-level head);
+ *                                    column 4: sum e, the signed error (serving has no loss; bias is what shows drift);
+ *                                    Q levels: 5 crossing count, 6 width sum, 7 + q hits y <= p_q, 7 + Q + q sum rho_q,
+ *                                    as msgat_quantile_metrics defines and computes them (fp32 per entry, fp64 sums).
+ *       node_sums [N, 3] fp64        {valid count, sum |e|, sum e} per node over all horizons, zeroed by the caller
+ * An entry is valid by the masked tail's rule: y is not NaN and, with has_null != 0, y != null_value.
+ *
+ * msgat_forecast_store: pred [N, out] moves, as 32-bit words, into row clock[0] mod P of book, and issued[row] = clock[0]:
+ *     one launch.  Storing twice for one origin is idempotent.
+ * msgat_forecast_score: raw [K, C, N] are the readings of the steps s + k, s = clock[0] -- enqueue it BEFORE the
+ *     msgat_ring_push that advances the clock.  Two launches, no floating-point atomics, one fixed order for every sum:
+ *     (1) a lane owns node n.  For k = 0 .. K-1 and, inside, h = 0 .. T_out-1: if origin o = s + k - h carries its stamp
+ *         and y = raw[k, 0, n] is valid, the entry's W terms are formed in fp32 and widened to double (count 1, |e|,
+ *         100 |e / y| or 0 where y <= mask_value, e * e in double, e, ...).  The lane adds count, |e| and e to its node totals
+ *         in this k-then-h order, each starting from +0.0, and node_sums[n, :] += them at the end (one owner per node).  It
+ *         adds every term to its slot partials[(c T_out + h) N + n], which starts as +0.0: the entries of a horizon in k order.
+ *     (2) block c, column c: for every horizon the slots of nodes 64 b .. 64 b + 63 are added in node order from +0.0,
+ *         those block sums in block order b from +0.0; sums[h, c] += the result, and sums[T_out, c] += the horizon results
+ *         added in horizon order from +0.0.
+ *     A numpy restatement in this order reproduces every bit.  partials: msgat_forecast_score_partial_doubles(N, T_out,
+ *     Q) doubles (0 for arguments the entry point refuses).
+ * Rows come from 64-bit floor-mods into [0, P): ANY clock content (cold, negative, a wild word) addresses rows inside book
+ * and issued, and settles nothing unless the stamps match.
+ * A NULL pointer (levels only when Q > 0): MSGAT_ERR_NULL.  K, C, N, T_out <= 0, Q < 0, P < T_out (store: N, out, P <= 0),
+ * levels not strictly increasing inside (0, 1), NaN included, point outside [0, Q): MSGAT_ERR_SHAPE, before any launch.
+ * Q > 8, max(Q, 1) * T_out > 64 or N above 2^31 - 256: MSGAT_ERR_UNSUPPORTED. */
+int msgat_forecast_store(const float* pred, float* book, int64_t* issued, const int64_t* clock, int32_t N, int32_t out,
+                         int64_t P, void* stream);
+size_t msgat_forecast_score_partial_doubles(int32_t N, int32_t T_out, int32_t Q);
+int msgat_forecast_score(const float* raw, const float* book, const int64_t* issued, const int64_t* clock, int32_t K,
+                         int32_t C, int32_t N, int32_t T_out, int32_t Q, const float* levels, int32_t point, int64_t P,
+                         int32_t has_null, float null_value, float mask_value, double* partials, double* sums,
+                         double* node_sums, void* stream);
 
 #ifdef __cplusplus
 }

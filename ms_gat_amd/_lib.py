@@ -216,6 +216,10 @@ _PROTOTYPES = {
                                                                                       C.c_void_p]),
     "msgat_ring_push": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
     "msgat_ring_windows": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 3 + [C.c_void_p]),
+    "msgat_forecast_store": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+    "msgat_forecast_score_partial_doubles": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "msgat_forecast_score": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [c_float_p, C.c_int32, C.c_int64, C.c_int32,
+                                                            C.c_float, C.c_float] + [C.c_void_p] * 4),
 }
 
 _lock = threading.Lock()

@@ -341,6 +341,53 @@ def _ring_windows_torch(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int
     return x, hour % 24, torch.div(hour, 24, rounding_mode="floor") % 7
 
 
+def _forecast_store_torch(pred: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, clock: torch.Tensor) -> None:
+    """`ops.forecast_store` restated with torch indexing: pred [N,out] goes into row clock[0] mod P of `book` [P,N,out]
+    and that row of `issued` [P] is stamped with clock[0]."""
+    row = clock[0] % book.shape[0]                                            # `%` of tensors is the floor-mod
+    book[row] = pred
+    issued[row] = clock[0]
+
+
+def _forecast_score_torch(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, clock: torch.Tensor, t_out: int,
+                          sums: torch.Tensor, node_sums: torch.Tensor, levels=(), point: int = 0,
+                          null_value: float | None = None, mask_value: float = 0.0) -> None:
+    """`ops.forecast_score` restated with torch ops; serves CPU tensors and states what the kernels settle: for k in order
+    and every horizon h the forecast of origin clock[0] + k - h counts if `issued` carries its stamp (and the origin is
+    >= 0), against the truth raw[k, 0]; every entry's terms are formed in fp32 as the kernel forms them and widened to
+    float64.  A node's totals are added in the kernel's k-then-h order; the sums over the nodes are torch's (the kernel
+    adds them in node order: tests/online_score_ref.py restates that bit for bit)."""
+    P, n_levels = book.shape[0], len(levels)
+    start = int(clock[0])
+    stamps = issued.tolist()
+    tau = torch.tensor([float(q) for q in levels], dtype=torch.float32, device=raw.device)
+    tau_m1 = (tau.double() - 1.0).float()
+    for k in range(raw.shape[0]):
+        y = raw[k, 0]
+        valid = ~torch.isnan(y)
+        if null_value is not None:
+            valid = valid & (y != null_value)
+        for h in range(t_out):
+            origin = start + k - h
+            row = origin % P
+            if origin < 0 or stamps[row] != origin or not bool(valid.any()):
+                continue
+            p = book[row].reshape(book.shape[1], max(n_levels, 1), t_out)[:, :, h]                      # [N, Q]
+            e = p[:, point] - y
+            zero = torch.zeros_like(y, dtype=torch.float64)
+            ape = torch.where(y > mask_value, 100.0 * (e / y).abs().double(), zero)
+            terms = [torch.ones_like(zero), e.abs().double(), ape, e.double() * e.double(), e.double()]
+            if n_levels:
+                u = y[:, None] - p
+                rho = torch.maximum(tau * u, tau_m1 * u)
+                terms += [(p[:, :-1] > p[:, 1:]).any(1).double(), (p[:, -1] - p[:, 0]).double(),
+                          *(y[:, None] <= p).double().t(), *rho.double().t()]
+            terms = torch.where(valid[None], torch.stack(terms), zero)                                   # [W, N]
+            sums[h] += terms.sum(1)
+            sums[t_out] += terms.sum(1)
+            node_sums += terms[[0, 1, 4]].t()
+
+
 class DeviceWindows:
     """A loader whose series lives on the device: every batch is built there from its forecast origins, by one launch
     of `ops.window_gather` -- no per-sample Python, no collate, no pinning, no host-to-device copy of the batch.

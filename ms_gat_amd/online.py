@@ -43,10 +43,27 @@ class OnlineForecaster:
     restatements (`data._ring_push_torch`, `data._ring_windows_torch`).
 
     `state_dict()` / `load_state_dict()`: ring, clock and start_step -- a restarted service resumes where it stopped.
-    One process, one origin per step: multi-rank serving and batched origins are not provided."""
+    One process, one origin per step: multi-rank serving and batched origins are not provided.
+
+    `score=True` keeps a book of the forecasts it returned and settles it as their readings arrive, on the device
+    (`ops.forecast_store` / `ops.forecast_score`): the forecast of origin o is due at horizon h when the reading of step
+    o + h is pushed, its truth is channel 0 of that raw reading, valid unless NaN or equal to `score_null_value` (default
+    `stats.input_null_value`).  `push` settles its K readings before it normalises them, `forecast()` and `step()` store
+    what they return (`forecast()` twice at one origin changes nothing), and the captured step becomes score -> push ->
+    advance -> windows -> forward -> store: still ONE replay, three more kernels.  The head's width must be Q * T_out
+    with Q = len(`score_quantiles`) (1 for a point head), else ValueError at the first forecast, which sizes the book
+    (T_out rows).  `scores(at=None)` reads the totals back once: {"count", "MAE", "MAPE", "RMSE", "bias", "horizons":
+    {the same as lists per horizon; `at=[3, 6, 12]` picks those 1-based steps}} with `Metrics`' definitions over the
+    valid entries, "bias" the mean signed error p - y, and for `score_quantiles` "quantiles": {levels, coverage, pinball,
+    crossing, width} as `Metrics.quantile_summary()` gives them.  `node_scores()` -> float64 [N, 3] on the host: count,
+    MAE and bias per sensor over all horizons, NaN where the count is 0.  `reset_scores()` zeroes the totals in place (the
+    book stays: forecasts in flight are still settled).  `state_dict()` then also holds book, issued, score_sums and
+    score_node_sums; a state without them loads as a cold book with zero totals.  Without `score` there is no buffer, no
+    state key and no launch of all this."""
 
     def __init__(self, model: nn.Module, stats: "_data.SeriesStats", start_step: int, capacity: int | None = None,
-                 hip_graph="auto"):
+                 hip_graph="auto", score: bool = False, score_quantiles=None, score_null_value="stats",
+                 score_mask_value: float = 0.0):
         if hip_graph not in (True, False, "auto"):
             raise ValueError(f"hip_graph must be True, False or 'auto', not {hip_graph!r}")
         tensors = list(model.parameters()) + list(model.buffers())
@@ -84,6 +101,15 @@ class OnlineForecaster:
         self.resident_bytes = self.ring.numel() * 4
         self._pushed = 0                      # host mirror of clock[1] before it saturates: nothing is read back
         self._graph = self._prediction = None
+        self.score = bool(score)
+        self._score_state = None              # (book, issued, sums, node_sums), sized by the first forecast
+        if self.score:
+            from . import ops
+            self.score_levels = () if score_quantiles is None else ops.quantile_levels(score_quantiles)
+            self.score_point = ops.quantile_point(self.score_levels) if self.score_levels else 0
+            null = stats.input_null_value if isinstance(score_null_value, str) else score_null_value   # "stats"
+            self.score_null_value = None if null is None else float(null)
+            self.score_mask_value = float(score_mask_value)
         if on_gpu:
             from . import ops
             self._offsets = ops.window_offsets(self.hours, self.tau, dev)
@@ -116,6 +142,49 @@ class OnlineForecaster:
         with torch.no_grad():
             return self.model(*batch)[0]
 
+    # ---- scoring: the book of issued forecasts and its totals, on whichever state they are handed -------------------------
+    def _score_setup(self, out: int) -> None:
+        """Sizes book and totals for a head of `out` outputs per node (the first forecast knows it); cold and zero."""
+        if self._score_state is not None:
+            if self._score_state[0].shape[2] != out:
+                raise ValueError(f"the model's head has {out} outputs per node, the book was sized for "
+                                 f"{self._score_state[0].shape[2]}")
+            return
+        from . import ops
+        n_levels = max(len(self.score_levels), 1)
+        if out % n_levels or not 1 <= out <= 64:
+            raise ValueError(f"score=True: the model's head has {out} outputs per node, which is not Q * T_out for Q = "
+                             f"{n_levels} level(s) with Q * T_out <= 64")
+        self.score_t_out = out // n_levels
+        dev, N = self.device, self.n_nodes
+        self._score_state = (torch.zeros((self.score_t_out, N, out), dtype=torch.float32, device=dev),
+                             torch.full((self.score_t_out,), ops.SCORE_NEVER, dtype=torch.int64, device=dev),
+                             torch.zeros((self.score_t_out + 1, ops.score_columns(len(self.score_levels))),
+                                         dtype=torch.float64, device=dev),
+                             torch.zeros((N, ops.SCORE_NODE_COLUMNS), dtype=torch.float64, device=dev))
+        if dev.type == "cuda":
+            need = int(ops._lib.lib().msgat_forecast_score_partial_doubles(N, self.score_t_out, len(self.score_levels)))
+            self._score_partials = torch.empty(need, dtype=torch.float64, device=dev)
+
+    def _settle(self, reading: torch.Tensor, state, clock: torch.Tensor) -> None:
+        book, issued, sums, node_sums = state
+        kw = dict(levels=self.score_levels or None, point=self.score_point, null_value=self.score_null_value,
+                  mask_value=self.score_mask_value)
+        if self.device.type == "cuda":
+            from . import ops
+            ops.forecast_score(reading, book, issued, clock, self.score_t_out, sums, node_sums,
+                               partials=self._score_partials, **kw)
+        else:
+            kw["levels"] = self.score_levels
+            _data._forecast_score_torch(reading, book, issued, clock, self.score_t_out, sums, node_sums, **kw)
+
+    def _store(self, pred: torch.Tensor, state, clock: torch.Tensor) -> None:
+        if self.device.type == "cuda":
+            from . import ops
+            ops.forecast_store(pred.contiguous(), state[0], state[1], clock)
+        else:
+            _data._forecast_store_torch(pred, state[0], state[1], clock)
+
     # ---- public ------------------------------------------------------------------------------------------------------
     @property
     def ready(self) -> bool:
@@ -137,15 +206,21 @@ class OnlineForecaster:
         return reading
 
     def push(self, reading: torch.Tensor) -> None:
-        reading = self._checked(reading)
-        self._push(reading.to(self.device).contiguous(), self.ring, self.clock)
+        reading = self._checked(reading).to(self.device).contiguous()
+        if self._score_state is not None:     # before the push: the clock still names the first of these steps
+            self._settle(reading, self._score_state, self.clock)
+        self._push(reading, self.ring, self.clock)
         self._pushed = min(self._pushed + reading.shape[0], self.capacity)
 
     def forecast(self) -> torch.Tensor:
         if not self.ready:
             raise RuntimeError(f"forecast() needs {self.history} readings in the ring, {self._pushed} were pushed")
         out = self._out if self.device.type == "cuda" else None
-        return self._forward(self._windows(self.ring, self.clock, out=out))
+        pred = self._forward(self._windows(self.ring, self.clock, out=out))
+        if self.score:
+            self._score_setup(pred.shape[-1])
+            self._store(pred, self._score_state, self.clock)
+        return pred
 
     def step(self, reading: torch.Tensor) -> torch.Tensor:
         reading = self._checked(reading)
@@ -163,21 +238,96 @@ class OnlineForecaster:
         """Warm the whole step up on a side stream and on a SCRATCH ring and clock (the live ones must not move), then
         capture it on the live ones into the static buffers."""
         ring, clock, out = self.ring.clone(), self.clock.clone(), self._window_buffers()
+        scratch = None                        # the scoring state's scratch copy, made once the book is sized
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(2):
+                if scratch is not None:
+                    self._settle(self._reading, scratch, clock)
                 self._push(self._reading, ring, clock)
-                self._forward(self._windows(ring, clock, out=out))
+                pred = self._forward(self._windows(ring, clock, out=out))
+                if self.score:
+                    self._score_setup(pred.shape[-1])
+                    scratch = scratch or tuple(t.clone() for t in self._score_state)
+                    self._store(pred, scratch, clock)
         torch.cuda.current_stream(self.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            if self.score:
+                self._settle(self._reading, self._score_state, self.clock)
             self._push(self._reading, self.ring, self.clock)
             self._prediction = self._forward(self._windows(self.ring, self.clock, out=self._out))
+            if self.score:
+                self._store(self._prediction, self._score_state, self.clock)
         self._graph = graph
 
+    # ---- the scores, read back -------------------------------------------------------------------------------------------
+    def scores(self, at=None) -> dict:
+        """The totals since the last `reset_scores()`, read back once (see the class docstring)."""
+        if not self.score:
+            raise RuntimeError("scores() needs OnlineForecaster(score=True)")
+        n_levels = len(self.score_levels)
+        if self._score_state is None:         # no forecast yet: nothing was due
+            found = {"count": 0.0, "MAE": 0.0, "MAPE": 0.0, "RMSE": 0.0, "bias": 0.0,
+                     "horizons": {k: [] for k in ("count", "MAE", "MAPE", "RMSE", "bias")}}
+            if n_levels:
+                found["quantiles"] = {"levels": list(self.score_levels), "coverage": [0.0] * n_levels,
+                                      "pinball": [0.0] * n_levels, "crossing": 0.0, "width": 0.0}
+            return found
+        rows = self._score_state[2].cpu()
+        n = rows[:, 0].clamp(min=1.0)
+        named = {"count": rows[:, 0], "MAE": rows[:, 1] / n, "MAPE": rows[:, 2] / n, "RMSE": (rows[:, 3] / n).sqrt(),
+                 "bias": rows[:, 4] / n}
+        found = {k: float(v[-1]) for k, v in named.items()}
+        horizons = {k: v[:-1].tolist() for k, v in named.items()}
+        if n_levels:
+            from .engine import Metrics
+            horizons.update(Metrics._quantile_columns(rows[:-1], n[:-1], n_levels))
+            last = Metrics._quantile_columns(rows[-1:], n[-1:], n_levels)
+            found["quantiles"] = {"levels": list(self.score_levels), "coverage": [c[0] for c in last["coverage"]],
+                                  "pinball": [c[0] for c in last["pinball"]], "crossing": last["crossing"][0],
+                                  "width": last["width"][0]}
+        if at is not None:
+            for step in at:
+                if not 1 <= int(step) <= self.score_t_out:
+                    raise IndexError(f"horizon step {step} outside 1..{self.score_t_out}")
+            pick = lambda v: [v[int(step) - 1] for step in at]  # noqa: E731
+            horizons = {k: [pick(level) for level in v] if k in ("coverage", "pinball") else pick(v)
+                        for k, v in horizons.items()}
+        found["horizons"] = horizons
+        return found
+
+    def node_scores(self) -> torch.Tensor:
+        """float64 [N, 3] on the host: valid count, MAE and bias per node over all horizons; NaN where the count is 0."""
+        if not self.score:
+            raise RuntimeError("node_scores() needs OnlineForecaster(score=True)")
+        if self._score_state is None:
+            found = torch.full((self.n_nodes, 3), float("nan"), dtype=torch.float64)
+            found[:, 0] = 0.0
+            return found
+        rows = self._score_state[3].cpu()
+        count = rows[:, 0]
+        nan = torch.full((), float("nan"), dtype=torch.float64)
+        safe = count.clamp(min=1.0)
+        return torch.stack([count, torch.where(count > 0, rows[:, 1] / safe, nan),
+                            torch.where(count > 0, rows[:, 2] / safe, nan)], dim=1)
+
+    def reset_scores(self) -> None:
+        """Zeroes the totals IN PLACE (a captured step holds their addresses); the book stays."""
+        if not self.score:
+            raise RuntimeError("reset_scores() needs OnlineForecaster(score=True)")
+        if self._score_state is not None:
+            self._score_state[2].zero_()
+            self._score_state[3].zero_()
+
     def state_dict(self) -> dict:
-        return {"ring": self.ring.detach().clone(), "clock": self.clock.detach().clone(), "start_step": self.start_step}
+        state = {"ring": self.ring.detach().clone(), "clock": self.clock.detach().clone(), "start_step": self.start_step}
+        if self._score_state is not None:
+            state.update({k: t.detach().clone() for k, t in zip(self._SCORE_KEYS, self._score_state)})
+        return state
+
+    _SCORE_KEYS = ("book", "issued", "score_sums", "score_node_sums")
 
     def load_state_dict(self, state: dict) -> None:
         ring, clock = state["ring"], state["clock"]
@@ -189,6 +339,22 @@ class OnlineForecaster:
         if now < int(state["start_step"]) or not 0 <= held <= self.capacity:
             raise ValueError(f"state's clock [{now}, {held}] does not fit its start_step {state['start_step']} and a ring "
                              f"of {self.capacity} rows")
+        scored = self.score and all(k in state for k in self._SCORE_KEYS)
+        if scored:
+            self._score_setup(int(state["book"].shape[-1]) if state["book"].dim() == 3 else 0)
+            for key, mine in zip(self._SCORE_KEYS, self._score_state):
+                if tuple(state[key].shape) != tuple(mine.shape) or state[key].dtype != mine.dtype:
+                    raise ValueError(f"state holds {key} {tuple(state[key].shape)} {state[key].dtype}; this forecaster's "
+                                     f"is {tuple(mine.shape)} {mine.dtype}")
         self.ring.copy_(ring)                 # in place: a captured step keeps reading these addresses
         self.clock.copy_(clock)
         self.start_step, self._pushed = int(state["start_step"]), held
+        if scored:
+            for key, mine in zip(self._SCORE_KEYS, self._score_state):
+                mine.copy_(state[key])
+        elif self._score_state is not None:   # a state without a book: cold, with zero totals
+            from . import ops
+            book, issued, sums, node_sums = self._score_state
+            issued.fill_(ops.SCORE_NEVER)
+            sums.zero_()
+            node_sums.zero_()

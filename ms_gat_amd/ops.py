@@ -2543,6 +2543,102 @@ def ring_windows(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int, clima
     return X, H, D
 
 
+# ---- online forecasting, scored: the book of issued forecasts and the totals it is settled into -----------------------
+SCORE_NODE_COLUMNS = 3        # node_sums [N, 3]: {valid count, sum |e|, sum e}
+SCORE_NEVER = -2 ** 63        # what `issued` holds for a row that was never written
+
+
+def score_columns(n_levels: int) -> int:
+    """Columns of the totals `forecast_score` adds to: 5 for a point head, 7 + 2Q for Q quantile levels."""
+    return 5 if not n_levels else QUANTILE_BASE_COLUMNS + 2 * int(n_levels)
+
+
+def _check_book(what, book, issued, clock, others):
+    """`book` float32 [P,N,out], `issued` int64 [P] and `clock` int64 [2] on one device with the tensors `others` =
+    [(name, tensor, dtype, shape)], all contiguous; returns (P, N, out)."""
+    for name, t, dtype, _ in [("book", book, torch.float32, None), ("issued", issued, torch.int64, None),
+                              ("clock", clock, torch.int64, None)] + others:
+        if t.dtype != dtype:
+            raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if book.dim() != 3 or book.numel() == 0:
+        raise ValueError(f"{what}: book {tuple(book.shape)} must be a non-empty [P, N, out]")
+    for name, t, _, shape in [("issued", issued, None, (book.shape[0],)), ("clock", clock, None, (2,))] + others:
+        if t.device != book.device:
+            raise ValueError(f"{what}: book on {book.device} and {name} on {t.device} must share one device")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} must be {list(shape)}")
+    if not all(t.is_contiguous() for t in [book, issued, clock] + [t for _, t, _, _ in others]):
+        raise ValueError(f"{what}: book, issued, clock, {', '.join(name for name, _, _, _ in others)} must be contiguous")
+    _require_device_tensor("book", book)
+    return tuple(book.shape)
+
+
+def forecast_store(pred: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, clock: torch.Tensor) -> None:
+    """The forecast `pred` [N,out] of origin `clock[0]` goes into row `clock[0] mod P` of `book` [P,N,out] and that row of
+    `issued` [P] (int64) is stamped with the origin, on the device (`msgat_forecast_store`: one launch, nothing read
+    back; twice for one origin changes nothing).  Writes `book` and `issued` in place.  No autograd: data."""
+    if pred.dim() != 2:
+        raise ValueError(f"forecast_store: pred {tuple(pred.shape)} must be [N, out]")
+    P, N, out = _check_book("forecast_store", book, issued, clock, [("pred", pred, torch.float32, book.shape[1:])])
+    dev = book.device
+    with torch.cuda.device(dev):
+        st = _lib.lib().msgat_forecast_store(_ptr(pred), _ptr(book), _ptr(issued), _ptr(clock), N, out, P,
+                                             _stream_handle(dev))
+    _lib.check(st, "msgat_forecast_store")
+
+
+def forecast_score(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, clock: torch.Tensor, t_out: int,
+                   sums: torch.Tensor, node_sums: torch.Tensor, levels=None, point: Optional[int] = None,
+                   null_value: Optional[float] = None, mask_value: float = 0.0,
+                   partials: Optional[torch.Tensor] = None) -> None:
+    """Settles the forecasts in `book` [P,N,out] that the readings `raw` [K,C,N] (float32, RAW, of the steps
+    `clock[0] + k`) make due: call it BEFORE the `ring_push` of the same readings.  For k in order and every horizon
+    h < t_out the forecast of origin `clock[0] + k - h` counts if `issued` carries its stamp; its truth is `raw[k, 0]`,
+    valid unless NaN or equal to `null_value`.  Adds to `sums` (float64 [t_out + 1, W], W = `score_columns(Q)`: per horizon
+    and over all, {count, |e|, 100 |e / y| (y > mask_value), e^2, e} and for `levels` the crossing count, width sum, hit
+    counts and pinball sums of `quantile_metrics`) and to `node_sums` (float64 [N, 3]: count, |e|, e per node), both
+    zeroed by the caller (`msgat_forecast_score`: two launches, a fixed summation order, nothing read back).
+
+    `levels`: None for a point head (out = t_out) or the Q quantile levels of a head with out = Q * t_out, `point` the
+    level that serves as the point forecast (default: nearest 0.5).  `partials`: a caller-owned float64 buffer of
+    `msgat_forecast_score_partial_doubles(N, t_out, Q)` elements (a captured step keeps one).  No autograd: data."""
+    what = "forecast_score"
+    levels = () if levels is None else quantile_levels(levels)
+    n_levels, t_out = len(levels), int(t_out)
+    if raw.dim() != 3 or raw.shape[0] < 1:
+        raise ValueError(f"{what}: raw {tuple(raw.shape)} must be [K >= 1, C, N]")
+    if t_out < 1 or max(n_levels, 1) * t_out > 64:
+        raise ValueError(f"{what}: t_out = {t_out} with {n_levels} levels: between 1 and 64 outputs per node")
+    cols = score_columns(n_levels)
+    if book.dim() == 3 and raw.shape[2] != book.shape[1]:
+        raise ValueError(f"{what}: raw {tuple(raw.shape)} and book {tuple(book.shape)} must agree in N")
+    P, N, out = _check_book(what, book, issued, clock, [
+        ("raw", raw, torch.float32, None), ("sums", sums, torch.float64, (t_out + 1, cols)),
+        ("node_sums", node_sums, torch.float64, (book.shape[1] if book.dim() == 3 else 0, SCORE_NODE_COLUMNS))])
+    if out != max(n_levels, 1) * t_out:
+        raise ValueError(f"{what}: a head of {max(n_levels, 1)} x {t_out} outputs needs book [P, N, "
+                         f"{max(n_levels, 1) * t_out}], got out = {out}")
+    if P < t_out:
+        raise ValueError(f"{what}: the book's P = {P} rows must be at least t_out = {t_out}")
+    point = (quantile_point(levels) if n_levels else 0) if point is None else int(point)
+    if n_levels and not 0 <= point < n_levels:
+        raise ValueError(f"{what}: point = {point} outside the {n_levels} levels")
+    dev, K, C_ = book.device, raw.shape[0], raw.shape[1]
+    L = _lib.lib()
+    need = int(L.msgat_forecast_score_partial_doubles(N, t_out, n_levels))
+    if partials is None:
+        partials = torch.empty(max(need, 1), device=dev, dtype=torch.float64)
+    elif partials.dtype != torch.float64 or partials.device != dev or partials.numel() < need or not partials.is_contiguous():
+        raise ValueError(f"{what}: partials must be a contiguous float64 tensor of at least {need} elements on {dev}")
+    host_levels = (C.c_float * n_levels)(*levels) if n_levels else None
+    with torch.cuda.device(dev):
+        st = L.msgat_forecast_score(_ptr(raw), _ptr(book), _ptr(issued), _ptr(clock), K, C_, N, t_out, n_levels,
+                                    host_levels, point, P, int(null_value is not None),
+                                    0.0 if null_value is None else float(null_value), float(mask_value), _ptr(partials),
+                                    _ptr(sums), _ptr(node_sums), _stream_handle(dev))
+    _lib.check(st, "msgat_forecast_score")
+
+
 # ---- boundary hygiene for every autograd.Function above -----------------------------------------------------------
 # (a) the library's launches act on the CURRENT HIP device (hipFuncSetAttribute for > 64 KB LDS, occupancy queries),
 #     while the reference's API lets the caller name any device (`run_epoch(..., gpu_id=k)`, engine.py:40,50):
