@@ -1082,18 +1082,48 @@ extern "C" int msgat_gate_sum_backward(const float* dout, const float* pred, con
 }
 
 // ---- step tail: fused Huber loss + metric sums, flat Adam ------------------------------------------------------
+// The checks the tail's entries share.  Each entry reports what it always reported, in the order it always did.
+
+// the operands and results of a loss entry: every one of them is required (`sums` is optional and not among them)
+template <class... P>
+static int check_loss_io(const P*... ptrs) {
+  return (... && (ptrs != nullptr)) ? MSGAT_OK : MSGAT_ERR_NULL;
+}
+
+// a chunk table of n_chunks rows and the buffers it indexes: a negative count is a shape error; a missing pointer
+// matters only where there is a row to read (n_chunks == 0 passes: what an empty table means is the entry's to say)
+template <class... P>
+static int check_chunk_table(int32_t n_chunks, const P*... ptrs) {
+  if (n_chunks < 0) return MSGAT_ERR_SHAPE;
+  return n_chunks > 0 && !(... && (ptrs != nullptr)) ? MSGAT_ERR_NULL : MSGAT_OK;
+}
+
+// the arguments every msgat_adam_step* has.  `extras`: the entry's own required pointers (guard, shadow) are present
+static int check_adam(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
+                      const int32_t* chunk_tensor, int32_t n_chunks, const int32_t* active_tensors, int32_t n_active,
+                      const float* grad, const float* exp_avg, const float* exp_avg_sq, const float* steps, const float* lr,
+                      double beta1, double beta2, double eps, double weight_decay, bool extras) {
+  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
+  if (!steps || !lr || !extras) return MSGAT_ERR_NULL;
+  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
+  if (int st = check_chunk_table(n_chunks, chunk_param, chunk_off, chunk_len, chunk_tensor, grad, exp_avg, exp_avg_sq))
+    return st;
+  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
+  return MSGAT_OK;
+}
+
 extern "C" size_t msgat_huber_partial_doubles(int64_t n) { return n > 0 ? huber_partial_doubles(n) : 0; }
 
 extern "C" int msgat_huber_metrics(const float* pred, const float* truth, int64_t n, float delta, float mask_value,
                                    double* partials, float* loss, double* sums, float loss_weight, void* stream) {
-  if (!pred || !truth || !partials || !loss) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, partials, loss)) return st;
   if (n <= 0 || !(delta > 0.f) || !(loss_weight >= 0.f)) return MSGAT_ERR_SHAPE;
   return launch_huber_metrics(pred, truth, n, delta, mask_value, partials, loss, sums, loss_weight, (hipStream_t)stream);
 }
 
 extern "C" int msgat_huber_grad(const float* pred, const float* truth, const float* dloss, int64_t n, float delta,
                                 float* dpred, void* stream) {
-  if (!pred || !truth || !dloss || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, dloss, dpred)) return st;
   if (n <= 0 || !(delta > 0.f)) return MSGAT_ERR_SHAPE;
   return launch_huber_grad(pred, truth, dloss, n, delta, dpred, (hipStream_t)stream);
 }
@@ -1106,7 +1136,7 @@ static int check_gauss(float sigma, float delta) {
 extern "C" int msgat_gauss_metrics(const float* pred, const float* truth, int64_t n, float sigma, float delta,
                                    float mask_value, double* partials, float* loss, double* sums, float loss_weight,
                                    void* stream) {
-  if (!pred || !truth || !partials || !loss) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, partials, loss)) return st;
   if (n <= 0 || !(loss_weight >= 0.f)) return MSGAT_ERR_SHAPE;
   if (int st = check_gauss(sigma, delta)) return st;
   return launch_gauss_metrics(pred, truth, n, sigma, delta, mask_value, partials, loss, sums, loss_weight,
@@ -1115,7 +1145,7 @@ extern "C" int msgat_gauss_metrics(const float* pred, const float* truth, int64_
 
 extern "C" int msgat_gauss_grad(const float* pred, const float* truth, const float* dloss, int64_t n, float sigma,
                                 float delta, float* dpred, void* stream) {
-  if (!pred || !truth || !dloss || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, dloss, dpred)) return st;
   if (n <= 0) return MSGAT_ERR_SHAPE;
   if (int st = check_gauss(sigma, delta)) return st;
   return launch_gauss_grad(pred, truth, dloss, n, sigma, delta, dpred, (hipStream_t)stream);
@@ -1128,13 +1158,12 @@ extern "C" int msgat_adam_step(float* const* chunk_param, const int64_t* chunk_o
                                int32_t n_active, const float* grad, float* exp_avg, float* exp_avg_sq, float* steps,
                                const float* lr, double beta1, double beta2, double eps, double weight_decay,
                                const float* grad_divisor, void* stream) {
-  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
-  if (!steps || !lr) return MSGAT_ERR_NULL;
-  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
-  if (n_chunks > 0 && (!chunk_param || !chunk_off || !chunk_len || !chunk_tensor || !grad || !exp_avg || !exp_avg_sq)) return MSGAT_ERR_NULL;
-  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
+  if (int st = check_adam(chunk_param, chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active, grad, exp_avg,
+                          exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, true))
+    return st;
   return launch_adam(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active,
-                     grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, (hipStream_t)stream);
+                     grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, nullptr, nullptr, 0.,
+                     (hipStream_t)stream);
 }
 
 // ---- the guard on the optimizer step: global-norm clipping, non-finite steps left out -------------------------------
@@ -1145,10 +1174,9 @@ extern "C" size_t msgat_grad_guard_partial_doubles(int32_t n_chunks) { return n_
 extern "C" int msgat_grad_guard(const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks, const float* grad,
                                 const float* grad_divisor, float max_norm, double* partials, float* guard,
                                 void* stream) {
-  if (n_chunks < 0) return MSGAT_ERR_SHAPE;
-  if (!(max_norm > 0.f)) return MSGAT_ERR_SHAPE;   // <= 0 and NaN; +inf = no clipping
+  if (n_chunks < 0 || !(max_norm > 0.f)) return MSGAT_ERR_SHAPE;   // max_norm <= 0 and NaN; +inf = no clipping
   if (!guard) return MSGAT_ERR_NULL;
-  if (n_chunks > 0 && (!chunk_off || !chunk_len || !grad || !partials)) return MSGAT_ERR_NULL;
+  if (int st = check_chunk_table(n_chunks, chunk_off, chunk_len, grad, partials)) return st;
   return launch_grad_guard((const long long*)chunk_off, chunk_len, n_chunks, grad, grad_divisor, max_norm, partials, guard,
                            (hipStream_t)stream);
 }
@@ -1159,14 +1187,12 @@ extern "C" int msgat_adam_step_guarded(float* const* chunk_param, const int64_t*
                                        float* steps, const float* lr, double beta1, double beta2, double eps,
                                        double weight_decay, const float* grad_divisor, const float* guard,
                                        void* stream) {
-  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
-  if (!steps || !lr || !guard) return MSGAT_ERR_NULL;
-  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
-  if (n_chunks > 0 && (!chunk_param || !chunk_off || !chunk_len || !chunk_tensor || !grad || !exp_avg || !exp_avg_sq)) return MSGAT_ERR_NULL;
-  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
-  return launch_adam_guarded(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors,
-                             n_active, grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor,
-                             guard, (hipStream_t)stream);
+  if (int st = check_adam(chunk_param, chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active, grad, exp_avg,
+                          exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, guard != nullptr))
+    return st;
+  return launch_adam(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active,
+                     grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard, nullptr, 0.,
+                     (hipStream_t)stream);
 }
 
 // ---- averaged weights: the update that also moves the shadow, and the in-place exchange ------------------------------
@@ -1176,31 +1202,57 @@ extern "C" int msgat_adam_step_averaged(float* const* chunk_param, const int64_t
                                         float* steps, const float* lr, double beta1, double beta2, double eps,
                                         double weight_decay, const float* grad_divisor, const float* guard, float* shadow,
                                         double decay, void* stream) {
-  if (n_chunks < 0 || n_active < 0) return MSGAT_ERR_SHAPE;
-  if (!steps || !lr || !shadow) return MSGAT_ERR_NULL;   // guard may be NULL: the unguarded update
-  if (n_active > 0 && !active_tensors) return MSGAT_ERR_NULL;
-  if (n_chunks > 0 && (!chunk_param || !chunk_off || !chunk_len || !chunk_tensor || !grad || !exp_avg || !exp_avg_sq)) return MSGAT_ERR_NULL;
-  if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.)) return MSGAT_ERR_SHAPE;
+  if (int st = check_adam(chunk_param, chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active, grad, exp_avg,
+                          exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, shadow != nullptr))
+    return st;                                                // guard may be NULL: the unguarded update
   if (!(decay >= 0. && decay < 1.)) return MSGAT_ERR_SHAPE;   // also NaN
-  return launch_adam_averaged(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors,
-                              n_active, grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor,
-                              guard, shadow, decay, (hipStream_t)stream);
+  return launch_adam(chunk_param, (const long long*)chunk_off, chunk_len, chunk_tensor, n_chunks, active_tensors, n_active,
+                     grad, exp_avg, exp_avg_sq, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard, shadow, decay,
+                     (hipStream_t)stream);
 }
 
 extern "C" int msgat_param_swap(float* const* chunk_param, const int64_t* chunk_off, const int32_t* chunk_len,
                                 int32_t n_chunks, float* flat, void* stream) {
-  if (n_chunks < 0) return MSGAT_ERR_SHAPE;
+  if (int st = check_chunk_table(n_chunks, chunk_param, chunk_off, chunk_len, flat)) return st;
   if (n_chunks == 0) return MSGAT_OK;
-  if (!chunk_param || !chunk_off || !chunk_len || !flat) return MSGAT_ERR_NULL;
   return launch_param_swap(chunk_param, (const long long*)chunk_off, chunk_len, n_chunks, flat, (hipStream_t)stream);
+}
+
+// ---- gather of the gradients into the flat buffer: overwriting or accumulating (a later micro-batch of a window), the
+// scale by value or read from device memory.  An empty table is a shape error here.
+template <class... P>
+static int check_gather(int32_t n_chunks, const P*... ptrs) {
+  return n_chunks == 0 ? MSGAT_ERR_SHAPE : check_chunk_table(n_chunks, ptrs...);
 }
 
 extern "C" int msgat_gather_scaled(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
                                    int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
-  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
-  if (!chunk_src || !chunk_off || !chunk_len || !flat) return MSGAT_ERR_NULL;
-  return launch_gather_scaled(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat, weight_index,
-                              (hipStream_t)stream);
+  if (int st = check_gather(n_chunks, chunk_src, chunk_off, chunk_len, flat)) return st;
+  return launch_gather(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, nullptr, false, flat,
+                       weight_index, (hipStream_t)stream);
+}
+
+extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                                       int32_t n_chunks, const float* scale, float* flat, int64_t weight_index,
+                                       void* stream) {
+  if (int st = check_gather(n_chunks, chunk_src, chunk_off, chunk_len, scale, flat)) return st;
+  return launch_gather(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, 0.f, scale, false, flat, weight_index,
+                       (hipStream_t)stream);
+}
+
+extern "C" int msgat_gather_accumulate(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
+                                       int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
+  if (int st = check_gather(n_chunks, chunk_src, chunk_off, chunk_len, flat)) return st;
+  return launch_gather(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, nullptr, true, flat,
+                       weight_index, (hipStream_t)stream);
+}
+
+extern "C" int msgat_gather_accumulate_dev(const float* const* chunk_src, const int64_t* chunk_off,
+                                           const int32_t* chunk_len, int32_t n_chunks, const float* scale, float* flat,
+                                           int64_t weight_index, void* stream) {
+  if (int st = check_gather(n_chunks, chunk_src, chunk_off, chunk_len, scale, flat)) return st;
+  return launch_gather(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, 0.f, scale, true, flat, weight_index,
+                       (hipStream_t)stream);
 }
 
 // ---- step tail with missing readings: masked Huber loss + per-horizon metric sums ------------------------------------
@@ -1219,7 +1271,7 @@ extern "C" size_t msgat_masked_huber_partial_doubles(int64_t rows, int32_t T_out
 extern "C" int msgat_masked_huber_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float delta,
                                           float null_value, float mask_value, double* partials, float* loss,
                                           float* valid, double* sums, void* stream) {
-  if (!pred || !truth || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, partials, loss, valid)) return st;
   if (int st = check_masked(rows, T_out, delta)) return st;
   return launch_masked_huber_metrics(pred, truth, rows, T_out, delta, null_value, mask_value, partials, loss, valid, sums,
                                      (hipStream_t)stream);
@@ -1228,7 +1280,7 @@ extern "C" int msgat_masked_huber_metrics(const float* pred, const float* truth,
 extern "C" int msgat_masked_huber_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
                                        int64_t rows, int32_t T_out, float delta, float null_value, float* dpred,
                                        void* stream) {
-  if (!pred || !truth || !dloss || !valid || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, dloss, valid, dpred)) return st;
   if (int st = check_masked(rows, T_out, delta)) return st;
   return launch_masked_huber_grad(pred, truth, dloss, valid, rows, T_out, delta, null_value, dpred, (hipStream_t)stream);
 }
@@ -1236,7 +1288,7 @@ extern "C" int msgat_masked_huber_grad(const float* pred, const float* truth, co
 extern "C" int msgat_masked_gauss_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, float sigma,
                                           float delta, float null_value, float mask_value, double* partials,
                                           float* loss, float* valid, double* sums, void* stream) {
-  if (!pred || !truth || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, partials, loss, valid)) return st;
   if (int st = check_gauss(sigma, delta)) return st;
   if (int st = check_masked(rows, T_out, 1.f)) return st;
   return launch_masked_gauss_metrics(pred, truth, rows, T_out, sigma, delta, null_value, mask_value, partials, loss, valid,
@@ -1246,45 +1298,24 @@ extern "C" int msgat_masked_gauss_metrics(const float* pred, const float* truth,
 extern "C" int msgat_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
                                        int64_t rows, int32_t T_out, float sigma, float delta, float null_value,
                                        float* dpred, void* stream) {
-  if (!pred || !truth || !dloss || !valid || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, dloss, valid, dpred)) return st;
   if (int st = check_gauss(sigma, delta)) return st;
   if (int st = check_masked(rows, T_out, 1.f)) return st;
   return launch_masked_gauss_grad(pred, truth, dloss, valid, rows, T_out, sigma, delta, null_value, dpred,
                                   (hipStream_t)stream);
 }
 
-extern "C" int msgat_gather_scaled_dev(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
-                                       int32_t n_chunks, const float* scale, float* flat, int64_t weight_index,
-                                       void* stream) {
-  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
-  if (!chunk_src || !chunk_off || !chunk_len || !scale || !flat) return MSGAT_ERR_NULL;
-  return launch_gather_scaled_dev(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat, weight_index,
-                                  (hipStream_t)stream);
-}
-
-// ---- gradient accumulation: a later micro-batch of a window, added into the flat buffer (the siblings' checks) ---------
-extern "C" int msgat_gather_accumulate(const float* const* chunk_src, const int64_t* chunk_off, const int32_t* chunk_len,
-                                       int32_t n_chunks, float scale, float* flat, int64_t weight_index, void* stream) {
-  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
-  if (!chunk_src || !chunk_off || !chunk_len || !flat) return MSGAT_ERR_NULL;
-  return launch_gather_accumulate(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat, weight_index,
-                                  (hipStream_t)stream);
-}
-
-extern "C" int msgat_gather_accumulate_dev(const float* const* chunk_src, const int64_t* chunk_off,
-                                           const int32_t* chunk_len, int32_t n_chunks, const float* scale, float* flat,
-                                           int64_t weight_index, void* stream) {
-  if (n_chunks <= 0) return MSGAT_ERR_SHAPE;
-  if (!chunk_src || !chunk_off || !chunk_len || !scale || !flat) return MSGAT_ERR_NULL;
-  return launch_gather_accumulate_dev(chunk_src, (const long long*)chunk_off, chunk_len, n_chunks, scale, flat,
-                                      weight_index, (hipStream_t)stream);
-}
-
 // ---- quantile forecasts in the step tail: pinball loss, point metrics, coverage / width / crossing sums ----------------
+// the limits of the kernels: 1 to 8 levels, Q * T_out <= 64 outputs per node, every count exact in the fp32 `valid`
+static int check_quantile_dims(int64_t rows, int32_t T_out, int32_t Q) {
+  return Q < 1 || Q > 8 || T_out < 1 || Q * (int64_t)T_out > 64 || rows > kMaskedMaxEntries / T_out ? MSGAT_ERR_UNSUPPORTED
+                                                                                                     : MSGAT_OK;
+}
+
 // limits first (they bound the loop over `levels`), then the levels themselves; nothing is launched on a refusal
 static int check_quantile(int64_t rows, int32_t T_out, int32_t Q, const float* levels) {
   if (rows < 0) return MSGAT_ERR_SHAPE;
-  if (Q < 1 || Q > 8 || T_out < 1 || Q * (int64_t)T_out > 64 || rows > kMaskedMaxEntries / T_out) return MSGAT_ERR_UNSUPPORTED;
+  if (int st = check_quantile_dims(rows, T_out, Q)) return st;
   for (int q = 0; q < Q; ++q) {   // strictly increasing inside (0, 1); a NaN fails its comparison
     if (!(levels[q] > (q == 0 ? 0.f : levels[q - 1]) && levels[q] < 1.f)) return MSGAT_ERR_SHAPE;
   }
@@ -1292,14 +1323,13 @@ static int check_quantile(int64_t rows, int32_t T_out, int32_t Q, const float* l
 }
 
 extern "C" size_t msgat_quantile_partial_doubles(int64_t rows, int32_t T_out, int32_t Q) {
-  if (rows <= 0 || Q < 1 || Q > 8 || T_out < 1 || Q * (int64_t)T_out > 64 || rows > kMaskedMaxEntries / T_out) return 0;
-  return quantile_partial_doubles(rows, T_out, Q);
+  return rows > 0 && check_quantile_dims(rows, T_out, Q) == MSGAT_OK ? quantile_partial_doubles(rows, T_out, Q) : 0;
 }
 
 extern "C" int msgat_quantile_metrics(const float* pred, const float* truth, int64_t rows, int32_t T_out, int32_t Q,
                                       const float* levels, int32_t point, float null_value, float mask_value,
                                       double* partials, float* loss, float* valid, double* sums, void* stream) {
-  if (!pred || !truth || !levels || !partials || !loss || !valid) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, levels, partials, loss, valid)) return st;
   if (int st = check_quantile(rows, T_out, Q, levels)) return st;
   if (point < 0 || point >= Q) return MSGAT_ERR_SHAPE;
   return launch_quantile_metrics(pred, truth, rows, T_out, Q, levels, point, null_value, mask_value, partials, loss, valid,
@@ -1309,7 +1339,7 @@ extern "C" int msgat_quantile_metrics(const float* pred, const float* truth, int
 extern "C" int msgat_quantile_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
                                    int64_t rows, int32_t T_out, int32_t Q, const float* levels, float null_value,
                                    float* dpred, void* stream) {
-  if (!pred || !truth || !dloss || !valid || !levels || !dpred) return MSGAT_ERR_NULL;
+  if (int st = check_loss_io(pred, truth, dloss, valid, levels, dpred)) return st;
   if (int st = check_quantile(rows, T_out, Q, levels)) return st;
   return launch_quantile_grad(pred, truth, dloss, valid, rows, T_out, Q, levels, null_value, dpred, (hipStream_t)stream);
 }

@@ -516,27 +516,21 @@ int launch_gauss_metrics(const float* pred, const float* truth, long long n, dou
 int launch_gauss_grad(const float* pred, const float* truth, const float* dloss, long long n, double sigma, double delta,
                       float* dpred, hipStream_t s);
 int adam_chunk_elems();
-int launch_adam(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, const int* chunk_tensor,
-                int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
-                const float* lr, double beta1, double beta2, double eps, double weight_decay, const float* grad_divisor,
-                hipStream_t s);
 constexpr int kGuardFloats = 5;   // MSGAT_GUARD_FLOATS
 int launch_grad_guard(const long long* chunk_off, const int* chunk_len, int nchunks, const float* grad,
                       const float* grad_divisor, float max_norm, double* part, float* guard, hipStream_t s);
-int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                        const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
-                        float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
-                        double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s);
-// the update that also moves the flat shadow (the averaged weights); guard == nullptr: the unguarded update
-int launch_adam_averaged(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                         const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
-                         float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
-                         double weight_decay, const float* grad_divisor, const float* guard, float* shadow, double decay,
-                         hipStream_t s);
+// the fused update; guard != nullptr: the guarded form, shadow != nullptr: it also moves the flat shadow (the averaged
+// weights) with `decay`
+int launch_adam(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, const int* chunk_tensor,
+                int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
+                const float* lr, double beta1, double beta2, double eps, double weight_decay, const float* grad_divisor,
+                const float* guard, float* shadow, double decay, hipStream_t s);
 int launch_param_swap(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, int nchunks,
                       float* flat, hipStream_t s);
-int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                         float scale, float* flat, long long weight_index, hipStream_t s);
+// flat = scale * src over a chunk table, flat[weight_index] = scale; accumulate: += both (gradient accumulation).
+// scale_dev != nullptr: the scale is read from device memory instead of `scale`
+int launch_gather(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks, float scale,
+                  const float* scale_dev, bool accumulate, float* flat, long long weight_index, hipStream_t s);
 size_t masked_huber_partial_doubles(long long rows, int T);
 int launch_masked_huber_metrics(const float* pred, const float* truth, long long rows, int T, float delta,
                                 float null_value, float mask_value, double* part, float* loss, float* valid,
@@ -549,13 +543,6 @@ int launch_masked_gauss_metrics(const float* pred, const float* truth, long long
 int launch_masked_gauss_grad(const float* pred, const float* truth, const float* dloss, const float* valid,
                              long long rows, int T, double sigma, double delta, float null_value, float* dpred,
                              hipStream_t s);
-int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                             const float* scale, float* flat, long long weight_index, hipStream_t s);
-// gradient accumulation: flat += scale * src on the same chunk tables, flat[weight_index] += scale
-int launch_gather_accumulate(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                             float scale, float* flat, long long weight_index, hipStream_t s);
-int launch_gather_accumulate_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len,
-                                 int nchunks, const float* scale, float* flat, long long weight_index, hipStream_t s);
 // quantile forecasts: pred [rows, Q, T], truth [rows, T], levels [Q] on the host (checked by the caller)
 size_t quantile_partial_doubles(long long rows, int T, int Q);
 int launch_quantile_metrics(const float* pred, const float* truth, long long rows, int T, int Q, const float* levels,

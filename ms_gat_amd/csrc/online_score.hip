@@ -13,7 +13,7 @@
 //                        n (blocks of 64 nodes).  For k = 0 .. K-1, then h = 0 .. T_out-1: origin o = s + k - h is due at
 //                        horizon h; if its stamp matches and y = raw[k, 0, n] is valid (not NaN, != null_value when there
 //                        is one) the entry's terms are formed in fp32 from p = book[row(o), n, q T_out + h]
-//                        (tail.hip's k_quantile_metrics arithmetic) and widened to double:
+//                        (tail_terms.hpp: the functions k_quantile_metrics calls) and widened to double:
 //                          0 count 1, 1 |e|, 2 100 |e / y| if y > mask_value else 0, 3 e^2, 4 e        e = p_point - y
 //                          Q levels: 5 any p_q > p_{q+1}, 6 p_{Q-1} - p_0, 7 + q  y <= p_q, 7 + Q + q  rho_q
 //                        The lane adds them (a) into its three node totals {count, |e|, e} in registers, in this k-then-h
@@ -29,13 +29,13 @@
 // Rows come from a 64-bit floor-mod into [0, P) for ANY clock content (cold, negative, a wild word): no launch reads or
 // writes outside book and issued, and what does not carry the stamp settles nothing.
 #include "common.hpp"
+#include "tail_terms.hpp"
 
 namespace msgat {
 
 constexpr int kScoreBlock = 64;          // one wave: the first launch's block, and the unit the finish adds in lane order
 constexpr int kScoreFinishBlock = 1024;
 constexpr int kScoreMaxT = 64;
-constexpr int kScoreMaxQ = 8;
 constexpr int kScoreNodeCols = 3;
 
 __device__ __forceinline__ long long score_floor_mod(long long a, long long n) {   // n > 0
@@ -51,10 +51,6 @@ __device__ __forceinline__ long long score_wrap_add(long long a, long long b) {
 __device__ __forceinline__ long long score_wrap_sub(long long a, long long b) {
   return (long long)((unsigned long long)a - (unsigned long long)b);
 }
-
-struct ScoreLevels { float tau[kScoreMaxQ], tau_m1[kScoreMaxQ]; };
-
-__host__ __device__ constexpr int score_cols(int Q) { return Q == 0 ? 5 : 7 + 2 * Q; }
 
 __global__ __launch_bounds__(kScoreBlock) void k_forecast_store(const unsigned* __restrict__ pred,
                                                                 unsigned* __restrict__ book,
@@ -73,10 +69,10 @@ __global__ __launch_bounds__(kScoreBlock) void k_forecast_store(const unsigned* 
 template <int Q, bool kNull>
 __global__ __launch_bounds__(kScoreBlock) void k_forecast_score(
     const float* __restrict__ raw, const float* __restrict__ book, const long long* __restrict__ issued,
-    const long long* __restrict__ clock, int K, long long step_stride, int N, int T, long long P, ScoreLevels lv,
+    const long long* __restrict__ clock, int K, long long step_stride, int N, int T, long long P, QuantLevels lv,
     int point, float null_value, float mask_value, double* __restrict__ part, double* __restrict__ node_sums) {
 #pragma clang fp contract(off)
-  constexpr int kCols = score_cols(Q);
+  constexpr int kCols = Q == 0 ? kPointCols : quant_cols(Q);
   constexpr int kLevels = Q == 0 ? 1 : Q;
   constexpr int kChunk = kLevels == 1 ? 16 : kLevels <= 4 ? 8 : 4;    // horizons whose loads are in flight together
   const int n = (int)blockIdx.x * kScoreBlock + (int)threadIdx.x;
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(kScoreBlock) void k_forecast_score(
     }
     const unsigned long long due = __ballot(mine);
     const float y = owner ? raw[(long long)k * step_stride + n] : 0.f;   // channel 0 of step s + k
-    const bool valid = owner && y == y && (!kNull || y != null_value);
+    const bool valid = owner && entry_valid(y, kNull ? null_value : __builtin_nanf(""));   // no null value: NaN only
     for (int h0 = 0; h0 < T; h0 += kChunk) {
       float p[kChunk][kLevels];
       bool hit[kChunk];
@@ -122,31 +118,25 @@ __global__ __launch_bounds__(kScoreBlock) void k_forecast_score(
 #pragma unroll
         for (int c = 0; c < kCols; ++c) t[c] = 0.0;
         if (hit[u]) {
-          float pp = p[u][0];
-#pragma unroll
-          for (int q = 1; q < kLevels; ++q) pp = q == point ? p[u][q] : pp;
-          const float e = pp - y, a = fabsf(e);
-          t[0] = 1.0;
-          t[1] = (double)a;
-          if (y > mask_value) t[2] = 100.0 * (double)fabsf(e / y);
-          t[3] = (double)e * (double)e;
-          t[4] = (double)e;
+          const PointTerms pt = point_terms(point_forecast(p[u], point), y, mask_value);
+          t[kColCount] = 1.0;
+          t[kColAbs] = (double)pt.abs_err;
+          if (pt.ape_counts) t[kColApe] = pt.ape;
+          t[kColSq] = pt.sq_err;
+          t[kScoreBiasCol] = (double)pt.err;
           if constexpr (Q > 0) {
-            bool crossing = false;
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
-              const float v = y - p[u][q];
-              const float rho = fmaxf(lv.tau[q] * v, lv.tau_m1[q] * v);
-              t[7 + Q + q] = (double)rho;
-              if (y <= p[u][q]) t[7 + q] = 1.0;
-              if (q + 1 < Q) crossing = crossing || p[u][q] > p[u][q + 1];
+              const LevelTerm lt = level_term(p[u][q], y, lv.tau[q], lv.tau_m1[q]);
+              t[quant_rho_col(Q, q)] = (double)lt.rho;
+              if (lt.hit) t[quant_hit_col(q)] = 1.0;
             }
-            if (crossing) t[5] = 1.0;
-            t[6] = (double)(p[u][Q - 1] - p[u][0]);
+            if (levels_cross(p[u])) t[kQuantCrossCol] = 1.0;
+            t[kQuantWidthCol] = (double)levels_width(p[u]);
           }
-          node[0] += t[0];
-          node[1] += t[1];
-          node[2] += t[4];
+          node[0] += t[kColCount];
+          node[1] += t[kColAbs];
+          node[2] += t[kScoreBiasCol];
         }
         if (k == 0 || hit[u]) {
 #pragma unroll
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(kScoreFinishBlock) void k_forecast_score_finish(con
 template <int Q>
 static void launch_forecast_score_q(bool has_null, dim3 grid, hipStream_t s, const float* raw, const float* book,
                                     const long long* issued, const long long* clock, int K, long long step_stride, int N,
-                                    int T, long long P, const ScoreLevels& lv, int point, float null_value,
+                                    int T, long long P, const QuantLevels& lv, int point, float null_value,
                                     float mask_value, double* part, double* node_sums) {
   if (has_null)
     hipLaunchKernelGGL((k_forecast_score<Q, true>), grid, dim3(kScoreBlock), 0, s, raw, book, issued, clock, K,
@@ -218,7 +208,7 @@ static void launch_forecast_score_q(bool has_null, dim3 grid, hipStream_t s, con
 static int check_forecast_score(int32_t K, int32_t C, int32_t N, int32_t T_out, int32_t Q, const float* levels,
                                 int32_t point, int64_t P) {
   if (K <= 0 || C <= 0 || N <= 0 || T_out <= 0 || Q < 0 || P < (int64_t)T_out) return MSGAT_ERR_SHAPE;
-  if (Q > kScoreMaxQ || (int64_t)(Q > 0 ? Q : 1) * T_out > kScoreMaxT || (long long)N > 0x7fffff00LL)
+  if (Q > kQuantMaxQ || (int64_t)(Q > 0 ? Q : 1) * T_out > kScoreMaxT || (long long)N > 0x7fffff00LL)
     return MSGAT_ERR_UNSUPPORTED;                                         // N plus a tile is held in an int
   for (int q = 0; q < Q; ++q)   // strictly increasing inside (0, 1); a NaN fails its comparison
     if (!(levels[q] > (q == 0 ? 0.f : levels[q - 1]) && levels[q] < 1.f)) return MSGAT_ERR_SHAPE;
@@ -246,10 +236,10 @@ extern "C" int msgat_forecast_store(const float* pred, float* book, int64_t* iss
 
 extern "C" size_t msgat_forecast_score_partial_doubles(int32_t N, int32_t T_out, int32_t Q) {
   using namespace msgat;
-  if (N <= 0 || T_out <= 0 || Q < 0 || Q > kScoreMaxQ || (int64_t)(Q > 0 ? Q : 1) * T_out > kScoreMaxT ||
+  if (N <= 0 || T_out <= 0 || Q < 0 || Q > kQuantMaxQ || (int64_t)(Q > 0 ? Q : 1) * T_out > kScoreMaxT ||
       (long long)N > 0x7fffff00LL)
     return 0;
-  return (size_t)score_cols(Q) * (size_t)T_out * (size_t)N;
+  return (size_t)(Q == 0 ? kPointCols : quant_cols(Q)) * (size_t)T_out * (size_t)N;
 }
 
 extern "C" int msgat_forecast_score(const float* raw, const float* book, const int64_t* issued, const int64_t* clock,
@@ -259,11 +249,7 @@ extern "C" int msgat_forecast_score(const float* raw, const float* book, const i
   using namespace msgat;
   if (!raw || !book || !issued || !clock || !partials || !sums || !node_sums || (Q > 0 && !levels)) return MSGAT_ERR_NULL;
   if (int st = check_forecast_score(K, C, N, T_out, Q, levels, point, P)) return st;
-  ScoreLevels lv = {};
-  for (int q = 0; q < Q; ++q) {
-    lv.tau[q] = levels[q];
-    lv.tau_m1[q] = (float)((double)levels[q] - 1.0);
-  }
+  const QuantLevels lv = quant_levels(levels, Q);
   const dim3 grid((unsigned)((N + kScoreBlock - 1) / kScoreBlock));
   const long long step_stride = (long long)C * N;
   hipStream_t s = (hipStream_t)stream;
@@ -287,8 +273,8 @@ extern "C" int msgat_forecast_score(const float* raw, const float* book, const i
   }
 #undef MSGAT_SCORE_CASE
   MSGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_forecast_score_finish, dim3(score_cols(Q)), dim3(kScoreFinishBlock), 0, s, partials, N, T_out,
-                     score_cols(Q), sums);
+  const int cols = Q == 0 ? kPointCols : quant_cols(Q);
+  hipLaunchKernelGGL(k_forecast_score_finish, dim3(cols), dim3(kScoreFinishBlock), 0, s, partials, N, T_out, cols, sums);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }

@@ -21,17 +21,12 @@
 //                        exponential moving average, warmed up by the tensor's step count); k_param_swap exchanges
 //                        parameters and shadow in place, so validation reads the average at the addresses it holds.
 #include "common.hpp"
+#include "tail_terms.hpp"
 
 namespace msgat {
 
 constexpr int kTailBlock = 256;
 constexpr int kTailPerThread = 8;  // elements per lane per block trip
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---- the loss of the step tail: a policy of the metrics and gradient kernels, plain and masked -------------------------
 // value(a) is the loss of one entry at |e| = a, slope(e) its derivative at e; both are evaluated per entry in fp32 and the
@@ -130,17 +125,17 @@ __global__ __launch_bounds__(kTailBlock) void k_loss_grad(const float* __restric
   dpred[i] = g * (dloss[0] / (float)n);
 }
 
-static int huber_blocks(long long n) {
+static int loss_blocks(long long n) {
   const long long want = (n + (long long)kTailBlock * kTailPerThread - 1) / ((long long)kTailBlock * kTailPerThread);
   return (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
 }
 
-size_t huber_partial_doubles(long long n) { return (size_t)huber_blocks(n) * 4; }
+size_t huber_partial_doubles(long long n) { return (size_t)loss_blocks(n) * 4; }
 
 template <class Loss>
 static int launch_loss_metrics(const float* pred, const float* truth, long long n, Loss lf, float mask_value,
                                double* part, float* loss, double* sums, float loss_weight, hipStream_t s) {
-  const int nb = huber_blocks(n);
+  const int nb = loss_blocks(n);
   hipLaunchKernelGGL(k_loss_metrics<Loss>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, lf, mask_value, part);
   MSGAT_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(256), 0, s, part, nb, n, loss, sums, loss_weight);
@@ -446,74 +441,27 @@ __global__ __launch_bounds__(kTailBlock) void k_adam(float* const* __restrict__ 
   }
 }
 
-template <bool kGuard>
-static int launch_adam_form(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                            const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad,
-                            float* m, float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
-                            double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s) {
-  if (n_active > 0) {
-    hipLaunchKernelGGL(k_adam_advance<kGuard>, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active,
-                       n_active, guard);
-    MSGAT_CHECK_LAUNCH();
-  }
-  if (nchunks > 0) {
-    hipLaunchKernelGGL(k_adam<kGuard>, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len,
-                       chunk_tensor, grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor,
-                       guard);
-    MSGAT_CHECK_LAUNCH();
-  }
-  return MSGAT_OK;
-}
-
+// guard == nullptr: the unguarded update; shadow == nullptr: no averaged weights (decay is not read)
 int launch_adam(float* const* chunk_param, const long long* chunk_off, const int* chunk_len, const int* chunk_tensor,
                 int nchunks, const int* active, int n_active, const float* grad, float* m, float* v, float* steps,
                 const float* lr, double beta1, double beta2, double eps, double weight_decay, const float* grad_divisor,
-                hipStream_t s) {
-  return launch_adam_form<false>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad, m, v,
-                                 steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, nullptr, s);
-}
-
-int launch_adam_guarded(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                        const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
-                        float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
-                        double weight_decay, const float* grad_divisor, const float* guard, hipStream_t s) {
-  return launch_adam_form<true>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad, m, v,
-                                steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard, s);
-}
-
-template <bool kGuard>
-static int launch_adam_averaged_form(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                                     const int* chunk_tensor, int nchunks, const int* active, int n_active,
-                                     const float* grad, float* m, float* v, float* steps, const float* lr, double beta1,
-                                     double beta2, double eps, double weight_decay, const float* grad_divisor,
-                                     const float* guard, float* shadow, double decay, hipStream_t s) {
+                const float* guard, float* shadow, double decay, hipStream_t s) {
   if (n_active > 0) {
-    hipLaunchKernelGGL(k_adam_advance<kGuard>, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active,
-                       n_active, guard);
+    const auto advance = guard ? k_adam_advance<true> : k_adam_advance<false>;
+    hipLaunchKernelGGL(advance, dim3(cdiv(n_active, kTailBlock)), dim3(kTailBlock), 0, s, steps, active, n_active, guard);
     MSGAT_CHECK_LAUNCH();
   }
   if (nchunks > 0) {
-    hipLaunchKernelGGL((k_adam<kGuard, Shadow>), dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len,
-                       chunk_tensor, grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor,
-                       guard, Shadow{shadow, (float)decay});
+    auto launch = [&](auto kernel, auto... average) {
+      hipLaunchKernelGGL(kernel, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_param, chunk_off, chunk_len, chunk_tensor,
+                         grad, m, v, steps, lr, beta1, beta2, (float)eps, (float)weight_decay, grad_divisor, guard,
+                         average...);
+    };
+    if (shadow) launch(guard ? k_adam<true, Shadow> : k_adam<false, Shadow>, Shadow{shadow, (float)decay});
+    else launch(guard ? k_adam<true> : k_adam<false>);
     MSGAT_CHECK_LAUNCH();
   }
   return MSGAT_OK;
-}
-
-// guard == nullptr: the unguarded update
-int launch_adam_averaged(float* const* chunk_param, const long long* chunk_off, const int* chunk_len,
-                         const int* chunk_tensor, int nchunks, const int* active, int n_active, const float* grad, float* m,
-                         float* v, float* steps, const float* lr, double beta1, double beta2, double eps,
-                         double weight_decay, const float* grad_divisor, const float* guard, float* shadow, double decay,
-                         hipStream_t s) {
-  if (guard)
-    return launch_adam_averaged_form<true>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active,
-                                           grad, m, v, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, guard,
-                                           shadow, decay, s);
-  return launch_adam_averaged_form<false>(chunk_param, chunk_off, chunk_len, chunk_tensor, nchunks, active, n_active, grad,
-                                          m, v, steps, lr, beta1, beta2, eps, weight_decay, grad_divisor, nullptr, shadow,
-                                          decay, s);
 }
 
 // ---- parameters <-> a flat buffer, exchanged in place --------------------------------------------------------------
@@ -546,48 +494,94 @@ int launch_param_swap(float* const* chunk_param, const long long* chunk_off, con
 int adam_chunk_elems() { return kAdamChunk; }
 
 // ---- gather of the gradients into the flat buffer a data-parallel step all-reduces -----------------------------------
-// flat[chunk_off[c] + i] = scale * chunk_src[c][i]; block 0 also writes flat[weight_index] = scale: the rank's weight
-// (its sample count) rides in the buffer's last element, so sum(w g) and sum(w) come out of ONE collective.  Replaces
-// a multi-tensor copy + mul_ + fill_ over the 7.8 MB buffer by one pass.
-__global__ __launch_bounds__(kTailBlock) void k_gather_scaled(const float* const* __restrict__ chunk_src,
-                                                              const long long* __restrict__ chunk_off,
-                                                              const int* __restrict__ chunk_len, float scale,
-                                                              float* __restrict__ flat, long long weight_index) {
+// Overwriting form: flat[chunk_off[c] + i] = scale * chunk_src[c][i]; block 0 also writes flat[weight_index] = scale: the
+// rank's weight (its sample count) rides in the buffer's last element, so sum(w g) and sum(w) come out of ONE collective.
+// Replaces a multi-tensor copy + mul_ + fill_ over the 7.8 MB buffer by one pass.
+// Accumulating form (gradient accumulation: a later micro-batch of a window): flat[chunk_off[c] + i] += scale *
+// chunk_src[c][i], and block 0 does flat[weight_index] += scale.  The first micro-batch of a window overwrites (no zeroing
+// pass), every later one accumulates, so after k micro-batches the buffer holds sum(w g) and sum(w) in call order -- what
+// the all-reduce of k ranks would have summed.  The product and the sum are rounded one after the other in fp32
+// (contraction off, as in average_move: an fma would round once), which is what makes two accumulated micro-batches
+// bit-equal to the two-rank all-reduce sum of the same two gradients, and a numpy float32 restatement bit-equal to both.
+// The scale travels by value (a sample count) or is read from device memory once per block (the valid count of a masked
+// batch, which only the device knows and which is never read back).
+// Every element is read and written by one lane of one block, block 0's lane 0 alone touches the weight: no atomics, one
+// fixed order.  Parameter views and flat offsets are 4-byte aligned only: scalar accesses, as in k_adam.
+__device__ __forceinline__ float scale_of(float scale) { return scale; }
+__device__ __forceinline__ float scale_of(const float* scale) { return scale[0]; }
+
+__device__ __forceinline__ void accumulate_chunk(const float* __restrict__ src, float* __restrict__ dst, int len,
+                                                 float scale) {
+#pragma clang fp contract(off)
+  for (int i = threadIdx.x; i < len; i += kTailBlock) {
+    const float term = scale * src[i];
+    dst[i] = dst[i] + term;
+  }
+}
+
+template <bool kAccumulate, class Scale>   // Scale: float or const float*
+__global__ __launch_bounds__(kTailBlock) void k_gather(const float* const* __restrict__ chunk_src,
+                                                       const long long* __restrict__ chunk_off,
+                                                       const int* __restrict__ chunk_len, Scale scale,
+                                                       float* __restrict__ flat, long long weight_index) {
   const int c = blockIdx.x;
+  const float sc = scale_of(scale);
   const float* __restrict__ src = chunk_src[c];
   float* __restrict__ dst = flat + chunk_off[c];
   const int len = chunk_len[c];
-  for (int i = threadIdx.x; i < len; i += kTailBlock) dst[i] = scale * src[i];
-  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] = scale;
+  if (kAccumulate) {
+    accumulate_chunk(src, dst, len, sc);
+  } else {
+    for (int i = threadIdx.x; i < len; i += kTailBlock) dst[i] = sc * src[i];   // no sum to fuse
+  }
+  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] = kAccumulate ? flat[weight_index] + sc : sc;
 }
 
-int launch_gather_scaled(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                         float scale, float* flat, long long weight_index, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather_scaled, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale, flat,
-                     weight_index);
+// scale_dev != nullptr: the scale is scale_dev[0], read by the kernel; otherwise `scale`
+int launch_gather(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks, float scale,
+                  const float* scale_dev, bool accumulate, float* flat, long long weight_index, hipStream_t s) {
+  auto launch = [&](auto kernel, auto sc) {
+    hipLaunchKernelGGL(kernel, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, sc, flat,
+                       weight_index);
+  };
+  if (scale_dev) launch(accumulate ? k_gather<true, const float*> : k_gather<false, const float*>, scale_dev);
+  else launch(accumulate ? k_gather<true, float> : k_gather<false, float>, scale);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
 
 // ---- masked loss (Huber or Gauss: the policies above) + per-horizon metric sums ---------------------------------------------------------------------
-// An entry of the truth counts when it is a measurement: not NaN and not the null value (a PEMS reading of 0 = sensor
-// down).  With null_value = NaN only the NaN entries drop out (y != NaN holds for every y).
+// An entry of the truth counts when it is a measurement (entry_valid, tail_terms.hpp).
 //   k_masked_loss_metrics    the first (256 / T) * T lanes of a block walk the elements with a stride that is a multiple
 //                            of T, so a lane keeps ONE horizon (element i has horizon i mod T) and its five sums
 //                            {valid count, |e|, 100 |e / y| (y > mask), e^2, loss} stay in registers, while a block
-//                            trip still reads consecutive addresses.  The lanes of a horizon hand their sums over
-//                            through LDS once per block and are added in lane order: one record [5][T] per block,
-//                            stored column-major over the blocks (part[(c T + h) nblocks + b]).
-//   k_masked_loss_finish     block c adds column c: a wave per horizon, lane l takes blocks l, l + 64, ... in order, then
+//                            trip still reads consecutive addresses.
+//   horizon_handover         the lanes of a horizon hand their sums over through LDS once per block and are added in
+//                            lane order: one record [cols][T] per block, stored column-major over the blocks
+//                            (part[(c T + h) nblocks + b]).
+//   k_horizon_finish         block c adds column c: a wave per horizon, lane l takes blocks l, l + 64, ... in order, then
 //                            the butterfly of wave_sum; the all-horizon row is the sum of the horizon rows in horizon
 //                            order.  The block of the loss column adds the count column too and writes loss and valid.
+//                            It only adds partials: the column count and the loss column are arguments.
 // Every sum has one fixed order: bitwise reproducible.  No floating-point atomics.
-constexpr int kMaskCols = 5;
+constexpr int kMaskCols = kPointCols;
 constexpr int kMaskMaxT = 64;
 constexpr int kMaskMaxBlocks = 512;
 constexpr int kMaskFinishBlock = 1024;
 
-__device__ __forceinline__ bool entry_valid(float y, float null_value) { return y == y && y != null_value; }
+template <int kCols>
+__device__ __forceinline__ void horizon_handover(const double (&s)[kCols], double (&red)[kCols][kTailBlock], int T,
+                                                 int lanes, double* __restrict__ part) {
+#pragma unroll
+  for (int c = 0; c < kCols; ++c) red[c][threadIdx.x] = s[c];
+  __syncthreads();
+  for (int o = threadIdx.x; o < kCols * T; o += kTailBlock) {
+    const int c = o / T, h = o - c * T;
+    double t = 0.0;
+    for (int j = h; j < lanes; j += T) t += red[c][j];
+    part[(size_t)o * gridDim.x + blockIdx.x] = t;
+  }
+}
 
 template <class Loss>
 __global__ __launch_bounds__(kTailBlock) void k_masked_loss_metrics(const float* __restrict__ pred,
@@ -601,34 +595,26 @@ __global__ __launch_bounds__(kTailBlock) void k_masked_loss_metrics(const float*
     for (long long i = (long long)blockIdx.x * lanes + threadIdx.x; i < n; i += stride) {
       const float p = pred[i], y = truth[i];
       if (!entry_valid(y, null_value)) continue;
-      const float e = p - y, a = fabsf(e);
-      s[0] += 1.0;
-      s[1] += a;
-      if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
-      s[3] += (double)e * (double)e;
-      s[4] += loss.value(a);
+      const PointTerms t = point_terms(p, y, mask_value);
+      s[kColCount] += 1.0;
+      s[kColAbs] += t.abs_err;
+      if (t.ape_counts) s[kColApe] += t.ape;
+      s[kColSq] += t.sq_err;
+      s[kMaskLossCol] += loss.value(t.abs_err);
     }
   }
-#pragma unroll
-  for (int c = 0; c < kMaskCols; ++c) red[c][threadIdx.x] = s[c];
-  __syncthreads();
-  for (int o = threadIdx.x; o < kMaskCols * T; o += kTailBlock) {
-    const int c = o / T, h = o - c * T;
-    double t = 0.0;
-    for (int j = h; j < lanes; j += T) t += red[c][j];
-    part[(size_t)o * gridDim.x + blockIdx.x] = t;
-  }
+  horizon_handover(s, red, T, lanes, part);
 }
 
-__global__ __launch_bounds__(kMaskFinishBlock) void k_masked_loss_finish(const double* __restrict__ part, int nblocks,
-                                                                         int T, float* __restrict__ loss,
-                                                                         float* __restrict__ valid,
-                                                                         double* __restrict__ sums) {
+__global__ __launch_bounds__(kMaskFinishBlock) void k_horizon_finish(const double* __restrict__ part, int nblocks, int T,
+                                                                     int cols, int loss_col, float* __restrict__ loss,
+                                                                     float* __restrict__ valid,
+                                                                     double* __restrict__ sums) {
   __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (loss block)
   const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool is_loss = c == kMaskCols - 1;
+  const bool is_loss = c == loss_col;
   for (int q = 0; q < (is_loss ? 2 : 1); ++q) {
-    const int col = q == 0 ? c : 0;
+    const int col = q == 0 ? c : kColCount;
     for (int h = wave; h < T; h += kMaskFinishBlock / 64) {
       const double* __restrict__ p = part + (size_t)(col * T + h) * nblocks;
       double t = 0.0;
@@ -638,11 +624,11 @@ __global__ __launch_bounds__(kMaskFinishBlock) void k_masked_loss_finish(const d
     }
   }
   __syncthreads();
-  if ((int)threadIdx.x < T && sums != nullptr) sums[(size_t)threadIdx.x * kMaskCols + c] += rows[0][threadIdx.x];
+  if ((int)threadIdx.x < T && sums != nullptr) sums[(size_t)threadIdx.x * cols + c] += rows[0][threadIdx.x];
   if (threadIdx.x != 0) return;
   double total = 0.0, count = 0.0;
   for (int h = 0; h < T; ++h) total += rows[0][h];
-  if (sums != nullptr) sums[(size_t)T * kMaskCols + c] += total;
+  if (sums != nullptr) sums[(size_t)T * cols + c] += total;
   if (!is_loss) return;
   for (int h = 0; h < T; ++h) count += rows[1][h];
   valid[0] = (float)count;
@@ -666,16 +652,16 @@ __global__ __launch_bounds__(kTailBlock) void k_masked_loss_grad(const float* __
   dpred[i] = entry_valid(y, null_value) ? g * (dloss[0] / fmaxf(valid[0], 1.f)) : 0.f;
 }
 
-static int masked_huber_lanes(int T) { return (kTailBlock / T) * T; }
+static int horizon_lanes(int T) { return (kTailBlock / T) * T; }
 
-static int masked_huber_blocks(long long n, int T) {
-  const long long per_block = (long long)masked_huber_lanes(T) * kTailPerThread;
+static int horizon_blocks(long long n, int T) {
+  const long long per_block = (long long)horizon_lanes(T) * kTailPerThread;
   const long long want = (n + per_block - 1) / per_block;
   return (int)(want < 1 ? 1 : (want > kMaskMaxBlocks ? kMaskMaxBlocks : want));
 }
 
 size_t masked_huber_partial_doubles(long long rows, int T) {
-  return (size_t)masked_huber_blocks(rows * T, T) * kMaskCols * T;
+  return (size_t)horizon_blocks(rows * T, T) * kMaskCols * T;
 }
 
 template <class Loss>
@@ -683,11 +669,12 @@ static int launch_masked_loss_metrics(const float* pred, const float* truth, lon
                                       float null_value, float mask_value, double* part, float* loss, float* valid,
                                       double* sums, hipStream_t s) {
   const long long n = rows * T;
-  const int nb = masked_huber_blocks(n, T);
+  const int nb = horizon_blocks(n, T);
   hipLaunchKernelGGL(k_masked_loss_metrics<Loss>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T,
-                     masked_huber_lanes(T), lf, null_value, mask_value, part);
+                     horizon_lanes(T), lf, null_value, mask_value, part);
   MSGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_masked_loss_finish, dim3(kMaskCols), dim3(kMaskFinishBlock), 0, s, part, nb, T, loss, valid, sums);
+  hipLaunchKernelGGL(k_horizon_finish, dim3(kMaskCols), dim3(kMaskFinishBlock), 0, s, part, nb, T, kMaskCols, kMaskLossCol,
+                     loss, valid, sums);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
@@ -732,22 +719,15 @@ int launch_masked_gauss_grad(const float* pred, const float* truth, const float*
 //   rho_q = max(tau_q u, (tau_q - 1) u);  d rho_q / d p_q = -tau_q (y > p_q), 1 - tau_q (y < p_q), 1/2 - tau_q at a tie
 //   (autograd's rule for torch.maximum).  tau_q - 1 and the three slopes over Q are formed in double on the host and
 //   rounded to fp32 once; they travel by value (QuantLevels / QuantSlopes), like the policies above.
-// Columns of a record and of sums [T + 1, 7 + 2Q]:
+// Columns of a record and of sums [T + 1, 7 + 2Q] (tail_terms.hpp, where an entry's terms are formed):
 //   0-3 the masked tail's {count, |e|, 100 |e / y| (y > mask), e^2} with e = p_point - y;  4 sum of (1/Q) sum_q rho_q;
 //   5 entries with any p_q > p_{q+1};  6 sum of p_{Q-1} - p_0;  7 + q entries with y <= p_q;  7 + Q + q sum of rho_q.
 //   k_quantile_metrics<Q>    k_masked_loss_metrics' walk (a lane keeps ONE horizon, its 7 + 2Q sums stay in registers in
-//                            double -- Q is a template parameter so that they ARE registers) and its hand-over: one
+//                            double -- Q is a template parameter so that they ARE registers) and horizon_handover: one
 //                            [7 + 2Q][256] LDS image (26 KB at Q = 3, 46 KB at Q = 8: under the 64 KB static limit, and
-//                            with at most 512 blocks of this launch on 256 CUs no limit on residency), ONE barrier, the
-//                            lanes of a horizon added in lane order, part[(c T + h) nblocks + b].
-//   k_quantile_finish        k_masked_loss_finish with the column count as an argument: block c adds column c, the block of
-//                            column 4 adds the count column too and writes loss and valid.
+//                            with at most 512 blocks of this launch on 256 CUs no limit on residency), ONE barrier.
+//                            k_horizon_finish then adds 7 + 2Q columns, loss column 4.
 // One fixed order for every sum, no floating-point atomics: bitwise reproducible.
-constexpr int kQuantMaxQ = 8;
-constexpr int kQuantBase = 7;   // the columns in front of the per-level ones
-constexpr int kQuantLossCol = 4;
-
-struct QuantLevels { float tau[kQuantMaxQ], tau_m1[kQuantMaxQ]; };
 struct QuantSlopes { float above[kQuantMaxQ], below[kQuantMaxQ], tie[kQuantMaxQ]; };   // y > p_q, y < p_q, y == p_q
 
 template <int Q>
@@ -755,7 +735,7 @@ __global__ __launch_bounds__(kTailBlock) void k_quantile_metrics(const float* __
                                                                  const float* __restrict__ truth, int n, int T, int lanes,
                                                                  QuantLevels lv, int point, float null_value,
                                                                  float mask_value, double* __restrict__ part) {
-  constexpr int kCols = kQuantBase + 2 * Q;
+  constexpr int kCols = quant_cols(Q);
   __shared__ double red[kCols][kTailBlock];
   double s[kCols];
 #pragma unroll
@@ -770,68 +750,25 @@ __global__ __launch_bounds__(kTailBlock) void k_quantile_metrics(const float* __
 #pragma unroll
       for (int q = 0; q < Q; ++q) p[q] = pr[q * T];
       if (!entry_valid(y, null_value)) continue;
-      float pp = p[0];
-#pragma unroll
-      for (int q = 1; q < Q; ++q) pp = q == point ? p[q] : pp;   // a select per level: p[] stays in registers
-      const float e = pp - y, a = fabsf(e);
-      s[0] += 1.0;
-      s[1] += a;
-      if (y > mask_value) s[2] += 100.0 * (double)fabsf(e / y);
-      s[3] += (double)e * (double)e;
+      const PointTerms pt = point_terms(point_forecast(p, point), y, mask_value);
+      s[kColCount] += 1.0;
+      s[kColAbs] += pt.abs_err;
+      if (pt.ape_counts) s[kColApe] += pt.ape;
+      s[kColSq] += pt.sq_err;
       double total = 0.0;
-      bool crossing = false;
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
-        const float u = y - p[q];
-        const float rho = fmaxf(lv.tau[q] * u, lv.tau_m1[q] * u);
-        total += (double)rho;
-        s[kQuantBase + Q + q] += (double)rho;
-        if (y <= p[q]) s[kQuantBase + q] += 1.0;
-        if (q + 1 < Q) crossing = crossing || p[q] > p[q + 1];
+        const LevelTerm lt = level_term(p[q], y, lv.tau[q], lv.tau_m1[q]);
+        total += (double)lt.rho;
+        s[quant_rho_col(Q, q)] += (double)lt.rho;
+        if (lt.hit) s[quant_hit_col(q)] += 1.0;
       }
       s[kQuantLossCol] += total * (1.0 / Q);
-      if (crossing) s[5] += 1.0;
-      s[6] += (double)(p[Q - 1] - p[0]);
+      if (levels_cross(p)) s[kQuantCrossCol] += 1.0;
+      s[kQuantWidthCol] += (double)levels_width(p);
     }
   }
-#pragma unroll
-  for (int c = 0; c < kCols; ++c) red[c][threadIdx.x] = s[c];
-  __syncthreads();
-  for (int o = threadIdx.x; o < kCols * T; o += kTailBlock) {
-    const int c = o / T, h = o - c * T;
-    double t = 0.0;
-    for (int j = h; j < lanes; j += T) t += red[c][j];
-    part[(size_t)o * gridDim.x + blockIdx.x] = t;
-  }
-}
-
-__global__ __launch_bounds__(kMaskFinishBlock) void k_quantile_finish(const double* __restrict__ part, int nblocks, int T,
-                                                                      int cols, float* __restrict__ loss,
-                                                                      float* __restrict__ valid,
-                                                                      double* __restrict__ sums) {
-  __shared__ double rows[2][kMaskMaxT];   // [0]: this block's column per horizon, [1]: the count column (loss block)
-  const int c = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool is_loss = c == kQuantLossCol;
-  for (int q = 0; q < (is_loss ? 2 : 1); ++q) {
-    const int col = q == 0 ? c : 0;
-    for (int h = wave; h < T; h += kMaskFinishBlock / 64) {
-      const double* __restrict__ p = part + (size_t)(col * T + h) * nblocks;
-      double t = 0.0;
-      for (int b = lane; b < nblocks; b += 64) t += p[b];
-      t = wave_sum(t);
-      if (lane == 0) rows[q][h] = t;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < T && sums != nullptr) sums[(size_t)threadIdx.x * cols + c] += rows[0][threadIdx.x];
-  if (threadIdx.x != 0) return;
-  double total = 0.0, count = 0.0;
-  for (int h = 0; h < T; ++h) total += rows[0][h];
-  if (sums != nullptr) sums[(size_t)T * cols + c] += total;
-  if (!is_loss) return;
-  for (int h = 0; h < T; ++h) count += rows[1][h];
-  valid[0] = (float)count;
-  loss[0] = (float)(total / fmax(count, 1.0));
+  horizon_handover(s, red, T, lanes, part);
 }
 
 // dpred[r,q,t] = c_q (dloss[0] / max(valid[0], 1)) at the valid entries, c_q the slope of its sign case over Q; +0
@@ -859,13 +796,13 @@ __global__ __launch_bounds__(kTailBlock) void k_quantile_grad(const float* __res
 }
 
 size_t quantile_partial_doubles(long long rows, int T, int Q) {
-  return (size_t)masked_huber_blocks(rows * T, T) * (size_t)(kQuantBase + 2 * Q) * T;
+  return (size_t)horizon_blocks(rows * T, T) * (size_t)quant_cols(Q) * T;
 }
 
 template <int Q>
 static void launch_quantile_metrics_q(const float* pred, const float* truth, int n, int T, const QuantLevels& lv, int point,
                                       float null_value, float mask_value, double* part, int nb, hipStream_t s) {
-  hipLaunchKernelGGL(k_quantile_metrics<Q>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T, masked_huber_lanes(T), lv,
+  hipLaunchKernelGGL(k_quantile_metrics<Q>, dim3(nb), dim3(kTailBlock), 0, s, pred, truth, n, T, horizon_lanes(T), lv,
                      point, null_value, mask_value, part);
 }
 
@@ -877,12 +814,8 @@ int launch_quantile_metrics(const float* pred, const float* truth, long long row
     if (e == hipSuccess) e = hipMemsetAsync(valid, 0, sizeof(float), s);
     return e == hipSuccess ? MSGAT_OK : MSGAT_ERR_HIP_BASE - (int)e;
   }
-  QuantLevels lv = {};
-  for (int q = 0; q < Q; ++q) {
-    lv.tau[q] = levels[q];
-    lv.tau_m1[q] = (float)((double)levels[q] - 1.0);
-  }
-  const int n = (int)(rows * T), nb = masked_huber_blocks(n, T);
+  const QuantLevels lv = quant_levels(levels, Q);
+  const int n = (int)(rows * T), nb = horizon_blocks(n, T);
   switch (Q) {
     case 1: launch_quantile_metrics_q<1>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
     case 2: launch_quantile_metrics_q<2>(pred, truth, n, T, lv, point, null_value, mask_value, part, nb, s); break;
@@ -895,8 +828,8 @@ int launch_quantile_metrics(const float* pred, const float* truth, long long row
     default: return MSGAT_ERR_UNSUPPORTED;
   }
   MSGAT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_quantile_finish, dim3(kQuantBase + 2 * Q), dim3(kMaskFinishBlock), 0, s, part, nb, T,
-                     kQuantBase + 2 * Q, loss, valid, sums);
+  hipLaunchKernelGGL(k_horizon_finish, dim3(quant_cols(Q)), dim3(kMaskFinishBlock), 0, s, part, nb, T, quant_cols(Q),
+                     kQuantLossCol, loss, valid, sums);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
@@ -914,85 +847,6 @@ int launch_quantile_grad(const float* pred, const float* truth, const float* dlo
   const int n = (int)(rows * T);
   hipLaunchKernelGGL(k_quantile_grad, dim3((unsigned)((n + kTailBlock - 1) / kTailBlock)), dim3(kTailBlock), 0, s, pred,
                      truth, dloss, valid, n, T, Q, sl, null_value, dpred);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
-}
-
-// k_gather_scaled with the scale read from device memory: the rank's weight of a masked step is its batch's valid
-// count, which only the device knows
-__global__ __launch_bounds__(kTailBlock) void k_gather_scaled_dev(const float* const* __restrict__ chunk_src,
-                                                                  const long long* __restrict__ chunk_off,
-                                                                  const int* __restrict__ chunk_len,
-                                                                  const float* __restrict__ scale,
-                                                                  float* __restrict__ flat, long long weight_index) {
-  const int c = blockIdx.x;
-  const float sc = scale[0];
-  const float* __restrict__ src = chunk_src[c];
-  float* __restrict__ dst = flat + chunk_off[c];
-  const int len = chunk_len[c];
-  for (int i = threadIdx.x; i < len; i += kTailBlock) dst[i] = sc * src[i];
-  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] = sc;
-}
-
-int launch_gather_scaled_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                             const float* scale, float* flat, long long weight_index, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather_scaled_dev, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
-                     flat, weight_index);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
-}
-
-// ---- gradient accumulation: a later micro-batch of a window is added into the flat buffer ----------------------------
-// flat[chunk_off[c] + i] = flat[chunk_off[c] + i] + scale * chunk_src[c][i]; block 0 also does flat[weight_index] +=
-// scale.  The first micro-batch of a window is k_gather_scaled (it overwrites: no zeroing pass), every later one comes
-// through here, so after k micro-batches the buffer holds sum(w g) and sum(w) in call order -- what the all-reduce of
-// k ranks would have summed.  The product and the sum are rounded one after the other in fp32 (contraction off, as in
-// average_move: an fma would round once), which is what makes two accumulated micro-batches bit-equal to the two-rank
-// all-reduce sum of the same two gradients, and a numpy float32 restatement bit-equal to both.  Every element is read
-// and written by one lane of one block, block 0's lane 0 alone touches the weight: no atomics, one fixed order.
-// Parameter views and flat offsets are 4-byte aligned only: scalar accesses, as in k_gather_scaled.
-__device__ __forceinline__ void accumulate_chunk(const float* __restrict__ src, float* __restrict__ dst, int len,
-                                                 float scale) {
-#pragma clang fp contract(off)
-  for (int i = threadIdx.x; i < len; i += kTailBlock) {
-    const float term = scale * src[i];
-    dst[i] = dst[i] + term;
-  }
-}
-
-__global__ __launch_bounds__(kTailBlock) void k_gather_accumulate(const float* const* __restrict__ chunk_src,
-                                                                  const long long* __restrict__ chunk_off,
-                                                                  const int* __restrict__ chunk_len, float scale,
-                                                                  float* __restrict__ flat, long long weight_index) {
-  const int c = blockIdx.x;
-  accumulate_chunk(chunk_src[c], flat + chunk_off[c], chunk_len[c], scale);
-  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] += scale;
-}
-
-// the scale read from device memory: the valid count of a masked micro-batch is never read back
-__global__ __launch_bounds__(kTailBlock) void k_gather_accumulate_dev(const float* const* __restrict__ chunk_src,
-                                                                      const long long* __restrict__ chunk_off,
-                                                                      const int* __restrict__ chunk_len,
-                                                                      const float* __restrict__ scale,
-                                                                      float* __restrict__ flat, long long weight_index) {
-  const int c = blockIdx.x;
-  const float sc = scale[0];
-  accumulate_chunk(chunk_src[c], flat + chunk_off[c], chunk_len[c], sc);
-  if (c == 0 && threadIdx.x == 0 && weight_index >= 0) flat[weight_index] += sc;
-}
-
-int launch_gather_accumulate(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len, int nchunks,
-                             float scale, float* flat, long long weight_index, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather_accumulate, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
-                     flat, weight_index);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
-}
-
-int launch_gather_accumulate_dev(const float* const* chunk_src, const long long* chunk_off, const int* chunk_len,
-                                 int nchunks, const float* scale, float* flat, long long weight_index, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather_accumulate_dev, dim3(nchunks), dim3(kTailBlock), 0, s, chunk_src, chunk_off, chunk_len, scale,
-                     flat, weight_index);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }

@@ -769,15 +769,16 @@ class FlatAdam(optim.Optimizer):
         if not self._params or self.flat_grad is None or self._params[0].device != self.flat_grad.device:
             self._build()
         active = tuple(p.grad is not None for p in self._params)
-        grads = [p.grad for p in self._params if p.grad is not None]
         divisor = 0
         several_ranks = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if rank_weight is not None and (self._pending or several_ranks):
+            # the current gradients are the last micro-batch of the open window, or -- a data-parallel step -- a window of
+            # their own: one launch before the collective (the gather, scaled by the weight, which also rides in the
+            # buffer's last element).  Without a weight an open window closes as it stands (the shorter last one of an epoch)
+            self._add_micro_batch(rank_weight, several_ranks)
         if self._pending:
-            # an accumulation window is open: the current gradients are its last micro-batch (rank_weight None: nothing
-            # is added, the window closes as it stands -- the shorter last window of an epoch).  Then the collective,
-            # the clamp and the divisor exactly as the data-parallel step below has them: flat = sum(w g), last = sum(w)
-            if rank_weight is not None:
-                self._add_micro_batch(rank_weight, several_ranks)
+            # the window closes: flat = sum(w g), last = sum(w) over its micro-batches and, after the collective, over the
+            # ranks; the update divides by the summed weight on the way in (device counts: clamped to at least 1)
             active = self._window_active
             if several_ranks:
                 parallel.all_reduce_flat(self.flat_grad)
@@ -785,24 +786,9 @@ class FlatAdam(optim.Optimizer):
                 self.flat_grad[self.numel:].clamp_(min=1.0)
             divisor = self.flat_grad.data_ptr() + 4 * self.numel
             self._pending, self._window_active = 0, None
-        elif rank_weight is not None and several_ranks:
-            # one launch before the collective (gather, scaled by the rank's weight, which also rides in the last
-            # element) and one after it (the update divides by the summed weight on the way in)
-            if active != self._last_active:
-                self.flat_grad.zero_()           # parameters without a gradient contribute zeros on every rank
-            on_device = torch.is_tensor(rank_weight)
-            if grads:
-                self._gather(grads, active, rank_weight if on_device else float(rank_weight))
-            elif on_device:
-                self.flat_grad[self.numel:].copy_(rank_weight.reshape(1))
-            else:
-                self.flat_grad[self.numel:].fill_(float(rank_weight))
-            parallel.all_reduce_flat(self.flat_grad)
-            if on_device:
-                self.flat_grad[self.numel:].clamp_(min=1.0)
-            divisor = self.flat_grad.data_ptr() + 4 * self.numel
-        elif grads:
-            torch._foreach_copy_([v for v, on in zip(self._grad_views, active) if on], grads)
+        elif any(active):
+            torch._foreach_copy_([v for v, on in zip(self._grad_views, active) if on],
+                                 [p.grad for p in self._params if p.grad is not None])
         self._last_active = active
         self.sync_lr()
         ptrs, offs, lens, tens, act, n, n_act = self._table(active)

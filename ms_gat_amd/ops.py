@@ -9,6 +9,7 @@ arithmetic step runs in libmsgat_hip.so through the C ABI of include/msgat_hip.h
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import threading
 from typing import Optional
@@ -2108,45 +2109,95 @@ def gauss_params(sigma, delta) -> tuple:
     return sigma, delta
 
 
-class _LossMetricsFunction(torch.autograd.Function):
-    """pred, truth (same shape) -> mean loss (0-dim); adds |e|, 100|e/y| (y > mask) and e^2 sums plus the loss
-    itself to the running fp64 totals `sums` [4] on the device (engine.py:56,66-70; loss.py:51-52 or :94-95;
-    metrics.py:20-35)."""
+@dataclasses.dataclass(frozen=True)
+class _TailCall:
+    """One call of the step tail, as its entry points take it: `msgat_<stem>_metrics(pred, truth, *dims, *params, *null,
+    mask_value, partials, loss, [valid,] sums, *weight, stream)`, sized by `<partials>(*dims)`, and the backward
+    `msgat_<stem>_grad(pred, truth, dloss, [valid,] *dims, *grad_params, *null, dpred, stream)`."""
+    stem: str              # "huber", "masked_gauss", "quantile", ...
+    partials: str          # the entry that sizes the partials
+    dims: tuple            # the leading dimension arguments: (n,), (rows, T_out) or (rows, T_out, Q)
+    params: tuple          # the loss parameters of the forward ...
+    grad_params: tuple     # ... and of the backward
+    null: tuple = ()       # (null_value,) of a masked tail
+    weight: tuple = ()     # (loss_weight,) of the plain tail
+
+
+class _TailMetricsFunction(torch.autograd.Function):
+    """pred, truth -> the mean loss (0-dim) of the tail `call` describes; adds the batch's sums to the running fp64 totals
+    `sums` on the device (engine.py:56,66-70; loss.py:51-52 or :94-95; metrics.py:20-35).  With a `valid` slot [1] the
+    mean is over the VALID entries of truth (not NaN, != null_value) and the slot receives their count."""
 
     @staticmethod
-    def forward(ctx, pred, truth, kind: str, params: tuple, mask_value: float, sums, loss_weight: float = 1.0):
+    def forward(ctx, pred, truth, call: _TailCall, mask_value: float, sums, valid):
         L = _lib.lib()
         pred_c, truth_c = pred.contiguous(), truth.contiguous()
-        n = pred_c.numel()
-        part = torch.empty(max(int(L.msgat_huber_partial_doubles(n)), 1), device=pred.device, dtype=torch.float64)
+        n_part = int(getattr(L, call.partials)(*call.dims))
+        part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        name = f"msgat_{kind}_metrics"
-        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), n, *params, float(mask_value), _ptr(part), _ptr(loss),
-                              _ptr(sums), float(loss_weight), _stream_handle(pred.device))
+        slot = () if valid is None else (_ptr(valid),)
+        name = f"msgat_{call.stem}_metrics"
+        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), *call.dims, *call.params, *call.null, float(mask_value),
+                              _ptr(part), _ptr(loss), *slot, _ptr(sums), *call.weight, _stream_handle(pred.device))
         _lib.check(st, name)
-        ctx.kind, ctx.params = kind, params
-        ctx.save_for_backward(pred_c, truth_c)
+        ctx.call = call
+        ctx.save_for_backward(pred_c, truth_c, *(() if valid is None else (valid,)))
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        pred, truth = ctx.saved_tensors
+        pred, truth, *valid = ctx.saved_tensors
+        call = ctx.call
         dpred = torch.empty_like(pred)
-        name = f"msgat_{ctx.kind}_grad"
-        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), pred.numel(), *ctx.params,
-                                       _ptr(dpred), _stream_handle(pred.device))
+        name = f"msgat_{call.stem}_grad"
+        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), *(_ptr(v) for v in valid),
+                                       *call.dims, *call.grad_params, *call.null, _ptr(dpred), _stream_handle(pred.device))
         _lib.check(st, name)
-        return dpred, None, None, None, None, None, None
+        return dpred, None, None, None, None, None
+
+
+def _check_tail_operands(pred, truth, per_horizon: bool) -> None:
+    """Prediction and target on one device, of one non-empty shape (`per_horizon`: whose last dimension is T_out)."""
+    _require_device_tensor("prediction", pred)
+    _require_device_tensor("target", truth, pred.device)
+    if pred.shape != truth.shape or pred.numel() == 0 or (per_horizon and pred.dim() == 0):
+        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(truth.shape)} must match and be non-empty")
+
+
+def _check_totals(sums, shape: tuple, device) -> None:
+    """`sums` is None or the running float64 totals of `shape` on `device`: contiguous and of exactly that shape, except
+    the plain tail's flat [4], of which only the element count is asked."""
+    flat = len(shape) == 1
+    if sums is not None and (sums.dtype != torch.float64 or sums.device != device or (
+            sums.numel() != shape[0] if flat else tuple(sums.shape) != shape or not sums.is_contiguous())):
+        raise ValueError(f"sums must be a {'' if flat else 'contiguous '}float64 {list(shape)} tensor on the prediction's device")
+
+
+def _valid_slot(valid, device) -> torch.Tensor:
+    """The float32 [1] device tensor that receives a batch's valid count: the caller's, checked, or a fresh one."""
+    if valid is None:
+        return torch.empty(1, device=device, dtype=torch.float32)
+    if valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != device:
+        raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
+    return valid
 
 
 def _loss_metrics(kind: str, params: tuple, pred, truth, mask_value, sums, loss_weight) -> torch.Tensor:
-    _require_device_tensor("prediction", pred)
-    _require_device_tensor("target", truth, pred.device)
-    if pred.shape != truth.shape or pred.numel() == 0:
-        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(truth.shape)} must match and be non-empty")
-    if sums is not None and (sums.dtype != torch.float64 or sums.numel() != 4 or sums.device != pred.device):
-        raise ValueError("sums must be a float64 [4] tensor on the prediction's device")
-    return _LossMetricsFunction.apply(pred, truth, kind, params, mask_value, sums, float(loss_weight))
+    _check_tail_operands(pred, truth, per_horizon=False)
+    _check_totals(sums, (4,), pred.device)
+    call = _TailCall(kind, "msgat_huber_partial_doubles", (pred.numel(),), params, params, weight=(float(loss_weight),))
+    return _TailMetricsFunction.apply(pred, truth, call, mask_value, sums, None)
+
+
+def _masked_loss_metrics(kind: str, params: tuple, pred, truth, null_value, mask_value, sums, valid) -> torch.Tensor:
+    _check_tail_operands(pred, truth, per_horizon=True)
+    t_out = pred.shape[-1]
+    if t_out > 64:
+        raise ValueError(f"T_out = {t_out}: the masked step tail supports forecast horizons up to 64 steps")
+    _check_totals(sums, (t_out + 1, 5), pred.device)
+    call = _TailCall(f"masked_{kind}", "msgat_masked_huber_partial_doubles", (pred.numel() // t_out, t_out), params, params,
+                     null=(float(null_value),))
+    return _TailMetricsFunction.apply(pred, truth, call, mask_value, sums, _valid_slot(valid, pred.device))
 
 
 def huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, mask_value: float = 0.0,
@@ -2161,60 +2212,6 @@ def gauss_metrics(pred: torch.Tensor, truth: torch.Tensor, sigma: float, delta: 
     """`huber_metrics` with the Gauss loss (loss.py:94-95): the mean of sigma^2 (1 - exp(-e^2 / 2 sigma^2)) + delta |e|.
     `sigma` finite and > 0, `delta` finite and >= 0 (ValueError otherwise)."""
     return _loss_metrics("gauss", gauss_params(sigma, delta), pred, truth, mask_value, sums, loss_weight)
-
-
-class _MaskedLossMetricsFunction(torch.autograd.Function):
-    """pred, truth [..., T_out] -> the loss averaged over the VALID entries of truth (not NaN, != null_value); adds
-    the per-horizon and all-horizon {count, |e|, 100|e/y| (y > mask), e^2, loss} sums to the running fp64 totals
-    `sums` [T_out + 1, 5] and leaves the batch's valid count in `valid` [1], both on the device."""
-
-    @staticmethod
-    def forward(ctx, pred, truth, kind: str, params: tuple, null_value: float, mask_value: float, sums, valid):
-        L = _lib.lib()
-        pred_c, truth_c = pred.contiguous(), truth.contiguous()
-        t_out = pred_c.shape[-1]
-        rows = pred_c.numel() // t_out
-        n_part = int(L.msgat_masked_huber_partial_doubles(rows, t_out))
-        part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
-        loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        name = f"msgat_masked_{kind}_metrics"
-        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), rows, t_out, *params, float(null_value),
-                              float(mask_value), _ptr(part), _ptr(loss), _ptr(valid), _ptr(sums),
-                              _stream_handle(pred.device))
-        _lib.check(st, name)
-        ctx.kind, ctx.params, ctx.null_value = kind, params, float(null_value)
-        ctx.save_for_backward(pred_c, truth_c, valid)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        pred, truth, valid = ctx.saved_tensors
-        dpred = torch.empty_like(pred)
-        t_out = pred.shape[-1]
-        name = f"msgat_masked_{ctx.kind}_grad"
-        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid),
-                                       pred.numel() // t_out, t_out, *ctx.params, ctx.null_value, _ptr(dpred),
-                                       _stream_handle(pred.device))
-        _lib.check(st, name)
-        return dpred, None, None, None, None, None, None, None
-
-
-def _masked_loss_metrics(kind: str, params: tuple, pred, truth, null_value, mask_value, sums, valid) -> torch.Tensor:
-    _require_device_tensor("prediction", pred)
-    _require_device_tensor("target", truth, pred.device)
-    if pred.shape != truth.shape or pred.numel() == 0 or pred.dim() == 0:
-        raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(truth.shape)} must match and be non-empty")
-    t_out = pred.shape[-1]
-    if t_out > 64:
-        raise ValueError(f"T_out = {t_out}: the masked step tail supports forecast horizons up to 64 steps")
-    if sums is not None and (sums.dtype != torch.float64 or tuple(sums.shape) != (t_out + 1, 5) or sums.device != pred.device
-                             or not sums.is_contiguous()):
-        raise ValueError(f"sums must be a contiguous float64 [{t_out + 1}, 5] tensor on the prediction's device")
-    if valid is None:
-        valid = torch.empty(1, device=pred.device, dtype=torch.float32)
-    elif valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != pred.device:
-        raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
-    return _MaskedLossMetricsFunction.apply(pred, truth, kind, params, null_value, mask_value, sums, valid)
 
 
 def masked_huber_metrics(pred: torch.Tensor, truth: torch.Tensor, delta: float, null_value: float,
@@ -2271,41 +2268,6 @@ def quantile_slopes(levels, dtype=torch.float32) -> torch.Tensor:
     return torch.stack([-tau / n, (1.0 - tau) / n, (0.5 - tau) / n]).to(dtype)
 
 
-class _QuantileMetricsFunction(torch.autograd.Function):
-    """pred [..., Q * T_out] (level-major: [..., Q, T_out]), truth [..., T_out] -> the pinball loss averaged over the levels
-    and the VALID entries of truth; adds the totals of `quantile_metrics` to `sums` and leaves the batch's valid count in
-    `valid` [1], both on the device."""
-
-    @staticmethod
-    def forward(ctx, pred, truth, levels: tuple, point: int, null_value: float, mask_value: float, sums, valid):
-        L = _lib.lib()
-        pred_c, truth_c = pred.contiguous(), truth.contiguous()
-        t_out, n_levels = truth_c.shape[-1], len(levels)
-        rows = truth_c.numel() // t_out
-        n_part = int(L.msgat_quantile_partial_doubles(rows, t_out, n_levels))
-        part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
-        loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        host_levels = (C.c_float * n_levels)(*levels)
-        st = L.msgat_quantile_metrics(_ptr(pred_c), _ptr(truth_c), rows, t_out, n_levels, host_levels, int(point),
-                                      float(null_value), float(mask_value), _ptr(part), _ptr(loss), _ptr(valid),
-                                      _ptr(sums), _stream_handle(pred.device))
-        _lib.check(st, "msgat_quantile_metrics")
-        ctx.host_levels, ctx.null_value, ctx.dims = host_levels, float(null_value), (rows, t_out, n_levels)
-        ctx.save_for_backward(pred_c, truth_c, valid)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        pred, truth, valid = ctx.saved_tensors
-        dpred = torch.empty_like(pred)
-        rows, t_out, n_levels = ctx.dims
-        st = _lib.lib().msgat_quantile_grad(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), _ptr(valid), rows, t_out,
-                                            n_levels, ctx.host_levels, ctx.null_value, _ptr(dpred),
-                                            _stream_handle(pred.device))
-        _lib.check(st, "msgat_quantile_grad")
-        return dpred, None, None, None, None, None, None, None
-
-
 def quantile_widths(pred: torch.Tensor, truth: torch.Tensor, n_levels: int) -> int:
     """T_out of a quantile batch, or ValueError: pred [..., Q * T_out] (or [..., Q, T_out]) against truth [..., T_out]."""
     t_out = truth.shape[-1] if truth.dim() else 0
@@ -2345,16 +2307,11 @@ def quantile_metrics(pred: torch.Tensor, truth: torch.Tensor, levels, null_value
     point = quantile_point(levels) if point is None else int(point)
     if not 0 <= point < n_levels:
         raise ValueError(f"point = {point} outside the {n_levels} levels")
-    cols = QUANTILE_BASE_COLUMNS + 2 * n_levels
-    if sums is not None and (sums.dtype != torch.float64 or tuple(sums.shape) != (t_out + 1, cols) or sums.device != pred.device
-                             or not sums.is_contiguous()):
-        raise ValueError(f"sums must be a contiguous float64 [{t_out + 1}, {cols}] tensor on the prediction's device")
-    if valid is None:
-        valid = torch.empty(1, device=pred.device, dtype=torch.float32)
-    elif valid.dtype != torch.float32 or valid.numel() != 1 or valid.device != pred.device:
-        raise ValueError("valid must be a float32 [1] tensor on the prediction's device")
-    null_value = float("nan") if null_value is None else float(null_value)
-    return _QuantileMetricsFunction.apply(pred, truth, levels, point, null_value, mask_value, sums, valid)
+    _check_totals(sums, (t_out + 1, QUANTILE_BASE_COLUMNS + 2 * n_levels), pred.device)
+    host_levels = (C.c_float * n_levels)(*levels)
+    call = _TailCall("quantile", "msgat_quantile_partial_doubles", (truth.numel() // t_out, t_out, n_levels),
+                     (host_levels, point), (host_levels,), null=(float("nan") if null_value is None else float(null_value),))
+    return _TailMetricsFunction.apply(pred, truth, call, mask_value, sums, _valid_slot(valid, pred.device))
 
 
 # ---- input windows of a batch from a series resident in device memory ---------------------------------------------
