@@ -46,6 +46,13 @@ __device__ __forceinline__ float f4dot(const float4& a, const float4& b, float a
   acc = fmaf(a.w, b.w, acc);
   return acc;
 }
+// the table row an index tensor selects for sample b, clamped into the table's `rows` (torch's gather traps on the device);
+// idx == nullptr: row 0.  The gated sum (tail.hip) and the time-dependent edge weights (edge_time.hip) share it.
+__device__ __forceinline__ int gate_row(const long long* idx, int b, int rows) {
+  if (idx == nullptr) return 0;
+  const long long v = idx[b];
+  return (int)(v < 0 ? 0 : (v >= rows ? rows - 1 : v));
+}
 // v_exp_f32: 2^x, 1 ulp, no denormal results (flushes to 0 below 2^-126) -- what the
 // softmax needs; exp2f() from the device library adds range scaling we do not want.
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }

@@ -12,20 +12,16 @@
 //                        forwards followed by their two backwards each see their own masks.
 //     k_edge_dropout_advance   one thread: state.step += 1.  It follows the forward in stream order, so every block of the
 //                        forward has read the step before it moves; no ticket, no counter to reset, nothing read back.
-//     k_edge_dropout_bwd_sum   w [nnz] shared by the samples: dw[e] = sum_v dout[v,e] * m[v,e].  A block owns 64 edges.  Its
-//                        256 lanes first form the rounded products of a tile of samples in parallel -- a lane per (quad,
-//                        sample), one Philox call and four loads each -- into an LDS tile prod[sample][edge]; then a lane
-//                        per edge adds its column from +0 in ascending sample order (the idiom of k_edge_time_bwd).  The
-//                        generator's ~80 integer operations per call are spread over the block that way, not chained 4 V deep
-//                        in front of one lane's sum.  Every entry is written, nothing is atomic.
-#include "common.hpp"
+//     k_edge_dropout_bwd_sum   w [nnz] shared by the samples: dw[e] = sum_v dout[v,e] * m[v,e] under the
+//                        ascending-sample-order contract, as edge_batch_sum (edge_batch.hpp) with a unit of one
+//                        quad: a lane per (quad, sample) forms four rounded products from one Philox call and four loads.
+//                        The generator's ~80 integer operations per call are spread over the block that way, not chained
+//                        4 V deep in front of one lane's sum.
+#include "edge_batch.hpp"
 
 namespace msgat {
 
 constexpr int kEdBlock = 256;       // quads per block of the elementwise kernel: 1024 edges
-constexpr int kEdSumEdges = 64;     // edges per block of the summing backward: one wave adds them
-constexpr int kEdSumQuads = kEdSumEdges / 4;
-constexpr int kEdSumSamples = 64;   // samples per LDS tile of products (16 KiB)
 
 struct Philox4 {
   uint32_t w[4];
@@ -92,41 +88,26 @@ __global__ __launch_bounds__(kEdBlock) void k_edge_dropout(const float* __restri
 
 __global__ void k_edge_dropout_advance(long long* __restrict__ state) { state[1] = state[1] + 1; }
 
-__global__ __launch_bounds__(kEdBlock) void k_edge_dropout_bwd_sum(const float* __restrict__ dout,
-                                                                   const unsigned char* __restrict__ exempt,
-                                                                   const long long* __restrict__ state,
-                                                                   const long long* __restrict__ used, float* __restrict__ dw,
-                                                                   int V, long long nnz, uint32_t sample_offset, uint32_t thr,
-                                                                   float scale) {
-  __shared__ float prod[kEdSumSamples][kEdSumEdges];
+__global__ __launch_bounds__(kEbSumBlock) void k_edge_dropout_bwd_sum(const float* __restrict__ dout,
+                                                                      const unsigned char* __restrict__ exempt,
+                                                                      const long long* __restrict__ state,
+                                                                      const long long* __restrict__ used,
+                                                                      float* __restrict__ dw, int V, long long nnz,
+                                                                      uint32_t sample_offset, uint32_t thr, float scale) {
   const unsigned long long seed = (unsigned long long)state[0], step = (unsigned long long)used[0];
-  const int tid = threadIdx.x;
-  const long long eb = (long long)blockIdx.x * kEdSumEdges;      // the block's first edge: a multiple of 4
-  const int ql = tid & (kEdSumQuads - 1);                        // this lane's quad inside the block
-  const long long e0 = eb + 4 * ql;
-  const int n = e0 >= nnz ? 0 : (nnz - e0 < 4 ? (int)(nnz - e0) : 4);
+  // this lane's quad, as edge_batch_sum<4> assigns it: its four flags are read once
+  const long long q0 = (long long)blockIdx.x * kEbSumEdges + 4 * (threadIdx.x & (kEbSumEdges / 4 - 1));
   bool ex[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) ex[k] = exempt != nullptr && k < n && exempt[e0 + k] != 0;
-  float acc = 0.f;
-  for (int v0 = 0; v0 < V; v0 += kEdSumSamples) {
-    const int nv = V - v0 < kEdSumSamples ? V - v0 : kEdSumSamples;
-    __syncthreads();                                             // the previous tile's products have been added
-    for (int i = tid >> 4; i < nv; i += kEdBlock / kEdSumQuads) {
-      if (n > 0) {
-        float m[4];
-        edge_dropout_quad((uint32_t)(e0 >> 2), sample_offset + (uint32_t)(v0 + i), seed, step, thr, scale, ex, m);
-        const long long row = (long long)(v0 + i) * nnz + e0;
+  for (int k = 0; k < 4; ++k) ex[k] = exempt != nullptr && q0 + k < nnz && exempt[q0 + k] != 0;
+  edge_batch_sum<4>(dw, V, nnz, [&](long long e0, int n, int v, float* dst) {
+    float m[4];
+    edge_dropout_quad((uint32_t)(e0 >> 2), sample_offset + (uint32_t)v, seed, step, thr, scale, ex, m);
+    const long long row = (long long)v * nnz + e0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (k < n) prod[i][4 * ql + k] = dout[row + k] * m[k];
-      }
-    }
-    __syncthreads();
-    if (tid < kEdSumEdges && eb + tid < nnz)
-      for (int i = 0; i < nv; ++i) acc += prod[i][tid];          // rounded products, added from +0 in sample order
-  }
-  if (tid < kEdSumEdges && eb + tid < nnz) dw[eb + tid] = acc;
+    for (int k = 0; k < 4; ++k)
+      if (k < n) dst[k] = dout[row + k] * m[k];
+  });
 }
 
 }  // namespace msgat
@@ -145,11 +126,9 @@ extern "C" int msgat_edge_dropout(const float* w, const uint8_t* exempt, int64_t
   if (int st = check_edge_dropout(V, nnz, sample_offset)) return st;
   if (V == 0 || nnz == 0) return MSGAT_OK;              // nothing is drawn: `used` is not written and the step stays
   if (!w || !state || !used || !out) return MSGAT_ERR_NULL;
-  const long long quads = (nnz + 3) / 4;
-  const dim3 grid((unsigned)((quads + kEdBlock - 1) / kEdBlock), (unsigned)(V < 65535 ? V : 65535));
-  hipLaunchKernelGGL(k_edge_dropout<false>, grid, dim3(kEdBlock), 0, (hipStream_t)stream, w, w_sets ? 1 : 0, exempt,
-                     (const long long*)state, (const long long*)state + 1, (long long*)used, out, V, (long long)nnz,
-                     (uint32_t)sample_offset, thr, scale);
+  hipLaunchKernelGGL(k_edge_dropout<false>, edge_sample_grid((nnz + 3) / 4, kEdBlock, V), dim3(kEdBlock), 0,
+                     (hipStream_t)stream, w, w_sets ? 1 : 0, exempt, (const long long*)state, (const long long*)state + 1,
+                     (long long*)used, out, V, (long long)nnz, (uint32_t)sample_offset, thr, scale);
   MSGAT_CHECK_LAUNCH();
   if (advance) {
     hipLaunchKernelGGL(k_edge_dropout_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)state);
@@ -166,14 +145,12 @@ extern "C" int msgat_edge_dropout_backward(const float* dout, const uint8_t* exe
   if (V == 0 || nnz == 0 || !dw) return MSGAT_OK;
   if (!dout || !state || !used) return MSGAT_ERR_NULL;
   if (w_sets) {
-    const long long quads = (nnz + 3) / 4;
-    const dim3 grid((unsigned)((quads + kEdBlock - 1) / kEdBlock), (unsigned)(V < 65535 ? V : 65535));
-    hipLaunchKernelGGL(k_edge_dropout<true>, grid, dim3(kEdBlock), 0, (hipStream_t)stream, dout, 1, exempt,
-                       (const long long*)state, (const long long*)used, (long long*)nullptr, dw, V, (long long)nnz,
-                       (uint32_t)sample_offset, thr, scale);
+    hipLaunchKernelGGL(k_edge_dropout<true>, edge_sample_grid((nnz + 3) / 4, kEdBlock, V), dim3(kEdBlock), 0,
+                       (hipStream_t)stream, dout, 1, exempt, (const long long*)state, (const long long*)used,
+                       (long long*)nullptr, dw, V, (long long)nnz, (uint32_t)sample_offset, thr, scale);
   } else {
-    const dim3 grid((unsigned)((nnz + kEdSumEdges - 1) / kEdSumEdges));
-    hipLaunchKernelGGL(k_edge_dropout_bwd_sum, grid, dim3(kEdBlock), 0, (hipStream_t)stream, dout, exempt,
+    const dim3 grid((unsigned)((nnz + kEbSumEdges - 1) / kEbSumEdges));
+    hipLaunchKernelGGL(k_edge_dropout_bwd_sum, grid, dim3(kEbSumBlock), 0, (hipStream_t)stream, dout, exempt,
                        (const long long*)state, (const long long*)used, dw, V, (long long)nnz, (uint32_t)sample_offset, thr,
                        scale);
   }

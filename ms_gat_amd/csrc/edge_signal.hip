@@ -16,11 +16,11 @@
 //                          without edges stores +0.  A walk is serial in the node's degree: any degree is correct, a hub of
 //                          hundreds is one slow lane group (left out: splitting long lists).
 //                          The remaining block columns: a lane per edge, dbase[e] = +0 + dout[0,e] + dout[1,e] + ... in
-//                          ascending b, additions only.
+//                          ascending b, additions only (the ascending-sample-order contract).
 // At the road graph's size (N = 883, nnz ~ 2.6 K, B = 32, d = 8) ab is 1.8 MB and stays in L2; every list is a handful of
 // dependent 16-byte reads -- latency, not bandwidth -- so the blocks are single waves spread over as many compute units as
 // the shape gives.
-#include "common.hpp"
+#include "edge_batch.hpp"
 
 namespace msgat {
 
@@ -66,17 +66,8 @@ __global__ __launch_bounds__(kEsLanes) void k_edge_signal_bwd(const int* __restr
   if ((int)blockIdx.x >= node_blocks) {              // dbase: wave-uniform branch
     const int e = ((int)blockIdx.x - node_blocks) * kEsLanes + threadIdx.x;
     if (blockIdx.y != 0 || e >= nnz) return;
-    const float* src = dout + e;
     float sum = 0.f;
-    int b = 0;
-    for (; b + kEsAhead <= B; b += kEsAhead) {
-      float g[kEsAhead];
-#pragma unroll
-      for (int k = 0; k < kEsAhead; ++k) g[k] = src[(long long)(b + k) * nnz];
-#pragma unroll
-      for (int k = 0; k < kEsAhead; ++k) sum += g[k];
-    }
-    for (; b < B; ++b) sum += src[(long long)b * nnz];
+    for_samples_ahead<kEsAhead>(dout + e, nnz, B, [&](float g, int) { sum += g; });
     dbase[e] = sum;
     return;
   }

@@ -2,7 +2,7 @@
 //
 //   torch ops            forward two embedding gathers and two adds; backward a batch sum, and per table a zero fill and an
 //                        embedding scatter whose summation order torch does not promise.
-//   here                 one launch each way, the idiom of the gated sum (tail.hip, k_gate_sum / k_gate_sum_bwd).
+//   here                 one launch each way; the gradients keep the ascending-sample-order contract.
 //     k_edge_time_fwd    a lane per edge, a block row per sample: three coalesced reads, one coalesced store.  Plain fp32 adds
 //                        in the order above (nothing to contract), so the result has the bits of the torch expression.
 //     k_edge_time_bwd    a lane per edge, ONE pass over dout: the lane walks the samples in ascending order and adds
@@ -15,7 +15,7 @@
 //                        further block rows that each re-read dout.
 // A block of the backward is one wave: at the road graph's size (nnz ~ 2.6 K, B = 32) the launch is 41 waves of 32 dependent
 // LDS updates each -- latency, not bandwidth -- and a wider block would only leave fewer compute units busy.
-#include "common.hpp"
+#include "edge_batch.hpp"
 
 namespace msgat {
 
@@ -25,13 +25,6 @@ constexpr int kEtRows = 32;        // table rows whose sums a block of the backw
 constexpr int kEtSamples = 256;    // samples whose table rows are staged per tile
 constexpr int kEtAhead = 8;        // samples of dout a lane loads before it adds them
 
-// the table row of sample b, clamped into the table as gate_row (tail.hip) does; idx == nullptr: row 0
-__device__ __forceinline__ int edge_time_row(const long long* idx, int b, int rows) {
-  if (idx == nullptr) return 0;
-  const long long v = idx[b];
-  return (int)(v < 0 ? 0 : (v >= rows ? rows - 1 : v));
-}
-
 __global__ __launch_bounds__(kEtFwdBlock) void k_edge_time_fwd(const float* __restrict__ base, const float* __restrict__ h_w,
                                                                const float* __restrict__ d_w, const long long* __restrict__ H,
                                                                const long long* __restrict__ D, float* __restrict__ out, int B,
@@ -40,8 +33,8 @@ __global__ __launch_bounds__(kEtFwdBlock) void k_edge_time_fwd(const float* __re
   if (e >= nnz) return;
   const float bv = base[e];
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    float v = bv + h_w[(long long)edge_time_row(H, b, nh) * nnz + e];
-    if (d_w) v = v + d_w[(long long)edge_time_row(D, b, nd) * nnz + e];
+    float v = bv + h_w[(long long)gate_row(H, b, nh) * nnz + e];
+    if (d_w) v = v + d_w[(long long)gate_row(D, b, nd) * nnz + e];
     out[(long long)b * nnz + e] = v;
   }
 }
@@ -65,8 +58,8 @@ __global__ __launch_bounds__(kEtLanes) void k_edge_time_bwd(const float* __restr
     const int nb = B - b0 < kEtSamples ? B - b0 : kEtSamples;
     __syncthreads();                                 // the previous tile's rows have been consumed
     for (int i = lane; i < nb; i += kEtLanes) {      // a sample's row inside this block's chunk, or -1
-      const int rh = nh > 0 ? edge_time_row(H, b0 + i, nh) - r0 : -1;
-      const int rd = nd > 0 ? nh + edge_time_row(D, b0 + i, nd) - r0 : -1;
+      const int rh = nh > 0 ? gate_row(H, b0 + i, nh) - r0 : -1;
+      const int rd = nd > 0 ? nh + gate_row(D, b0 + i, nd) - r0 : -1;
       rows_h[i] = (unsigned)rh < (unsigned)kEtRows ? rh : -1;
       rows_d[i] = (unsigned)rd < (unsigned)kEtRows ? rd : -1;
     }
@@ -80,15 +73,7 @@ __global__ __launch_bounds__(kEtLanes) void k_edge_time_bwd(const float* __restr
         if (rh >= 0) acc[rh][lane] += g;
         if (rd >= 0) acc[rd][lane] += g;
       };
-      int i = 0;
-      for (; i + kEtAhead <= nb; i += kEtAhead) {   // kEtAhead loads in flight ahead of the dependent LDS updates
-        float g[kEtAhead];
-#pragma unroll
-        for (int k = 0; k < kEtAhead; ++k) g[k] = src[(long long)(i + k) * nnz];
-#pragma unroll
-        for (int k = 0; k < kEtAhead; ++k) add(g[k], i + k);
-      }
-      for (; i < nb; ++i) add(src[(long long)i * nnz], i);
+      for_samples_ahead<kEtAhead>(src, nnz, nb, add);   // kEtAhead loads in flight ahead of the dependent LDS updates
     }
   }
   if (!live) return;
@@ -119,9 +104,8 @@ extern "C" int msgat_edge_time_weights(const float* base, const float* h_w, cons
   if (nnz == 0 || B == 0) return MSGAT_OK;
   if (!base || !h_w || !H || !out) return MSGAT_ERR_NULL;
   if ((d_w != nullptr) != (D != nullptr) || nh <= 0 || (d_w && nd <= 0)) return MSGAT_ERR_SHAPE;
-  const dim3 grid((unsigned)((nnz + kEtFwdBlock - 1) / kEtFwdBlock), (unsigned)(B < 65535 ? B : 65535));
-  hipLaunchKernelGGL(k_edge_time_fwd, grid, dim3(kEtFwdBlock), 0, (hipStream_t)stream, base, h_w, d_w, (const long long*)H,
-                     (const long long*)D, out, B, (long long)nnz, nh, d_w ? nd : 0);
+  hipLaunchKernelGGL(k_edge_time_fwd, edge_sample_grid(nnz, kEtFwdBlock, B), dim3(kEtFwdBlock), 0, (hipStream_t)stream, base,
+                     h_w, d_w, (const long long*)H, (const long long*)D, out, B, (long long)nnz, nh, d_w ? nd : 0);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }

@@ -13,24 +13,20 @@
 //                        in scalar registers -- and dst = exempt ? src : (g == 0 ? +0 : src * g), one fp32 multiply.
 //                        src is w (forward; src_sets = 0: [nnz] shared by the samples) or dout (backward of w [V,nnz]): the
 //                        two are the same expression.
-//     k_edge_validity_bwd_sum   w [nnz] shared by the samples: dw[e] = sum_v of those rounded terms.  A block owns 64 edges.
-//                        Its 256 lanes first form the terms of a tile of samples in parallel -- a lane per (edge, sample),
-//                        loads of dout coalesced along e -- into an LDS tile term[sample][edge]; then a lane per edge adds
-//                        its column from +0 in ascending sample order (the idiom of k_edge_dropout_bwd_sum).  Every entry is
-//                        written, nothing is atomic.
+//     k_edge_validity_bwd_sum   w [nnz] shared by the samples: dw[e] = sum_v of those rounded terms under the
+//                        ascending-sample-order contract.  The skeleton and tile constants of edge_batch_sum
+//                        (edge_batch.hpp), a lane per (edge, sample), loads of dout coalesced along e -- written out: as
+//                        edge_batch_sum<1> the pair's cold replay was slower than the parent's spread (lab_variants.txt).
 // At the road graph's size (N = 883, nnz ~ 2.6 K, V = 32, T = 12) the validity windows are 1.4 MB and each node's row is read
 // by its few out-edges: latency, not bandwidth.
-#include "common.hpp"
+#include "edge_batch.hpp"
 
 namespace msgat {
 
-constexpr int kEvBlock = 256;       // edges per block of the elementwise kernel
-constexpr int kEvSumEdges = 64;     // edges per block of the summing backward: one wave adds them
-constexpr int kEvSumSamples = 64;   // samples per LDS tile of terms (16 KiB)
-constexpr int kEvMaxT = 16;
+constexpr int kGateBlock = 256;     // edges per block of the elementwise kernel
 
 struct EvTable {
-  float g[kEvMaxT + 1];
+  float g[kMaxT + 1];
 };
 
 // table[count of val[0..T) > 0.5f]: row points at the T validity floats of one node of one sample
@@ -63,11 +59,11 @@ __device__ __forceinline__ float edge_validity_term(float x, float g, bool exemp
 }
 
 template <int T, bool kVec>
-__global__ __launch_bounds__(kEvBlock) void k_edge_validity(const int* __restrict__ col, const float* __restrict__ src,
-                                                            int src_sets, const unsigned char* __restrict__ exempt,
-                                                            const float* __restrict__ val, long long val_stride, EvTable tb,
-                                                            float* __restrict__ dst, int V, int nnz) {
-  const int e = (int)blockIdx.x * kEvBlock + threadIdx.x;
+__global__ __launch_bounds__(kGateBlock) void k_edge_validity(const int* __restrict__ col, const float* __restrict__ src,
+                                                              int src_sets, const unsigned char* __restrict__ exempt,
+                                                              const float* __restrict__ val, long long val_stride,
+                                                              EvTable tb, float* __restrict__ dst, int V, int nnz) {
+  const int e = (int)blockIdx.x * kGateBlock + threadIdx.x;
   if (e >= nnz) return;
   const long long node = (long long)col[e] * T;
   const bool ex = exempt != nullptr && exempt[e] != 0;
@@ -81,69 +77,35 @@ __global__ __launch_bounds__(kEvBlock) void k_edge_validity(const int* __restric
 }
 
 template <int T, bool kVec>
-__global__ __launch_bounds__(kEvBlock) void k_edge_validity_bwd_sum(const int* __restrict__ col, const float* __restrict__ dout,
-                                                                    const unsigned char* __restrict__ exempt,
-                                                                    const float* __restrict__ val, long long val_stride,
-                                                                    EvTable tb, float* __restrict__ dw, int V, int nnz) {
-  __shared__ float term[kEvSumSamples][kEvSumEdges];
+__global__ __launch_bounds__(kEbSumBlock) void k_edge_validity_bwd_sum(const int* __restrict__ col,
+                                                                       const float* __restrict__ dout,
+                                                                       const unsigned char* __restrict__ exempt,
+                                                                       const float* __restrict__ val, long long val_stride,
+                                                                       EvTable tb, float* __restrict__ dw, int V, int nnz) {
+  __shared__ float term[kEbSumSamples][kEbSumEdges];
   const int tid = threadIdx.x;
-  const int el = tid & (kEvSumEdges - 1);                          // this lane's edge inside the block
-  const int sl = tid / kEvSumEdges;                                // and its first sample inside a tile
-  const long long e = (long long)blockIdx.x * kEvSumEdges + el;
+  const int el = tid & (kEbSumEdges - 1);                          // this lane's edge inside the block
+  const int sl = tid / kEbSumEdges;                                // and its first sample inside a tile
+  const long long e = (long long)blockIdx.x * kEbSumEdges + el;
   const bool live = e < nnz;
   const long long node = live ? (long long)col[e] * T : 0;
   const bool ex = live && exempt != nullptr && exempt[e] != 0;
   float acc = 0.f;
-  for (int v0 = 0; v0 < V; v0 += kEvSumSamples) {
-    const int nv = V - v0 < kEvSumSamples ? V - v0 : kEvSumSamples;
+  for (int v0 = 0; v0 < V; v0 += kEbSumSamples) {
+    const int nv = V - v0 < kEbSumSamples ? V - v0 : kEbSumSamples;
     __syncthreads();                                               // the previous tile's terms have been added
     if (live) {
-      for (int i = sl; i < nv; i += kEvBlock / kEvSumEdges) {
+      for (int i = sl; i < nv; i += kEbSumBlock / kEbSumEdges) {
         const long long v = v0 + i;
         const float g = edge_validity_gate<T, kVec>(val + v * val_stride + node, tb);
         term[i][el] = edge_validity_term(dout[v * nnz + e], g, ex);
       }
     }
     __syncthreads();
-    if (tid < kEvSumEdges && live)
+    if (tid < kEbSumEdges && live)
       for (int i = 0; i < nv; ++i) acc += term[i][tid];            // rounded terms, added from +0 in sample order
   }
-  if (tid < kEvSumEdges && live) dw[e] = acc;
-}
-
-template <int T, bool kVec>
-static void launch_edge_validity(const int* col, const float* src, int src_sets, const unsigned char* exempt, const float* val,
-                                 long long val_stride, const EvTable& tb, float* dst, int V, int nnz, hipStream_t s) {
-  const dim3 grid((unsigned)((nnz + kEvBlock - 1) / kEvBlock), (unsigned)(V < 65535 ? V : 65535));
-  hipLaunchKernelGGL((k_edge_validity<T, kVec>), grid, dim3(kEvBlock), 0, s, col, src, src_sets, exempt, val, val_stride, tb,
-                     dst, V, nnz);
-}
-
-template <int T, bool kVec>
-static void launch_edge_validity_bwd_sum(const int* col, const float* dout, const unsigned char* exempt, const float* val,
-                                         long long val_stride, const EvTable& tb, float* dw, int V, int nnz, hipStream_t s) {
-  const dim3 grid((unsigned)((nnz + kEvSumEdges - 1) / kEvSumEdges));
-  hipLaunchKernelGGL((k_edge_validity_bwd_sum<T, kVec>), grid, dim3(kEvBlock), 0, s, col, dout, exempt, val, val_stride, tb,
-                     dw, V, nnz);
-}
-
-// sum = true: the batch-summing backward; else the elementwise kernel (forward, and the backward of w [V,nnz])
-template <bool kVec>
-static void dispatch_edge_validity(bool sum, int T, const int* col, const float* src, int src_sets,
-                                   const unsigned char* exempt, const float* val, long long val_stride, const EvTable& tb,
-                                   float* dst, int V, int nnz, hipStream_t s) {
-#define MSGAT_EV_CASE(TT)                                                                                        \
-  case TT:                                                                                                       \
-    if (sum) launch_edge_validity_bwd_sum<TT, kVec>(col, src, exempt, val, val_stride, tb, dst, V, nnz, s);      \
-    else launch_edge_validity<TT, kVec>(col, src, src_sets, exempt, val, val_stride, tb, dst, V, nnz, s);        \
-    break;
-  switch (T) {
-    MSGAT_EV_CASE(4)
-    MSGAT_EV_CASE(8)
-    MSGAT_EV_CASE(12)
-    MSGAT_EV_CASE(16)
-  }
-#undef MSGAT_EV_CASE
+  if (tid < kEbSumEdges && live) dw[e] = acc;
 }
 
 }  // namespace msgat
@@ -151,29 +113,36 @@ static void dispatch_edge_validity(bool sum, int T, const int* col, const float*
 static int check_edge_validity(const msgat_graph_t* graph, int32_t V, int32_t T, int64_t val_stride) {
   if (!graph) return MSGAT_ERR_NULL;
   if (V < 0 || T < 0 || val_stride < 0 || graph->n_nodes < 0 || graph->nnz < 0) return MSGAT_ERR_SHAPE;
-  if (T != 4 && T != 8 && T != 12 && T != 16) return MSGAT_ERR_UNSUPPORTED;
+  if (!msgat::t_supported(T)) return MSGAT_ERR_UNSUPPORTED;
   return MSGAT_OK;
 }
 
-// 16-byte pieces need an aligned base and sample stride; a node's row is T floats, T a multiple of 4
-static bool edge_validity_aligned(const float* val, int64_t val_stride) {
-  return (reinterpret_cast<uintptr_t>(val) & 15) == 0 && (val_stride & 3) == 0;
-}
-
+// the elementwise kernel (forward, and the backward of w [V,nnz]) or, sum = true, the batch-summing backward; 16-byte
+// pieces need an aligned base and sample stride (a node's row is T floats, T a multiple of 4)
 static int run_edge_validity(bool sum, const msgat_graph_t* graph, const float* src, int src_sets, const uint8_t* exempt,
                              const float* val, int64_t val_stride, const float* table, float* dst, int32_t V, int32_t T,
                              void* stream) {
   using namespace msgat;
   EvTable tb = {};
   for (int c = 0; c <= T; ++c) tb.g[c] = table[c];
-  if (edge_validity_aligned(val, val_stride))
-    dispatch_edge_validity<true>(sum, T, graph->col, src, src_sets, exempt, val, (long long)val_stride, tb, dst, V, graph->nnz,
-                                 (hipStream_t)stream);
-  else
-    dispatch_edge_validity<false>(sum, T, graph->col, src, src_sets, exempt, val, (long long)val_stride, tb, dst, V,
-                                  graph->nnz, (hipStream_t)stream);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  const bool aligned = (reinterpret_cast<uintptr_t>(val) & 15) == 0 && (val_stride & 3) == 0;
+  const int nnz = graph->nnz;
+  const int* col = graph->col;
+  const long long stride = val_stride;
+  hipStream_t s = (hipStream_t)stream;
+  auto launch = [&](auto t, auto vec) -> int {
+    constexpr int kT = decltype(t)::value;
+    constexpr bool kVec = decltype(vec)::value;
+    if (sum)
+      hipLaunchKernelGGL((k_edge_validity_bwd_sum<kT, kVec>), dim3((unsigned)cdiv(nnz, kEbSumEdges)), dim3(kEbSumBlock), 0, s,
+                         col, src, exempt, val, stride, tb, dst, V, nnz);
+    else
+      hipLaunchKernelGGL((k_edge_validity<kT, kVec>), edge_sample_grid(nnz, kGateBlock, V), dim3(kGateBlock), 0, s, col, src,
+                         src_sets, exempt, val, stride, tb, dst, V, nnz);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  };
+  return dispatch_T(T, [&](auto t) { return aligned ? launch(t, std::true_type{}) : launch(t, std::false_type{}); });
 }
 
 extern "C" int msgat_edge_validity(const msgat_graph_t* graph, const float* w, const uint8_t* exempt, const float* val,

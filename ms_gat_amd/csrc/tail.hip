@@ -177,14 +177,8 @@ int launch_gauss_grad(const float* pred, const float* truth, const float* dloss,
 // The reference runs two embedding gathers, an add, R multiplies and R - 1 adds forward and, backward, R + R multiplies,
 // a transposing copy and two dense embedding gradients (a zero fill and a scatter each): 17 launches for 4 MB tensors.
 // Here one launch each way.  Indices are clamped into the tables (torch's gather would trap on the device instead).
-// Static gate (msgat.py:189): H = D = nullptr, h_w = W[R,E] as a one-row table, d_w = nullptr.
+// Static gate (msgat.py:189): H = D = nullptr, h_w = W[R,E] as a one-row table, d_w = nullptr.  gate_row: common.hpp.
 constexpr int kGateMaxB = 1024;   // samples whose table rows a block of the backward keeps in LDS
-
-__device__ __forceinline__ int gate_row(const long long* idx, int b, int rows) {
-  if (idx == nullptr) return 0;
-  const long long v = idx[b];
-  return (int)(v < 0 ? 0 : (v >= rows ? rows - 1 : v));
-}
 
 __global__ __launch_bounds__(kTailBlock) void k_gate_sum(const float* __restrict__ pred, const long long* __restrict__ H,
                                                          const long long* __restrict__ D, const float* __restrict__ h_w,

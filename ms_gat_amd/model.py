@@ -606,6 +606,15 @@ class MSGAT(nn.Module):
         """[B,nnz]: `weights` ([nnz] or [B,nnz]) gated by the validity windows X[:, 0, -1], read where they are."""
         return ops.edge_validity(weights, X[:, 0, -1], crow, col, mode=self.missing_edges, exempt=self.edge_valid_exempt)
 
+    def _edge_adjacency(self, weights: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, samples: Optional[int],
+                        X: Optional[torch.Tensor]):
+        """The adjacency of `weights` on (crow, col): dropped (`samples`: their number, or None), then gated (X, or None)."""
+        if samples is not None:
+            weights = self._drop_edges(weights, samples)
+        if X is not None:
+            weights = self._gate_missing(weights, X, crow, col)
+        return ops.edge_adjacency(crow, col, weights)
+
     def edge_dropout_state(self) -> Optional[Dict[str, int]]:
         """{"seed", "step"} of the mask stream (reads two words back from the device); None for a model that drops nothing."""
         return _read_edge_dropout_state(self.edge_drop_state) if self.edge_dropout > 0 else None
@@ -645,11 +654,7 @@ class MSGAT(nn.Module):
             crow, col, index = ((self.edge_valid_crow, self.edge_valid_col, self.edge_valid_index) if gate else
                                 (self.edge_drop_crow, self.edge_drop_col, self.edge_drop_index))
             weights = self.adj.detach().reshape(-1).index_select(0, index)
-            if drop:
-                weights = self._drop_edges(weights, samples)
-            if gate:
-                weights = self._gate_missing(weights, X, crow, col)
-            return ops.edge_adjacency(crow, col, weights)
+            return self._edge_adjacency(weights, crow, col, samples, X if gate else None)
         if self.learn_edge_weights == "signal":
             if X is None:
                 raise ValueError('learn_edge_weights="signal": the adjacency depends on the batch, pass its inputs X')
@@ -661,11 +666,7 @@ class MSGAT(nn.Module):
             weights = ops.edge_time_weights(self.edge_weight, self.edge_h_ebd.weight, self.edge_d_ebd.weight, H, D)
         else:
             weights = self.edge_weight
-        if drop:
-            weights = self._drop_edges(weights, samples)
-        if gate:
-            weights = self._gate_missing(weights, X, self.edge_crow, self.edge_col)
-        return ops.edge_adjacency(self.edge_crow, self.edge_col, weights)
+        return self._edge_adjacency(weights, self.edge_crow, self.edge_col, samples, X if gate else None)
 
     def batch_adjacency(self, X: torch.Tensor, H: torch.Tensor, D: torch.Tensor):
         """`adjacency` for one batch of `forward`'s inputs; only "signal" and `missing_edges` are handed X."""

@@ -1311,43 +1311,77 @@ def edge_time_weights(base: torch.Tensor, h_weight: torch.Tensor, d_weight: torc
     return _EdgeTimeWeightsFunction.apply(base, h_weight, d_weight, H.contiguous(), D.contiguous())
 
 
+class _CallerOrder:
+    """The crossing between a SparsePattern's caller order of (crow, col) and the library's edge order: a pattern whose order
+    inside a row is not the library's is permuted with torch gathers on either side of a launch, any other passes through.
+    The edge axis is a tensor's last ([nnz], [V,nnz])."""
+
+    def __init__(self, pattern, device):
+        self.perm = None if pattern.identity else pattern._perm(device)      # (library edge -> input position, its inverse)
+
+    def to_library(self, t):
+        """`t` (or None) contiguous, its edges in library order"""
+        if t is None:
+            return None
+        return t.contiguous() if self.perm is None else t.index_select(t.dim() - 1, self.perm[0])
+
+    def to_caller(self, t):
+        """a launch's result (or None), its edges back in the caller's order"""
+        return t if t is None or self.perm is None else t.index_select(t.dim() - 1, self.perm[1])
+
+
+def _edge_exempt(op: str, exempt, nnz: int, device):
+    """`exempt` of `op`, checked as uint8 or bool [nnz] on `device`, as a launch reads it: contiguous uint8 (None stays)."""
+    if exempt is None:
+        return None
+    if (not torch.is_tensor(exempt) or exempt.dtype not in (torch.uint8, torch.bool) or tuple(exempt.shape) != (nnz,)
+            or exempt.device != device):
+        raise ValueError(f"{op}: exempt must be uint8 or bool [{nnz}] on {device}, got "
+                         f"{getattr(exempt, 'dtype', type(exempt).__name__)} {tuple(getattr(exempt, 'shape', ()))}")
+    exempt = exempt.contiguous()
+    return exempt.view(torch.uint8) if exempt.dtype == torch.bool else exempt
+
+
+def _shared_weight_grad(dout: torch.Tensor, V: int, nnz: int, sets):
+    """The gradient of a weight [V,nnz] (`sets`) or [nnz] shared by the samples, for a backward launch to fill -- or, with no
+    sample or no edge, the empty sum: the caller launches nothing then (`V and nnz`)."""
+    shape = (V, nnz) if sets else (nnz,)
+    return torch.zeros(shape, device=dout.device, dtype=dout.dtype) if V == 0 or nnz == 0 else _new(dout, *shape)
+
+
 class _EdgeSignalWeightsFunction(torch.autograd.Function):
     """base [nnz], ab [B,N,2d] -> base[e] + <a[b,row(e)], b[b,col(e)]> [B,nnz] on `pattern`'s structure, one launch each way.
-    Values cross in the caller's order of (crow, col); a pattern whose order inside a row is not the library's is permuted
-    with torch gathers on either side of the launch."""
+    Values cross in the caller's order of (crow, col) (`_CallerOrder`)."""
 
     @staticmethod
     def forward(ctx, base, ab, pattern):
         L = _lib.lib()
-        base, ab = base.contiguous(), ab.contiguous()
+        ab = ab.contiguous()
         B, N, d = ab.shape[0], ab.shape[1], ab.shape[2] // 2
         nnz = pattern.structure.nnz
         gstruct, keep = pattern.structure.on(ab.device)
-        perm = None if pattern.identity else pattern._perm(ab.device)        # (library edge -> input position, its inverse)
-        if perm is not None:
-            base = base.index_select(0, perm[0])
+        order = _CallerOrder(pattern, ab.device)
+        base = order.to_library(base)
         out = _new(ab, B, nnz)
         st = L.msgat_edge_signal_weights(C.byref(gstruct), _ptr(base), _ptr(ab), B, d, _ptr(out), _stream_handle(ab.device))
         _lib.check(st, "msgat_edge_signal_weights")
-        ctx.call = (gstruct, keep, perm, B, N, d, nnz)
+        ctx.call = (gstruct, keep, order, B, N, d, nnz)
         ctx.save_for_backward(ab)
-        return out if perm is None else out.index_select(1, perm[1])
+        return order.to_caller(out)
 
     @staticmethod
     def backward(ctx, dout):
         L = _lib.lib()
         ab, = ctx.saved_tensors
-        gstruct, _, perm, B, N, d, nnz = ctx.call
+        gstruct, _, order, B, N, d, nnz = ctx.call
         need = ctx.needs_input_grad
-        dout = dout.contiguous() if perm is None else dout.index_select(1, perm[0])
+        dout = order.to_library(dout)
         dbase = _new(dout, nnz) if need[0] else None
         dab = _new(dout, B, N, 2 * d) if need[1] else None
         st = L.msgat_edge_signal_weights_backward(C.byref(gstruct), _ptr(dout), _ptr(ab), B, d, _ptr(dbase), _ptr(dab),
                                                   _stream_handle(dout.device))
         _lib.check(st, "msgat_edge_signal_weights_backward")
-        if dbase is not None and perm is not None:
-            dbase = dbase.index_select(0, perm[1])
-        return dbase, dab, None
+        return order.to_caller(dbase), dab, None
 
 
 def edge_signal_weights(base: torch.Tensor, ab: torch.Tensor, crow: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
@@ -1419,12 +1453,11 @@ class _EdgeDropoutFunction(torch.autograd.Function):
         if not ctx.needs_input_grad[0]:
             return (None,) * 7
         dout = dout.contiguous()
-        if V == 0 or nnz == 0:                             # nothing was drawn: the empty sum
-            return (torch.zeros((V, nnz) if sets else (nnz,), device=dout.device, dtype=dout.dtype),) + (None,) * 6
-        dw = _new(dout, V, nnz) if sets else _new(dout, nnz)
-        st = L.msgat_edge_dropout_backward(_ptr(dout), _ptr(exempt), _ptr(state), _ptr(used), _ptr(dw), V, nnz, sets,
-                                           sample_offset, thr, scale, _stream_handle(dout.device))
-        _lib.check(st, "msgat_edge_dropout_backward")
+        dw = _shared_weight_grad(dout, V, nnz, sets)
+        if V and nnz:                                      # else nothing was drawn
+            st = L.msgat_edge_dropout_backward(_ptr(dout), _ptr(exempt), _ptr(state), _ptr(used), _ptr(dw), V, nnz, sets,
+                                               sample_offset, thr, scale, _stream_handle(dout.device))
+            _lib.check(st, "msgat_edge_dropout_backward")
         return (dw,) + (None,) * 6
 
 
@@ -1469,14 +1502,7 @@ def edge_dropout(weight: torch.Tensor, p: float, state: torch.Tensor, *, sample_
         raise ValueError(f"edge_dropout: sample_offset = {sample_offset!r} with {V} samples: global sample indices are 32 bits")
     if nnz >= 1 << 34:
         raise ValueError(f"edge_dropout: {nnz} stored edges, at most 2^34 - 1 are supported")
-    if exempt is not None:
-        if (not torch.is_tensor(exempt) or exempt.dtype not in (torch.uint8, torch.bool) or tuple(exempt.shape) != (nnz,)
-                or exempt.device != weight.device):
-            raise ValueError(f"edge_dropout: exempt must be uint8 or bool [{nnz}] on {weight.device}, got "
-                             f"{getattr(exempt, 'dtype', type(exempt).__name__)} {tuple(getattr(exempt, 'shape', ()))}")
-        exempt = exempt.contiguous()
-        if exempt.dtype == torch.bool:
-            exempt = exempt.view(torch.uint8)
+    exempt = _edge_exempt("edge_dropout", exempt, nnz, weight.device)
     return _EdgeDropoutFunction.apply(weight, exempt, state, V, sample_offset, thr, scale)
 
 
@@ -1502,7 +1528,7 @@ def edge_validity_table(mode, T: int) -> tuple:
 
 
 def _edge_validity_operands(weight, validity, crow, col, exempt, samples):
-    """Shape and type checks shared by the op and its restatement; returns (V, N, T, nnz)."""
+    """Shape and type checks shared by the op and its restatement; returns (V, N, T, nnz, exempt as contiguous uint8)."""
     if not torch.is_tensor(weight) or not torch.is_tensor(validity):
         raise ValueError("edge_validity: weight and validity must be tensors")
     if weight.dtype != torch.float32 or validity.dtype != torch.float32:
@@ -1520,11 +1546,7 @@ def _edge_validity_operands(weight, validity, crow, col, exempt, samples):
     if any(t.device != weight.device for t in (validity, crow, col)):
         raise ValueError(f"edge_validity: weight is on {weight.device}, validity on {validity.device}, crow on {crow.device} "
                          f"and col on {col.device}")
-    if exempt is not None and (not torch.is_tensor(exempt) or exempt.dtype not in (torch.uint8, torch.bool)
-                               or tuple(exempt.shape) != (nnz,) or exempt.device != weight.device):
-        raise ValueError(f"edge_validity: exempt must be uint8 or bool [{nnz}] on {weight.device}, got "
-                         f"{getattr(exempt, 'dtype', type(exempt).__name__)} {tuple(getattr(exempt, 'shape', ()))}")
-    return V, N, T, nnz
+    return V, N, T, nnz, _edge_exempt("edge_validity", exempt, nnz, weight.device)
 
 
 _EDGE_VALIDITY_TABLES = {}            # (mode, T, device) -> the table as a tensor there, for the torch restatement
@@ -1536,7 +1558,7 @@ def edge_validity_reference(weight: torch.Tensor, validity: torch.Tensor, crow: 
     """`edge_validity` restated with torch ops, on whichever device the operands are: a compare and a sum for the counts, a
     table gather, a gather by source node, a compare, a select, one fp32 multiply and the exempt edges' select.  What the op
     runs for CPU tensors, and the torch-op formulation the measurements compare against."""
-    V, N, T, nnz = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
+    V, N, T, nnz, exempt = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
     key = (mode, T, str(weight.device))
     table = _EDGE_VALIDITY_TABLES.get(key)
     if table is None:                  # kept per (mode, T, device): a captured step cannot copy it from the host
@@ -1550,52 +1572,45 @@ def edge_validity_reference(weight: torch.Tensor, validity: torch.Tensor, crow: 
 
 class _EdgeValidityFunction(torch.autograd.Function):
     """w [nnz] or [V,nnz], validity [V,N,T] -> w * g [V,nnz] on `pattern`'s structure (msgat_edge_validity); backward
-    re-creates the gate from `validity`.  Values cross in the caller's order of (crow, col), as in
-    `_EdgeSignalWeightsFunction`."""
+    re-creates the gate from `validity`.  Values cross in the caller's order of (crow, col) (`_CallerOrder`)."""
 
     @staticmethod
     def forward(ctx, w, validity, exempt, pattern, table):
         L = _lib.lib()
-        w = w.contiguous()
         V, N, T = validity.shape
         if validity.stride(2) != 1 or validity.stride(1) != T or (V > 1 and validity.stride(0) < 0):
             validity = validity.contiguous()               # the kernel wants [N,T] rows contiguous; any sample stride is read
         nnz = pattern.structure.nnz
         sets = int(w.dim() == 2)
         gstruct, keep = pattern.structure.on(w.device)
-        perm = None if pattern.identity else pattern._perm(w.device)         # (library edge -> input position, its inverse)
-        if perm is not None:
-            w = w.index_select(w.dim() - 1, perm[0])
-            exempt = None if exempt is None else exempt.index_select(0, perm[0])
+        order = _CallerOrder(pattern, w.device)
+        w, exempt = order.to_library(w), order.to_library(exempt)
         stride = validity.stride(0) if V > 1 else N * T
         ctable = (C.c_float * (T + 1))(*table)
         out = _new(w, V, nnz)
         st = L.msgat_edge_validity(C.byref(gstruct), _ptr(w), _ptr(exempt), _ptr(validity), stride, ctable, _ptr(out), V, T,
                                    sets, _stream_handle(w.device))
         _lib.check(st, "msgat_edge_validity")
-        ctx.call = (gstruct, keep, perm, V, T, nnz, sets, stride, ctable)
+        ctx.call = (gstruct, keep, order, V, T, nnz, sets, stride, ctable)
         ctx.operands = (exempt,)                           # an integer tensor the launch reads by address: nothing to version
         ctx.save_for_backward(validity)
-        return out if perm is None else out.index_select(1, perm[1])
+        return order.to_caller(out)
 
     @staticmethod
     def backward(ctx, dout):
         L = _lib.lib()
         validity, = ctx.saved_tensors
         exempt, = ctx.operands
-        gstruct, _, perm, V, T, nnz, sets, stride, ctable = ctx.call
+        gstruct, _, order, V, T, nnz, sets, stride, ctable = ctx.call
         if not ctx.needs_input_grad[0]:
             return (None,) * 5
-        dout = dout.contiguous() if perm is None else dout.index_select(1, perm[0])
-        if V == 0 or nnz == 0:                             # nothing is launched: the empty sum
-            return (torch.zeros((V, nnz) if sets else (nnz,), device=dout.device, dtype=dout.dtype),) + (None,) * 4
-        dw = _new(dout, V, nnz) if sets else _new(dout, nnz)
-        st = L.msgat_edge_validity_backward(C.byref(gstruct), _ptr(dout), _ptr(exempt), _ptr(validity), stride, ctable,
-                                            _ptr(dw), V, T, sets, _stream_handle(dout.device))
-        _lib.check(st, "msgat_edge_validity_backward")
-        if perm is not None:
-            dw = dw.index_select(dw.dim() - 1, perm[1])
-        return (dw,) + (None,) * 4
+        dout = order.to_library(dout)
+        dw = _shared_weight_grad(dout, V, nnz, sets)
+        if V and nnz:
+            st = L.msgat_edge_validity_backward(C.byref(gstruct), _ptr(dout), _ptr(exempt), _ptr(validity), stride, ctable,
+                                                _ptr(dw), V, T, sets, _stream_handle(dout.device))
+            _lib.check(st, "msgat_edge_validity_backward")
+        return (order.to_caller(dw),) + (None,) * 4
 
 
 def edge_validity(weight: torch.Tensor, validity: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, *, mode="scale",
@@ -1615,14 +1630,10 @@ def edge_validity(weight: torch.Tensor, validity: torch.Tensor, crow: torch.Tens
     `weight` [V,nnz] gets `dout * g`, `weight` [nnz] the sum over the samples in ascending order; one launch each way, no
     atomics, capturable (msgat_edge_validity{,_backward}).  Row v depends on sample v alone, so rows [lo, hi) of a V-row
     call are the call on that shard.  CPU tensors run `edge_validity_reference`, the same arithmetic in torch ops."""
-    V, N, T, nnz = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
+    V, N, T, nnz, exempt = _edge_validity_operands(weight, validity, crow, col, exempt, samples)
     table = edge_validity_table(mode, T)
     if not weight.is_cuda:
         return edge_validity_reference(weight, validity, crow, col, mode=mode, exempt=exempt, samples=samples)
-    if exempt is not None:
-        exempt = exempt.contiguous()
-        if exempt.dtype == torch.bool:
-            exempt = exempt.view(torch.uint8)
     return _EdgeValidityFunction.apply(weight, validity.detach(), exempt, edge_pattern_of(crow, col), table)
 
 

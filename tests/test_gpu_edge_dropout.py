@@ -24,6 +24,9 @@ DEV = torch.device("cuda:0")
 SEED, STEP = (1 << 32) + 5, (1 << 32) + 3         # the high words of key and counter are exercised
 NNZ = (1, 3, 4, 5, 255, 256, 257, 1027)
 VS = (1, 2, 5, 33)
+TILE = 64         # kEbSumSamples of csrc/edge_batch.hpp: the samples whose terms a block of a summing backward forms at a time
+TILE_VS = (TILE, TILE + 1, 2 * TILE + 1)          # exactly a tile, a tile plus one, two tiles plus one
+TILE_NNZ = (5, 65)                                # a partial quad; a second block that holds one edge
 PS = (0.0, 0.1, 0.5, 0.9)
 
 
@@ -111,11 +114,12 @@ def test_step_bookkeeping():
     assert _same_bits(e, ref.forward(w.cpu().numpy(), (1 << 64) - 3, 0, V, p))
 
 
-@pytest.mark.parametrize("nnz", NNZ)
+@pytest.mark.parametrize("nnz", NNZ + tuple(n for n in TILE_NNZ if n not in NNZ))
 def test_backward_forms_have_the_bits_of_the_restatement(nnz):
     rng = np.random.default_rng(100 + nnz)
     ex = _exempt(nnz)
-    for V in VS + (70,):                                  # 70: more samples than an LDS tile of the summing form holds
+    # 70: more samples than an LDS tile of the summing form holds; the tile's own edges at TILE_NNZ
+    for V in (VS + (70,) if nnz in NNZ else ()) + (TILE_VS if nnz in TILE_NNZ else ()):
         dout = rng.standard_normal((V, nnz)).astype(np.float32)
         dout_t = _dev(dout)
         for p in (0.0, 0.1, 0.5, 0.9):

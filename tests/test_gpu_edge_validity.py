@@ -26,6 +26,9 @@ DEV = torch.device("cuda:0")
 
 NNZ = (1, 3, 4, 5, 255, 256, 257, 1027)
 VS = (1, 2, 5, 33)
+TILE = 64         # kEbSumSamples of csrc/edge_batch.hpp: the samples whose terms a block of a summing backward forms at a time
+TILE_VS = (TILE, TILE + 1, 2 * TILE + 1)          # exactly a tile, a tile plus one, two tiles plus one
+TILE_NNZ = (5, 65)                                # a partial quad; a second block that holds one edge
 
 
 def _dev(a, dtype=torch.float32):
@@ -163,11 +166,12 @@ def test_a_nan_weight_on_a_fully_gated_edge_is_plus_zero():
             assert not dw[gated].view(np.int32).any()
 
 
-@pytest.mark.parametrize("nnz", NNZ)
+@pytest.mark.parametrize("nnz", NNZ + tuple(n for n in TILE_NNZ if n not in NNZ))
 def test_backward_forms_have_the_bits_of_the_restatement(nnz):
     pat = Pattern(nnz)
     rng = np.random.default_rng(100 + nnz)
-    for V in VS + (70,):                                  # 70: more samples than an LDS tile of the summing form holds
+    # 70: more samples than an LDS tile of the summing form holds; the tile's own edges at TILE_NNZ
+    for V in (VS + (70,) if nnz in NNZ else ()) + (TILE_VS if nnz in TILE_NNZ else ()):
         dout = rng.standard_normal((V, nnz)).astype(np.float32)
         dout_t = _dev(dout)
         for T in ref.T_SET:
@@ -249,6 +253,24 @@ def test_two_calls_give_the_same_bits_and_the_op_agrees_with_autograd_of_its_res
         (g,) = torch.autograd.grad(ops.edge_validity(w, val, pat.crow, pat.col), w, dout.clone().requires_grad_(True),
                                    create_graph=True)
         g.sum().backward()
+
+
+def test_op_takes_columns_in_any_order_inside_a_row():
+    """(crow, col) with every row's columns reversed: weights, exempt flags, values and gradients stay in the caller's order"""
+    V, T, nnz = 5, 12, 257
+    pat = Pattern(nnz)
+    perm = np.concatenate([np.arange(pat.crow_np[i], pat.crow_np[i + 1])[::-1] for i in range(pat.N)])
+    col = _dev(pat.col_np[perm], torch.int64)
+    assert not graph.edge_pattern_of(pat.crow, col).identity
+    rng = np.random.default_rng(5)
+    val_np, dout_np = ref.validity(V, pat.N, T), rng.standard_normal((V, nnz)).astype(np.float32)
+    for w_np in (rng.standard_normal(nnz).astype(np.float32), rng.standard_normal((V, nnz)).astype(np.float32)):
+        w = _dev(w_np[..., perm]).requires_grad_(True)
+        out = ops.edge_validity(w, _dev(val_np), pat.crow, col, exempt=_dev(pat.exempt_np[perm], torch.uint8))
+        assert _same_bits(out.detach(), ref.forward(w_np, val_np, pat.col_np, "scale", pat.exempt_np)[:, perm])
+        out.backward(_dev(dout_np[:, perm]))
+        back = ref.backward_shared if w_np.ndim == 1 else ref.backward_sets
+        assert _same_bits(w.grad, back(dout_np, val_np, pat.col_np, "scale", pat.exempt_np)[..., perm])
 
 
 @pytest.mark.parametrize("V,nnz", [(7, 257), (33, 1027)])
