@@ -12,6 +12,7 @@
 // gather-from-L2 kernel.  Either way the kernel is HBM-bound: algorithmic bytes =
 // read u once + write v once.
 #include "common.hpp"
+#include "edge_window.hpp"
 #include "sell.hpp"
 
 namespace msgat {
@@ -22,13 +23,7 @@ namespace msgat {
 // blocks per CU keep the CU's 32 wave slots full while one block streams its slab in or out.
 // kAggBlock (1024 lanes per block): sell.hpp
 
-// 4 edges per trip, fetched as ONE 16-byte load of indices and one of weights.  Edge ranges start
-// at arbitrary dword offsets; gfx950 global loads of 128 bits need only dword alignment, which the
-// packed types tell the compiler.  A trip may read past the row's last edge (into the next row's,
-// always inside the array: the window is clamped to end at nnz) -- those slots get weight 0.
-struct __attribute__((packed, aligned(4))) int4u { int v[4]; };
-struct __attribute__((packed, aligned(4))) float4u { float v[4]; };
-
+// One row's neighbours, gathered from `rows` (an LDS slab or global memory): the row walk of edge_window.hpp.
 template <int T4, typename RowPtr>
 __device__ __forceinline__ float4 gather_row(const int* __restrict__ idx, const float* __restrict__ Eg,
                                              int e0, int e1, int nnz, RowPtr rows, int j) {
@@ -41,27 +36,16 @@ __device__ __forceinline__ float4 gather_row(const int* __restrict__ idx, const 
   // one dependent global round trip per extra window as soon as ONE of its rows is longer than 4 edges
   // -- and with PEMS-like degrees (1 + ~Poisson(2)) that is practically every wave: the loop form ran
   // at 45 us against 33 us for the same kernel on rows of at most 4 edges (tools/slab_copy.hip).
-  const int b0 = min(e0, nnz - 8);
-  const int4u m0 = *reinterpret_cast<const int4u*>(idx + b0);
-  const int4u m1 = *reinterpret_cast<const int4u*>(idx + b0 + 4);
-  const float4u w0 = *reinterpret_cast<const float4u*>(Eg + b0);
-  const float4u w1 = *reinterpret_cast<const float4u*>(Eg + b0 + 4);
+  const EdgeWindow win = load_edge_window(idx, Eg, e0, nnz);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float wa = (b0 + k >= e0 && b0 + k < e1) ? w0.v[k] : 0.f;
-    const float wb = (b0 + 4 + k >= e0 && b0 + 4 + k < e1) ? w1.v[k] : 0.f;
-    f4fma(wa, rows[m0.v[k] * T4 + j], acc);
-    f4fma(wb, rows[m1.v[k] * T4 + j], acc);
+  for (int k = 0; k < 4; ++k) {  // the window's halves alternate (slots 0, 4, 1, 5, ...): this form's summation order, its bits hang on it
+    f4fma(win.valid(k, e0, e1) ? win.coef(k) : 0.f, rows[win.index(k) * T4 + j], acc);
+    f4fma(win.valid(4 + k, e0, e1) ? win.coef(4 + k) : 0.f, rows[win.index(4 + k) * T4 + j], acc);
   }
-  for (int e = b0 + 8; e < e1; e += 4) {  // rows with more than 8 edges
-    const int b = min(e, nnz - 4);
-    const int4u m = *reinterpret_cast<const int4u*>(idx + b);
-    const float4u w = *reinterpret_cast<const float4u*>(Eg + b);
+  for (int e = win.b0 + 8; e < e1; e += 4) {  // rows with more than 8 edges
+    const EdgeTrip t = load_edge_trip(idx, Eg, e, nnz);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float wk = (b + k >= e && b + k < e1) ? w.v[k] : 0.f;
-      f4fma(wk, rows[m.v[k] * T4 + j], acc);
-    }
+    for (int k = 0; k < 4; ++k) f4fma(t.valid(k, e, e1) ? t.w.v[k] : 0.f, rows[t.m.v[k] * T4 + j], acc);
   }
   return acc;
 }
@@ -79,10 +63,10 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_lds(
   __shared__ float dred[kAggBlock / 64][kAggDotMaxC];
   const int g = blockIdx.y;
   const int r = g / Bg;
-  const int c0 = blockIdx.x * CH;
-  const int ch = min(CH, Cu - c0);
   const int NT4 = N * T4;
-  const size_t base = ((size_t)g * Cu + c0) * NT4;
+  const ChannelChunk ck = channel_chunk(blockIdx.x, CH, Cu, g, NT4);
+  const int c0 = ck.c0, ch = ck.ch;
+  const size_t base = ck.base;
   const int total = ch * NT4;
 
   for (int i = threadIdx.x; i < total; i += kAggBlock) slab[i] = u4[base + i];
@@ -95,8 +79,7 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_lds(
   float da[kAggDotMaxC] = {0.f, 0.f, 0.f, 0.f};
   const float* Eg = E + (size_t)g * nnz;
   for (int s = blockIdx.z * seg + threadIdx.x; s < s_end; s += kAggBlock) {
-    const int n = s / T4;
-    const int j = s - n * T4;
+    const auto [n, j] = slot_node<T4>(s);
     const int e0 = ptr[n], e1 = ptr[n + 1];
     float4 ex = f4zero();
     if (addvec != nullptr) ex = extra4[(size_t)g * NT4 + s];
@@ -106,9 +89,8 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_lds(
         if (c < ch) da[c] = f4dot(ex, xdot4[base + (size_t)c * NT4 + s], da[c]);
     }
     for (int c = 0; c < ch; ++c) {
-      float4 acc = gather_row<T4>(idx, Eg, e0, e1, nnz, slab + c * NT4, j);
-      if (addvec != nullptr) f4fma(addvec[r * Cu + c0 + c], ex, acc);
-      v4[base + (size_t)c * NT4 + s] = acc;
+      const float4 acc = gather_row<T4>(idx, Eg, e0, e1, nnz, slab + c * NT4, j);
+      store_plus_extra(v4 + base + (size_t)c * NT4 + s, acc, addvec, addvec_at(addvec, r * Cu + c0 + c), &ex);
     }
   }
   if (DOT) {
@@ -180,28 +162,26 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_ring(
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
     slot[k] = min((int)threadIdx.x + kAggBlock * k, NT4 - 1);
-    const int n = slot[k] / T4;
-    jof[k] = slot[k] - n * T4;
+    const auto [n, j] = slot_node<T4>(slot[k]);
+    jof[k] = j;
     e0s[k] = ptr[n];
     e1s[k] = ptr[n + 1];
-    b0s[k] = min(e0s[k], nnz - 8);
-    const int4u ia = *reinterpret_cast<const int4u*>(idx + b0s[k]), ib = *reinterpret_cast<const int4u*>(idx + b0s[k] + 4);
+    EdgeWindow win = edge_window_at(e0s[k], nnz);
+    b0s[k] = win.b0;
+    win.load_indices(idx);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {   // rows of edges outside [e0, e1) read row 0 with coefficient 0
-      m[k][q] = (b0s[k] + q >= e0s[k] && b0s[k] + q < e1s[k]) ? ia.v[q] * T4 + jof[k] : jof[k];
-      m[k][4 + q] = (b0s[k] + 4 + q >= e0s[k] && b0s[k] + 4 + q < e1s[k]) ? ib.v[q] * T4 + jof[k] : jof[k];
-    }
+    for (int q = 0; q < 8; ++q)   // rows of edges outside [e0, e1) read row 0 with coefficient 0
+      m[k][q] = win.valid(q, e0s[k], e1s[k]) ? win.index(q) * T4 + jof[k] : jof[k];
   }
   auto load_weights = [&](int g) {
     const float* Eg = E + (size_t)g * nnz;
 #pragma unroll
     for (int k = 0; k < KI; ++k) {
-      const float4u wa = *reinterpret_cast<const float4u*>(Eg + b0s[k]), wb = *reinterpret_cast<const float4u*>(Eg + b0s[k] + 4);
+      EdgeWindow win;
+      win.b0 = b0s[k];
+      win.load_coefs(Eg);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        w[k][q] = (b0s[k] + q >= e0s[k] && b0s[k] + q < e1s[k]) ? wa.v[q] : 0.f;
-        w[k][4 + q] = (b0s[k] + 4 + q >= e0s[k] && b0s[k] + 4 + q < e1s[k]) ? wb.v[q] : 0.f;
-      }
+      for (int q = 0; q < 8; ++q) w[k][q] = win.valid(q, e0s[k], e1s[k]) ? win.coef(q) : 0.f;
     }
   };
   int gcur = s0 / Cu;
@@ -227,7 +207,8 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_ring(
       float4 acc = f4zero();
 #pragma unroll
       for (int q = 0; q < 8; ++q) f4fma(w[k][q], buf[m[k][q]], acc);
-      for (int e = b0s[k] + 8; e < e1s[k]; ++e) f4fma(Eg[e], buf[idx[e] * T4 + jof[k]], acc);   // rows with more than 8 edges
+      // rows with more than 8 edges: one edge at a time, not in trips of four (load_edge_trip) -- no slot to mask, ascending as it is
+      for (int e = b0s[k] + 8; e < e1s[k]; ++e) f4fma(Eg[e], buf[idx[e] * T4 + jof[k]], acc);
       out[slot[k]] = acc;
     }
   }
@@ -253,14 +234,13 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_cols(
   const int c = blockIdx.x;
   const size_t base = ((size_t)g * Cu + c) * N * T4;
   const float* Eg = E + (size_t)g * nnz;
-  const float av = (addvec != nullptr) ? addvec[r * Cu + c] : 0.f;
+  const float av = addvec_at(addvec, r * Cu + c);
   for (int j = 0; j < T4; ++j) {
     for (int n = threadIdx.x; n < N; n += kAggBlock) slab[n] = u4[base + (size_t)n * T4 + j];
     __syncthreads();
     for (int n = threadIdx.x; n < N; n += kAggBlock) {
-      float4 acc = gather_row<1>(idx, Eg, ptr[n], ptr[n + 1], nnz, slab, 0);
-      if (addvec != nullptr) f4fma(av, extra4[((size_t)g * N + n) * T4 + j], acc);
-      v4[base + (size_t)n * T4 + j] = acc;
+      const float4 acc = gather_row<1>(idx, Eg, ptr[n], ptr[n + 1], nnz, slab, 0);
+      store_plus_extra(v4 + base + (size_t)n * T4 + j, acc, addvec, av, extra4 + ((size_t)g * N + n) * T4 + j);
     }
     __syncthreads();
   }
@@ -280,8 +260,7 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_sell(
     const float4* __restrict__ extra4, float4* __restrict__ v4, int G, int Bg, int Cu, int N, int n_pos,
     int n_slices) {
   extern __shared__ float4 slab[];  // [N]: column j of the [N][T4] slab
-  // XCD-aware block -> (group, channel, column) map.  Workgroups are dealt round-robin over the 8 XCDs (block b
-  // runs on XCD b % 8), each with its own 4 MB L2.  Two things must meet in ONE L2 at the same time:
+  // XCD-aware block -> (group, channel, column) map (xcd_group_slot).  Two things must meet in ONE L2 at the same time:
   //   - the Cu x T/4 blocks of a group all read the same E[g] (0.6 MB at the stress graph): group g is pinned to
   //     XCD g % 8, so an L2 serves one or two groups' coefficients instead of eleven;
   //   - the T/4 column blocks of one (group, channel) slab touch the same 128-B lines (a column is 16 B of every
@@ -289,16 +268,15 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_sell(
   //     the fabric sees every line once instead of T/4 times, the partial-line stores merging in L2.
   // Without either the kernel moved 3-5x its algorithmic bytes over the fabric and ran at the same 4.2 ms
   // whatever its instruction count (profiles/r02/stress_*).
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  int g, slot;
+  if (!xcd_group_slot(T4 * Cu, G, &g, &slot)) return;
   const int j = slot % T4;
-  const int c = (slot / T4) % Cu;
-  const int g = (slot / (T4 * Cu)) * 8 + xcd;
-  if (g >= G) return;  // grid is padded to a multiple of 8 groups
+  const int c = slot / T4;
   const int r = g / Bg;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const size_t base = ((size_t)g * Cu + c) * N * T4;
   const float* Eg = Es + (size_t)g * n_pos;
-  const float av = (addvec != nullptr) ? addvec[r * Cu + c] : 0.f;
+  const float av = addvec_at(addvec, r * Cu + c);
   stage_column<T4>(slab, u4 + base, j, N);
   __syncthreads();
   // The rows of a slice are scattered over N (the layout is sorted by degree), so results are not stored from
@@ -349,11 +327,8 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_sell(
     }
   }
   __syncthreads();
-  for (int n = threadIdx.x; n < N; n += kAggBlock) {
-    float4 acc = slab[n];
-    if (addvec != nullptr) f4fma(av, extra4[((size_t)g * N + n) * T4 + j], acc);
-    v4[base + (size_t)n * T4 + j] = acc;
-  }
+  for (int n = threadIdx.x; n < N; n += kAggBlock)
+    store_plus_extra(v4 + base + (size_t)n * T4 + j, slab[n], addvec, av, extra4 + ((size_t)g * N + n) * T4 + j);
 }
 
 // (A half-column form -- 2-timestep columns of 64 KB, two resident blocks per CU, so that one block's staging and stores run
@@ -372,12 +347,10 @@ __global__ __launch_bounds__(kBlock) void k_agg_glb(
   const int NT4 = N * T4;
   const int s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= NT4) return;
-  const int n = s / T4;
-  const int j = s - n * T4;
+  const auto [n, j] = slot_node<T4>(s);
   const float4* sl = u4 + ((size_t)g * Cu + c) * NT4;
-  float4 acc = gather_row<T4>(idx, E + (size_t)g * nnz, ptr[n], ptr[n + 1], nnz, sl, j);
-  if (addvec != nullptr) f4fma(addvec[r * Cu + c], extra4[(size_t)g * NT4 + s], acc);
-  v4[((size_t)g * Cu + c) * NT4 + s] = acc;
+  const float4 acc = gather_row<T4>(idx, E + (size_t)g * nnz, ptr[n], ptr[n + 1], nnz, sl, j);
+  store_plus_extra(v4 + ((size_t)g * Cu + c) * NT4 + s, acc, addvec, addvec_at(addvec, r * Cu + c), extra4 + (size_t)g * NT4 + s);
 }
 
 template <int T4>
@@ -386,57 +359,47 @@ static int launch_aggregate_t(const int* ptr, const int* idx, int nnz, const msg
                               int Cu, int N, hipStream_t s, const float* xdot, float* dap, int* dot_done) {
   const int T = 4 * T4;
   const int CH = slab_channels(N, T, Cu, kLdsBudget);
+  const float4 *u4 = (const float4*)u, *extra4 = (const float4*)extra;
+  float4* v4 = (float4*)v;
   if (sell != nullptr) {  // E is in the position order of this layout (the caller permuted it by sell->src)
-    const size_t lds = (size_t)N * sizeof(float4);
-    static LdsGrant granted;
-    if (int st = grant_dynamic_lds(&k_agg_sell<T4>, lds, granted)) return st;
-    hipLaunchKernelGGL((k_agg_sell<T4>), dim3((unsigned)cdiv(G, 8) * 8 * Cu * T4), dim3(kAggBlock), lds, s,
-                       sell->slice_off, sell->lane_row, sell->idx, (const float4*)u, E, addvec, (const float4*)extra,
-                       (float4*)v, G, Bg, Cu, N, sell->n_pos, sell->n_slices);
-  } else if (addvec == nullptr && xdot == nullptr && nnz >= 8 && N * T4 <= 3 * kAggBlock && G * Cu >= 512) {
+    return launch_lds<k_agg_sell<T4>>(dim3(xcd_grid(G, Cu * T4)), dim3(kAggBlock), (size_t)N * sizeof(float4), s,
+                                      sell->slice_off, sell->lane_row, sell->idx, u4, E, addvec, extra4, v4, G, Bg, Cu, N,
+                                      sell->n_pos, sell->n_slices);
+  }
+  if (addvec == nullptr && xdot == nullptr && nnz >= 8 && N * T4 <= 3 * kAggBlock && G * Cu >= 512) {
     // plain aggregate on a small graph: the persistent LDS-DMA ring, one block per CU
     const int ncu = device_cu_count();
     const int nslab = G * Cu, per = cdiv(nslab, ncu), nb = cdiv(nslab, per);
     const int KI = cdiv(N * T4, kAggBlock);
     const size_t lds = (size_t)3 * KI * kAggBlock * sizeof(float4);
-#define MSGAT_RING(ki)                                                                                            \
-    {                                                                                                               \
-      static LdsGrant granted;                                                                                      \
-      if (int st = grant_dynamic_lds(&k_agg_ring<T4, ki>, lds, granted)) return st;                                 \
-      hipLaunchKernelGGL((k_agg_ring<T4, ki>), dim3(nb), dim3(kAggBlock), lds, s, ptr, idx, (const float4*)u, E,    \
-                         (float4*)v, Cu, N, nnz, nslab, per);                                                       \
-    }
-    if (KI == 1) MSGAT_RING(1) else if (KI == 2) MSGAT_RING(2) else MSGAT_RING(3)
-#undef MSGAT_RING
-  } else if (CH >= 1) {
+    return dispatch_range<1, 3>(KI, [&](auto ki) {
+      return launch_lds<k_agg_ring<T4, decltype(ki)::value>>(dim3(nb), dim3(kAggBlock), lds, s, ptr, idx, u4, E, v4, Cu, N,
+                                                             nnz, nslab, per);
+    });
+  }
+  if (CH >= 1) {
     const size_t lds = (size_t)CH * N * T * sizeof(float);
-    static LdsGrant granted_plain, granted_dot;
-    if (int st = grant_dynamic_lds(&k_agg_lds<T4, false>, lds, granted_plain)) return st;
-    if (int st = grant_dynamic_lds(&k_agg_lds<T4, true>, lds, granted_dot)) return st;
     // few blocks (the first MEAM's backward: G of them): up to kAggMaxSplit blocks share a slab's rows
     const int nblocks = cdiv(Cu, CH) * G;
     int split = device_cu_count() / max(nblocks, 1);
     split = max(1, min(min(split, kAggMaxSplit), (N * T4) / 256));
     dim3 grid(cdiv(Cu, CH), G, split);
     if (xdot != nullptr && dap != nullptr && addvec != nullptr && Cu <= kAggDotMaxC) {
-      hipLaunchKernelGGL((k_agg_lds<T4, true>), grid, dim3(kAggBlock), lds, s, ptr, idx, (const float4*)u, E, addvec,
-                         (const float4*)extra, (float4*)v, Bg, Cu, N, nnz, CH, (const float4*)xdot, dap);
+      if (int st = launch_lds<k_agg_lds<T4, true>>(grid, dim3(kAggBlock), lds, s, ptr, idx, u4, E, addvec, extra4, v4, Bg,
+                                                   Cu, N, nnz, CH, (const float4*)xdot, dap))
+        return st;
       if (dot_done != nullptr) *dot_done = split;   // partials per group
-    } else {
-      hipLaunchKernelGGL((k_agg_lds<T4, false>), grid, dim3(kAggBlock), lds, s, ptr, idx, (const float4*)u, E, addvec,
-                         (const float4*)extra, (float4*)v, Bg, Cu, N, nnz, CH, nullptr, nullptr);
+      return MSGAT_OK;
     }
-  } else if ((size_t)N * sizeof(float4) <= (size_t)kLdsMax - 1024 && nnz >= 8) {
-    const size_t lds = (size_t)N * sizeof(float4);
-    static LdsGrant granted;
-    if (int st = grant_dynamic_lds(&k_agg_cols<T4>, lds, granted)) return st;
-    hipLaunchKernelGGL(k_agg_cols<T4>, dim3(Cu, G), dim3(kAggBlock), lds, s, ptr, idx, (const float4*)u, E,
-                       addvec, (const float4*)extra, (float4*)v, Bg, Cu, N, nnz);
-  } else {
-    dim3 grid(cdiv(N * T4, kBlock), Cu, G);
-    hipLaunchKernelGGL(k_agg_glb<T4>, grid, dim3(kBlock), 0, s, ptr, idx, (const float4*)u, E, addvec,
-                       (const float4*)extra, (float4*)v, Bg, Cu, N, nnz);
+    return launch_lds<k_agg_lds<T4, false>>(grid, dim3(kAggBlock), lds, s, ptr, idx, u4, E, addvec, extra4, v4, Bg, Cu, N,
+                                            nnz, CH, nullptr, nullptr);
   }
+  if ((size_t)N * sizeof(float4) <= (size_t)kLdsMax - 1024 && nnz >= 8) {
+    return launch_lds<k_agg_cols<T4>>(dim3(Cu, G), dim3(kAggBlock), (size_t)N * sizeof(float4), s, ptr, idx, u4, E, addvec,
+                                      extra4, v4, Bg, Cu, N, nnz);
+  }
+  dim3 grid(cdiv(N * T4, kBlock), Cu, G);
+  hipLaunchKernelGGL(k_agg_glb<T4>, grid, dim3(kBlock), 0, s, ptr, idx, u4, E, addvec, extra4, v4, Bg, Cu, N, nnz);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
@@ -445,13 +408,10 @@ int launch_aggregate(const int* ptr, const int* idx, int nnz, const msgat_sell_t
                      const float* E, const float* addvec, const float* extra, float* v, int G, int Bg, int Cu,
                      int N, int T, hipStream_t s, const float* xdot, float* dap, int* dot_done) {
   if (dot_done != nullptr) *dot_done = 0;
-  switch (T) {
-    case 4: return launch_aggregate_t<1>(ptr, idx, nnz, sell, u, E, addvec, extra, v, G, Bg, Cu, N, s, xdot, dap, dot_done);
-    case 8: return launch_aggregate_t<2>(ptr, idx, nnz, sell, u, E, addvec, extra, v, G, Bg, Cu, N, s, xdot, dap, dot_done);
-    case 12: return launch_aggregate_t<3>(ptr, idx, nnz, sell, u, E, addvec, extra, v, G, Bg, Cu, N, s, xdot, dap, dot_done);
-    case 16: return launch_aggregate_t<4>(ptr, idx, nnz, sell, u, E, addvec, extra, v, G, Bg, Cu, N, s, xdot, dap, dot_done);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
+  return dispatch_T(T, [&](auto t) {
+    return launch_aggregate_t<decltype(t)::value / 4>(ptr, idx, nnz, sell, u, E, addvec, extra, v, G, Bg, Cu, N, s, xdot, dap,
+                                                      dot_done);
+  });
 }
 
 // E re-ordered for a gather: Eo[g,k] = E[g, perm[k]] (CSC order: perm = cperm; SELL position order: perm =
@@ -495,8 +455,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_proj(
   const int NT4 = N * T4;
   const int s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= NT4) return;
-  const int n = s / T4;
-  const int j = s - n * T4;
+  const auto [n, j] = slot_node<T4>(s);
   const float* Eg = E + (size_t)g * nnz;
   const int e0 = rowptr[n], e1 = rowptr[n + 1];
 
@@ -550,13 +509,7 @@ static int launch_agg_proj_o(const msgat_graph_t& gr, const float* x, const floa
 int launch_aggregate_project(const msgat_graph_t& gr, const float* x, const float* E,
                              const float* W, float* y, float* z, int G, int Bg, int C, int Co,
                              int N, int T, hipStream_t s) {
-  switch (T) {
-    case 4: return launch_agg_proj_o<1>(gr, x, E, W, y, z, G, Bg, C, Co, N, s);
-    case 8: return launch_agg_proj_o<2>(gr, x, E, W, y, z, G, Bg, C, Co, N, s);
-    case 12: return launch_agg_proj_o<3>(gr, x, E, W, y, z, G, Bg, C, Co, N, s);
-    case 16: return launch_agg_proj_o<4>(gr, x, E, W, y, z, G, Bg, C, Co, N, s);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
+  return dispatch_T(T, [&](auto t) { return launch_agg_proj_o<decltype(t)::value / 4>(gr, x, E, W, y, z, G, Bg, C, Co, N, s); });
 }
 
 // ---- SDDMM: dE partials per channel chunk ---------------------------------------------------------
@@ -571,10 +524,10 @@ __global__ __launch_bounds__(kBlock) void k_sddmm(
   extern __shared__ float4 slab[];
   const int g = blockIdx.z;
   const int k = blockIdx.y;
-  const int c0 = k * CH;
-  const int ch = min(CH, Cu - c0);
   const int NT4 = N * T4;
-  const size_t base = ((size_t)g * Cu + c0) * NT4;
+  const ChannelChunk ck = channel_chunk(k, CH, Cu, g, NT4);
+  const int ch = ck.ch;
+  const size_t base = ck.base;
   if (USE_LDS) {
     const int total = ch * NT4;
     for (int i = threadIdx.x; i < total; i += kBlock) slab[i] = u4[base + i];
@@ -603,23 +556,8 @@ __global__ __launch_bounds__(kBlock) void k_sddmm(
 // their shares of an edge's dot in LDS (lane-private entries, no atomics); after a barrier lane k adds them in a
 // fixed order and stores the chunk's partial in CSC order (k_edge_grad_csc maps it back through cperm).
 
-// The first eight edge slots of a column: sources and coefficients, two 16-byte loads each.  They depend on the
-// column's colptr entry only -- not on the slab -- so the caller asks for them ahead of the gather that reads them.
-struct EdgeWindow {
-  int b0;
-  int4u m0, m1;
-  float4u w0, w1;
-};
-__device__ __forceinline__ EdgeWindow load_edge_window(const int* __restrict__ idx, const float* __restrict__ Eg,
-                                                       int e0, int nnz) {
-  EdgeWindow w;
-  w.b0 = min(e0, nnz - 8);  // nnz >= 8 (launch condition)
-  w.m0 = *reinterpret_cast<const int4u*>(idx + w.b0);
-  w.m1 = *reinterpret_cast<const int4u*>(idx + w.b0 + 4);
-  w.w0 = *reinterpret_cast<const float4u*>(Eg + w.b0);
-  w.w1 = *reinterpret_cast<const float4u*>(Eg + w.b0 + 4);
-  return w;
-}
+// The edge window of a column (edge_window.hpp) depends on the column's colptr entry only -- not on the slab -- so the
+// caller asks for it ahead of the gather that reads it.
 
 // LDS rows in flight at a time in the gather: eight cost the second resident block its registers
 constexpr int kAgsRows = 4;
@@ -638,9 +576,6 @@ __device__ __forceinline__ float4 gather_row_dot(const EdgeWindow& win, const in
     const int a = valid ? k * T4 + j : dummy;
     pd[a] = FIRST ? d : pd[a] + d;
   };
-  const int b0 = win.b0;
-  const int4u &m0 = win.m0, &m1 = win.m1;
-  const float4u &w0 = win.w0, &w1 = win.w1;
   // in groups of kAgsRows rows, each closed by a scheduling barrier: nothing of what follows (the caller's next
   // requests, the long columns' loop) is scheduled beside a group's rows.  The register count hangs on this form:
   // 72 in k_agg_sddmm as written, 84 -- one resident block -- with the two groups written out one after the other
@@ -649,18 +584,15 @@ __device__ __forceinline__ float4 gather_row_dot(const EdgeWindow& win, const in
   for (int h = 0; h < 8; h += kAgsRows) {
     float4 r[kAgsRows];
 #pragma unroll
-    for (int k = 0; k < kAgsRows; ++k) r[k] = rows[(h + k < 4 ? m0.v[(h + k) & 3] : m1.v[(h + k) & 3]) * T4 + j];
+    for (int k = 0; k < kAgsRows; ++k) r[k] = rows[win.index(h + k) * T4 + j];
 #pragma unroll
-    for (int k = 0; k < kAgsRows; ++k)
-      edge(b0 + h + k, b0 + h + k >= e0 && b0 + h + k < e1, h + k < 4 ? w0.v[(h + k) & 3] : w1.v[(h + k) & 3], r[k]);
+    for (int k = 0; k < kAgsRows; ++k) edge(win.b0 + h + k, win.valid(h + k, e0, e1), win.coef(h + k), r[k]);
     __builtin_amdgcn_sched_barrier(0);
   }
-  for (int e = b0 + 8; e < e1; e += 4) {  // columns with more than 8 edges
-    const int b = min(e, nnz - 4);
-    const int4u m = *reinterpret_cast<const int4u*>(idx + b);
-    const float4u w = *reinterpret_cast<const float4u*>(Eg + b);
+  for (int e = win.b0 + 8; e < e1; e += 4) {  // columns with more than 8 edges
+    const EdgeTrip t = load_edge_trip(idx, Eg, e, nnz);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) edge(b + k, b + k >= e && b + k < e1, w.v[k], rows[m.v[k] * T4 + j]);
+    for (int k = 0; k < 4; ++k) edge(t.b + k, t.valid(k, e, e1), t.w.v[k], rows[t.m.v[k] * T4 + j]);
   }
   return acc;
 }
@@ -683,10 +615,10 @@ __global__ __launch_bounds__(kAgsBlock) void k_agg_sddmm(
   extern __shared__ float4 slab[];  // [CH][N][T4] of dv, then nnz * T4 floats of per-edge shares + a dummy per lane
   const int g = blockIdx.y;
   const int kc = blockIdx.x;
-  const int c0 = kc * CH;
-  const int ch = min(CH, Cu - c0);
   const int NT4 = N * T4;
-  const size_t base = ((size_t)g * Cu + c0) * NT4;
+  const ChannelChunk ck = channel_chunk(kc, CH, Cu, g, NT4);
+  const int c0 = ck.c0, ch = ck.ch;
+  const size_t base = ck.base;
   const int total = ch * NT4;
   float* pd = reinterpret_cast<float*>(slab + CH * NT4);
   const int dummy = nnz * T4 + threadIdx.x;
@@ -730,8 +662,7 @@ __global__ __launch_bounds__(kAgsBlock) void k_agg_sddmm(
   for (int k = 0; k < kAgsAhead; ++k) {
     const int s = tid + k * kAgsBlock;
     if (s >= NT4) break;
-    const int n = s / T4;
-    const int j = s - n * T4;
+    const auto [n, j] = slot_node<T4>(s);
     if (k > 0) {
       win = load_edge_window(idx, Eg, e0, nnz);
       own = nown;
@@ -747,8 +678,7 @@ __global__ __launch_bounds__(kAgsBlock) void k_agg_sddmm(
     e0 = f0, e1 = f1;
   }
   for (int s = tid + kAgsAhead * kAgsBlock; s < NT4; s += kAgsBlock) {  // slabs of more than kAgsAhead * 768 slots
-    const int n = s / T4;
-    const int j = s - n * T4;
+    const auto [n, j] = slot_node<T4>(s);
     const int e0 = ptr[n], e1 = ptr[n + 1];
     const EdgeWindow w = load_edge_window(idx, Eg, e0, nnz);
     du4[base + s] = gather_row_dot<T4, true>(w, idx, Eg, e0, e1, nnz, slab, j, u4[base + s], pd, dummy);
@@ -785,26 +715,14 @@ static int launch_agg_sddmm_t(const msgat_graph_t& gr, const float* dv, const fl
   const int T = 4 * T4;
   const int CH = slab_channels(N, T, Cu, kLdsBudget);
   const size_t lds = agg_sddmm_lds(N, T, Cu, gr.nnz);
-  {
-    static LdsGrant granted;
-    if (int st = grant_dynamic_lds(&k_agg_sddmm<T4>, lds, granted)) return st;
-  }
   const int nchunks = cdiv(Cu, CH);
-  hipLaunchKernelGGL(k_agg_sddmm<T4>, dim3(nchunks, G), dim3(kAgsBlock), lds, s, gr.colptr, gr.crow, (const float4*)dv,
-                     Ec, (const float4*)u, (float4*)du, dEp, Cu, N, gr.nnz, CH, nchunks, dvgs > 0 ? dvgs : Cu);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return launch_lds<k_agg_sddmm<T4>>(dim3(nchunks, G), dim3(kAgsBlock), lds, s, gr.colptr, gr.crow, (const float4*)dv, Ec,
+                                     (const float4*)u, (float4*)du, dEp, Cu, N, gr.nnz, CH, nchunks, dvgs > 0 ? dvgs : Cu);
 }
 
 int launch_agg_sddmm(const msgat_graph_t& gr, const float* dv, const float* Ec, const float* u, float* du, float* dEp,
                      int G, int Cu, int N, int T, hipStream_t s, int dvgs) {
-  switch (T) {
-    case 4: return launch_agg_sddmm_t<1>(gr, dv, Ec, u, du, dEp, G, Cu, N, s, dvgs);
-    case 8: return launch_agg_sddmm_t<2>(gr, dv, Ec, u, du, dEp, G, Cu, N, s, dvgs);
-    case 12: return launch_agg_sddmm_t<3>(gr, dv, Ec, u, du, dEp, G, Cu, N, s, dvgs);
-    case 16: return launch_agg_sddmm_t<4>(gr, dv, Ec, u, du, dEp, G, Cu, N, s, dvgs);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
+  return dispatch_T(T, [&](auto t) { return launch_agg_sddmm_t<decltype(t)::value / 4>(gr, dv, Ec, u, du, dEp, G, Cu, N, s, dvgs); });
 }
 
 // ---- SDDMM on the SELL layout: one 4-timestep column of u in LDS per pass -------------------------------------
@@ -821,13 +739,12 @@ __global__ __launch_bounds__(kAggBlock) void k_sddmm_sell(
   extern __shared__ float4 slab[];  // [N]
   const int g = blockIdx.y;
   const int kc = blockIdx.x;
-  const int c0 = kc * CH;
-  const int ch = min(CH, Cu - c0);
+  const ChannelChunk ck = channel_chunk(kc, CH, Cu, g, N * T4);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   float* out = dEp + ((size_t)g * nchunks + kc) * n_pos;
-  for (int pass = 0; pass < ch * T4; ++pass) {
-    const int c = pass / T4, j = pass - c * T4;
-    const size_t base = ((size_t)g * Cu + c0 + c) * N * T4;
+  for (int pass = 0; pass < ck.ch * T4; ++pass) {
+    const auto [c, j] = slot_node<T4>(pass);  // pass = (channel of the chunk, column)
+    const size_t base = ck.base + (size_t)c * N * T4;
     stage_column<T4>(slab, u4 + base, j, N);
     __syncthreads();
     for (int s = wave; s < n_slices; s += kAggBlock / 64) {
@@ -839,12 +756,8 @@ __global__ __launch_bounds__(kAggBlock) void k_sddmm_sell(
       float4* po4 = reinterpret_cast<float4*>(out + off) + lane;
       const float4 a = dv4[base + (size_t)max(row, 0) * T4 + j];  // lanes past N own padding only
       auto finish = [&](const SellTrip& x, int t) {  // .e carries the running partials of the trip's 4 edges
-        const int4 id = sell_unpack(x.id);
-        float4 o;
-        o.x = f4dot(a, slab[id.x], pass == 0 ? 0.f : x.e.x);
-        o.y = f4dot(a, slab[id.y], pass == 0 ? 0.f : x.e.y);
-        o.z = f4dot(a, slab[id.z], pass == 0 ? 0.f : x.e.z);
-        o.w = f4dot(a, slab[id.w], pass == 0 ? 0.f : x.e.w);
+        float4 o = pass == 0 ? f4zero() : x.e;
+        sell_dot(a, slab, x.id, o);
         po4[64 * t] = o;
       };
       SellTrip ta, tb;
@@ -879,10 +792,8 @@ __global__ __launch_bounds__(kAggBlock) void k_sddmm_sellreg(
     int n_pos, int n_slices, int Q) {
   extern __shared__ float4 slab[];  // [N]
   // XCD-aware map (see k_agg_sell): the Q blocks of a group sit in consecutive slots of XCD g % 8
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int q = slot % Q;
-  const int g = (slot / Q) * 8 + xcd;
-  if (g >= G) return;
+  int g, q;
+  if (!xcd_group_slot(Q, G, &g, &q)) return;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int W = q * (kAggBlock / 64) + wave;  // pair index
   const int sA = W, sB = n_slices - 1 - W;
@@ -918,7 +829,7 @@ __global__ __launch_bounds__(kAggBlock) void k_sddmm_sellreg(
   // CU (staging round trip, then ~770 conflicted ds_read_b128 per pass, one block per CU); reading a wave's dv rows
   // whole, once per channel, needs 16 more registers than 4 waves per SIMD leave (scratch: 5.3 ms).
   for (int pass = 0; pass < Cu * T4; ++pass) {
-    const int c = pass / T4, jr = pass - c * T4;
+    const auto [c, jr] = slot_node<T4>(pass);
     const int j = (jr + q) % T4;
     const size_t base = ((size_t)g * Cu + c) * N * T4;
     const float4 aA = dv4[base + (size_t)rowA * T4 + j];
@@ -930,11 +841,7 @@ __global__ __launch_bounds__(kAggBlock) void k_sddmm_sellreg(
       if (t < nt) {  // wave-uniform; LDS reads and FMAs only
         const bool inA = t < ntA;
         const float4 a = make_float4(inA ? aA.x : aB.x, inA ? aA.y : aB.y, inA ? aA.z : aB.z, inA ? aA.w : aB.w);
-        const int4 id = sell_unpack(ids[t]);
-        acc[t].x = f4dot(a, slab[id.x], acc[t].x);
-        acc[t].y = f4dot(a, slab[id.y], acc[t].y);
-        acc[t].z = f4dot(a, slab[id.z], acc[t].z);
-        acc[t].w = f4dot(a, slab[id.w], acc[t].w);
+        sell_dot(a, slab, ids[t], acc[t]);
       }
     }
     __syncthreads();
@@ -967,43 +874,27 @@ static int launch_sddmm_t(const msgat_graph_t& gr, const float* u, const float* 
                           int G, int Cu, int N, hipStream_t s) {
   const int T = 4 * T4;
   const int CH = slab_channels(N, T, Cu, kLdsBudget);
+  const float4 *u4 = (const float4*)u, *dv4 = (const float4*)dv;
   if (sell_usable(gr.sell_rows, gr.nnz, N, T)) {  // partials come out in SELL position order (k_edge_grad: pos)
     const msgat_sell_t& sl = gr.sell_rows;
     const int nch = sddmm_chunks(G, Cu, N, T, &sl);
     const int chj = cdiv(Cu, nch);
     const size_t lds = (size_t)N * sizeof(float4);
     if (sddmm_in_registers(sl)) {
-      {
-        static LdsGrant granted;
-        if (int st = grant_dynamic_lds(&k_sddmm_sellreg<T4>, lds, granted)) return st;
-      }
       const int Q = cdiv(sl.n_slices, 2 * (kAggBlock / 64));
-      hipLaunchKernelGGL(k_sddmm_sellreg<T4>, dim3((unsigned)cdiv(G, 8) * 8 * Q), dim3(kAggBlock), lds, s, sl.slice_off,
-                         sl.lane_row, sl.idx, (const float4*)u, (const float4*)dv, dEp, G, Cu, N, sl.n_pos, sl.n_slices, Q);
-      MSGAT_CHECK_LAUNCH();
-      return MSGAT_OK;
+      return launch_lds<k_sddmm_sellreg<T4>>(dim3(xcd_grid(G, Q)), dim3(kAggBlock), lds, s, sl.slice_off, sl.lane_row, sl.idx,
+                                             u4, dv4, dEp, G, Cu, N, sl.n_pos, sl.n_slices, Q);
     }
-    {
-      static LdsGrant granted;
-      if (int st = grant_dynamic_lds(&k_sddmm_sell<T4>, lds, granted)) return st;
-    }
-    hipLaunchKernelGGL(k_sddmm_sell<T4>, dim3(nch, G), dim3(kAggBlock), lds, s, sl.slice_off, sl.lane_row, sl.idx,
-                       (const float4*)u, (const float4*)dv, dEp, Cu, N, sl.n_pos, sl.n_slices, chj, nch);
-  } else if (CH >= 1) {
-    const size_t lds = (size_t)CH * N * T * sizeof(float);
-    {
-      static LdsGrant granted;
-      if (int st = grant_dynamic_lds(&k_sddmm<T4, true>, lds, granted)) return st;
-    }
-    const int nchunks = cdiv(Cu, CH);
-    dim3 grid(1, nchunks, G);
-    hipLaunchKernelGGL((k_sddmm<T4, true>), grid, dim3(kBlock), lds, s, gr.erow, gr.col,
-                       (const float4*)u, (const float4*)dv, dEp, Cu, N, gr.nnz, CH, nchunks);
-  } else {
-    dim3 grid(min(cdiv(gr.nnz, kBlock), 1024), 1, G);
-    hipLaunchKernelGGL((k_sddmm<T4, false>), grid, dim3(kBlock), 0, s, gr.erow, gr.col,
-                       (const float4*)u, (const float4*)dv, dEp, Cu, N, gr.nnz, Cu, 1);
+    return launch_lds<k_sddmm_sell<T4>>(dim3(nch, G), dim3(kAggBlock), lds, s, sl.slice_off, sl.lane_row, sl.idx, u4, dv4,
+                                        dEp, Cu, N, sl.n_pos, sl.n_slices, chj, nch);
   }
+  if (CH >= 1) {
+    const int nchunks = cdiv(Cu, CH);
+    return launch_lds<k_sddmm<T4, true>>(dim3(1, nchunks, G), dim3(kBlock), (size_t)CH * N * T * sizeof(float), s, gr.erow,
+                                         gr.col, u4, dv4, dEp, Cu, N, gr.nnz, CH, nchunks);
+  }
+  dim3 grid(min(cdiv(gr.nnz, kBlock), 1024), 1, G);
+  hipLaunchKernelGGL((k_sddmm<T4, false>), grid, dim3(kBlock), 0, s, gr.erow, gr.col, u4, dv4, dEp, Cu, N, gr.nnz, Cu, 1);
   MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
@@ -1011,13 +902,7 @@ static int launch_sddmm_t(const msgat_graph_t& gr, const float* u, const float* 
 int launch_sddmm(const msgat_graph_t& gr, const float* u, const float* dv, float* dEp, int G,
                  int Cu, int N, int T, hipStream_t s) {
   if (gr.nnz == 0) return MSGAT_OK;
-  switch (T) {
-    case 4: return launch_sddmm_t<1>(gr, u, dv, dEp, G, Cu, N, s);
-    case 8: return launch_sddmm_t<2>(gr, u, dv, dEp, G, Cu, N, s);
-    case 12: return launch_sddmm_t<3>(gr, u, dv, dEp, G, Cu, N, s);
-    case 16: return launch_sddmm_t<4>(gr, u, dv, dEp, G, Cu, N, s);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
+  return dispatch_T(T, [&](auto t) { return launch_sddmm_t<decltype(t)::value / 4>(gr, u, dv, dEp, G, Cu, N, s); });
 }
 
 }  // namespace msgat

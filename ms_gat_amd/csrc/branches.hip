@@ -111,13 +111,9 @@ int launch_tmix(const float* src, const float* A, int per_group, const float* bi
                 int K, int N, int T, int backward, int R, hipStream_t s, int src_gs) {
   const int Bg = G / R;
   if (src_gs <= 0 || !backward) src_gs = Co;
-  switch (T) {
-    case 4: return launch_tmix_t<4>(src, A, per_group, bias, dst, G, Co, K, N, backward, Bg, src_gs, s);
-    case 8: return launch_tmix_t<8>(src, A, per_group, bias, dst, G, Co, K, N, backward, Bg, src_gs, s);
-    case 12: return launch_tmix_t<12>(src, A, per_group, bias, dst, G, Co, K, N, backward, Bg, src_gs, s);
-    case 16: return launch_tmix_t<16>(src, A, per_group, bias, dst, G, Co, K, N, backward, Bg, src_gs, s);
-  }
-  return MSGAT_ERR_UNSUPPORTED;
+  return dispatch_T(T, [&](auto t) {
+    return launch_tmix_t<decltype(t)::value>(src, A, per_group, bias, dst, G, Co, K, N, backward, Bg, src_gs, s);
+  });
 }
 
 // ---- gradient of the time-mixing matrices -------------------------------------------------------------
@@ -184,14 +180,10 @@ int launch_tmix_dA(const float* dout, const float* y, float* dA, float* part, in
                    hipStream_t s, int dout_gs) {
   if (dout_gs <= 0) dout_gs = Co;
   dim3 grid(kTmixChunks, K, G);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_tmix_dA<4>, grid, dim3(kBlock), 0, s, dout, y, part, Co, K, N, dout_gs); break;
-    case 8: hipLaunchKernelGGL(k_tmix_dA<8>, grid, dim3(kBlock), 0, s, dout, y, part, Co, K, N, dout_gs); break;
-    case 12: hipLaunchKernelGGL(k_tmix_dA<12>, grid, dim3(kBlock), 0, s, dout, y, part, Co, K, N, dout_gs); break;
-    case 16: hipLaunchKernelGGL(k_tmix_dA<16>, grid, dim3(kBlock), 0, s, dout, y, part, Co, K, N, dout_gs); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_tmix_dA<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, y, part, Co, K, N, dout_gs);
+      }))
+    return st;
   return launch_reduce_groups(part, G * K, kTmixChunks, T * T, dA, s);
 }
 
@@ -298,14 +290,10 @@ int launch_node_pool(const float* x, const float* w, float* pooled, long long sl
                      hipStream_t s, int C, int gs) {
   dim3 grid((unsigned)slabs);
   const int spr = (int)(slabs / R);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_node_pool<4>, grid, dim3(kBlock), 0, s, x, w, pooled, N, spr, C, gs); break;
-    case 8: hipLaunchKernelGGL(k_node_pool<8>, grid, dim3(kBlock), 0, s, x, w, pooled, N, spr, C, gs); break;
-    case 12: hipLaunchKernelGGL(k_node_pool<12>, grid, dim3(kBlock), 0, s, x, w, pooled, N, spr, C, gs); break;
-    case 16: hipLaunchKernelGGL(k_node_pool<16>, grid, dim3(kBlock), 0, s, x, w, pooled, N, spr, C, gs); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_node_pool<decltype(t)::value>, grid, dim3(kBlock), 0, s, x, w, pooled, N, spr, C, gs);
+      }))
+    return st;
   return MSGAT_OK;
 }
 
@@ -313,14 +301,10 @@ int launch_node_pool_dx(const float* w, const float* dp, const float* add, float
                         int R, hipStream_t s) {
   dim3 grid((unsigned)slabs, cdiv(N, kBlock));
   const int spr = (int)(slabs / R);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_node_pool_dx<4>, grid, dim3(kBlock), 0, s, w, dp, add, dx, N, spr); break;
-    case 8: hipLaunchKernelGGL(k_node_pool_dx<8>, grid, dim3(kBlock), 0, s, w, dp, add, dx, N, spr); break;
-    case 12: hipLaunchKernelGGL(k_node_pool_dx<12>, grid, dim3(kBlock), 0, s, w, dp, add, dx, N, spr); break;
-    case 16: hipLaunchKernelGGL(k_node_pool_dx<16>, grid, dim3(kBlock), 0, s, w, dp, add, dx, N, spr); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_node_pool_dx<decltype(t)::value>, grid, dim3(kBlock), 0, s, w, dp, add, dx, N, spr);
+      }))
+    return st;
   return MSGAT_OK;
 }
 
@@ -330,14 +314,10 @@ int launch_node_pool_dw(const float* x, const float* dp, float* dw, float* part,
                         hipStream_t s) {
   const int nck = cdiv(C, kPoolCC);
   dim3 grid(cdiv(N, kBlock), nck, G);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_node_pool_dw<4>, grid, dim3(kBlock), 0, s, x, dp, part, C, N); break;
-    case 8: hipLaunchKernelGGL(k_node_pool_dw<8>, grid, dim3(kBlock), 0, s, x, dp, part, C, N); break;
-    case 12: hipLaunchKernelGGL(k_node_pool_dw<12>, grid, dim3(kBlock), 0, s, x, dp, part, C, N); break;
-    case 16: hipLaunchKernelGGL(k_node_pool_dw<16>, grid, dim3(kBlock), 0, s, x, dp, part, C, N); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_node_pool_dw<decltype(t)::value>, grid, dim3(kBlock), 0, s, x, dp, part, C, N);
+      }))
+    return st;
   return launch_reduce_groups(part, R, (G / R) * nck, N, dw, s);  // dw [R,N]: the groups of a relation are contiguous
 }
 
@@ -855,15 +835,6 @@ size_t head_fwd_partial_floats(int B, int C, int N, int To) {
 }
 size_t head_dw_partial_floats(int C, int T, int To, int R) { return (size_t)R * C * kHeadChunks * To * T; }
 
-#define MSGAT_T_SWITCH(T, CALL)                 \
-  switch (T) {                                  \
-    case 4: { constexpr int TT = 4; CALL; } break;   \
-    case 8: { constexpr int TT = 8; CALL; } break;   \
-    case 12: { constexpr int TT = 12; CALL; } break; \
-    case 16: { constexpr int TT = 16; CALL; } break; \
-    default: return MSGAT_ERR_UNSUPPORTED;      \
-  }
-
 // T_out in (16, 64]: OT = ceil(T_out / 16) output tiles; the launchers below keep their T_out <= 16 launches as they were
 // and hand the wider heads to these, which launch the same grids with the OT-tile kernels.
 #define MSGAT_OT_DISPATCH(To, FN, ...)                      \
@@ -885,11 +856,18 @@ static int launch_head_fwd_tiles(const float* x, const float* W, const float* bi
   MSGAT_CHECK_LAUNCH();
   dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
   if (ln) {
-    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd_tiles<TT, true, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, xn));
+    if (int st = launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_head_fwd_tiles<decltype(t)::value, true, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out,
+                             C, N, To, Bg, lnw, lnb, eps, xn);
+        }))
+      return st;
   } else {
-    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd_tiles<TT, false, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, nullptr));
+    if (int st = launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_head_fwd_tiles<decltype(t)::value, false, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out,
+                             C, N, To, Bg, lnw, lnb, eps, nullptr);
+        }))
+      return st;
   }
-  MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
 
@@ -898,8 +876,10 @@ static int launch_head_dx_tiles(const float* dout, const float* W, float* dx, in
                                 hipStream_t s) {
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_dx<TT, OT>), grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL((k_head_dx<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg);
+      }))
+    return st;
   return MSGAT_OK;
 }
 
@@ -909,9 +889,11 @@ static int launch_lnhead_bwd_tiles(const float* dout, const float* W, const floa
                                    float eps, int relu_mask, hipStream_t s) {
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);   // the grid of the T_out <= 16 form: the partials keep their size
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_lnhead_bwd<TT, OT>), grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To,
-                                       Bg, eps, relu_mask));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL((k_lnhead_bwd<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N,
+                           To, Bg, eps, relu_mask);
+      }))
+    return st;
   return launch_reduce_split(part, R, Bg * (int)grid.y * (int)grid.x, 2 * T, dlnw, T, dlnb, T, s);
 }
 
@@ -919,8 +901,11 @@ template <int OT>
 static int launch_head_dW_tiles(const float* dout, const float* x, float* dWc, float* part, int B, int C, int N, int T,
                                 int To, int R, hipStream_t s) {
   dim3 grid(kHeadChunks, C, R);
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_dW_tiles<TT, OT>), grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL((k_head_dW_tiles<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N,
+                           To);
+      }))
+    return st;
   return launch_reduce_groups(part, R * C, kHeadChunks, To * T, dWc, s);
 }
 
@@ -935,11 +920,18 @@ int launch_head_fwd(const float* x, const float* W, const float* bias, float* ou
   MSGAT_CHECK_LAUNCH();
   dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
   if (ln) {
-    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd<TT, true>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, xn));
+    if (int st = launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_head_fwd<decltype(t)::value, true>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To,
+                             Bg, lnw, lnb, eps, xn);
+        }))
+      return st;
   } else {
-    MSGAT_T_SWITCH(T, hipLaunchKernelGGL((k_head_fwd<TT, false>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To, Bg, lnw, lnb, eps, nullptr));
+    if (int st = launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_head_fwd<decltype(t)::value, false>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To,
+                             Bg, lnw, lnb, eps, nullptr);
+        }))
+      return st;
   }
-  MSGAT_CHECK_LAUNCH();
   return MSGAT_OK;
 }
 
@@ -948,8 +940,10 @@ int launch_head_dx(const float* dout, const float* W, float* dx, int B, int C, i
   if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dx_tiles, dout, W, dx, B, C, N, T, To, R, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_head_dx<TT>, grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_head_dx<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg);
+      }))
+    return st;
   return MSGAT_OK;
 }
 
@@ -965,9 +959,11 @@ int launch_lnhead_bwd(const float* dout, const float* W, const float* x, const f
     MSGAT_OT_DISPATCH(To, launch_lnhead_bwd_tiles, dout, W, x, lnw, dx, dlnw, dlnb, part, B, C, N, T, To, R, eps, relu_mask, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_lnhead_bwd<TT>, grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To, Bg,
-                                       eps, relu_mask));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_lnhead_bwd<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To,
+                           Bg, eps, relu_mask);
+      }))
+    return st;
   // a relation's blocks are contiguous (b-major): J = Bg * channel chunks * node blocks partials of 2T columns each
   return launch_reduce_split(part, R, Bg * (int)grid.y * (int)grid.x, 2 * T, dlnw, T, dlnb, T, s);
 }
@@ -977,8 +973,10 @@ int launch_head_dW(const float* dout, const float* x, float* dWc, float* part, i
                    int R, hipStream_t s) {
   if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dW_tiles, dout, x, dWc, part, B, C, N, T, To, R, s);
   dim3 grid(kHeadChunks, C, R);
-  MSGAT_T_SWITCH(T, hipLaunchKernelGGL(k_head_dW<TT>, grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To));
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_head_dW<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To);
+      }))
+    return st;
   return launch_reduce_groups(part, R * C, kHeadChunks, To * T, dWc, s);   // dWc [R,C,To,T]
 }
 

@@ -99,6 +99,36 @@ inline int grant_dynamic_lds(K kernel, size_t lds, LdsGrant& granted) {
   if (slot >= 0) granted.bytes[slot].store((int)lds, std::memory_order_release);
   return MSGAT_OK;
 }
+#if defined(__HIPCC__)
+// A launch of kernel K with `lds` bytes of dynamic LDS: the grant, the launch and the launch check, in that order, the
+// first failure returned.  The record is the instantiation's own static -- the ceiling is an attribute of the kernel
+// function, so one record per kernel is the right key.
+template <auto K, typename... Args>
+inline int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static LdsGrant granted;
+  if (int st = grant_dynamic_lds(K, lds, granted)) return st;
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+  MSGAT_CHECK_LAUNCH();
+  return MSGAT_OK;
+}
+#endif
+
+// XCD-aware one-dimensional grids.  Workgroups are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8), each
+// with its own 4 MB L2.  The `per_group` blocks of group g take consecutive slots of XCD g % 8, so they run side by
+// side and share that L2 (the aggregate's column blocks of a slab, the SDDMM's slice blocks of a group, the z-blocks of a
+// contraction run).  The grid is padded to a multiple of 8 groups.
+inline unsigned xcd_grid(int G, int per_group) { return (unsigned)cdiv(G, 8) * 8 * per_group; }
+#if defined(__HIPCC__)
+// this block's group and its slot among the group's blocks; false: the block is padding and returns at once.
+// cp_block (contract.hip) is the same map with a run for a group and keeps its own three lines: through this helper
+// the prologue of every contraction kernel compiled to other code, and those kernels are the hot path's.
+__device__ __forceinline__ bool xcd_group_slot(int per_group, int G, int* g, int* slot) {
+  const int xcd = blockIdx.x & 7, s = blockIdx.x >> 3;
+  *slot = s % per_group;
+  *g = (s / per_group) * 8 + xcd;
+  return *g < G;
+}
+#endif
 
 #ifdef MSGAT_LAB
 inline int lab_env(const char* name, int dflt) {   // lab builds only: a launch parameter from the environment
@@ -128,6 +158,15 @@ template <int LO, int HI, typename F>
 inline int dispatch_range(int v, F&& f) {
   if constexpr (LO > HI) return MSGAT_ERR_UNSUPPORTED;
   else return v == LO ? f(std::integral_constant<int, LO>{}) : dispatch_range<LO + 1, HI>(v, f);
+}
+// The common case, one launch of a kernel instantiated on T: f(t) launches, the launch check follows
+template <typename F>
+inline int launch_on_T(int T, F&& f) {
+  return dispatch_T(T, [&](auto t) -> int {
+    f(t);
+    MSGAT_CHECK_LAUNCH();
+    return MSGAT_OK;
+  });
 }
 inline bool t_supported(int T) {
   return dispatch_T(T, [](auto) -> int { return MSGAT_OK; }) == MSGAT_OK;

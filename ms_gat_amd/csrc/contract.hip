@@ -51,7 +51,7 @@ constexpr int kTile = 32 * kCpWaves;   // positions per staged tile (default): 3
 // False: the grid is padded to a multiple of 8 runs and this block is padding -- it returns at once and writes nothing.
 __device__ __forceinline__ bool cp_block(int nz, int nblk, int R, int& bx, int& r, int& zb) {
   if (nz > 1) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;   // the map of xcd_group_slot (common.hpp: why it is written out)
     zb = slot % nz;
     const int k = (slot / nz) * 8 + xcd;
     r = k / nblk;
@@ -689,7 +689,7 @@ static CpLeaf cp_leaf(const CpArgs& a, int Ca, int MA, int NB, int per_cu = 1) {
   // runs per relation
   l.nblk = nz > 1 ? min(a.nblk_max, max(1, per_cu * a.nblk_max / nz)) : a.nblk_max;
   *a.nblk_used = l.nblk;
-  l.grid = nz > 1 ? dim3((unsigned)cdiv(l.nblk * a.R, 8) * 8 * nz) : dim3(l.nblk, a.R, 1);
+  l.grid = nz > 1 ? dim3(xcd_grid(l.nblk * a.R, nz)) : dim3(l.nblk, a.R, 1);
   return l;
 }
 // true: the form query is running -- the kernel's name and z-block cut are written and nothing must be launched
@@ -712,12 +712,8 @@ static int launch_chanpair_t(const CpArgs& a, TimeShift ts) {
   if (cp_probed(l, "k_chanpair_mfma<%d,%d,%s,%d%s>", MA, NB, TWO ? "true" : "false", TILE, ts.d ? ",shift" : "")) return MSGAT_OK;
   auto launch = [&](auto shift) -> int {
     constexpr bool SHIFT = decltype(shift)::value;
-    static LdsGrant granted;
-    if (int st = grant_dynamic_lds(&k_chanpair_mfma<MA, NB, TWO, TILE, SHIFT>, lds, granted)) return st;
-    hipLaunchKernelGGL((k_chanpair_mfma<MA, NB, TWO, TILE, SHIFT>), l.grid, dim3(kCpBlock), lds, a.s, a.A, a.B, a.part, a.Cb,
-                       a.P, a.Bg, l.nzb, a.b_ones, l.nza, l.nblk, a.R, ts);
-    MSGAT_CHECK_LAUNCH();
-    return MSGAT_OK;
+    return launch_lds<k_chanpair_mfma<MA, NB, TWO, TILE, SHIFT>>(l.grid, dim3(kCpBlock), lds, a.s, a.A, a.B, a.part, a.Cb, a.P,
+                                                                 a.Bg, l.nzb, a.b_ones, l.nza, l.nblk, a.R, ts);
   };
   return ts.d ? launch(std::true_type{}) : launch(std::false_type{});
 }
@@ -741,12 +737,8 @@ static int launch_chanpair_glds_t(const CpArgs& a, ChanMix mix = ChanMix()) {
   const size_t lds = chanpair_glds_lds<MA, NB, TILE, NBUF>(Ca, a.Cb);
   if (lds > (size_t)kLdsMax || lds < (size_t)(MA * NB < 8 ? MA * NB : 8) * kCpWaves * 1024) return MSGAT_ERR_UNSUPPORTED;
   if (cp_probed(l, "k_chanpair_glds<%d,%d,%d,%d,%d>", MA, NB, TILE, NBUF, MODE)) return MSGAT_OK;
-  static LdsGrant granted;
-  if (int st = grant_dynamic_lds(&k_chanpair_glds<MA, NB, TILE, NBUF, MODE>, lds, granted)) return st;
-  hipLaunchKernelGGL((k_chanpair_glds<MA, NB, TILE, NBUF, MODE>), l.grid, dim3(kCpBlock), lds, a.s, a.A, a.B, a.part, a.Cb,
-                     a.P, a.Bg, l.nzb, a.b_ones, l.nza, l.nblk, a.R, mix);
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return launch_lds<k_chanpair_glds<MA, NB, TILE, NBUF, MODE>>(l.grid, dim3(kCpBlock), lds, a.s, a.A, a.B, a.part, a.Cb, a.P,
+                                                               a.Bg, l.nzb, a.b_ones, l.nza, l.nblk, a.R, mix);
 }
 
 // ---- which LDS-DMA form for which channel block -----------------------------------------------------------------

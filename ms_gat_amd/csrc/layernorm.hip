@@ -245,25 +245,17 @@ int launch_layernorm_fwd(const float* x, const float* w, const float* b, float* 
   if (pool_w != nullptr && (pool_part == nullptr || pooled == nullptr || N < kWave || rows % N != 0 || rows > 0x7fffffffLL))
     return MSGAT_ERR_SHAPE;
   const int nb = ln_blocks(rows);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_ln_fwd<4>, dim3(nb, R), dim3(kBlock), 0, s, x, w, b, y, rows, eps, pool_w, pool_part, N); break;
-    case 8: hipLaunchKernelGGL(k_ln_fwd<8>, dim3(nb, R), dim3(kBlock), 0, s, x, w, b, y, rows, eps, pool_w, pool_part, N); break;
-    case 12: hipLaunchKernelGGL(k_ln_fwd<12>, dim3(nb, R), dim3(kBlock), 0, s, x, w, b, y, rows, eps, pool_w, pool_part, N); break;
-    case 16: hipLaunchKernelGGL(k_ln_fwd<16>, dim3(nb, R), dim3(kBlock), 0, s, x, w, b, y, rows, eps, pool_w, pool_part, N); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
-  if (pool_w != nullptr) {
-    const dim3 grid(cdiv((int)(rows / N) * T, kBlock), R);
-    switch (T) {
-      case 4: hipLaunchKernelGGL(k_pool_trips<4>, grid, dim3(kBlock), 0, s, pool_part, pooled, rows, N); break;
-      case 8: hipLaunchKernelGGL(k_pool_trips<8>, grid, dim3(kBlock), 0, s, pool_part, pooled, rows, N); break;
-      case 12: hipLaunchKernelGGL(k_pool_trips<12>, grid, dim3(kBlock), 0, s, pool_part, pooled, rows, N); break;
-      default: hipLaunchKernelGGL(k_pool_trips<16>, grid, dim3(kBlock), 0, s, pool_part, pooled, rows, N); break;
-    }
+  return dispatch_T(T, [&](auto t) -> int {   // one dispatch around both launches: the pooling pass never sees another T
+    constexpr int TT = decltype(t)::value;
+    hipLaunchKernelGGL(k_ln_fwd<TT>, dim3(nb, R), dim3(kBlock), 0, s, x, w, b, y, rows, eps, pool_w, pool_part, N);
     MSGAT_CHECK_LAUNCH();
-  }
-  return MSGAT_OK;
+    if (pool_w != nullptr) {
+      const dim3 grid(cdiv((int)(rows / N) * TT, kBlock), R);
+      hipLaunchKernelGGL(k_pool_trips<TT>, grid, dim3(kBlock), 0, s, pool_part, pooled, rows, N);
+      MSGAT_CHECK_LAUNCH();
+    }
+    return MSGAT_OK;
+  });
 }
 
 int launch_layernorm_bwd(const float* x, const float* w, const float* dy, const float* add, float* dx, float* dw,
@@ -272,14 +264,11 @@ int launch_layernorm_bwd(const float* x, const float* w, const float* dy, const 
   rows /= R;  // per relation
   if (pool_w != nullptr && (dpooled == nullptr || N <= 0 || rows % N != 0 || rows > 0x7fffffffLL)) return MSGAT_ERR_SHAPE;
   const int nb = ln_blocks(rows);
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_ln_bwd<4>, dim3(nb, R), dim3(kBlock), 0, s, x, w, dy, add, dx, part, rows, eps, relu_mask, pool_w, dpooled, N, lnb, dpw_rows); break;
-    case 8: hipLaunchKernelGGL(k_ln_bwd<8>, dim3(nb, R), dim3(kBlock), 0, s, x, w, dy, add, dx, part, rows, eps, relu_mask, pool_w, dpooled, N, lnb, dpw_rows); break;
-    case 12: hipLaunchKernelGGL(k_ln_bwd<12>, dim3(nb, R), dim3(kBlock), 0, s, x, w, dy, add, dx, part, rows, eps, relu_mask, pool_w, dpooled, N, lnb, dpw_rows); break;
-    case 16: hipLaunchKernelGGL(k_ln_bwd<16>, dim3(nb, R), dim3(kBlock), 0, s, x, w, dy, add, dx, part, rows, eps, relu_mask, pool_w, dpooled, N, lnb, dpw_rows); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_ln_bwd<decltype(t)::value>, dim3(nb, R), dim3(kBlock), 0, s, x, w, dy, add, dx, part, rows, eps,
+                           relu_mask, pool_w, dpooled, N, lnb, dpw_rows);
+      }))
+    return st;
   ReduceJobs jobs{};   // both sums in one launch
   if (int st = launch_reduce_split(part, R, nb, 2 * T, dw, T, db, T, s, &jobs)) return st;
   if (pool_w != nullptr && dpw_rows != nullptr && dpw != nullptr)   // dpool_w [R,N]: the column sums of a relation's [rows / N, N] terms

@@ -297,35 +297,21 @@ int launch_bwd_rows(const msgat_graph_t& gr, const float* dEp, int nchunks, cons
     const hipError_t e = hipMemcpyAsync(gE, dEx, sizeof(float) * (size_t)G * gr.nnz, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return MSGAT_ERR_HIP_BASE - (int)e;
   }
-#define MSGAT_ROWS(TT, DC)                                                                                          \
-  hipLaunchKernelGGL((k_bwd_rows<TT, DC>), grid, dim3(kRowBlock), 0, s, gr.rowptr, gr.col, E, u, dv, q, pq, Wg, gE,  \
-                     delta, dkW, dq, dwg_part, Bg, N, gr.nnz, nblk)
   // the direct form takes the extra edge gradient through gE (k_bwd_rows<T, -DC>); with DC = 0 it is inside gE already
-#define MSGAT_ROWS_DC(TT, DC)  \
-  if (dEx != nullptr)          \
-    MSGAT_ROWS(TT, -DC);       \
-  else                         \
-    MSGAT_ROWS(TT, DC)
-#define MSGAT_ROWS_T(TT)                        \
-  switch (direct_c) {                           \
-    case 0: MSGAT_ROWS(TT, 0); break;           \
-    case 1: MSGAT_ROWS_DC(TT, 1); break;        \
-    case 2: MSGAT_ROWS_DC(TT, 2); break;        \
-    case 3: MSGAT_ROWS_DC(TT, 3); break;        \
-    case 4: MSGAT_ROWS_DC(TT, 4); break;        \
-    default: return MSGAT_ERR_UNSUPPORTED;      \
-  }
-  switch (T) {
-    case 4: MSGAT_ROWS_T(4); break;
-    case 8: MSGAT_ROWS_T(8); break;
-    case 12: MSGAT_ROWS_T(12); break;
-    case 16: MSGAT_ROWS_T(16); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_ROWS_T
-#undef MSGAT_ROWS_DC
-#undef MSGAT_ROWS
-  MSGAT_CHECK_LAUNCH();
+  const int st = dispatch_T(T, [&](auto t) {
+    return dispatch_range<0, 4>(direct_c, [&](auto dc) -> int {
+      constexpr int TT = decltype(t)::value, DC = decltype(dc)::value;
+      auto rows = [&](auto k) {
+        hipLaunchKernelGGL(k, grid, dim3(kRowBlock), 0, s, gr.rowptr, gr.col, E, u, dv, q, pq, Wg, gE, delta, dkW, dq, dwg_part,
+                           Bg, N, gr.nnz, nblk);
+      };
+      if (dEx != nullptr) rows(k_bwd_rows<TT, -DC>);
+      else rows(k_bwd_rows<TT, DC>);
+      MSGAT_CHECK_LAUNCH();
+      return MSGAT_OK;
+    });
+  });
+  if (st != MSGAT_OK) return st;
   return launch_reduce_groups_defer(dwg_part, G / Bg, Bg * nblk, T * T, dWg, s, defer);
 }
 

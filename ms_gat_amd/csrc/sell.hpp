@@ -34,6 +34,14 @@ __device__ __forceinline__ void sell_gather(const SellTrip& x, const float4* sla
   f4fma(x.e.z, slab[id.z], acc);
   f4fma(x.e.w, slab[id.w], acc);
 }
+// the SDDMM's trip: the running sum of each of the 4 edges (packed indices `id`) takes <a, slab[neighbour]>
+__device__ __forceinline__ void sell_dot(const float4& a, const float4* slab, uint2 id, float4& acc) {
+  const int4 i = sell_unpack(id);
+  acc.x = f4dot(a, slab[i.x], acc.x);
+  acc.y = f4dot(a, slab[i.y], acc.y);
+  acc.z = f4dot(a, slab[i.z], acc.z);
+  acc.w = f4dot(a, slab[i.w], acc.w);
+}
 
 // stage column j of the [N][T4] slab at `src`: NB loads in flight per lane; lanes past N re-write entry N-1 with
 // the value they re-read from it (no branch, so the loads stay in flight together)

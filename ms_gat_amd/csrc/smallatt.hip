@@ -172,33 +172,13 @@ bool chanatt_fused(int C, int cb, int T) {
 
 size_t chanatt_partial_floats(int G, int C, int cb, int T) { return (size_t)G * ((size_t)T * T + (size_t)cb * C); }
 
-// one grant record per kernel instantiation (the template argument makes the static distinct)
-template <typename K, K kernel>
-static int raise_lds(size_t lds) {
-  static LdsGrant granted;
-  return grant_dynamic_lds(kernel, lds, granted);
-}
-
 int launch_chanatt_fwd(const float* pooled, const float* Wc, const float* conv, float* att, float* Mc, int G, int R,
                        int C, int cb, int T, hipStream_t s) {
   const size_t lds = chanatt_fwd_lds(C, cb, T);
   if (lds > (size_t)kLdsMax - 1024) return MSGAT_ERR_UNSUPPORTED;
-#define MSGAT_CA_FWD(TT)                                                                                      \
-  {                                                                                                           \
-    int st = raise_lds<decltype(&k_chanatt_fwd<TT>), &k_chanatt_fwd<TT>>(lds);                                                              \
-    if (st) return st;                                                                                        \
-    hipLaunchKernelGGL(k_chanatt_fwd<TT>, dim3(G), dim3(kCaBlock), lds, s, pooled, Wc, conv, att, Mc, G / R, C, cb); \
-  }
-  switch (T) {
-    case 4: MSGAT_CA_FWD(4) break;
-    case 8: MSGAT_CA_FWD(8) break;
-    case 12: MSGAT_CA_FWD(12) break;
-    case 16: MSGAT_CA_FWD(16) break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_CA_FWD
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return dispatch_T(T, [&](auto t) {
+    return launch_lds<k_chanatt_fwd<decltype(t)::value>>(dim3(G), dim3(kCaBlock), lds, s, pooled, Wc, conv, att, Mc, G / R, C, cb);
+  });
 }
 
 int launch_chanatt_bwd(const float* dMc, const float* att, const float* pooled, const float* Wc, const float* conv,
@@ -208,22 +188,11 @@ int launch_chanatt_bwd(const float* dMc, const float* att, const float* pooled, 
   if (lds > (size_t)kLdsMax - 1024) return MSGAT_ERR_UNSUPPORTED;
   float* pWc = part;                         // [G,T,T]
   float* pconv = part + (size_t)G * T * T;   // [G,cb,C]
-#define MSGAT_CA_BWD(TT)                                                                                       \
-  {                                                                                                            \
-    int st = raise_lds<decltype(&k_chanatt_bwd<TT>), &k_chanatt_bwd<TT>>(lds);                                                               \
-    if (st) return st;                                                                                         \
-    hipLaunchKernelGGL(k_chanatt_bwd<TT>, dim3(G), dim3(kCaBlock), lds, s, dMc, att, pooled, Wc, conv, dpooled, pWc, \
-                       pconv, G / R, C, cb);                                                                   \
-  }
-  switch (T) {
-    case 4: MSGAT_CA_BWD(4) break;
-    case 8: MSGAT_CA_BWD(8) break;
-    case 12: MSGAT_CA_BWD(12) break;
-    case 16: MSGAT_CA_BWD(16) break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-#undef MSGAT_CA_BWD
-  MSGAT_CHECK_LAUNCH();
+  if (int st = dispatch_T(T, [&](auto t) {
+        return launch_lds<k_chanatt_bwd<decltype(t)::value>>(dim3(G), dim3(kCaBlock), lds, s, dMc, att, pooled, Wc, conv, dpooled,
+                                                             pWc, pconv, G / R, C, cb);
+      }))
+    return st;
   ReduceJobs jobs{};   // both sums in one launch
   if (int st = launch_reduce_groups_defer(pWc, R, G / R, T * T, dWc, s, &jobs)) return st;
   if (int st = launch_reduce_groups_defer(pconv, R, G / R, cb * C, dconv, s, &jobs)) return st;
@@ -433,15 +402,10 @@ size_t tempatt_partial_floats(int G, int K, int N) { return (size_t)2 * G * K * 
 int launch_tempatt_fwd(const float* pooled, const float* Wt1, const float* Wt2, float* lr, float* att, float* taps,
                        int G, int R, int N, int K, int T, int dil, hipStream_t s) {
   if (K < 1 || K > kTaRankMax || 2 * T * K > kSaBlock) return MSGAT_ERR_UNSUPPORTED;
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_tempatt_fwd<4>, dim3(G), dim3(kSaBlock), 0, s, pooled, Wt1, Wt2, lr, att, taps, G / R, N, K, dil); break;
-    case 8: hipLaunchKernelGGL(k_tempatt_fwd<8>, dim3(G), dim3(kSaBlock), 0, s, pooled, Wt1, Wt2, lr, att, taps, G / R, N, K, dil); break;
-    case 12: hipLaunchKernelGGL(k_tempatt_fwd<12>, dim3(G), dim3(kSaBlock), 0, s, pooled, Wt1, Wt2, lr, att, taps, G / R, N, K, dil); break;
-    case 16: hipLaunchKernelGGL(k_tempatt_fwd<16>, dim3(G), dim3(kSaBlock), 0, s, pooled, Wt1, Wt2, lr, att, taps, G / R, N, K, dil); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
-  return MSGAT_OK;
+  return launch_on_T(T, [&](auto t) {
+    hipLaunchKernelGGL(k_tempatt_fwd<decltype(t)::value>, dim3(G), dim3(kSaBlock), 0, s, pooled, Wt1, Wt2, lr, att, taps, G / R, N, K,
+                       dil);
+  });
 }
 
 int launch_tempatt_bwd(const float* dtaps, const float* att, const float* lr, const float* pooled, const float* Wt1,
@@ -450,14 +414,11 @@ int launch_tempatt_bwd(const float* dtaps, const float* att, const float* lr, co
   if (K < 1 || K > kTaRankMax || 2 * T * K > kSaBlock) return MSGAT_ERR_UNSUPPORTED;
   float* p1 = part;
   float* p2 = part + (size_t)G * K * N;
-  switch (T) {
-    case 4: hipLaunchKernelGGL(k_tempatt_bwd<4>, dim3(G), dim3(kTbBlock), 0, s, dtaps, att, lr, pooled, Wt1, Wt2, dpooled, p1, p2, G / R, N, K, dil); break;
-    case 8: hipLaunchKernelGGL(k_tempatt_bwd<8>, dim3(G), dim3(kTbBlock), 0, s, dtaps, att, lr, pooled, Wt1, Wt2, dpooled, p1, p2, G / R, N, K, dil); break;
-    case 12: hipLaunchKernelGGL(k_tempatt_bwd<12>, dim3(G), dim3(kTbBlock), 0, s, dtaps, att, lr, pooled, Wt1, Wt2, dpooled, p1, p2, G / R, N, K, dil); break;
-    case 16: hipLaunchKernelGGL(k_tempatt_bwd<16>, dim3(G), dim3(kTbBlock), 0, s, dtaps, att, lr, pooled, Wt1, Wt2, dpooled, p1, p2, G / R, N, K, dil); break;
-    default: return MSGAT_ERR_UNSUPPORTED;
-  }
-  MSGAT_CHECK_LAUNCH();
+  if (int st = launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL(k_tempatt_bwd<decltype(t)::value>, dim3(G), dim3(kTbBlock), 0, s, dtaps, att, lr, pooled, Wt1, Wt2, dpooled,
+                           p1, p2, G / R, N, K, dil);
+      }))
+    return st;
   ReduceJobs jobs{};   // both sums in one launch
   if (int st = launch_reduce_groups_defer(p1, R, G / R, K * N, dWt1, s, &jobs)) return st;
   if (int st = launch_reduce_groups_defer(p2, R, G / R, K * N, dWt2, s, &jobs)) return st;

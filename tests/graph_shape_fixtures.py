@@ -39,6 +39,7 @@ HUB_ZERO_COLS = (5, 63, 64, 129)
 LONELY_ROW = 33
 EDGE70 = (3, 41)            # the one stored entry of `edge70`: row, column
 CROSS_ROW, CROSS_COL = 9, 30
+LARGE_N, LARGE_ROW, LARGE_COL = 2545, 7, 11    # 2545 * 16 * 4 B > 160 KiB - 1 KiB: the first N without a slab at T = 16
 
 
 def _rng(name, seed, salt=0):
@@ -133,6 +134,23 @@ def _cross(n):
     return build
 
 
+def _large(few):
+    """N = LARGE_N, where no [N,16] slab fits the LDS but one 4-timestep column does: a row and a column of more than 8
+    entries, a chain through the first 200 nodes, and nothing in the other rows; `few`: five stored entries in all"""
+    def build(rng):
+        n = LARGE_N
+        mask = np.zeros((n, n), dtype=bool)
+        if few:
+            mask[[3, 3, 100, n - 1, n - 1], [41, 2000, 3, 0, n - 1]] = True
+            return mask
+        i = np.arange(200)
+        mask[i, i + 1] = True
+        mask[LARGE_ROW, rng.choice(n, size=20, replace=False)] = True
+        mask[rng.choice(n, size=15, replace=False), LARGE_COL] = True
+        return mask
+    return build
+
+
 def _values(mask, rng):
     return np.where(mask, rng.uniform(0.25, 1.5, size=mask.shape), 0.0).astype(np.float32)
 
@@ -158,6 +176,8 @@ def _base(name, seed):
         mask = _edge70(rng)
     elif name in ("cross64", "cross65"):
         mask = _cross(int(name[5:]))(rng)
+    elif name in ("wide2545", "few2545"):
+        mask = _large(name == "few2545")(rng)
     else:
         raise KeyError(name)
     return mask, _values(mask, _rng(name, seed, 1))
@@ -200,6 +220,8 @@ LAYER = ("ladder64", "ladder64_signed", "trips12", "trips13", "pair12", "pair13"
 ONEROW = ("onerow1024", "onerow1025", "onerow1024_T", "onerow1025_T")
 SMALL = ("edge70", "cross64", "cross65")
 NAMES = LAYER + ONEROW + SMALL
+# beyond the LDS slab (their own GPU tests; what they are is asserted there, on the host, before the kernels run)
+LARGE = ("wide2545", "few2545")
 
 # What each fixture is built to be.  n, the largest row / column degree, the number of rows / columns without an entry,
 # and per side of the SELL layout (rows form, columns form) `pair_trips` and the number of slices of width 0; None where

@@ -106,6 +106,71 @@ def test_sell_kernels_at_the_other_timestep_counts(name, T, mode):
     _assert_empty_rows_are_exact_zeros(name, got["z"])
 
 
+@pytest.mark.parametrize("mode", ["AGG_FIRST", "PROJ_FIRST"])
+def test_csr_kernels_at_eight_timesteps(mode):
+    """`hub130` with sell="never" at T = 8: the CSR / CSC forms (the ring's neighbours k_agg_lds and k_agg_proj, the fused
+    k_agg_sddmm in PROJ_FIRST) at a timestep count that the other cases reach on the SELL forms only."""
+    C, Co = F.MODES[mode]
+    got = _got("hub130", C, Co, "never", T=8)
+    assert_close(got, _want("hub130", C, Co, T=8), what=f"graph shapes hub130 {mode} T=8 CSR")
+    _assert_empty_rows_are_exact_zeros("hub130", got["z"])
+
+
+# ---- a': the CSR forms of graphs whose [N,T] slab does not fit the LDS ------------------------------------------------------
+
+_LDS_MAX = 160 * 1024       # kLdsMax (common.hpp); a kernel's dynamic LDS may take all of it but 1 KiB
+_DIRECT_MAX = 4             # bwd_rows_direct_max_channels() (scores.hip): up to here the row pass forms the edge gradient itself
+
+
+def _oracle_f64_gpu(x, adj, Wg, alpha, W, dz):
+    """oracle/dense_torch.py in float64 with autograd on the GPU (the numpy oracle's dense [N,N] passes take minutes here)"""
+    from oracle import dense_torch
+    f = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).to(DEV)  # noqa: E731
+    R = Wg.shape[0]
+    Bg = x.shape[0] // R
+    outs = dict(z=[], dx=[], dWg=[], dalpha=[], dW=[])
+    for r in range(R):
+        xt, Wgt, at, Wt = (f(v).requires_grad_(True) for v in (x[r * Bg:(r + 1) * Bg], Wg[r], alpha[r], W[r]))
+        z = dense_torch.gacn_dense(xt, f(adj), Wgt, at, Wt)
+        z.backward(f(dz[r * Bg:(r + 1) * Bg]))
+        for k, v in (("z", z.detach()), ("dx", xt.grad), ("dWg", Wgt.grad), ("dalpha", at.grad), ("dW", Wt.grad)):
+            outs[k].append(v.cpu().numpy())
+    return dict(z=np.concatenate(outs["z"]), dx=np.concatenate(outs["dx"]), dWg=np.stack(outs["dWg"]),
+                dalpha=np.stack(outs["dalpha"]), dW=np.stack(outs["dW"]))
+
+
+@pytest.mark.parametrize("name,C,Co,form", [("wide2545", 6, 3, "k_agg_cols"), ("few2545", 6, 3, "k_agg_glb"),
+                                            ("wide2545", 10, 5, "k_sddmm<T4, false>")],
+                         ids=["agg_cols", "agg_glb", "sddmm_no_slab"])
+def test_csr_forms_without_a_slab(name, C, Co, form):
+    """PROJ_FIRST at T = 16, R = 1, Bg = 2, sell="never", N = 2545: the smallest N whose [N,16] slab does not fit the LDS
+    (launch_aggregate_t, launch_sddmm_t: slab_channels() == 0), so that the aggregate -- forward on the CSR, backward on the
+    CSC, the backward cannot fuse -- runs one 4-timestep column at a time (k_agg_cols: nnz >= 8, a row of 20 and a column of
+    15 entries against the 8-slot window) or, on the graph of five entries, gathers from memory with the scalar walk of
+    gather_row (k_agg_glb).  On Cu = 3 channels the row pass forms the edge gradient itself (direct_c) and no SDDMM is launched
+    at all; the third case has Cu = 5 and reaches k_sddmm<T4, false>, the SDDMM without a slab.  The conditions of each form
+    are asserted here as the launchers state them, so a threshold that moves fails the test.  Against float64; two runs
+    with equal bits (_got); rows without an entry exact zeros."""
+    import ms_gat_amd
+    T, Bg, R = 16, 2, 1
+    adj = F.adjacency(name)
+    N = adj.shape[0]
+    graph = ms_gat_amd.SparseGraph(torch.from_numpy(adj), sell="never")
+    row_deg, col_deg = F.degrees(name)
+    assert not graph.has_sell
+    assert N * T * 4 > _LDS_MAX - 1024 and N * 16 <= _LDS_MAX - 1024      # no slab (nor a fused backward); a column fits
+    if form == "k_agg_glb":
+        assert graph.nnz < 8
+    else:
+        assert graph.nnz >= 8 and row_deg.max() > 8 and col_deg.max() > 8
+    assert (row_deg == 0).any()
+    assert (Co > _DIRECT_MAX) == form.startswith("k_sddmm")
+    prob = F.problem(name, C, Co, T, Bg, R, _seed(C))
+    got = _got(name, C, Co, "never", T=T, Bg=Bg, R=R)
+    assert_close(got, _oracle_f64_gpu(*prob), what=f"graph shapes {name} PROJ_FIRST C={C}->{Co} T={T} {form}")
+    _assert_empty_rows_are_exact_zeros(name, got["z"])
+
+
 # ---- b: both sides of the SDDMM's register form -------------------------------------------------------------------------
 
 _SDDMM_WIDTHS = [(mode, *F.MODES[mode]) for mode in F.MODES] + [(mode, *F.WIDE[mode]) for mode in F.WIDE]

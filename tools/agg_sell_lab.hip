@@ -36,11 +36,10 @@ __global__ __launch_bounds__(kAggBlock) void k_agg_sell_lab(
     const float4* __restrict__ u4, const float* __restrict__ Es, float4* __restrict__ v4, int G, int Cu, int N, int n_pos,
     int n_slices) {
   extern __shared__ float4 slab[];
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  int g, slot;
+  if (!xcd_group_slot(T4 * Cu, G, &g, &slot)) return;
   const int j = slot % T4;
-  const int c = (slot / T4) % Cu;
-  const int g = (slot / (T4 * Cu)) * 8 + xcd;
-  if (g >= G) return;
+  const int c = slot / T4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const size_t base = ((size_t)g * Cu + c) * N * T4;
   const float* Eg = Es + (size_t)g * n_pos;
@@ -103,7 +102,7 @@ extern "C" int msgat_lab_aggregate_sell(const msgat_shape_t* sh, const msgat_gra
   const msgat_sell_t& sl = gr->sell_rows;
   const int G = sh->R * sh->Bg, N = sh->N;
   const size_t lds = (size_t)N * sizeof(float4);
-  const dim3 grid((unsigned)cdiv(G, 8) * 8 * Cu * 3), block(kAggBlock);
+  const dim3 grid(xcd_grid(G, Cu * 3)), block(kAggBlock);
 #define MSGAT_LAB_RUN(L)                                                                                             \
   do {                                                                                                               \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_agg_sell_lab<3, L>),                                  \

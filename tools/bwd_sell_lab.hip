@@ -21,10 +21,8 @@ __global__ __launch_bounds__(64 * NW) void k_bwd_sell_fused_lab(
     float4* __restrict__ du4, float* __restrict__ dE, int G, int Cu, int N, int n_pos, int n_slices, int Q) {
   extern __shared__ float4 slab[];  // [N]
   constexpr int kThreads = 64 * NW;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int q = slot % Q;
-  const int g = (slot / Q) * 8 + xcd;
-  if (g >= G) return;
+  int g, q;
+  if (!xcd_group_slot(Q, G, &g, &q)) return;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int W = q * NW + wave;
   const int sA = W, sB = n_slices - 1 - W;
@@ -124,7 +122,7 @@ extern "C" int msgat_lab_bwd_sell_fused(const msgat_shape_t* sh, const msgat_gra
     const int Q = cdiv(sl.n_slices, 2 * NW);                                                                           \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_sell_fused_lab<3, NW, L>),                          \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                   \
-    hipLaunchKernelGGL((k_bwd_sell_fused_lab<3, NW, L>), dim3((unsigned)cdiv(G, 8) * 8 * Q), dim3(64 * NW), lds,       \
+    hipLaunchKernelGGL((k_bwd_sell_fused_lab<3, NW, L>), dim3(xcd_grid(G, Q)), dim3(64 * NW), lds,                     \
                        (hipStream_t)stream, sl.slice_off, sl.lane_row, sl.idx, (const float4*)dz, (const float4*)u, Es, \
                        (float4*)du, dE, G, Cu, N, sl.n_pos, sl.n_slices, Q);                                           \
   } while (0)
