@@ -315,8 +315,12 @@ class _GACNFunction(torch.autograd.Function):
         # `needs_input_grad` is True under torch.no_grad() as well (it mirrors requires_grad); whether a graph is being
         # recorded is known only to the caller (inside forward grad mode is always off).  Inference then skips everything
         # backward alone needs: pq (4 of the 7 matrix-core instructions per score tile), E in CSC order, the saved y.
-        need_bwd = bool(recording) and any(ctx.needs_input_grad)
-        plan = _gacn_plan(graph, dev, R, G // R, Cin, Co, N, T, need_bwd)
+        # The FORM of the forward follows the grad mode alone: the score kernel that also forms pq takes its row sums
+        # from the matrix core and rounds lse differently, so a form chosen by `needs_input_grad` would let a frozen
+        # backbone change the bits of a prediction.  What is frozen decides only whether anything is saved.
+        training_form = bool(recording)
+        need_bwd = training_form and any(ctx.needs_input_grad)
+        plan = _gacn_plan(graph, dev, R, G // R, Cin, Co, N, T, training_form)
 
         if not x.is_contiguous():
             x = x.contiguous()
@@ -332,7 +336,7 @@ class _GACNFunction(torch.autograd.Function):
         scratch_t = torch.empty(plan.nscratch, device=dev, dtype=torch.float32) if plan.nscratch else None
         scratch = _ptr(scratch_t)
         dense_t = torch.empty(plan.ndense, device=dev, dtype=torch.uint8) if plan.ndense else None
-        io = _lib.Fwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), _ptr(z), q, kW, lse, pq, E, u, int(need_bwd), scratch, Ec,
+        io = _lib.Fwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), _ptr(z), q, kW, lse, pq, E, u, int(training_form), scratch, Ec,
                       _ptr(dense_t))
         st = L.msgat_gacn_forward(C.byref(plan.shape), C.byref(plan.gstruct), C.byref(io), _stream_handle(dev))
         _lib.check(st, "msgat_gacn_forward")
@@ -557,7 +561,7 @@ class _LayerNormTFunction(torch.autograd.Function):
         y = torch.empty_like(x)
         w = None if weight is None else weight.contiguous()
         b = None if bias is None else bias.contiguous()
-        R = 1 if w is None else w.numel() // T          # weight [T] or [R,T]: R parameter sets, relation-major rows
+        R, ctx.param_shape = _ln_sets(w, b, T)          # weight / bias [T] or [R,T]: R parameter sets, relation-major rows
         st = L.msgat_layernorm_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, T, eps, R, _stream_handle(x.device))
         _lib.check(st, "msgat_layernorm_forward")
         ctx.eps, ctx.has_w, ctx.has_b, ctx.R = eps, weight is not None, bias is not None, R
@@ -576,7 +580,7 @@ class _LayerNormTFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         R = ctx.R
         dw = torch.empty_like(w) if ctx.has_w else None
-        db = torch.empty(w.shape if ctx.has_w else (T,), device=x.device, dtype=torch.float32) if ctx.has_b else None
+        db = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if ctx.has_b else None
         part = torch.empty(max(int(L.msgat_layernorm_partial_floats(rows, T, R)), 1), device=x.device,
                            dtype=torch.float32)
         st = L.msgat_layernorm_backward(_ptr(x), _ptr(w), _ptr(dy), None, _ptr(dx), _ptr(dw), _ptr(db), _ptr(part),
@@ -601,7 +605,7 @@ class _LnPoolTeeFunction(torch.autograd.Function):
         w = None if weight is None else weight.contiguous()
         b = None if bias is None else bias.contiguous()
         pw = pool_w.contiguous()
-        R = 1 if w is None else w.numel() // T
+        R, ctx.param_shape = _ln_sets(w, b, T)
         stream = _stream_handle(x.device)
         pooled = _new(x, B, Cc, T)
         Rp = pw.numel() // N
@@ -614,7 +618,8 @@ class _LnPoolTeeFunction(torch.autograd.Function):
             _lib.check(L.msgat_node_pool(_ptr(y), _ptr(pw), _ptr(pooled), B * Cc, N, T, Rp, 0, 0, stream), "msgat_node_pool")
         ctx.eps, ctx.relu_input, ctx.has_w, ctx.has_b, ctx.R, ctx.Rp = eps, bool(relu_input), w is not None, b is not None, R, Rp
         ctx.save_for_backward(*([x, y, pw] + ([w] if w is not None else []) + ([b] if b is not None else [])))
-        return y, x.view_as(x), pooled
+        ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None (backward handles each): no
+        return y, x.view_as(x), pooled        # zero-filled [B,C,N,T] for the second output of a frozen x
 
     @staticmethod
     def backward(ctx, dy, dx_other, dpooled):
@@ -644,7 +649,7 @@ class _LnPoolTeeFunction(torch.autograd.Function):
         other = None if dx_other is None else dx_other.contiguous()
         dx = torch.empty_like(x)
         dw = torch.empty_like(w) if ctx.has_w else None
-        db = torch.empty(w.shape if ctx.has_w else (T,), device=x.device, dtype=torch.float32) if ctx.has_b else None
+        db = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if ctx.has_b else None
         part = _new(x, max(int(L.msgat_layernorm_partial_floats(rows, T, ctx.R)), 1))
         if fused:
             want_pw = bool(need[5])
@@ -670,13 +675,27 @@ class _LnPoolTeeFunction(torch.autograd.Function):
 
 
 def _check_ln_params(x: torch.Tensor, **params):
-    """LayerNorm parameters over the last axis of x: each None, [T] or [R,T] with R dividing the leading axis."""
+    """LayerNorm parameters over the last axis of x: each None, [T] or [R,T] with R dividing the leading axis, and all
+    that are given of one shape (the kernels index both by the relation: a [T] bias beside an [R,T] weight would be read
+    past its end)."""
     T = x.shape[-1]
-    for name, t in params.items():
-        if t is not None:
-            _require_device_tensor(name, t, x.device)
-            if t.shape[-1] != T or t.dim() > 2 or (t.dim() == 2 and x.shape[0] % t.shape[0]):
-                raise ValueError(f"{name} must be [{T}] or [R,{T}] with R dividing the leading axis, got {tuple(t.shape)}")
+    given = {name: t for name, t in params.items() if t is not None}
+    for name, t in given.items():
+        _require_device_tensor(name, t, x.device)
+        if t.shape[-1] != T or t.dim() > 2 or (t.dim() == 2 and x.shape[0] % t.shape[0]):
+            raise ValueError(f"{name} must be [{T}] or [R,{T}] with R dividing the leading axis, got {tuple(t.shape)}")
+    if len({tuple(t.shape) for t in given.values()}) > 1:
+        raise ValueError(" and ".join(given) + " must have the same shape, got "
+                         + " and ".join(str(tuple(t.shape)) for t in given.values()))
+
+
+def _ln_sets(weight, bias, T: int):
+    """(parameter sets R, shape of a parameter gradient) of a LayerNorm: read from the weight, or from the bias where there
+    is no weight -- a [R,T] bias alone is R sets too, and its gradient has R rows."""
+    ref = weight if weight is not None else bias
+    if ref is None:
+        return 1, (T,)
+    return ref.numel() // T, tuple(ref.shape)
 
 
 def layer_norm_pool_tee(x: torch.Tensor, weight, bias, eps: float, relu_input: bool, pool_w: torch.Tensor):
@@ -687,11 +706,20 @@ def layer_norm_pool_tee(x: torch.Tensor, weight, bias, eps: float, relu_input: b
     _require_device_tensor("weights", pool_w, x.device)
     if x.dim() != 4 or pool_w.shape[-1] != x.shape[2] or pool_w.dim() > 2 or (pool_w.dim() == 2 and x.shape[0] % pool_w.shape[0]):
         raise ValueError(f"layer_norm_pool_tee: signals {tuple(x.shape)}, pooling weights {tuple(pool_w.shape)}")
-    if x.numel() == 0 or not x.requires_grad:
+    _check_ln_params(x, weight=weight, bias=bias)
+    # The node's forward takes the pooling's sums out of the LayerNorm pass (other bits than node_pool's own pass) when
+    # the two have the same parameter-set count and N >= 64.  There the form follows the grad mode alone, as the graph
+    # attention's does (_GACNFunction.forward): in grad mode everything goes through the node, whatever requires grad --
+    # a frozen x (every component's first block in ordinary training, where x is the model's input), a wholly frozen
+    # block of a fine-tuned model -- so that what is frozen does not change the forward.  A frozen x gets back the x it
+    # gave, not the node's output, and nothing downstream forms a gradient for it.  Elsewhere, and under no_grad, a
+    # frozen x takes the two ops, which launch what the node would.
+    same_sets = pool_w.numel() // x.shape[2] == _ln_sets(weight, bias, x.shape[-1])[0] if x.numel() else False
+    if x.numel() == 0 or not (x.requires_grad or (torch.is_grad_enabled() and same_sets and x.shape[2] >= 64)):
         normed = layer_norm_t(x, weight, bias, eps, relu_input)
         return normed, x, node_pool(normed, pool_w)
-    _check_ln_params(x, weight=weight, bias=bias)
-    return _LnPoolTeeFunction.apply(x, weight, bias, float(eps), bool(relu_input), pool_w)
+    normed, again, pooled = _LnPoolTeeFunction.apply(x, weight, bias, float(eps), bool(relu_input), pool_w)
+    return normed, (again if x.requires_grad else x), pooled
 
 
 def layer_norm_t(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
@@ -703,8 +731,6 @@ def layer_norm_t(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: O
     applies -- for a producer that was told to skip it (`mix_multi(..., relu=True, relu_grad_premasked=True)`)."""
     _require_device_tensor("signals", x)
     _check_ln_params(x, weight=weight, bias=bias)
-    if weight is not None and bias is not None and weight.shape != bias.shape:
-        raise ValueError("weight and bias must have the same shape")
     if x.numel() == 0:
         return torch.empty_like(x)
     return _LayerNormTFunction.apply(x, weight, bias, float(eps), bool(relu_input))
@@ -1124,6 +1150,7 @@ class _LnHeadFunction(torch.autograd.Function):
         _lib.check(st, "msgat_head_forward_ln")
         ctx.eps, ctx.relu_input, ctx.has_lnw, ctx.has_lnb, ctx.has_bias = eps, bool(relu_input), w is not None, lb is not None, bias is not None
         ctx.has_xn = keep
+        ctx.param_shape = _ln_sets(w, lb, T)[1]
         ctx.save_for_backward(*([x, W] + ([xn] if keep else []) + ([w] if w is not None else [])))
         return out
 
@@ -1144,7 +1171,7 @@ class _LnHeadFunction(torch.autograd.Function):
         if need[0] or need[1] or need[2]:
             dx = torch.empty_like(x)
             dlnw = torch.empty_like(w) if (ctx.has_lnw and need[1]) else None
-            dlnb = torch.empty(w.shape if ctx.has_lnw else (T,), device=x.device, dtype=torch.float32) if (ctx.has_lnb and need[2]) else None
+            dlnb = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if (ctx.has_lnb and need[2]) else None
             part = _new(x, max(int(L.msgat_layernorm_head_backward_partial_floats(B, Cc, N, T)), 1))
             st = L.msgat_layernorm_head_backward(_ptr(dout), _ptr(W), _ptr(x), _ptr(w), _ptr(dx), _ptr(dlnw), _ptr(dlnb),
                                                  _ptr(part), B, Cc, N, T, To, R, ctx.eps, int(ctx.relu_input), stream)
@@ -1169,7 +1196,8 @@ def ln_head(x: torch.Tensor, ln_weight: Optional[torch.Tensor], ln_bias: Optiona
     _check_ln_params(x, ln_weight=ln_weight, ln_bias=ln_bias)
     if ln_weight is not None and W.dim() == 5 and ln_weight.dim() == 2 and ln_weight.shape[0] != W.shape[0]:
         raise ValueError("ln_head: the LayerNorm and the head must have the same number of parameter sets")
-    if x.numel() == 0 or (ln_weight is not None and ln_weight.numel() // T != (1 if W.dim() == 4 else W.shape[0])):
+    if x.numel() == 0 or ((ln_weight is not None or ln_bias is not None)
+                          and _ln_sets(ln_weight, ln_bias, T)[0] != (1 if W.dim() == 4 else W.shape[0])):
         return head(layer_norm_t(x, ln_weight, ln_bias, eps, relu_input), W, bias)   # mixed parameter-set counts: the two ops
     return _LnHeadFunction.apply(x, ln_weight, ln_bias, float(eps), W, bias, bool(relu_input))
 
@@ -1804,10 +1832,11 @@ class _AttentionCoreFunction(torch.autograd.Function):
         G, Cu, N, T = u.shape
         R = Wg.shape[0]
         dev = u.device
-        need_bwd = bool(recording) and any(ctx.needs_input_grad)   # see _GACNFunction.forward
+        training_form = bool(recording)                              # see _GACNFunction.forward: the grad mode alone
+        need_bwd = training_form and any(ctx.needs_input_grad)
         # the GACN plan of a graph attention over Cu channels, without the q slot: kW, lse, pq, E, E in CSC order in one
         # buffer, the scratch sizes asked for once
-        plan = _gacn_plan(graph, dev, R, G // R, Cu, 0, N, T, need_bwd, own_q=False)
+        plan = _gacn_plan(graph, dev, R, G // R, Cu, 0, N, T, training_form, own_q=False)
         z = torch.empty_like(u)
         buf = torch.empty(plan.total, device=dev, dtype=torch.float32)
         _, kW, lse, pq, E, Ec, _ = plan.pointers(buf)

@@ -9,6 +9,7 @@ import torch
 from conftest import record_err, rel_err
 
 from branch_edge_fixtures import channel_attention_mix_dense, temporal_attention_taps_dense
+from grad_subset_fixtures import causal_conv_dense, head_dense, mix_dense, mix_multi_dense
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -64,13 +65,7 @@ def test_mix_matches_dense_ops(G, R, Ci, Co, N, T, bias, add, relu):
     ref = _leaf64(*ins)
     it = iter(ref)
     x64, M64 = next(it), next(it)
-    o64 = torch.einsum("roc,rgcnt->rgont", M64, x64.view(R, G // R, Ci, N, T)).reshape(G, Co, N, T)
-    if bias:
-        o64 = o64 + next(it).view(1, Co, 1, 1)
-    if add:
-        o64 = o64 + next(it)
-    if relu:
-        o64 = torch.relu(o64)
+    o64 = mix_dense(x64, M64, next(it) if bias else None, next(it) if add else None, relu)
     g_ref = _grads(o64, ref, dout.double())
     assert rel_err(out.double(), o64) < TOL
     _check(g_mine, g_ref, ["dx", "dM", "dbias", "dadd"])
@@ -166,18 +161,14 @@ def test_causal_conv_is_the_dilated_convolution_and_its_autograd_in_one_pass_eac
     dout = wide[:, 2:2 + Co]                                          # a channel slice: read in place
     out = ops.causal_conv(h, taps, bias_l, d)
     out.backward(dout)
-    # float64 reference: the reference's own module sequence, relation by relation
+    # float64 reference: the reference's own module sequence, relation by relation (grad_subset_fixtures.causal_conv_dense)
     h64 = h.detach().double().requires_grad_(True)
-    w64, b64 = w.double().requires_grad_(True), bias.double().requires_grad_(True)
-    refs = []
-    for r in range(R):
-        y = torch.nn.functional.conv2d(h64[r * Bg:(r + 1) * Bg], w64[r], b64[r], padding=(0, d), dilation=(1, d))
-        refs.append(y[..., : y.size(-1) - d])
-    ref = torch.cat(refs)
+    t64, b64 = taps.detach().double().requires_grad_(True), bias.double().requires_grad_(True)
+    ref = causal_conv_dense(h64, t64, b64, d)
     ref.backward(dout.double())
     what = f"causal_conv R={R} {Ci}->{Co} N={N} T={T} d={d}"
     for key, got, want in (("out", out.detach(), ref.detach()), ("dh", h.grad, h64.grad), ("dbias", bias_l.grad, b64.grad),
-                           ("dtaps", taps.grad, torch.cat([w64.grad[..., 0, 0], w64.grad[..., 0, 1]], dim=1))):
+                           ("dtaps", taps.grad, t64.grad)):
         err = rel_err(got, want)
         record_err(what, key, err, 1e-5)
         assert err < 1e-5, key
@@ -231,7 +222,7 @@ def test_prediction_head_matches_the_transposed_convolution(B, C, N, T, To):
     out = ops.head(*mine)
     g_mine = _grads(out, mine, dout)
     ref = _leaf64(x, W, b)
-    o64 = torch.nn.functional.conv2d(ref[0].transpose(1, 3), ref[1], ref[2])[..., 0].transpose(1, 2)
+    o64 = head_dense(ref[0], ref[1], ref[2])
     assert out.shape == o64.shape
     assert rel_err(out.double(), o64) < TOL
     _check(g_mine, _grads(o64, ref, dout.double()), ["dx", "dW", "dbias"])
@@ -257,10 +248,7 @@ def test_mix_multi_reads_channel_slices_in_place_and_writes_several_outputs():
 
     ref = _leaf64(wide, c, M, bias, *adds)
     w64, c64, M64, b64, *ad64 = ref
-    x = torch.cat([w64[:, 2:9], w64[:, 11:20], c64], dim=1)
-    o = torch.einsum("roc,rgcnt->rgont", M64, x.view(2, 2, 21, N, T)).reshape(G, 30, N, T) + b64.view(1, 30, 1, 1)
-    o = o + torch.cat(ad64, dim=1)
-    o_split = torch.split(o, [4, 16, 10], dim=1)
+    o_split = mix_multi_dense([w64[:, 2:9], w64[:, 11:20], c64], M64, b64, ad64, out_channels=[4, 16, 10])
     for mine, want in zip(outs, o_split):
         assert rel_err(mine.double(), want) < TOL
     g_ref = torch.autograd.grad(o_split, ref, [d.double() for d in douts])

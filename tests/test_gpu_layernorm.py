@@ -10,6 +10,8 @@ import torch.nn.functional as F
 
 from conftest import rel_err
 
+from grad_subset_fixtures import layer_norm_pool_tee_dense, ln_head_dense
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
@@ -145,20 +147,12 @@ def test_ln_head_is_the_two_ops_with_one_backward_pass(B, R, C, N, T, To, relu):
     names = ("out", "dx", "dln_weight", "dln_bias", "dW", "dbias")
     for name, a, b in zip(names, got, two):           # the head kernels normalise in their own lane order: rounding only
         assert rel_err(a, b) < 2e-6, name
-    # float64: the reference's op sequence, relation by relation
-    Bg = B // R
+    # float64: the reference's op sequence, relation by relation, behind the mask of the ReLU that produced x (relu_input)
     x64 = x.double().requires_grad_(True)
     p64 = [t.double().requires_grad_(True) for t in (lw, lb, W, hb)]
-    outs = []
-    for r in range(R):
-        sl = slice(r * Bg, (r + 1) * Bg)
-        pr = [p if R == 1 else p[r] for p in p64]
-        xn = F.layer_norm(x64[sl], [T], pr[0], pr[1], 1e-5)
-        outs.append(F.conv2d(xn.transpose(1, 3), pr[2], pr[3])[..., 0].transpose(1, 2))
-    ref = torch.cat(outs)
+    ref = ln_head_dense(x64, p64[0], p64[1], 1e-5, p64[2], p64[3], relu)
     ref.backward(dout.double())
-    dx64 = x64.grad if not relu else x64.grad * (x > 0)       # the mask of the ReLU that produced x (relu_input)
-    for name, a, b in zip(names, got, [ref.detach(), dx64] + [p.grad for p in p64]):
+    for name, a, b in zip(names, got, [ref.detach(), x64.grad] + [p.grad for p in p64]):
         assert rel_err(a.double(), b) < TOL, name
 
 
@@ -195,18 +189,9 @@ def test_layer_norm_pool_tee_adds_the_pooling_gradient_inside_the_layernorm_back
     names = ("y", "pooled", "dx", "dln_weight", "dln_bias", "dpool_w")
     for name, a, b in zip(names, got, two):
         assert rel_err(a, b) < 2e-6, name
-    Bg = B // R
     x64 = x.double().requires_grad_(True)
     p64 = [t.double().requires_grad_(True) for t in (lw, lb, pw)]
-    ys, ps = [], []
-    for r in range(R):
-        sl = slice(r * Bg, (r + 1) * Bg)
-        pr = [p if R == 1 else p[r] for p in p64]
-        yr = F.layer_norm(x64[sl], [T], pr[0], pr[1], 1e-5)
-        ys.append(yr)
-        ps.append(torch.einsum("bcnt,n->bct", yr, pr[2]))
-    y64, pp64 = torch.cat(ys), torch.cat(ps)
-    torch.autograd.backward([y64, x64 * 1.0, pp64], [d_y.double(), d_x2.double(), d_p.double()])
-    dx64 = x64.grad if not relu else x64.grad * (x > 0)
-    for name, a, b in zip(names, got, [y64.detach(), pp64.detach(), dx64] + [p.grad for p in p64]):
+    y64, x2_64, pp64 = layer_norm_pool_tee_dense(x64, p64[0], p64[1], 1e-5, relu, p64[2])
+    torch.autograd.backward([y64, x2_64, pp64], [d_y.double(), d_x2.double(), d_p.double()])
+    for name, a, b in zip(names, got, [y64.detach(), pp64.detach(), x64.grad] + [p.grad for p in p64]):
         assert rel_err(a.double(), b) < TOL, name

@@ -10,6 +10,8 @@ from torch import nn, optim
 
 from conftest import record_err, rel_err
 
+from grad_subset_fixtures import gate_sum_dense
+
 pytestmark = pytest.mark.gpu
 
 
@@ -215,15 +217,8 @@ def test_gate_sum_is_the_models_last_line(R, B, N, To, te):
 
     def reference(dtype):
         ps = [p.detach().to(dtype).requires_grad_(True) for p in params]
-        if te:
-            gate = (torch.nn.functional.embedding(H, ps[1]) + torch.nn.functional.embedding(D, ps[2])).view(B, R, N, To)
-            gates = gate.unbind(1)
-        else:
-            gates = ps[1].unbind(0)
-        o = None
-        for r in range(R):                                   # msgat.py:204-205: the generator summed left to right
-            term = ps[0][r] * gates[r]
-            o = term if o is None else o + term
+        # msgat.py:204-205, the generator summed left to right (grad_subset_fixtures.gate_sum_dense)
+        o = gate_sum_dense(ps[0], H, D, ps[1], ps[2]) if te else gate_sum_dense(ps[0], None, None, ps[1])
         o.backward(dout.to(dtype))
         return [o.detach()] + [p.grad for p in ps]
 
