@@ -18,6 +18,7 @@
 // Every kernel reads and writes the reference's [B,C,N,T] layout: a lane owns one row of T contiguous
 // floats (T/4 16-byte loads), neighbouring lanes neighbouring rows.  All are HBM-bound.
 #include "common.hpp"
+#include "row_kernels.hpp"
 #include "rowtile.hpp"
 
 namespace msgat {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_tmix_dA(const float* __restrict__ do
   const float colmask = m < T ? 1.f : 0.f;
   const float* dbase = dout + (size_t)g * dout_gs * N * T + mc;  // dout may be a channel slice of a wider tensor
   const float* ybase = y + ((size_t)g * K + k) * rows * T + mc;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[1] = {f32x4_zero()};
   // wave w takes k-steps w, w + 4, ... of the chunk, kTdaUnroll at a time
   constexpr int kWaves = kBlock / kWave;
   for (int s0 = r0 + 4 * wave * kTdaUnroll; s0 < r1; s0 += 4 * kWaves * kTdaUnroll) {
@@ -160,18 +161,10 @@ __global__ __launch_bounds__(kBlock) void k_tmix_dA(const float* __restrict__ do
       b[u] = ybase[(size_t)rc * T] * keep;
     }
 #pragma unroll
-    for (int u = 0; u < kTdaUnroll; ++u) acc = mfma_16x16x4(a[u], b[u], acc);
+    for (int u = 0; u < kTdaUnroll; ++u) acc[0] = mfma_16x16x4(a[u], b[u], acc[0]);
   }
-  // D[t = 4 * (lane >> 4) + reg][i = lane & 15]; the four waves' tiles are added in a fixed order
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) red[wave][(4 * kq + reg) * 16 + m] = acc[reg];
-  __syncthreads();
-  if (threadIdx.x < T * T) {
-    const int t = threadIdx.x / T, i = threadIdx.x - t * T;
-    const int e = t * 16 + i;
-    part[(((size_t)g * K + k) * gridDim.x + blockIdx.x) * (T * T) + threadIdx.x] =
-        (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-  }
+  // D[t = 4 * (lane >> 4) + reg][i = lane & 15]; the four waves' tiles are added in a fixed order (row_kernels.hpp)
+  mfma_tiles_partial<T>(acc, red, part + (((size_t)g * K + k) * gridDim.x + blockIdx.x) * (T * T), T * T);
 }
 
 size_t tmix_partial_floats(int G, int K, int T) { return (size_t)G * K * kTmixChunks * T * T; }
@@ -200,9 +193,9 @@ __global__ __launch_bounds__(kBlock) void k_node_pool(const float* __restrict__ 
   __shared__ float4 tiles[kBlock / kWave][RowTile<T>::kFloat4s];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const RowTile<T> rt(tiles[wave], lane);
-  float acc[T];
+  float acc[1][T];
 #pragma unroll
-  for (int t = 0; t < T; ++t) acc[t] = 0.f;
+  for (int t = 0; t < T; ++t) acc[0][t] = 0.f;
   // a wave takes 64 consecutive nodes = rows per trip, read in flat order (rowtile.hpp)
   for (int n0 = wave * kWave; n0 < N; n0 += kBlock) {
     const int nf = min(kWave, N - n0) * (T / 4);
@@ -213,19 +206,9 @@ __global__ __launch_bounds__(kBlock) void k_node_pool(const float* __restrict__ 
     float v[T];
     rt.to_row(in, v);
 #pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = fmaf(wn, v[t], acc[t]);
+    for (int t = 0; t < T; ++t) acc[0][t] = fmaf(wn, v[t], acc[0][t]);
   }
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    float a = acc[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    if (lane == 0) red[wave][t] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x < T)
-    pooled[sl * T + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  block_partial(acc, red, pooled + sl * T);
 }
 
 // dx[s,n,t] = w[n] dpooled[s,t] (+ add[s,n,t]: the gradient that reached x along its other path)
@@ -362,85 +345,9 @@ __global__ __launch_bounds__(kBlock) void k_head_wperm(const float* __restrict__
 // one node, so its mean and variance are two sums over the kq lanes (xor 16, xor 32) per channel, and the normalised
 // float4 goes straight into the MFMAs -- the [B,C,N,T] LayerNorm output is never written (round 5: a 586 MB pass, 98 us
 // at PEMSD7 size, for an activation only the head reads).
-template <int T, bool LN>
-__global__ __launch_bounds__(kBlock) void k_head_fwd(const float* __restrict__ x, const float* __restrict__ W,
-                                                     const float* __restrict__ bias, float* __restrict__ out,
-                                                     int C, int N, int To, int Bg, const float* __restrict__ lnw,
-                                                     const float* __restrict__ lnb, float eps, float* __restrict__ xn) {
-  constexpr int T4 = T / 4;
-  __shared__ float Wl[kHeadFwdCC * T * kHeadTo];
-  const int b = blockIdx.y;
-  W += (size_t)(b / Bg) * C * T * kHeadTo;   // pre-laid-out weights Wp [R,C,T,16] (k_head_wperm), bias [R,To]
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int m = lane & 15, kq = lane >> 4;
-  const int n0 = (blockIdx.x * (kBlock / kWave) + wave) * 16;
-  const int nrow = min(n0 + m, N - 1);  // clamped: rows past N are computed from row N-1 and never stored
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int c0 = 0; c0 < C; c0 += kHeadFwdCC) {
-    const int cn = min(kHeadFwdCC, C - c0);
-    __syncthreads();  // the previous chunk's weights are no longer read
-    for (int i = threadIdx.x; i < kHeadFwdCC * T * kHeadTo; i += kBlock)   // one contiguous copy (Wp is zero past To)
-      Wl[i] = (i < cn * T * kHeadTo) ? W[(size_t)c0 * T * kHeadTo + i] : 0.f;
-    __syncthreads();
-    const int kqc = min(kq, T4 - 1);
-    const float kmask = kq < T4 ? 1.f : 0.f;
-    const float4* src = reinterpret_cast<const float4*>(x + (((size_t)b * C + c0) * N + nrow) * T) + kqc;
-    float4 lw4 = make_float4(1.f, 1.f, 1.f, 1.f), lb4 = f4zero();
-    if (LN) {
-      const int rel = b / Bg;
-      if (lnw) lw4 = make_float4(lnw[rel * T + 4 * kqc], lnw[rel * T + 4 * kqc + 1], lnw[rel * T + 4 * kqc + 2], lnw[rel * T + 4 * kqc + 3]);
-      if (lnb) lb4 = make_float4(lnb[rel * T + 4 * kqc], lnb[rel * T + 4 * kqc + 1], lnb[rel * T + 4 * kqc + 2], lnb[rel * T + 4 * kqc + 3]);
-    }
-    for (int cc = 0; cc < cn; cc += kHeadFwdUn) {
-      float4 av[kHeadFwdUn];
-#pragma unroll
-      for (int u = 0; u < kHeadFwdUn; ++u) av[u] = src[(size_t)min(cc + u, cn - 1) * N * T4];
-      if (LN) {   // normalise the row: its T values are this lane's float4 and those of the lanes 16 and 32 away
-#pragma unroll
-        for (int u = 0; u < kHeadFwdUn; ++u) {
-          float4 v = av[u];
-          float s1 = ((v.x + v.y) + (v.z + v.w)) * kmask;
-          s1 += __shfl_xor(s1, 16);
-          s1 += __shfl_xor(s1, 32);
-          const float mean = s1 * (1.0f / T);
-          v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
-          float s2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w))) * kmask;
-          s2 += __shfl_xor(s2, 16);
-          s2 += __shfl_xor(s2, 32);
-          const float rstd = rsqrtf(s2 * (1.0f / T) + eps);
-          av[u] = make_float4(fmaf(v.x * rstd, lw4.x, lb4.x), fmaf(v.y * rstd, lw4.y, lb4.y), fmaf(v.z * rstd, lw4.z, lb4.z),
-                              fmaf(v.w * rstd, lw4.w, lb4.w));
-        }
-        if (xn != nullptr && kq < T4 && n0 + m < N) {   // training: the weight gradient reads the normalised rows
-          float4* dst = reinterpret_cast<float4*>(xn + (((size_t)b * C + c0) * N + n0 + m) * T) + kq;
-#pragma unroll
-          for (int u = 0; u < kHeadFwdUn; ++u)
-            if (cc + u < cn) dst[(size_t)(cc + u) * N * T4] = av[u];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kHeadFwdUn; ++u)
-        if (cc + u < cn) {  // wave-uniform; no loads inside
-          const float* wl = Wl + ((cc + u) * T + 4 * kqc) * kHeadTo + m;
-          acc = mfma_16x16x4(av[u].x, wl[0 * kHeadTo] * kmask, acc);
-          acc = mfma_16x16x4(av[u].y, wl[1 * kHeadTo] * kmask, acc);
-          acc = mfma_16x16x4(av[u].z, wl[2 * kHeadTo] * kmask, acc);
-          acc = mfma_16x16x4(av[u].w, wl[3 * kHeadTo] * kmask, acc);
-        }
-    }
-  }
-  // D[node = 4 * (lane >> 4) + reg][o = lane & 15]
-  const float bo = (bias != nullptr && m < To) ? bias[(size_t)(b / Bg) * To + m] : 0.f;
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int n = n0 + 4 * kq + reg;
-    if (n < N && m < To) out[((size_t)b * N + n) * To + m] = acc[reg] + bo;
-  }
-}
-
-// T_out > 16: k_head_fwd with OT output tiles, every loaded x float4 feeding all of them (4 OT MFMAs per channel)
+// OT output tiles of 16, every loaded x float4 feeding all of them (4 OT MFMAs per channel); OT = 1 is the T_out <= 16 form.
 template <int T, bool LN, int OT>
-__global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restrict__ x, const float* __restrict__ W,
+__global__ __launch_bounds__(kBlock) void k_head_fwd(const float* __restrict__ x, const float* __restrict__ W,
                                                      const float* __restrict__ bias, float* __restrict__ out,
                                                      int C, int N, int To, int Bg, const float* __restrict__ lnw,
                                                      const float* __restrict__ lnb, float eps, float* __restrict__ xn) {
@@ -452,9 +359,11 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restri
   const int m = lane & 15, kq = lane >> 4;
   const int n0 = (blockIdx.x * (kBlock / kWave) + wave) * 16;
   const int nrow = min(n0 + m, N - 1);  // clamped: rows past N are computed from row N-1 and never stored
-  f32x4 acc[OT];   // one 16-output tile each, all fed from the same loaded x
+  // one 16-output tile each, all fed from the same loaded x.  OT = 1 keeps its tile in a plain variable: as acc[0] the T_out <= 16
+  // kernels take 4 more VGPRs (84 with LN at T = 8, 12: five waves per SIMD from six; profiles/branch_shared/lab_variants.txt)
+  f32x4 acc1 = f32x4_zero(), acc[OT];
 #pragma unroll
-  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4_zero();
   for (int c0 = 0; c0 < C; c0 += CC) {
     const int cn = min(CC, C - c0);
     __syncthreads();  // the previous chunk's weights are no longer read
@@ -476,20 +385,7 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restri
       for (int u = 0; u < kHeadFwdUn; ++u) av[u] = src[(size_t)min(cc + u, cn - 1) * N * T4];
       if (LN) {   // normalise the row: its T values are this lane's float4 and those of the lanes 16 and 32 away
 #pragma unroll
-        for (int u = 0; u < kHeadFwdUn; ++u) {
-          float4 v = av[u];
-          float s1 = ((v.x + v.y) + (v.z + v.w)) * kmask;
-          s1 += __shfl_xor(s1, 16);
-          s1 += __shfl_xor(s1, 32);
-          const float mean = s1 * (1.0f / T);
-          v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
-          float s2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w))) * kmask;
-          s2 += __shfl_xor(s2, 16);
-          s2 += __shfl_xor(s2, 32);
-          const float rstd = rsqrtf(s2 * (1.0f / T) + eps);
-          av[u] = make_float4(fmaf(v.x * rstd, lw4.x, lb4.x), fmaf(v.y * rstd, lw4.y, lb4.y), fmaf(v.z * rstd, lw4.z, lb4.z),
-                              fmaf(v.w * rstd, lw4.w, lb4.w));
-        }
+        for (int u = 0; u < kHeadFwdUn; ++u) av[u] = ln_quarter_row<T>(av[u], kmask, eps, lw4, lb4);
         if (xn != nullptr && kq < T4 && n0 + m < N) {   // training: the weight gradient reads the normalised rows
           float4* dst = reinterpret_cast<float4*>(xn + (((size_t)b * C + c0) * N + n0 + m) * T) + kq;
 #pragma unroll
@@ -497,41 +393,60 @@ __global__ __launch_bounds__(kBlock) void k_head_fwd_tiles(const float* __restri
             if (cc + u < cn) dst[(size_t)(cc + u) * N * T4] = av[u];
         }
       }
-      // K slots kq >= T/4 hold a clamped duplicate row: zero it once here (4 multiplies per channel) rather than the
-      // weight of every MFMA (4 OT: the T_out <= 16 form's v_mul per MFMA)
+      // K slots kq >= T/4 hold a clamped duplicate row and must count for nothing.  OT = 1 zeroes the weight of each of its 4
+      // MFMAs, as it always has; OT > 1 zeroes the row once (4 multiplies per channel, not 4 OT)
+      if constexpr (OT > 1) {
 #pragma unroll
-      for (int u = 0; u < kHeadFwdUn; ++u)
-        av[u] = make_float4(av[u].x * kmask, av[u].y * kmask, av[u].z * kmask, av[u].w * kmask);
+        for (int u = 0; u < kHeadFwdUn; ++u)
+          av[u] = make_float4(av[u].x * kmask, av[u].y * kmask, av[u].z * kmask, av[u].w * kmask);
+      }
 #pragma unroll
       for (int u = 0; u < kHeadFwdUn; ++u)
         if (cc + u < cn) {  // wave-uniform; no loads inside
           const float* wl = Wl + ((cc + u) * T + 4 * kqc) * OW + m;
+          if constexpr (OT == 1) {
+            acc1 = mfma_16x16x4(av[u].x, wl[0 * OW] * kmask, acc1);
+            acc1 = mfma_16x16x4(av[u].y, wl[1 * OW] * kmask, acc1);
+            acc1 = mfma_16x16x4(av[u].z, wl[2 * OW] * kmask, acc1);
+            acc1 = mfma_16x16x4(av[u].w, wl[3 * OW] * kmask, acc1);
+          } else {
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].x, wl[0 * OW + kHeadTo * ot], acc[ot]);
+            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].x, wl[0 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].y, wl[1 * OW + kHeadTo * ot], acc[ot]);
+            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].y, wl[1 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].z, wl[2 * OW + kHeadTo * ot], acc[ot]);
+            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].z, wl[2 * OW + kHeadTo * ot], acc[ot]);
 #pragma unroll
-          for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].w, wl[3 * OW + kHeadTo * ot], acc[ot]);
+            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[u].w, wl[3 * OW + kHeadTo * ot], acc[ot]);
+          }
         }
     }
   }
-  // D[node = 4 * (lane >> 4) + reg][o = 16 ot + (lane & 15)]
-#pragma unroll
-  for (int ot = 0; ot < OT; ++ot) {
-    const int o = kHeadTo * ot + m;
-    const float bo = (bias != nullptr && o < To) ? bias[(size_t)(b / Bg) * To + o] : 0.f;
+  // D[node = 4 * (lane >> 4) + reg][o = 16 ot + (lane & 15)].  OT = 1 spells its one tile out: through the loop below (ot = 0)
+  // the T_out <= 16 kernels with LN take 84 VGPRs again
+  if constexpr (OT == 1) {
+    const float bo = (bias != nullptr && m < To) ? bias[(size_t)(b / Bg) * To + m] : 0.f;
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const int n = n0 + 4 * kq + reg;
-      if (n < N && o < To) out[((size_t)b * N + n) * To + o] = acc[ot][reg] + bo;
+      if (n < N && m < To) out[((size_t)b * N + n) * To + m] = acc1[reg] + bo;
+    }
+  } else {
+#pragma unroll
+    for (int ot = 0; ot < OT; ++ot) {
+      const int o = kHeadTo * ot + m;
+      const float bo = (bias != nullptr && o < To) ? bias[(size_t)(b / Bg) * To + o] : 0.f;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int n = n0 + 4 * kq + reg;
+        if (n < N && o < To) out[((size_t)b * N + n) * To + o] = acc[ot][reg] + bo;
+      }
     }
   }
 }
 
 // dx[b,c,n,t] = sum_o W[o,t,c] dout[b,n,o]
-template <int T, int OT = 1>
+template <int T, int OT>
 __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ dout, const float* __restrict__ W,
                                                     float* __restrict__ dx, int C, int N, int To, int Bg) {
   constexpr int OW = kHeadTo * OT;   // OT tiles of 16 outputs: d and a weight row hold all of them
@@ -540,31 +455,10 @@ __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ do
   const int b = blockIdx.z, ck = blockIdx.y;
   W += (size_t)(b / Bg) * To * T * C;
   const int c0 = ck * kHeadCC, cn = min(kHeadCC, C - c0);
-  // weights of this channel chunk and the lane's dout row: every load unconditional (clamped index, masked value) and
-  // issued together -- as loops with a load and its use per trip hipcc emitted load, s_waitcnt vmcnt(0), use: 6 + 12
-  // dependent round trips in front of every block's first store (110 us for a 293 MB write)
-  constexpr int kWn = (kHeadCC * OW * T + kBlock - 1) / kBlock;
-  float wv[kWn];
-#pragma unroll
-  for (int k = 0; k < kWn; ++k) {
-    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * OW * T - 1);
-    const int c = i / (OW * T), t = (i / OW) % T, o = i % OW;
-    const float w = W[((size_t)min(o, To - 1) * T + t) * C + c0 + min(c, cn - 1)];
-    wv[k] = (c < cn && o < To) ? w : 0.f;
-  }
+  // weights of this channel chunk and the lane's dout row, every load issued before any use (row_kernels.hpp)
   const int n = blockIdx.x * kBlock + threadIdx.x;
-  const float* src = dout + ((size_t)b * N + min(n, N - 1)) * To;
   float d[OW];
-#pragma unroll
-  for (int o = 0; o < OW; ++o) {
-    const float v = src[min(o, To - 1)];
-    d[o] = o < To ? v : 0.f;
-  }
-#pragma unroll
-  for (int k = 0; k < kWn; ++k) {
-    const int i = threadIdx.x + k * kBlock;
-    if (i < kHeadCC * OW * T) (&Wl[0][0][0])[i] = wv[k];
-  }
+  head_bwd_stage(W, dout + ((size_t)b * N + min(n, N - 1)) * To, C, c0, cn, To, true, d, Wl);
   __syncthreads();
   // a wave's 64 nodes are 64 consecutive rows of every channel: stored in flat order (rowtile.hpp)
   const int n0 = n - (int)(threadIdx.x & (kWave - 1));
@@ -585,23 +479,10 @@ __global__ __launch_bounds__(kBlock) void k_head_dx(const float* __restrict__ do
 
 // The head's input gradient AND the backward of the LayerNorm in front of it (msgat.py:158-159: fc(ln(x).transpose(1,3)))
 // in ONE pass: dy[b,c,n,:] = sum_o W[o,:,c] dout[b,n,o] is built in registers exactly as k_head_dx builds it and consumed
-// on the spot by the LayerNorm backward of row (b,c,n) (layernorm.hip: k_ln_bwd, same formulas, same order), whose x row
+// on the spot by the LayerNorm backward of row (b,c,n) (ln_bwd_row of row_kernels.hpp, which k_ln_bwd runs too), whose x row
 // the lane reads itself.  The [B,C,N,T] gradient between the two never exists: k_head_dx's 293 MB write and k_ln_bwd's
 // read of it (and one launch) go.  part[block][2T]: the block's share of (dweight | dbias) of the LayerNorm.
-template <int T>
-__device__ __forceinline__ float lnh_centre_row(float (&x)[T], float eps) {   // = layernorm.hip's centre_row
-  const float x0 = x[0];
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) { x[t] -= x0; s += x[t]; }
-  const float md = s * (1.0f / T);
-  float v = 0.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) { x[t] -= md; v = fmaf(x[t], x[t], v); }
-  return rsqrtf(v * (1.0f / T) + eps);
-}
-
-template <int T, int OT = 1>
+template <int T, int OT>
 __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__ dout, const float* __restrict__ W,
                                                        const float* __restrict__ x, const float* __restrict__ lnw,
                                                        float* __restrict__ dx, float* __restrict__ part, int C, int N,
@@ -613,33 +494,14 @@ __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__
   const int b = blockIdx.z, ck = blockIdx.y, rel = b / Bg;
   W += (size_t)rel * To * T * C;
   const int c0 = ck * kHeadCC, cn = min(kHeadCC, C - c0);
-  constexpr int kWn = (kHeadCC * OW * T + kBlock - 1) / kBlock;
-  float wv[kWn];
-#pragma unroll
-  for (int k = 0; k < kWn; ++k) {   // unconditional, clamped: see k_head_dx
-    const int i = min((int)threadIdx.x + k * kBlock, kHeadCC * OW * T - 1);
-    const int c = i / (OW * T), t = (i / OW) % T, o = i % OW;
-    const float w = W[((size_t)min(o, To - 1) * T + t) * C + c0 + min(c, cn - 1)];
-    wv[k] = (c < cn && o < To) ? w : 0.f;
-  }
   const int n = blockIdx.x * kBlock + threadIdx.x;
   const int nc = min(n, N - 1);
-  const bool live = n < N;
-  const float* src = dout + ((size_t)b * N + nc) * To;
+  const bool live = n < N;                 // lanes past N: a zero gradient row
   float d[OW];
+  head_bwd_stage(W, dout + ((size_t)b * N + nc) * To, C, c0, cn, To, live, d, Wl);   // as in k_head_dx
+  float gw[T], dwb[2][T];                  // dwb: this lane's share of (dweight, dbias)
 #pragma unroll
-  for (int o = 0; o < OW; ++o) {
-    const float v = src[min(o, To - 1)];
-    d[o] = (o < To && live) ? v : 0.f;     // lanes past N: a zero gradient row
-  }
-#pragma unroll
-  for (int k = 0; k < kWn; ++k) {
-    const int i = threadIdx.x + k * kBlock;
-    if (i < kHeadCC * OW * T) (&Wl[0][0][0])[i] = wv[k];
-  }
-  float gw[T], dwa[T], dba[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t) { gw[t] = lnw ? lnw[rel * T + t] : 1.f; dwa[t] = 0.f; dba[t] = 0.f; }
+  for (int t = 0; t < T; ++t) { gw[t] = lnw ? lnw[rel * T + t] : 1.f; dwb[0][t] = 0.f; dwb[1][t] = 0.f; }
   __syncthreads();
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const int n0 = n - lane;
@@ -678,41 +540,11 @@ __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__
 #pragma unroll
       for (int t = 0; t < T; ++t) xv[t] = 0.f;
     }
-    unsigned positive = 0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) positive |= (xv[t] > 0.f ? 1u : 0u) << t;
-    const float rstd = lnh_centre_row<T>(xv, eps);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      xv[t] *= rstd;                  // xhat
-      dba[t] += gv[t];
-      dwa[t] = fmaf(gv[t], xv[t], dwa[t]);
-      gv[t] *= gw[t];
-      s1 += gv[t];
-      s2 = fmaf(gv[t], xv[t], s2);
-    }
-    s1 *= (1.0f / T);
-    s2 *= (1.0f / T);
-#pragma unroll
-    for (int t = 0; t < T; ++t) gv[t] = rstd * (gv[t] - s1 - xv[t] * s2);
-    if (relu_mask) {
-#pragma unroll
-      for (int t = 0; t < T; ++t) gv[t] = ((positive >> t) & 1u) ? gv[t] : 0.f;
-    }
+    const unsigned positive = ln_bwd_row<T>(xv, gv, gw, eps, dwb);   // gv = dx
+    if (relu_mask) relu_mask_row<T>(gv, positive);
     if (nf > 0) rt.store(dx + (((size_t)b * C + c0 + c) * N + n0) * T, nf, gv);   // wave-uniform
   }
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    float a = dwa[t], cc = dba[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); cc += __shfl_xor(cc, o); }
-    if (lane == 0) { red[wave][t] = a; red[wave][T + t] = cc; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 * T)
-    part[(((size_t)b * gridDim.y + ck) * gridDim.x + blockIdx.x) * 2 * T + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  block_partial(dwb, red, part + (((size_t)b * gridDim.y + ck) * gridDim.x + blockIdx.x) * 2 * T);
 }
 
 // dW partial[c, j, o, t] = sum over the j-th share of samples, all nodes: dout[b,n,o] x[b,c,n,t] -- like k_tmix_dA a
@@ -723,50 +555,9 @@ __global__ __launch_bounds__(kBlock) void k_lnhead_bwd(const float* __restrict__
 // buffer left by k_lnhead_bwd cost that kernel 126 -> 265 us and this one a third load stream (259 us).
 constexpr int kHeadChunks = 8;    // sample chunks per (relation, channel): 95.7 / 90.0 / 88.7 us at 4 / 8 / 16 (PEMSD7 size)
 
-template <int T>
-__global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ dout, const float* __restrict__ x,
-                                                    float* __restrict__ part, int B, int C, int N, int To) {
-  __shared__ float red[kBlock / kWave][256];
-  const int c = blockIdx.y, j = blockIdx.x, rel = blockIdx.z;   // B = samples per relation
-  const int b0 = rel * B + (int)((long long)B * j / gridDim.x), b1 = rel * B + (int)((long long)B * (j + 1) / gridDim.x);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const int m = lane & 15, kq = lane >> 4;
-  const int mo = min(m, To - 1), mt = min(m, T - 1);
-  const float omask = m < To ? 1.f : 0.f, tmask = m < T ? 1.f : 0.f;
-  constexpr int kWaves = kBlock / kWave;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int b = b0; b < b1; ++b) {
-    const float* dsrc = dout + (size_t)b * N * To + mo;
-    const float* xsrc = x + ((size_t)b * C + c) * N * T + mt;
-    for (int s0 = 4 * wave * kTdaUnroll; s0 < N; s0 += 4 * kWaves * kTdaUnroll) {
-      float av[kTdaUnroll], bv[kTdaUnroll];
-#pragma unroll
-      for (int u = 0; u < kTdaUnroll; ++u) {
-        const int n = s0 + 4 * u + kq;
-        const int nc = min(n, N - 1);
-        const float keep = n < N ? 1.f : 0.f;
-        av[u] = dsrc[(size_t)nc * To] * (keep * omask);
-        bv[u] = xsrc[(size_t)nc * T] * (keep * tmask);
-      }
-#pragma unroll
-      for (int u = 0; u < kTdaUnroll; ++u) acc = mfma_16x16x4(av[u], bv[u], acc);
-    }
-  }
-  // D[o = 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) red[wave][(4 * kq + reg) * 16 + m] = acc[reg];
-  __syncthreads();
-  for (int i = threadIdx.x; i < To * T; i += kBlock) {
-    const int o = i / T, t = i - o * T;
-    const int e = o * 16 + t;
-    part[((((size_t)rel * gridDim.y + c) * gridDim.x + j) * To * T) + i] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-  }
-}
-
-
-// T_out > 16: k_head_dW with OT tiles of 16 outputs, each x float loaded once for all of them (one MFMA per tile and k-step).
+// OT tiles of 16 outputs, each x float loaded once for all of them (one MFMA per tile and k-step); OT = 1 is the T_out <= 16 form.
 template <int T, int OT>
-__global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restrict__ dout, const float* __restrict__ x,
+__global__ __launch_bounds__(kBlock) void k_head_dW(const float* __restrict__ dout, const float* __restrict__ x,
                                                     float* __restrict__ part, int B, int C, int N, int To) {
   __shared__ float red[kBlock / kWave][256 * OT];
   const int c = blockIdx.y, j = blockIdx.x, rel = blockIdx.z;   // B = samples per relation
@@ -785,28 +576,43 @@ __global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restric
   constexpr int kWaves = kBlock / kWave;
   f32x4 acc[OT];
 #pragma unroll
-  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ot = 0; ot < OT; ++ot) acc[ot] = f32x4_zero();
   for (int b = b0; b < b1; ++b) {
-    // one base pointer per operand and 32-bit element offsets, all loads issued before any use: with a pointer per tile
-    // (and the masks applied inside the load loop) hipcc put an s_waitcnt vmcnt(0) behind every load at OT = 2, 3
-    // (598 us at T_out = 36 against 207 us at 64, where it did not)
-    const float* dsrc = dout + (size_t)b * N * To;
-    const float* xsrc = x + ((size_t)b * C + c) * N * T;
     for (int s0 = 4 * wave * kTdaUnroll; s0 < N; s0 += 4 * kWaves * kTdaUnroll) {
       float av[OT][kTdaUnroll], bv[kTdaUnroll];
+      if constexpr (OT == 1) {
+        // a pointer per operand (64-bit row offsets), the masks applied in the load loop: the T_out <= 16 kernels' code as
+        // it has always been -- the form below changes it (profiles/branch_shared/lab_variants.txt)
+        const float* dsrc = dout + (size_t)b * N * To + mo[0];
+        const float* xsrc = x + ((size_t)b * C + c) * N * T + mt;
 #pragma unroll
-      for (int u = 0; u < kTdaUnroll; ++u) {
-        const int nc = min(s0 + 4 * u + kq, N - 1);
+        for (int u = 0; u < kTdaUnroll; ++u) {
+          const int n = s0 + 4 * u + kq;
+          const int nc = min(n, N - 1);
+          const float keep = n < N ? 1.f : 0.f;
+          av[0][u] = dsrc[(size_t)nc * To] * (keep * omask[0]);
+          bv[u] = xsrc[(size_t)nc * T] * (keep * tmask);
+        }
+      } else {
+        // one base pointer per operand and 32-bit element offsets, all loads issued before any use: with a pointer per tile
+        // (and the masks applied inside the load loop) hipcc put an s_waitcnt vmcnt(0) behind every load at OT = 2, 3
+        // (598 us at T_out = 36 against 207 us at 64, where it did not)
+        const float* dsrc = dout + (size_t)b * N * To;
+        const float* xsrc = x + ((size_t)b * C + c) * N * T;
 #pragma unroll
-        for (int ot = 0; ot < OT; ++ot) av[ot][u] = dsrc[nc * To + mo[ot]];
-        bv[u] = xsrc[nc * T + mt];
-      }
+        for (int u = 0; u < kTdaUnroll; ++u) {
+          const int nc = min(s0 + 4 * u + kq, N - 1);
 #pragma unroll
-      for (int u = 0; u < kTdaUnroll; ++u) {
-        const float keep = s0 + 4 * u + kq < N ? 1.f : 0.f;
-        bv[u] *= keep * tmask;   // a zero x row (or timestep) clears the products of every tile
+          for (int ot = 0; ot < OT; ++ot) av[ot][u] = dsrc[nc * To + mo[ot]];
+          bv[u] = xsrc[nc * T + mt];
+        }
 #pragma unroll
-        for (int ot = 0; ot < OT; ++ot) av[ot][u] *= omask[ot];
+        for (int u = 0; u < kTdaUnroll; ++u) {
+          const float keep = s0 + 4 * u + kq < N ? 1.f : 0.f;
+          bv[u] *= keep * tmask;   // a zero x row (or timestep) clears the products of every tile
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot) av[ot][u] *= omask[ot];
+        }
       }
 #pragma unroll
       for (int u = 0; u < kTdaUnroll; ++u)
@@ -814,17 +620,8 @@ __global__ __launch_bounds__(kBlock) void k_head_dW_tiles(const float* __restric
         for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma_16x16x4(av[ot][u], bv[u], acc[ot]);
     }
   }
-  // D[o = 16 ot + 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order
-#pragma unroll
-  for (int ot = 0; ot < OT; ++ot)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) red[wave][256 * ot + (4 * kq + reg) * 16 + m] = acc[ot][reg];
-  __syncthreads();
-  for (int i = threadIdx.x; i < To * T; i += kBlock) {
-    const int o = i / T, t = i - o * T;
-    const int e = o * 16 + t;   // = 256 (o / 16) + 16 (o % 16) + t
-    part[((((size_t)rel * gridDim.y + c) * gridDim.x + j) * To * T) + i] = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-  }
+  // D[o = 16 ot + 4 * (lane >> 4) + reg][t = lane & 15]; the four waves' tiles are added in a fixed order (row_kernels.hpp)
+  mfma_tiles_partial<T>(acc, red, part + (((size_t)rel * gridDim.y + c) * gridDim.x + j) * To * T, To * T);
 }
 
 // the buffer holds the pre-laid-out weights [R,C,T,16 OT] (R <= B, T <= 16); never smaller than the channel-chunk partials
@@ -835,116 +632,43 @@ size_t head_fwd_partial_floats(int B, int C, int N, int To) {
 }
 size_t head_dw_partial_floats(int C, int T, int To, int R) { return (size_t)R * C * kHeadChunks * To * T; }
 
-// T_out in (16, 64]: OT = ceil(T_out / 16) output tiles; the launchers below keep their T_out <= 16 launches as they were
-// and hand the wider heads to these, which launch the same grids with the OT-tile kernels.
-#define MSGAT_OT_DISPATCH(To, FN, ...)                      \
-  switch (cdiv(To, kHeadTo)) {                              \
-    case 2: return FN<2>(__VA_ARGS__);                      \
-    case 3: return FN<3>(__VA_ARGS__);                      \
-    case 4: return FN<4>(__VA_ARGS__);                      \
-    default: return MSGAT_ERR_UNSUPPORTED;                  \
-  }
-
-template <int OT>
-static int launch_head_fwd_tiles(const float* x, const float* W, const float* bias, float* out, float* part, int B, int C,
-                                 int N, int T, int To, int R, hipStream_t s, int ln, const float* lnw, const float* lnb,
-                                 float eps, float* xn) {
-  const int Bg = B / R;
-  const int total = R * C * T * kHeadTo * OT;
-  if ((size_t)total > head_fwd_partial_floats(B, C, N, To)) return MSGAT_ERR_WORKSPACE;
-  hipLaunchKernelGGL(k_head_wperm<OT>, dim3(cdiv(total, kBlock)), dim3(kBlock), 0, s, W, part, C, T, To, total);
-  MSGAT_CHECK_LAUNCH();
-  dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
-  if (ln) {
-    if (int st = launch_on_T(T, [&](auto t) {
-          hipLaunchKernelGGL((k_head_fwd_tiles<decltype(t)::value, true, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out,
-                             C, N, To, Bg, lnw, lnb, eps, xn);
-        }))
-      return st;
-  } else {
-    if (int st = launch_on_T(T, [&](auto t) {
-          hipLaunchKernelGGL((k_head_fwd_tiles<decltype(t)::value, false, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out,
-                             C, N, To, Bg, lnw, lnb, eps, nullptr);
-        }))
-      return st;
-  }
-  return MSGAT_OK;
-}
-
-template <int OT>
-static int launch_head_dx_tiles(const float* dout, const float* W, float* dx, int B, int C, int N, int T, int To, int R,
-                                hipStream_t s) {
-  const int Bg = B / R;
-  dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL((k_head_dx<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg);
-      }))
-    return st;
-  return MSGAT_OK;
-}
-
-template <int OT>
-static int launch_lnhead_bwd_tiles(const float* dout, const float* W, const float* x, const float* lnw, float* dx,
-                                   float* dlnw, float* dlnb, float* part, int B, int C, int N, int T, int To, int R,
-                                   float eps, int relu_mask, hipStream_t s) {
-  const int Bg = B / R;
-  dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);   // the grid of the T_out <= 16 form: the partials keep their size
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL((k_lnhead_bwd<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N,
-                           To, Bg, eps, relu_mask);
-      }))
-    return st;
-  return launch_reduce_split(part, R, Bg * (int)grid.y * (int)grid.x, 2 * T, dlnw, T, dlnb, T, s);
-}
-
-template <int OT>
-static int launch_head_dW_tiles(const float* dout, const float* x, float* dWc, float* part, int B, int C, int N, int T,
-                                int To, int R, hipStream_t s) {
-  dim3 grid(kHeadChunks, C, R);
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL((k_head_dW_tiles<decltype(t)::value, OT>), grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N,
-                           To);
-      }))
-    return st;
-  return launch_reduce_groups(part, R * C, kHeadChunks, To * T, dWc, s);
-}
+// Every head launcher picks its kernel's tile count OT = ceil(T_out / 16) in [1, 4] once (MSGAT_ERR_UNSUPPORTED beyond 64
+// outputs); the grids, workspaces and partial layouts do not depend on it.
+template <typename F>
+static int dispatch_OT(int To, F&& f) { return dispatch_range<1, 4>(cdiv(To, kHeadTo), f); }
 
 int launch_head_fwd(const float* x, const float* W, const float* bias, float* out, float* part, int B, int C, int N,
                     int T, int To, int R, hipStream_t s, int ln, const float* lnw, const float* lnb, float eps, float* xn) {
-  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_fwd_tiles, x, W, bias, out, part, B, C, N, T, To, R, s, ln, lnw, lnb, eps, xn);
-  // the matrix-core form needs no channel-chunk partials; the buffer holds the weights in staging order
-  const int Bg = B / R;
-  const int total = R * C * T * kHeadTo;
-  if ((size_t)total > head_fwd_partial_floats(B, C, N, To)) return MSGAT_ERR_WORKSPACE;
-  hipLaunchKernelGGL(k_head_wperm, dim3(cdiv(total, kBlock)), dim3(kBlock), 0, s, W, part, C, T, To, total);
-  MSGAT_CHECK_LAUNCH();
-  dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
-  if (ln) {
-    if (int st = launch_on_T(T, [&](auto t) {
-          hipLaunchKernelGGL((k_head_fwd<decltype(t)::value, true>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To,
-                             Bg, lnw, lnb, eps, xn);
-        }))
-      return st;
-  } else {
-    if (int st = launch_on_T(T, [&](auto t) {
-          hipLaunchKernelGGL((k_head_fwd<decltype(t)::value, false>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To,
-                             Bg, lnw, lnb, eps, nullptr);
-        }))
-      return st;
-  }
-  return MSGAT_OK;
+  return dispatch_OT(To, [&](auto ot) -> int {
+    constexpr int OT = decltype(ot)::value;
+    // the matrix-core form needs no channel-chunk partials; the buffer holds the weights in staging order
+    const int Bg = B / R;
+    const int total = R * C * T * kHeadTo * OT;
+    if ((size_t)total > head_fwd_partial_floats(B, C, N, To)) return MSGAT_ERR_WORKSPACE;
+    hipLaunchKernelGGL(k_head_wperm<OT>, dim3(cdiv(total, kBlock)), dim3(kBlock), 0, s, W, part, C, T, To, total);
+    MSGAT_CHECK_LAUNCH();
+    dim3 grid(cdiv(N, 16 * (kBlock / kWave)), B);
+    auto launch = [&](auto with_ln) {
+      constexpr bool LN = decltype(with_ln)::value;
+      return launch_on_T(T, [&](auto t) {
+        hipLaunchKernelGGL((k_head_fwd<decltype(t)::value, LN, OT>), grid, dim3(kBlock), 0, s, x, part, bias, out, C, N, To,
+                           Bg, lnw, lnb, eps, LN ? xn : nullptr);
+      });
+    };
+    return ln ? launch(std::true_type{}) : launch(std::false_type{});
+  });
 }
 
 int launch_head_dx(const float* dout, const float* W, float* dx, int B, int C, int N, int T, int To, int R,
                    hipStream_t s) {
-  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dx_tiles, dout, W, dx, B, C, N, T, To, R, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL(k_head_dx<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, W, dx, C, N, To, Bg);
-      }))
-    return st;
-  return MSGAT_OK;
+  return dispatch_OT(To, [&](auto ot) {
+    return launch_on_T(T, [&](auto t) {
+      hipLaunchKernelGGL((k_head_dx<decltype(t)::value, decltype(ot)::value>), grid, dim3(kBlock), 0, s, dout, W, dx, C, N,
+                         To, Bg);
+    });
+  });
 }
 
 size_t lnhead_partial_floats(int B, int C, int N, int T) {
@@ -955,13 +679,13 @@ size_t lnhead_partial_floats(int B, int C, int N, int T) {
 int launch_lnhead_bwd(const float* dout, const float* W, const float* x, const float* lnw, float* dx, float* dlnw,
                       float* dlnb, float* part, int B, int C, int N, int T, int To, int R, float eps, int relu_mask,
                       hipStream_t s) {
-  if (To > kHeadTo)
-    MSGAT_OT_DISPATCH(To, launch_lnhead_bwd_tiles, dout, W, x, lnw, dx, dlnw, dlnb, part, B, C, N, T, To, R, eps, relu_mask, s);
   const int Bg = B / R;
   dim3 grid(cdiv(N, kBlock), cdiv(C, kHeadCC), B);
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL(k_lnhead_bwd<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, W, x, lnw, dx, part, C, N, To,
-                           Bg, eps, relu_mask);
+  if (int st = dispatch_OT(To, [&](auto ot) {
+        return launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_lnhead_bwd<decltype(t)::value, decltype(ot)::value>), grid, dim3(kBlock), 0, s, dout, W, x,
+                             lnw, dx, part, C, N, To, Bg, eps, relu_mask);
+        });
       }))
     return st;
   // a relation's blocks are contiguous (b-major): J = Bg * channel chunks * node blocks partials of 2T columns each
@@ -971,10 +695,12 @@ int launch_lnhead_bwd(const float* dout, const float* W, const float* x, const f
 // dWc[c][o][t] (the caller permutes to the convolution's [To][T][1][C] layout)
 int launch_head_dW(const float* dout, const float* x, float* dWc, float* part, int B, int C, int N, int T, int To,
                    int R, hipStream_t s) {
-  if (To > kHeadTo) MSGAT_OT_DISPATCH(To, launch_head_dW_tiles, dout, x, dWc, part, B, C, N, T, To, R, s);
   dim3 grid(kHeadChunks, C, R);
-  if (int st = launch_on_T(T, [&](auto t) {
-        hipLaunchKernelGGL(k_head_dW<decltype(t)::value>, grid, dim3(kBlock), 0, s, dout, x, part, B / R, C, N, To);
+  if (int st = dispatch_OT(To, [&](auto ot) {
+        return launch_on_T(T, [&](auto t) {
+          hipLaunchKernelGGL((k_head_dW<decltype(t)::value, decltype(ot)::value>), grid, dim3(kBlock), 0, s, dout, x, part,
+                             B / R, C, N, To);
+        });
       }))
     return st;
   return launch_reduce_groups(part, R * C, kHeadChunks, To * T, dWc, s);   // dWc [R,C,To,T]

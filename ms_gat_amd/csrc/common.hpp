@@ -221,6 +221,20 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // are done.  Safe as long as at least N operations were really issued behind the one that is waited for.
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// Sum over the 64 lanes of a wave, result in lane 63: six v_add_f32 with DPP operands (quad_perm xor 1 / xor 2,
+// row_half_mirror, row_mirror, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) -- no LDS crossbar.
+// k_aggfirst_bwd (project.hip) reduces Co * C sums per wave this way; as __shfl_xor butterflies (ds_bpermute_b32 + address
+// arithmetic per step) the reduction was most of its instructions: 24.5 us at PEMSD4 (C = 3) for 28 MB.  k_ln_fwd's fused
+// pooling (layernorm.hip) is the other user.  Fixed order.
+__device__ __forceinline__ float wave_sum_to_lane63(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
+  return v;
+}
 #endif
 
 // Diagnostic builds only (tools/*_stamps.hip compile a kernel file with -DMSGAT_STAMPS): s_memtime

@@ -11,50 +11,10 @@
 //   backward  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w
 //             dw[t] = sum_rows dy * xhat,  db[t] = sum_rows dy     (per-block partials, fixed-order sum)
 #include "common.hpp"
+#include "row_kernels.hpp"
 #include "rowtile.hpp"
 
 namespace msgat {
-
-template <int T>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, float (&v)[T]) {
-#pragma unroll
-  for (int t4 = 0; t4 < T / 4; ++t4) {
-    const float4 a = reinterpret_cast<const float4*>(p)[t4];
-    v[4 * t4 + 0] = a.x; v[4 * t4 + 1] = a.y; v[4 * t4 + 2] = a.z; v[4 * t4 + 3] = a.w;
-  }
-}
-template <int T>
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&v)[T]) {
-#pragma unroll
-  for (int t4 = 0; t4 < T / 4; ++t4)
-    reinterpret_cast<float4*>(p)[t4] = make_float4(v[4 * t4], v[4 * t4 + 1], v[4 * t4 + 2], v[4 * t4 + 3]);
-}
-// Centres a row in place and returns rstd.  The mean is taken of the differences to the row's first
-// value (exact for nearby floats), so a large common offset costs no accuracy -- the two-pass
-// formula on shifted data.
-template <int T>
-__device__ __forceinline__ float centre_row(float (&x)[T], float eps) {
-  const float x0 = x[0];
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) { x[t] -= x0; s += x[t]; }
-  const float md = s * (1.0f / T);
-  float v = 0.f;
-#pragma unroll
-  for (int t = 0; t < T; ++t) { x[t] -= md; v = fmaf(x[t], x[t], v); }
-  return rsqrtf(v * (1.0f / T) + eps);
-}
-
-// Sum over the 64 lanes of a wave, result in lane 63 (six DPP adds, fixed order: project.hip's wave_sum_to_lane63)
-__device__ __forceinline__ float ln_wave_sum63(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
-  return v;
-}
 
 // pool_w / pool_part (optional, N >= 64): the node pooling of the OUTPUT, p[s,t] = sum_n pool_w[n] y[s,n,t] over its
 // [N,T] slabs (attention.py:89 on MEAM's normalised input), out of this pass: a wave's 64 consecutive rows lie in at
@@ -98,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void k_ln_fwd(const float* __restrict__ x, 
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         const float c = pw * v[t];
-        const float sa = ln_wave_sum63(inA ? c : 0.f), sb = ln_wave_sum63(inA ? 0.f : c);
+        const float sa = wave_sum_to_lane63(inA ? c : 0.f), sb = wave_sum_to_lane63(inA ? 0.f : c);
         if (lane == kWave - 1) { out[t] = sa; out[T + t] = sb; }
       }
     }
@@ -143,9 +103,9 @@ __global__ __launch_bounds__(kBlock) void k_ln_bwd(const float* __restrict__ x, 
   if (add != nullptr) add += (size_t)blockIdx.y * rows * T;
   __shared__ float4 tiles[kBlock / kWave][RowTile<T>::kFloat4s];
   const RowTile<T> rt(tiles[threadIdx.x >> 6], threadIdx.x & (kWave - 1));
-  float wv[T], dw[T], db[T];
+  float wv[T], dwb[2][T];   // dwb: this lane's share of (dweight, dbias)
 #pragma unroll
-  for (int t = 0; t < T; ++t) { wv[t] = w ? w[blockIdx.y * T + t] : 1.f; dw[t] = 0.f; db[t] = 0.f; }
+  for (int t = 0; t < T; ++t) { wv[t] = w ? w[blockIdx.y * T + t] : 1.f; dwb[0][t] = 0.f; dwb[1][t] = 0.f; }
   for (long long r0 = ((long long)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)) * kWave; r0 < rows;
        r0 += (long long)gridDim.x * kBlock) {
     const int nf = (int)min((long long)kWave, rows - r0) * (T / 4);
@@ -183,49 +143,17 @@ __global__ __launch_bounds__(kBlock) void k_ln_bwd(const float* __restrict__ x, 
 #pragma unroll
       for (int t = 0; t < T; ++t) { xv[t] = 0.f; gv[t] = 0.f; }
     }
-    unsigned positive = 0;  // x > 0, per element: x is a ReLU output when relu_mask is set
-#pragma unroll
-    for (int t = 0; t < T; ++t) positive |= (xv[t] > 0.f ? 1u : 0u) << t;
-    const float rstd = centre_row<T>(xv, eps);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      xv[t] *= rstd;                  // xhat
-      db[t] += gv[t];
-      dw[t] = fmaf(gv[t], xv[t], dw[t]);
-      gv[t] *= wv[t];                 // g = dy * w
-      s1 += gv[t];
-      s2 = fmaf(gv[t], xv[t], s2);
-    }
-    s1 *= (1.0f / T);
-    s2 *= (1.0f / T);
-#pragma unroll
-    for (int t = 0; t < T; ++t) gv[t] = rstd * (gv[t] - s1 - xv[t] * s2);
+    const unsigned positive = ln_bwd_row<T>(xv, gv, wv, eps, dwb);   // x > 0 per element, gv = dx (row_kernels.hpp)
     if (add != nullptr) {  // the gradient that reached x along its other path (MEAM's residual convolution reads x too)
       float av[T];
       load_row<T>(add + r * T, av);
 #pragma unroll
       for (int t = 0; t < T; ++t) gv[t] += av[t];
     }
-    if (relu_mask) {  // the ReLU that produced x (MEAM's tail, msgat.py:131): its backward, applied where x is at hand
-#pragma unroll
-      for (int t = 0; t < T; ++t) gv[t] = ((positive >> t) & 1u) ? gv[t] : 0.f;
-    }
+    if (relu_mask) relu_mask_row<T>(gv, positive);   // x is a ReLU output then: its backward, applied where x is at hand
     rt.store(dx + r0 * T, nf, gv);
   }
-  // block partial of (dw, db): wave shuffle tree, then the 4 waves in a fixed order
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    float a = dw[t], c = db[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); c += __shfl_xor(c, o); }
-    if (lane == 0) { red[wave][t] = a; red[wave][T + t] = c; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 * T)
-    part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * T + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  block_partial(dwb, red, part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * T);   // (dw | db)
 }
 
 static int ln_blocks(long long rows) {

@@ -45,20 +45,6 @@ int launch_qonly(const float* x, const float* alpha, float* q, int G, int Bg, in
 // partial per block, fixed order everywhere.
 constexpr int kAfChunk = 8;
 
-// Sum over the 64 lanes of a wave, result in lane 63: six v_add_f32 with DPP operands (quad_perm xor 1 / xor 2,
-// row_half_mirror, row_mirror, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) -- no LDS crossbar.
-// The kernel reduces Co * C sums per wave this way; as __shfl_xor butterflies (ds_bpermute_b32 + address arithmetic per
-// step) the reduction was most of its instructions: 24.5 us at PEMSD4 (C = 3) for 28 MB.  Fixed order.
-__device__ __forceinline__ float wave_sum_to_lane63(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
-  return v;
-}
-
 // ONES: a virtual channel of ones behind y's C real ones -- column C of the partial is sum_p dz[o,p], the bias gradient of a
 // 1x1 convolution with C <= 3 input channels (round 5: the first block's residual / tap / CACN convolutions take this
 // kernel for their whole backward through msgat_contract_mix_segments; as contraction + projection they read the

@@ -1,6 +1,7 @@
 """GPU: the prediction head at long forecast horizons, 16 < T_out <= 64 (the reference's `--out-timesteps`, main.py:34,
 which sizes the component head Conv2d(T_in -> T_out, [1, C]) of msgat.py:153,159).  The head kernels run such a horizon
-as ceil(T_out / 16) output tiles of 16 (csrc/branches.hip); T_out <= 16 keeps its own kernels.
+as ceil(T_out / 16) output tiles of 16 (csrc/branches.hip); T_out <= 16 is the one-tile instance of the same kernel
+templates, picked by the same launchers.
 
 Against the float64 op sequence (conv2d, LayerNorm) at 1e-4 relative, the reference's own model at the fixtures of
 tests/golden/make_golden_horizon.py, and the engine's HIP-graph replay against eager steps."""
@@ -102,6 +103,40 @@ def test_head_and_ln_head_match_the_float64_convolution_at_long_horizons(T, To):
     assert rel_err(out.double(), o64) < TOL, "ln out"
     for name, a, b in (("ln dx", gx, gx64), ("ln dW", gW, gW64), ("ln dbias", gb, gb64), ("dln_weight", glw, glw64),
                        ("dln_bias", glb, glb64)):
+        if b is not None:
+            assert rel_err(a.double(), b) < TOL, name
+
+
+TILE_SWITCH_HORIZONS = (1, 15, 16, 17, 49, 64)
+# (N, C): a node tail inside one wave, then one node past a whole block; a channel count one past the forward's 32-channel
+# chunk, then one past the backward's 8-channel chunk
+TILE_SWITCH_SHAPES = ((17, 33), (257, 9))
+
+
+@pytest.mark.parametrize("shape", TILE_SWITCH_SHAPES, ids=lambda s: f"n{s[0]}c{s[1]}")
+@pytest.mark.parametrize("To", TILE_SWITCH_HORIZONS)
+def test_head_launchers_pick_the_tile_count_at_every_switch(To, shape):
+    """One launcher per entry point picks ceil(T_out / 16) in [1, 4]: T_out on both sides of the first switch, at one output,
+    inside the last tile and at the limit, output and every gradient of ops.head and ops.ln_head against float64."""
+    i = TILE_SWITCH_HORIZONS.index(To) * len(TILE_SWITCH_SHAPES) + TILE_SWITCH_SHAPES.index(shape)
+    T = (4, 8, 12, 16)[i % 4]
+    _, _, _, relu, affine = _case(i, T, To)
+    (N, C), R, B = shape, 2, 4
+    x, W, hb, lw, lb, dout = _inputs(B, R, C, N, T, To, relu, seed=2000 + i)
+    if not affine:
+        hb = lw = lb = None
+    out, (gx, gW, gb, _, _) = _run(x, W, hb, None, None, dout, ln=False, relu=False)
+    o64, gx64, (gW64, gb64, _, _) = _ref64(x, W, hb, None, None, dout, R, ln=False)
+    assert out.shape == (B, N, To)
+    for name, a, b in (("out", out, o64), ("dx", gx, gx64), ("dW", gW, gW64), ("dbias", gb, gb64)):
+        if b is not None:
+            assert rel_err(a.double(), b) < TOL, name
+    out, (gx, gW, gb, glw, glb) = _run(x, W, hb, lw, lb, dout, ln=True, relu=relu)
+    o64, gx64, (gW64, gb64, glw64, glb64) = _ref64(x, W, hb, lw, lb, dout, R, ln=True)
+    if relu:
+        gx64 = gx64 * (x > 0)                            # the mask of the ReLU that produced x (relu_input)
+    for name, a, b in (("ln out", out, o64), ("ln dx", gx, gx64), ("ln dW", gW, gW64), ("ln dbias", gb, gb64),
+                       ("dln_weight", glw, glw64), ("dln_bias", glb, glb64)):
         if b is not None:
             assert rel_err(a.double(), b) < TOL, name
 

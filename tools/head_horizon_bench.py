@@ -5,7 +5,7 @@ and 24.  HIP events; prints one JSON line.
     python tools/head_horizon_bench.py [--no-step] [--reps 20]
 
 Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/head_horizon_bench.py
---no-step --reps 5` (k_head_fwd / k_head_fwd_tiles, k_lnhead_bwd, k_head_dW / k_head_dW_tiles)."""
+--no-step --reps 5` (k_head_fwd, k_lnhead_bwd, k_head_dW: one template each, T_out <= 16 is its one-tile instance)."""
 import argparse
 import json
 import os

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Device code of two source trees, compared per kernel symbol (needs hipcc, no GPU).
 
-    python tools/isa_diff.py PARENT_TREE TREE [FILE.hip ...] > profiles/<change>/isa_parent_vs_tree.txt
+    python tools/isa_diff.py PARENT_TREE TREE [--pair=OLD=NEW ...] [FILE.hip ...] > profiles/<change>/isa_parent_vs_tree.txt
 
 Every csrc/*.hip of both trees (or only the files named) is compiled with the product flags plus `--offload-device-only -S`.  A kernel's text is
 its body (label to .Lfunc_end) and its .amdhsa_kernel block (registers, LDS, scratch), with comment lines and
 .file / .ident dropped and local label numbers normalised, so a kernel that only moved to another file or position
 compares equal.  One line per kernel: identical, or the number of differing lines.
+
+A kernel that changed its symbol on purpose (a merged template, a new template argument) is paired explicitly: --pair=OLD=NEW
+rewrites the parent's symbols with re.sub(OLD, NEW) -- in its kernels' text as well -- before the comparison; the pairs are
+listed at the head of the output.
 """
 import concurrent.futures as cf
 import difflib
@@ -59,10 +63,27 @@ def kernels(tree, tmp, only):
     return found
 
 
+def renamed(found, pairs):
+    """the parent's kernels under the symbols the tree gives them"""
+    out = {}
+    for name, (src, body) in found.items():
+        new = name
+        for old, repl in pairs:
+            new = re.sub(old, repl, new)
+        if new != name:
+            body = [ln.replace(name, new) for ln in body]
+        out[new] = (src, body)
+    return out
+
+
 def main():
-    parent, tree, only = sys.argv[1], sys.argv[2], sys.argv[3:]
+    parent, tree = sys.argv[1], sys.argv[2]
+    pairs = [tuple(a[len("--pair="):].split("=", 1)) for a in sys.argv[3:] if a.startswith("--pair=")]
+    only = [a for a in sys.argv[3:] if not a.startswith("--pair=")]
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        a, b = kernels(parent, ta, only), kernels(tree, tb, only)
+        a, b = renamed(kernels(parent, ta, only), pairs), kernels(tree, tb, only)
+    for old, repl in pairs:
+        print(f"# parent symbols paired with the tree's: {old} -> {repl}")
     differing = 0
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
