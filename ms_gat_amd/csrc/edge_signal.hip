@@ -3,7 +3,9 @@
 //
 //   torch ops              forward two [B,nnz,d] gathers, a product, a reduction and an add; backward a batch sum, two products
 //                          and two index_add_ scatters whose summation order torch does not promise.
-//   here                   one launch each way, no atomics, nothing zeroed beforehand, nothing read back.
+//   here                   one launch each way, no atomics, nothing zeroed beforehand (held to it by
+//                          tests/test_gpu_poisoned_buffers.py::test_edge_weight_op: every output pre-filled three ways,
+//                          equal bits), nothing read back.
 //     k_edge_signal_fwd    a lane per edge, a block row per sample stripe: the lane reads its two node indices and base[e]
 //                          once and walks the stripe's samples; per sample the two d-float rows arrive as 16-byte pieces.
 //                          Each product is rounded, the products are added in ascending k and base[e] is added last, so

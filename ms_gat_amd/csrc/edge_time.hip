@@ -9,7 +9,9 @@
 //                        dout[b,e] to its base sum (a register) and to the running sums of the two table rows sample b
 //                        selected, which sit in an LDS column acc[row][lane] (a dynamic row index is an address in LDS; in
 //                        registers it would be scratch).  Every sum starts at +0 and adds in sample order, every row of both
-//                        tables is written (a row nobody selected is zero), nothing is atomic and nothing is read back.
+//                        tables is written (a row nobody selected is zero), nothing is atomic and nothing is read back;
+//                        nothing is zeroed beforehand either: tests/test_gpu_poisoned_buffers.py::test_edge_weight_op
+//                        pre-fills every output three ways and asks for equal bits.
 //                        The samples' clamped rows are staged in LDS a tile of kEtSamples at a time, so any B takes the same
 //                        path; a block keeps kEtRows table rows (hours first, then days: 31 for 24 + 7), more rows are
 //                        further block rows that each re-read dout.

@@ -5,7 +5,9 @@
 //   torch ops            forward a compare, a sum over T, a table gather, a [V,nnz] gather by column, a compare, a select and
 //                        a multiply (plus a select for the exempt edges); backward the same gate again or kept in between, a
 //                        multiply and a batch sum.
-//   here                 one launch each way, no atomics, nothing stored in between, nothing read back.
+//   here                 one launch each way, no atomics, nothing stored in between, nothing zeroed beforehand (checked by
+//                        tests/test_gpu_poisoned_buffers.py::test_edge_weight_op: outputs pre-filled three ways, equal
+//                        bits), nothing read back.
 //     k_edge_validity    a lane per edge, a block row per sample: the lane reads col(e) and exempt[e] once and walks its
 //                        block row's samples; per sample the T validity floats of the source node arrive as T/4 16-byte
 //                        pieces (kVec) or as T single loads (a base or sample stride that is not 16-byte aligned), the

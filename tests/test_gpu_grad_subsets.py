@@ -44,7 +44,6 @@ the node's forward is the fused LayerNorm-and-pooling pass (same parameter-set c
 another order than node_pool).  Hence the forward-bits checks: every subset against the full set, and each row once with
 NOTHING requiring grad in grad mode -- a wholly frozen block of a fine-tuned backbone.  The tee's node takes unused
 cotangents as None, and the output sweep runs its `dy is None` / `dpooled is None` branches."""
-import contextlib
 import copy
 import functools
 
@@ -54,6 +53,7 @@ import torch
 from conftest import assert_parity, record_err, rel_err
 
 import grad_subset_fixtures as gs
+from poison_fixtures import device_errors_end_the_session as _device_errors_end_the_session
 from oracle import dense_torch
 from ms_gat_amd import engine, ops
 
@@ -61,17 +61,6 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 WHAT = "grad_subsets"
 TOL = 1e-4
-
-
-@contextlib.contextmanager
-def _device_errors_end_the_session():
-    """A kernel form that faults leaves the device unusable: nothing more is launched on it, the session ends there"""
-    try:
-        yield
-    except RuntimeError as err:
-        if any(s in str(err) for s in ("HIP error", "CUDA error", "hipError", "illegal memory access")):
-            pytest.exit(f"device error, no further test is run: {err}", returncode=3)
-        raise
 
 
 def _run(row, inputs, cots, subset, outsel=None):
