@@ -67,7 +67,8 @@ extern "C" {
  *     + msgat_gather_accumulate and msgat_gather_accumulate_dev (gradient accumulation over the micro-batches of a window);
  *     + msgat_edge_validity{,_backward} (edges gated by the validity of their source node's input window, per sample);
  *     + msgat_ring_push and msgat_ring_windows (online forecasting: a ring of readings and the windows of its newest origin);
- *     + msgat_forecast_store and msgat_forecast_score{,_partial_doubles} (online forecasts scored as their readings arrive).
+ *     + msgat_forecast_store and msgat_forecast_score{,_partial_doubles} (online forecasts scored as their readings arrive);
+ *     + msgat_interval_update and msgat_interval_apply (calibrated prediction intervals from the settled errors).
  * 9: msgat_graph_t.val_sets (new last field: one adjacency value set per sample of a batched adjacency);
  * + msgat_graph_edge_values.
  * 8: - msgat_stage_aggregate_project (no caller: msgat_gacn_forward runs that stage itself); nothing else changed.
@@ -1140,6 +1141,44 @@ int msgat_forecast_score(const float* raw, const float* book, const int64_t* iss
                          int32_t C, int32_t N, int32_t T_out, int32_t Q, const float* levels, int32_t point, int64_t P,
                          int32_t has_null, float null_value, float mask_value, double* partials, double* sums,
                          double* node_sums, void* stream);
+
+/* ---- device: calibrated prediction intervals for online forecasts (no counterpart in the reference) ----
+ * Rolling split-conformal intervals around the point forecast: per series (n, h) the last W valid settled absolute errors
+ * |p - y| are kept, and the half-width r of level l is one order statistic of that window.  It reads the scoring book above
+ * (book, issued, clock: the same rows, stamps and validity rule) and keeps, in device memory, never read back in a step:
+ *       window      [N, T_out, W] fp32       a ring per series
+ *       cursor      [N, T_out] int32         c, taken as uint32: slot = c mod W, fill = min(c, W).  After an insert c + 1
+ *                                            while c < W, else W + (slot + 1) mod W: any word stays inside its window.
+ *       radius      [L, N, T_out] fp32       the current half-widths; +inf = no interval (a fresh state)
+ *       radius_book [P, L, N, T_out] fp32    the radii issued with the forecast of origin o, in row o mod P; trusted under
+ *                                            the book's test issued[row] == o && o >= 0 (a fresh one holds +inf)
+ *       counts      [L, N, T_out, 2] int64   {judged, covered}, zeroed by the caller
+ *       ranks       [L, W + 1] int32         ranks[l, m]: the 1-based order statistic used at fill m; 0 (or anything
+ *                                            outside 1 .. m) = no interval.  Built once on the host: the policy is not here.
+ * msgat_interval_update: raw [K, C, N] are the readings of the steps s + k, s = clock[0] -- enqueue it where
+ *     msgat_forecast_score is, BEFORE the msgat_ring_push that advances the clock.  One launch, a wave per series, the
+ *     window in registers.  For k = 0 .. K-1: if origin o = s + k - h carries its stamp and y = raw[k, 0, n] is valid,
+ *     a = |p - y| in fp32 with p = book[row(o), n, point T_out + h] (the scorer's |e|).  First it is JUDGED: for every level
+ *     whose issued radius r = radius_book[row(o), l, n, h] is finite, judged += 1 and covered += (a <= r) -- a NaN forecast
+ *     counts as not covered.  Then, if a is finite, it is INSERTED at the cursor's slot and the cursor advances.  After the
+ *     last k the changed slots and the cursor are written back and radius[l, n, h] = +inf for rank 0, else the
+ *     ranks[l, fill]-th smallest of the slots below fill: exactly a window element, bit for bit (a radix select over the
+ *     bit patterns, which order as unsigned integers because the inserted values are finite and non-negative).
+ * msgat_interval_apply: after the forecast pred [N, out] of origin clock[0] exists (beside msgat_forecast_store): one launch
+ *     over L N T_out elements, lo = p - r and hi = p + r (each one fp32 operation, p = pred[n, point T_out + h]), both
+ *     [L, N, T_out], and r goes into row clock[0] mod P of radius_book.  Twice at one origin changes nothing.
+ * Every cell has one owner: no reduction, no atomic.  Rows come from the 64-bit floor-mod of the scoring book: ANY clock
+ * content reads and writes inside the books, and settles nothing unless the stamps match.
+ * A NULL pointer: MSGAT_ERR_NULL.  K, C, N, T_out, out, L, W <= 0, P < T_out, out not a multiple of T_out or point outside
+ * [0, out / T_out): MSGAT_ERR_SHAPE, before any launch.  L > 4, W > 1024, T_out > 64, out > 64 or N above 2^31 - 256:
+ * MSGAT_ERR_UNSUPPORTED (apply takes no K, C, W). */
+int msgat_interval_update(const float* raw, const float* book, const int64_t* issued, const int64_t* clock,
+                          const float* radius_book, const int32_t* ranks, float* window, int32_t* cursor, float* radius,
+                          int64_t* counts, int32_t K, int32_t C, int32_t N, int32_t T_out, int32_t out, int32_t point,
+                          int64_t P, int32_t L, int32_t W, int32_t has_null, float null_value, void* stream);
+int msgat_interval_apply(const float* pred, const float* radius, const int64_t* clock, float* lo, float* hi,
+                         float* radius_book, int32_t N, int32_t T_out, int32_t out, int32_t point, int64_t P, int32_t L,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,9 @@ _PROTOTYPES = {
     "msgat_forecast_score_partial_doubles": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "msgat_forecast_score": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [c_float_p, C.c_int32, C.c_int64, C.c_int32,
                                                             C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "msgat_interval_update": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 6 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                             C.c_float, C.c_void_p]),
+    "msgat_interval_apply": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_void_p]),
 }
 
 _lock = threading.Lock()

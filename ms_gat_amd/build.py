@@ -21,8 +21,8 @@ INCLUDE = os.path.join(ROOT, "include")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(PKG, "libmsgat_hip.so")
 
-SOURCES = ["api.hip", "project.hip", "mfma.hip", "contract.hip", "dense.hip", "dense_bf16.hip", "scores.hip", "aggregate.hip", "reduce.hip", "layernorm.hip", "branches.hip", "smallatt.hip", "tail.hip", "edge_values.hip", "adjacency_grad.hip", "edge_weight_grad.hip", "attention_map.hip", "windows.hip", "edge_time.hip", "edge_signal.hip", "edge_dropout.hip", "edge_validity.hip", "online.hip", "online_score.hip", "graph_host.cpp"]
-HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "tail_terms.hpp"), os.path.join(CSRC, "sell.hpp"), os.path.join(CSRC, "edge_window.hpp"),os.path.join(CSRC, "rowtile.hpp"), os.path.join(CSRC, "row_kernels.hpp"), os.path.join(CSRC, "halfsplit.hpp"), os.path.join(CSRC, "softmax_recreate.hpp"), os.path.join(CSRC, "edge_batch.hpp"), os.path.join(INCLUDE, "msgat_hip.h")]
+SOURCES = ["api.hip", "project.hip", "mfma.hip", "contract.hip", "dense.hip", "dense_bf16.hip", "scores.hip", "aggregate.hip", "reduce.hip", "layernorm.hip", "branches.hip", "smallatt.hip", "tail.hip", "edge_values.hip", "adjacency_grad.hip", "edge_weight_grad.hip", "attention_map.hip", "windows.hip", "edge_time.hip", "edge_signal.hip", "edge_dropout.hip", "edge_validity.hip", "online.hip", "online_score.hip", "online_interval.hip", "graph_host.cpp"]
+HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "tail_terms.hpp"), os.path.join(CSRC, "sell.hpp"), os.path.join(CSRC, "edge_window.hpp"),os.path.join(CSRC, "rowtile.hpp"), os.path.join(CSRC, "row_kernels.hpp"), os.path.join(CSRC, "halfsplit.hpp"), os.path.join(CSRC, "softmax_recreate.hpp"), os.path.join(CSRC, "edge_batch.hpp"), os.path.join(CSRC, "score_clock.hpp"), os.path.join(INCLUDE, "msgat_hip.h")]
 # diagnostic translation units (never part of the product library): `build(lab=True)` / `--lab` adds them and their
 # extra, undeclared entry points for tools/stress_kernels.py --lab
 LAB_SOURCES = [os.path.join(ROOT, "tools", "agg_sell_lab.hip"), os.path.join(ROOT, "tools", "bwd_sell_lab.hip")]

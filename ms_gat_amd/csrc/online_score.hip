@@ -29,6 +29,7 @@
 // Rows come from a 64-bit floor-mod into [0, P) for ANY clock content (cold, negative, a wild word): no launch reads or
 // writes outside book and issued, and what does not carry the stamp settles nothing.
 #include "common.hpp"
+#include "score_clock.hpp"
 #include "tail_terms.hpp"
 
 namespace msgat {
@@ -37,20 +38,6 @@ constexpr int kScoreBlock = 64;          // one wave: the first launch's block, 
 constexpr int kScoreFinishBlock = 1024;
 constexpr int kScoreMaxT = 64;
 constexpr int kScoreNodeCols = 3;
-
-__device__ __forceinline__ long long score_floor_mod(long long a, long long n) {   // n > 0
-  const long long r = a % n;
-  return r < 0 ? r + n : r;
-}
-
-// two's-complement sum and difference: a wild clock word wraps instead of overflowing a signed type
-__device__ __forceinline__ long long score_wrap_add(long long a, long long b) {
-  return (long long)((unsigned long long)a + (unsigned long long)b);
-}
-
-__device__ __forceinline__ long long score_wrap_sub(long long a, long long b) {
-  return (long long)((unsigned long long)a - (unsigned long long)b);
-}
 
 __global__ __launch_bounds__(kScoreBlock) void k_forecast_store(const unsigned* __restrict__ pred,
                                                                 unsigned* __restrict__ book,

@@ -59,11 +59,31 @@ class OnlineForecaster:
     MAE and bias per sensor over all horizons, NaN where the count is 0.  `reset_scores()` zeroes the totals in place (the
     book stays: forecasts in flight are still settled).  `state_dict()` then also holds book, issued, score_sums and
     score_node_sums; a state without them loads as a cold book with zero totals.  Without `score` there is no buffer, no
-    state key and no launch of all this."""
+    state key and no launch of all this.
+
+    `intervals=0.9` or `(0.8, 0.95)` (needs `score=True`: it reads the scoring book) adds calibrated prediction intervals
+    around the point forecast, for any trained point model and with no retraining: rolling split-conformal half-widths
+    (`intervals.py`, csrc/online_interval.hip).  One to four nominal coverage levels, strictly increasing inside (0, 1).
+    Per sensor and horizon the last `interval_window` = W (1 .. 1024) VALID settled absolute errors are kept on the device,
+    and the half-width r of level c is the `ceil((m + 1) c)`-th smallest of the m held (`intervals.interval_ranks`); while
+    that rank does not exist, or m < `interval_min_count`, the series has no interval: r = +inf.  Under exchangeable
+    errors the interval covers with probability at least c.  `intervals()` -> `(lo, hi)`, each [L, N, T_out] on the
+    model's device, of the forecast most recently returned: lo = p - r, hi = p + r (static tensors on the captured path,
+    like the forecast; RuntimeError before the first forecast).  With a `score_quantiles` head the interval is around the
+    point level (`score_point`); conformalising the model's own quantile levels (CQR) is not provided.  Every settled
+    error is first JUDGED against the radii issued with its forecast, then inserted: `interval_scores(at=None)` reads
+    back once {"levels", "judged", "coverage", "width", "horizons": {the same per horizon}} -- coverage[l] = covered /
+    judged over the issued intervals that have settled, width[l] the mean 2 r over the series that now have a finite
+    radius (NaN where there is nothing to divide by) -- and `interval_node_scores()` -> float64 [N, L], the coverage per
+    sensor over all horizons, NaN where nothing was judged.  `reset_scores()` also zeroes the judged and covered counts
+    (windows and radii stay); `state_dict()` also holds interval_window, interval_cursor, interval_radius, interval_book
+    and interval_counts, and a state without them loads as empty windows, +inf radii and zero counts.  The captured step
+    becomes score -> interval update -> push -> advance -> windows -> forward -> store -> interval apply: still ONE replay,
+    two more kernels.  With `intervals=None` there is no buffer, no state key and no launch of all this."""
 
     def __init__(self, model: nn.Module, stats: "_data.SeriesStats", start_step: int, capacity: int | None = None,
                  hip_graph="auto", score: bool = False, score_quantiles=None, score_null_value="stats",
-                 score_mask_value: float = 0.0):
+                 score_mask_value: float = 0.0, intervals=None, interval_window: int = 288, interval_min_count=None):
         if hip_graph not in (True, False, "auto"):
             raise ValueError(f"hip_graph must be True, False or 'auto', not {hip_graph!r}")
         tensors = list(model.parameters()) + list(model.buffers())
@@ -110,6 +130,18 @@ class OnlineForecaster:
             null = stats.input_null_value if isinstance(score_null_value, str) else score_null_value   # "stats"
             self.score_null_value = None if null is None else float(null)
             self.score_mask_value = float(score_mask_value)
+        self.interval_levels = ()
+        self._interval_state = None           # (window, cursor, radius, radius_book, counts), sized with the book
+        if intervals is not None:
+            from . import intervals as _intervals
+            if not self.score:
+                raise ValueError("intervals needs score=True: it is calibrated on the errors the scoring book settles")
+            self.interval_levels = _intervals.interval_levels(intervals)
+            self.interval_window = int(interval_window)
+            self._interval_ranks = _intervals.interval_ranks(self.interval_levels, interval_window,
+                                                             interval_min_count).to(self.device)
+            self._interval_out = None         # (lo, hi) of the forecast most recently returned
+            self._interval_issued = False
         if on_gpu:
             from . import ops
             self._offsets = ops.window_offsets(self.hours, self.tau, dev)
@@ -165,6 +197,30 @@ class OnlineForecaster:
         if dev.type == "cuda":
             need = int(ops._lib.lib().msgat_forecast_score_partial_doubles(N, self.score_t_out, len(self.score_levels)))
             self._score_partials = torch.empty(need, dtype=torch.float64, device=dev)
+        if self.interval_levels:
+            from . import intervals as _intervals
+            n_levels = len(self.interval_levels)
+            self._interval_state = _intervals.interval_state(n_levels, N, self.score_t_out, self.interval_window,
+                                                             self.score_t_out, dev)
+            self._interval_out = self._interval_buffers()
+
+    def _interval_buffers(self):
+        shape = (len(self.interval_levels), self.n_nodes, self.score_t_out)
+        return (torch.zeros(shape, dtype=torch.float32, device=self.device),
+                torch.zeros(shape, dtype=torch.float32, device=self.device))
+
+    def _calibrate(self, reading: torch.Tensor, state, calibration, clock: torch.Tensor) -> None:
+        """The readings' settled errors: judged against the radii issued with their forecasts, then into the windows."""
+        from . import intervals as _intervals
+        window, cursor, radius, radius_book, counts = calibration
+        fn = _intervals.interval_update if self.device.type == "cuda" else _intervals._interval_update_torch
+        fn(reading, state[0], state[1], clock, radius_book, self._interval_ranks, window, cursor, radius, counts,
+           point=self.score_point, null_value=self.score_null_value)
+
+    def _apply(self, pred: torch.Tensor, calibration, out, clock: torch.Tensor) -> None:
+        from . import intervals as _intervals
+        fn = _intervals.interval_apply if self.device.type == "cuda" else _intervals._interval_apply_torch
+        fn(pred.contiguous(), calibration[2], clock, out[0], out[1], calibration[3], point=self.score_point)
 
     def _settle(self, reading: torch.Tensor, state, clock: torch.Tensor) -> None:
         book, issued, sums, node_sums = state
@@ -209,6 +265,8 @@ class OnlineForecaster:
         reading = self._checked(reading).to(self.device).contiguous()
         if self._score_state is not None:     # before the push: the clock still names the first of these steps
             self._settle(reading, self._score_state, self.clock)
+            if self._interval_state is not None:
+                self._calibrate(reading, self._score_state, self._interval_state, self.clock)
         self._push(reading, self.ring, self.clock)
         self._pushed = min(self._pushed + reading.shape[0], self.capacity)
 
@@ -220,6 +278,9 @@ class OnlineForecaster:
         if self.score:
             self._score_setup(pred.shape[-1])
             self._store(pred, self._score_state, self.clock)
+            if self.interval_levels:
+                self._apply(pred, self._interval_state, self._interval_out, self.clock)
+                self._interval_issued = True
         return pred
 
     def step(self, reading: torch.Tensor) -> torch.Tensor:
@@ -232,34 +293,45 @@ class OnlineForecaster:
         self._reading.copy_(reading, non_blocking=True)
         self._graph.replay()
         self._pushed = min(self._pushed + 1, self.capacity)
+        if self.interval_levels:
+            self._interval_issued = True
         return self._prediction
 
     def _capture(self) -> None:
         """Warm the whole step up on a side stream and on a SCRATCH ring and clock (the live ones must not move), then
         capture it on the live ones into the static buffers."""
         ring, clock, out = self.ring.clone(), self.clock.clone(), self._window_buffers()
-        scratch = None                        # the scoring state's scratch copy, made once the book is sized
+        scratch = calibration = None          # the scoring and interval states' scratch copies, made once they are sized
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(2):
                 if scratch is not None:
                     self._settle(self._reading, scratch, clock)
+                    if calibration is not None:
+                        self._calibrate(self._reading, scratch, calibration, clock)
                 self._push(self._reading, ring, clock)
                 pred = self._forward(self._windows(ring, clock, out=out))
                 if self.score:
                     self._score_setup(pred.shape[-1])
                     scratch = scratch or tuple(t.clone() for t in self._score_state)
                     self._store(pred, scratch, clock)
+                    if self.interval_levels:
+                        calibration = calibration or tuple(t.clone() for t in self._interval_state)
+                        self._apply(pred, calibration, self._interval_buffers(), clock)
         torch.cuda.current_stream(self.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             if self.score:
                 self._settle(self._reading, self._score_state, self.clock)
+                if self.interval_levels:
+                    self._calibrate(self._reading, self._score_state, self._interval_state, self.clock)
             self._push(self._reading, self.ring, self.clock)
             self._prediction = self._forward(self._windows(self.ring, self.clock, out=self._out))
             if self.score:
                 self._store(self._prediction, self._score_state, self.clock)
+                if self.interval_levels:
+                    self._apply(self._prediction, self._interval_state, self._interval_out, self.clock)
         self._graph = graph
 
     # ---- the scores, read back -------------------------------------------------------------------------------------------
@@ -320,11 +392,72 @@ class OnlineForecaster:
         if self._score_state is not None:
             self._score_state[2].zero_()
             self._score_state[3].zero_()
+        if self._interval_state is not None:
+            self._interval_state[4].zero_()
+
+    # ---- the intervals, and how they have done ----------------------------------------------------------------------------
+    def _need_intervals(self, what: str) -> None:
+        if not self.interval_levels:
+            raise RuntimeError(f"{what} needs OnlineForecaster(score=True, intervals=...)")
+
+    def intervals(self):
+        """`(lo, hi)`, each [L, N, T_out], of the forecast most recently returned (see the class docstring)."""
+        self._need_intervals("intervals()")
+        if not self._interval_issued:
+            raise RuntimeError("intervals() belongs to a forecast: none was made yet")
+        return self._interval_out
+
+    def interval_scores(self, at=None) -> dict:
+        """Coverage and width per level since the last `reset_scores()`, read back once (see the class docstring)."""
+        self._need_intervals("interval_scores()")
+        levels, nan = list(self.interval_levels), float("nan")
+        if self._interval_state is None:      # no forecast yet: nothing was issued
+            return {"levels": levels, "judged": [0] * len(levels), "coverage": [nan] * len(levels),
+                    "width": [nan] * len(levels), "horizons": {"judged": [[] for _ in levels],
+                                                               "coverage": [[] for _ in levels],
+                                                               "width": [[] for _ in levels]}}
+        _, _, radius, _, counts = self._interval_state
+        packed = torch.cat([counts.reshape(-1), radius.view(torch.int32).reshape(-1).to(torch.int64)]).cpu()
+        counts = packed[:counts.numel()].reshape(counts.shape)                                  # [L, N, T, 2]
+        radius = packed[counts.numel():].to(torch.int32).view(torch.float32).reshape(radius.shape)
+        per_h = counts.sum(1)                                                                   # [L, T, 2], in integers
+        finite = torch.isfinite(radius)
+        wide = torch.where(finite, 2.0 * radius.double(), torch.zeros((), dtype=torch.float64))
+        ratio = lambda a, b: (a / b if b else nan)  # noqa: E731
+        picks = range(self.score_t_out)
+        if at is not None:
+            for step in at:
+                if not 1 <= int(step) <= self.score_t_out:
+                    raise IndexError(f"horizon step {step} outside 1..{self.score_t_out}")
+            picks = [int(step) - 1 for step in at]
+        horizons = {"judged": [[int(per_h[l, h, 0]) for h in picks] for l in range(len(levels))],
+                    "coverage": [[ratio(int(per_h[l, h, 1]), int(per_h[l, h, 0])) for h in picks]
+                                 for l in range(len(levels))],
+                    "width": [[ratio(float(wide[l, :, h].sum()), int(finite[l, :, h].sum())) for h in picks]
+                              for l in range(len(levels))]}
+        total = per_h.sum(1)
+        return {"levels": levels, "judged": [int(t[0]) for t in total],
+                "coverage": [ratio(int(t[1]), int(t[0])) for t in total],
+                "width": [ratio(float(wide[l].sum()), int(finite[l].sum())) for l in range(len(levels))],
+                "horizons": horizons}
+
+    def interval_node_scores(self) -> torch.Tensor:
+        """float64 [N, L] on the host: the coverage per sensor over all horizons; NaN where nothing was judged."""
+        self._need_intervals("interval_node_scores()")
+        if self._interval_state is None:
+            return torch.full((self.n_nodes, len(self.interval_levels)), float("nan"), dtype=torch.float64)
+        per_node = self._interval_state[4].cpu().sum(2)                                         # [L, N, 2], in integers
+        judged, covered = per_node[..., 0], per_node[..., 1]
+        nan = torch.full((), float("nan"), dtype=torch.float64)
+        return torch.where(judged > 0, covered.double() / judged.clamp(min=1).double(), nan).t().contiguous()
 
     def state_dict(self) -> dict:
         state = {"ring": self.ring.detach().clone(), "clock": self.clock.detach().clone(), "start_step": self.start_step}
         if self._score_state is not None:
             state.update({k: t.detach().clone() for k, t in zip(self._SCORE_KEYS, self._score_state)})
+        if self._interval_state is not None:
+            from .intervals import STATE_KEYS
+            state.update({k: t.detach().clone() for k, t in zip(STATE_KEYS, self._interval_state)})
         return state
 
     _SCORE_KEYS = ("book", "issued", "score_sums", "score_node_sums")
@@ -346,6 +479,14 @@ class OnlineForecaster:
                 if tuple(state[key].shape) != tuple(mine.shape) or state[key].dtype != mine.dtype:
                     raise ValueError(f"state holds {key} {tuple(state[key].shape)} {state[key].dtype}; this forecaster's "
                                      f"is {tuple(mine.shape)} {mine.dtype}")
+        calibrated = False
+        if scored and self.interval_levels:
+            from .intervals import STATE_KEYS
+            calibrated = all(k in state for k in STATE_KEYS)
+            for key, mine in zip(STATE_KEYS, self._interval_state) if calibrated else ():
+                if tuple(state[key].shape) != tuple(mine.shape) or state[key].dtype != mine.dtype:
+                    raise ValueError(f"state holds {key} {tuple(state[key].shape)} {state[key].dtype}; this forecaster's "
+                                     f"is {tuple(mine.shape)} {mine.dtype}")
         self.ring.copy_(ring)                 # in place: a captured step keeps reading these addresses
         self.clock.copy_(clock)
         self.start_step, self._pushed = int(state["start_step"]), held
@@ -358,3 +499,15 @@ class OnlineForecaster:
             issued.fill_(ops.SCORE_NEVER)
             sums.zero_()
             node_sums.zero_()
+        if calibrated:
+            for key, mine in zip(STATE_KEYS, self._interval_state):
+                mine.copy_(state[key])
+        elif self._interval_state is not None:   # a state without them: empty windows, no intervals, zero counts
+            window, cursor, radius, radius_book, counts = self._interval_state
+            window.zero_()
+            cursor.zero_()
+            radius.fill_(float("inf"))
+            radius_book.fill_(float("inf"))
+            counts.zero_()
+        if self.interval_levels:
+            self._interval_issued = False        # lo and hi belong to a forecast of this state: the next one
