@@ -2046,7 +2046,10 @@ def temporal_attention_taps(pooled: torch.Tensor, Wt1: torch.Tensor, Wt2: torch.
 class _BiasJoinFunction(torch.autograd.Function):
     """wide [R,Co] + narrow [R,cb] added into its first cb columns: CACN's convolution bias joining the residual bias in
     front of MEAM's ReLU (both per-channel constants, msgat.py:94,123-131).  pad + add cost three launches forward and a
-    slice copy backward; here a copy and an in-place add, and backward hands out views of the incoming gradient."""
+    slice copy backward; here a copy and an in-place add, and backward hands the incoming gradient to `wide` and a copy
+    of its leading columns to `narrow`.  (Not a view of them: AccumulateGrad keeps a gradient it is the only holder of,
+    and a view counts as one, so the .grad of CACN's bias lay INSIDE the .grad of the residual bias -- a second backward
+    into them, or any in-place edit of one, changed the other.)"""
 
     @staticmethod
     def forward(ctx, wide, narrow):
@@ -2057,7 +2060,7 @@ class _BiasJoinFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return g, g[:, : ctx.cb]
+        return g, g[:, : ctx.cb].clone()
 
 
 def bias_join(wide: torch.Tensor, narrow: torch.Tensor) -> torch.Tensor:

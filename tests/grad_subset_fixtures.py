@@ -4,7 +4,8 @@ torch ops, evaluated in whatever dtype their arguments have.
 
 One `Row` per op and form: the library callable, its restatement, seeded CPU inputs, the names of its differentiable
 inputs.  `subsets` says which of them require grad in a run; `reference` differentiates the restatement for the same
-subset of inputs and the same subset of outputs.
+subset of inputs and the same subset of outputs.  `problem(name, seed=1)` is a second problem of a row -- the same shapes,
+call and graph, other values -- for the autograd-contract tests (test_gpu_autograd_contract.py); problem 0 is drawn as ever.
 
 Shapes are the smallest at which the kernel forms differ: R = 2 relations of Bg = 2 groups; widths 72 -> 24 and 5 -> 9 (no
 multiple of 4, 8 or 16; the causal convolution has no kernel for 5 -> 9 and runs 9 -> 9); N = 13 (156 positions: the
@@ -176,7 +177,7 @@ def gacn_dense(x, alpha, Wg, W, adj):
 class Row:
     name: str
     function: str                       # the torch.autograd.Function subclass of ops.py the row runs
-    make: Callable                      # () -> {input name: CPU tensor | None | plain value}, seeded
+    make: Callable                      # (seed=0) -> {input name: CPU tensor | None | plain value}, seeded by name and seed
     diff: tuple                         # names of the differentiable inputs
     lib: Callable                       # (ops, inputs) -> tuple of outputs
     dense: Callable                     # (inputs) -> tuple of outputs
@@ -199,8 +200,18 @@ def _n(gen, *shape, scale=1.0, shift=0.0):
 ROWS = []
 
 
+def seed_name(name, seed=0):
+    """What seeds the draws of a row's problem `seed`: the row's name for problem 0 (every value as it always was), the name
+    with a suffix for any other -- the same shapes, graph and call, other values"""
+    return name if not seed else f"{name} seed {seed}"
+
+
+def _seeded(make, name, seed=0):
+    return make(seed_name(name, seed))
+
+
 def _add(name, function, make, diff, lib, dense, bar, **kw):
-    ROWS.append(Row(name, function, functools.partial(make, name), tuple(diff), lib, dense, bar, **kw))
+    ROWS.append(Row(name, function, functools.partial(_seeded, make, name), tuple(diff), lib, dense, bar, **kw))
 
 
 # mix: backward launches dx (ops.py _MixFunction.backward `if need[0]`), dM (`if need[1]`) and dbias (`_channel_sums`) each
@@ -594,16 +605,18 @@ def _cast(v, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def problem(name):
-    """-> (row, inputs on the CPU in fp32, cotangents in fp32): seeded by the row's name; the cotangent of a ReLU row is
-    zero within MARGIN of the kink and, for a premasked row, wherever the output is zero"""
+def problem(name, seed=0, cot_seed=None):
+    """-> (row, inputs on the CPU in fp32, cotangents in fp32): seeded by the row's name (and `seed`, for a second problem
+    of the same shapes); the cotangent of a ReLU row is zero within MARGIN of the kink and, for a premasked row, wherever
+    the output is zero.  `cot_seed` (default: `seed`): the cotangent drawn as problem `cot_seed` draws it, masked for the
+    inputs of problem `seed` -- another cotangent for the same forward"""
     row = ROWS[[r.name for r in ROWS].index(name)]
-    inputs = row.make()
+    inputs = row.make(seed)
     with torch.no_grad():
         t64 = {k: _cast(v, torch.float64) for k, v in inputs.items()}
         outs = row.dense(t64)
         pres = row.pre(t64) if row.pre else None
-    g = _gen(name + " cotangent")
+    g = _gen(seed_name(name, seed if cot_seed is None else cot_seed) + " cotangent")
     cots = []
     for i, o in enumerate(outs):
         c = torch.randn(o.shape, generator=g)
@@ -635,10 +648,10 @@ def differentiable(outs, outsel=None):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, subset, outsel=None, dtype=torch.float64):
+def reference(name, subset, outsel=None, dtype=torch.float64, seed=0, cot_seed=None):
     """-> (outputs, {input name: gradient | None}) of the restatement by autograd on the CPU in `dtype`, exactly `subset`
-    requiring grad, a cotangent at the outputs `outsel` (None: all)"""
-    row, inputs, cots = problem(name)
+    requiring grad, a cotangent at the outputs `outsel` (None: all); `seed`, `cot_seed`: which problem (see `problem`)"""
+    row, inputs, cots = problem(name, seed, cot_seed)
     t = leaves(inputs, subset, dtype)
     outs = row.dense(t)
     sel = differentiable(outs, outsel)
@@ -653,12 +666,13 @@ MODEL_N, MODEL_B, MODEL_R, MODEL_T = 23, 3, 2, 12      # test_whole_model_matche
 SCENARIOS = ("input attribution", "head only", "biases frozen", "time embedding frozen")
 
 
-def model_problem(factory, cin):
-    """-> (model on the CPU, X, H, D, dout), drawn as test_whole_model_matches_the_dense_op_sequence draws them"""
+def model_problem(factory, cin, seed=0):
+    """-> (model on the CPU, X, H, D, dout), drawn as test_whole_model_matches_the_dense_op_sequence draws them; `seed`: a
+    second model and batch of the same shapes on the same graph"""
     import ms_gat_amd
     from ms_gat_amd import model
-    torch.manual_seed(7)
-    gen = torch.Generator().manual_seed(11)
+    torch.manual_seed(7 + seed)
+    gen = torch.Generator().manual_seed(11 + seed)
     N, B, Rm, T = MODEL_N, MODEL_B, MODEL_R, MODEL_T
     net = getattr(model, factory)(n_components=Rm, in_channels=cin, in_timesteps=T, out_timesteps=T, use_te=True,
                                   adj=ms_gat_amd.synthetic_adjacency(N, N + 7, seed=5))
