@@ -609,13 +609,13 @@ class FlatAdam(optim.Optimizer):
             self._gather_tables.clear()
             if self.guarded:          # here, not at the first guarded step: they exist before any capture
                 from . import _lib
-                chunk = int(_lib.lib().msgat_adam_chunk_elems())
+                chunk = int(_lib.checked().msgat_adam_chunk_elems())
                 n_chunks = sum(-(-p.numel() // chunk) for p in self._params)
                 old_guard = self._guard
                 self._guard = torch.zeros(_lib.GUARD_FLOATS, device=dev, dtype=torch.float32)
                 if old_guard is not None:     # new buffers (another layout or device): the counts so far go along
                     self._guard.copy_(old_guard)
-                self._guard_partials = torch.zeros(int(_lib.lib().msgat_grad_guard_partial_doubles(n_chunks)), device=dev,
+                self._guard_partials = torch.zeros(int(_lib.checked().msgat_grad_guard_partial_doubles(n_chunks)), device=dev,
                                                    dtype=torch.float64)
         self._grad_views = [self.flat_grad[o:o + p.numel()].view_as(p) for p, o in zip(self._params, self._offsets)]
         self._lr_on_device = float(self.param_groups[0]["lr"])
@@ -649,7 +649,7 @@ class FlatAdam(optim.Optimizer):
         hit = self._tables.get(key)
         if hit is None:
             from . import _lib
-            chunk = int(_lib.lib().msgat_adam_chunk_elems())
+            chunk = int(_lib.checked().msgat_adam_chunk_elems())
             ptrs, offs, lens, tens, act = [], [], [], [], []
             for i, (p, o, on) in enumerate(zip(self._params, self._offsets, active)):
                 if not on:
@@ -802,19 +802,15 @@ class FlatAdam(optim.Optimizer):
             # the norm of what the update is about to consume: the flat views (one GPU) or the all-reduced sum over
             # its clamped divisor (several ranks: the same bits, hence the same decision, on every rank)
             max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
-            st = _lib.lib().msgat_grad_guard(offs.data_ptr(), lens.data_ptr(), n, self.flat_grad.data_ptr(), divisor, max_norm,
-                                             self._guard_partials.data_ptr(), self._guard.data_ptr(), stream)
-            _lib.check(st, "msgat_grad_guard")
+            _lib.checked().msgat_grad_guard(offs.data_ptr(), lens.data_ptr(), n, self.flat_grad.data_ptr(), divisor, max_norm,
+                                            self._guard_partials.data_ptr(), self._guard.data_ptr(), stream)
         if self.shadow is not None:       # the guarded or the plain update, and the average, in the same launch
-            st = _lib.lib().msgat_adam_step_averaged(*adam, self._guard.data_ptr() if self.guarded else 0,
-                                                     self.shadow.data_ptr(), self.ema_decay, stream)
-            _lib.check(st, "msgat_adam_step_averaged")
+            _lib.checked().msgat_adam_step_averaged(*adam, self._guard.data_ptr() if self.guarded else 0,
+                                                    self.shadow.data_ptr(), self.ema_decay, stream)
         elif self.guarded:
-            st = _lib.lib().msgat_adam_step_guarded(*adam, self._guard.data_ptr(), stream)
-            _lib.check(st, "msgat_adam_step_guarded")
+            _lib.checked().msgat_adam_step_guarded(*adam, self._guard.data_ptr(), stream)
         else:
-            st = _lib.lib().msgat_adam_step(*adam, stream)
-            _lib.check(st, "msgat_adam_step")
+            _lib.checked().msgat_adam_step(*adam, stream)
         if torch.cuda.is_current_stream_capturing():
             self._captured_active = active
         else:
@@ -886,8 +882,7 @@ class FlatAdam(optim.Optimizer):
         self._refuse_while_pending("swap_averaged()")
         ptrs, offs, lens, _, _, n, _ = self._table((True,) * len(self._params))
         stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
-        st = _lib.lib().msgat_param_swap(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, self.shadow.data_ptr(), stream)
-        _lib.check(st, "msgat_param_swap")
+        _lib.checked().msgat_param_swap(ptrs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, self.shadow.data_ptr(), stream)
         self.swapped = not self.swapped
 
     @contextlib.contextmanager

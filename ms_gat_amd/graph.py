@@ -87,11 +87,11 @@ class SparseGraph:
             raise ValueError(f"adjacency must be [N,N], got {tuple(adjacency.shape)}")
         a = adjacency.detach().to(device="cpu", dtype=torch.float32).contiguous()
         n = a.size(0)
-        L = _lib.lib()
+        L = _lib.checked()
         nnz = C.c_int32(0)
-        _lib.check(L.msgat_graph_count(a.data_ptr(), n, n, C.byref(nnz)), "msgat_graph_count")
+        L.msgat_graph_count(a.data_ptr(), n, n, C.byref(nnz))
         self._alloc(n, int(nnz.value))
-        _lib.check(L.msgat_graph_build(a.data_ptr(), n, n, self.nnz, *self._ptrs(self._FIELDS)), "msgat_graph_build")
+        L.msgat_graph_build(a.data_ptr(), n, n, self.nnz, *self._ptrs(self._FIELDS))
         self._finish(sell)
 
     @classmethod
@@ -108,9 +108,9 @@ class SparseGraph:
             raise ValueError(f"rowptr must be [{n + 1}] and col 1-D, got {tuple(rp.shape)} and {tuple(ci.shape)}")
         self._alloc(n, int(ci.numel()))
         self.order = torch.zeros(max(self.nnz, 1), dtype=torch.int32)
-        _lib.check(_lib.lib().msgat_graph_build_indices(
+        _lib.checked().msgat_graph_build_indices(
             rp.data_ptr(), ci.data_ptr(), n, self.nnz,
-            *self._ptrs(("rowptr", "col", "erow", "colptr", "crow", "cperm", "cpos", "order"))), "msgat_graph_build_indices")
+            *self._ptrs(("rowptr", "col", "erow", "colptr", "crow", "cperm", "cpos", "order")))
         self._finish(sell)
         return self
 
@@ -139,19 +139,18 @@ class SparseGraph:
     _SELL_FIELDS = ("slice_off", "lane_row", "idx", "src", "pos")
 
     def _build_sell(self, ptr, idx, perm, with_pos: bool):
-        L = _lib.lib()
+        L = _lib.checked()
         ns, npos, pair = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        _lib.check(L.msgat_graph_sell_count(ptr.data_ptr(), self.n_nodes, C.byref(ns), C.byref(npos), C.byref(pair)),
-                   "msgat_graph_sell_count")
+        L.msgat_graph_sell_count(ptr.data_ptr(), self.n_nodes, C.byref(ns), C.byref(npos), C.byref(pair))
         ns, npos = int(ns.value), int(npos.value)
         t = dict(slice_off=torch.zeros(ns + 1, dtype=torch.int32), lane_row=torch.zeros(64 * ns, dtype=torch.int32),
                  idx=torch.zeros(npos + _lib.SELL_SLACK, dtype=torch.int16), src=torch.zeros(max(npos, 1), dtype=torch.int32))
         if with_pos:
             t["pos"] = torch.zeros(self.nnz, dtype=torch.int32)
-        _lib.check(L.msgat_graph_sell_build(ptr.data_ptr(), idx.data_ptr(), None if perm is None else perm.data_ptr(),
-                                            self.n_nodes, self.nnz, ns, npos, t["slice_off"].data_ptr(),
-                                            t["lane_row"].data_ptr(), t["idx"].data_ptr(), t["src"].data_ptr(),
-                                            t["pos"].data_ptr() if with_pos else None), "msgat_graph_sell_build")
+        L.msgat_graph_sell_build(ptr.data_ptr(), idx.data_ptr(), None if perm is None else perm.data_ptr(),
+                                 self.n_nodes, self.nnz, ns, npos, t["slice_off"].data_ptr(),
+                                 t["lane_row"].data_ptr(), t["idx"].data_ptr(), t["src"].data_ptr(),
+                                 t["pos"].data_ptr() if with_pos else None)
         t["n_slices"], t["n_pos"], t["pair_trips"] = ns, npos, int(pair.value)
         return t
 
@@ -186,7 +185,7 @@ class SparseGraph:
 
     def validate(self) -> None:
         hs = self.host_struct()
-        _lib.check(_lib.lib().msgat_graph_validate(C.byref(hs)), "msgat_graph_validate")
+        _lib.checked().msgat_graph_validate(C.byref(hs))
 
     def on(self, device: torch.device):
         """(ctypes struct of device pointers, tensors kept alive) for `device`."""
@@ -520,9 +519,8 @@ class BatchedGraph(ValuedGraph):
             return self
         gstruct, _ = s.on(a.device)
         counter = self._outside.data_ptr() + (0 if _capturing(a) else 4)
-        _lib.check(_lib.lib().msgat_graph_edge_values(C.byref(gstruct), a.data_ptr(), self.n_sets, self.val.data_ptr(),
-                                                      counter, _lib.stream_handle(a.device)),
-                   "msgat_graph_edge_values")
+        _lib.checked().msgat_graph_edge_values(C.byref(gstruct), a.data_ptr(), self.n_sets, self.val.data_ptr(),
+                                               counter, _lib.stream_handle(a.device))
         return self
 
     def outside_counts(self) -> Tuple[int, int]:

@@ -143,12 +143,11 @@ def interval_update(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor,
                         ("counts", counts, torch.int64, (L, N, T, 2))])
     dev = book.device
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_interval_update(_ptr(raw), _ptr(book), _ptr(issued), _ptr(clock), _ptr(radius_book),
-                                              _ptr(ranks), _ptr(window), _ptr(cursor), _ptr(radius), _ptr(counts),
-                                              raw.shape[0], raw.shape[1], N, T, out, int(point), P, L, W,
-                                              int(null_value is not None),
-                                              0.0 if null_value is None else float(null_value), _stream_handle(dev))
-    _lib.check(st, "msgat_interval_update")
+        _lib.checked().msgat_interval_update(_ptr(raw), _ptr(book), _ptr(issued), _ptr(clock), _ptr(radius_book),
+                                             _ptr(ranks), _ptr(window), _ptr(cursor), _ptr(radius), _ptr(counts),
+                                             raw.shape[0], raw.shape[1], N, T, out, int(point), P, L, W,
+                                             int(null_value is not None),
+                                             0.0 if null_value is None else float(null_value), _stream_handle(dev))
 
 
 def interval_apply(pred: torch.Tensor, radius: torch.Tensor, clock: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
@@ -167,9 +166,8 @@ def interval_apply(pred: torch.Tensor, radius: torch.Tensor, clock: torch.Tensor
                         ("hi", hi, torch.float32, (L, N, T)), ("radius_book", radius_book, torch.float32, (P, L, N, T))])
     dev = pred.device
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_interval_apply(_ptr(pred), _ptr(radius), _ptr(clock), _ptr(lo), _ptr(hi), _ptr(radius_book),
-                                             N, T, out, int(point), P, L, _stream_handle(dev))
-    _lib.check(st, "msgat_interval_apply")
+        _lib.checked().msgat_interval_apply(_ptr(pred), _ptr(radius), _ptr(clock), _ptr(lo), _ptr(hi), _ptr(radius_book),
+                                            N, T, out, int(point), P, L, _stream_handle(dev))
 
 
 # ---- the torch restatements: CPU tensors, and what the kernels must give ------------------------------------------------

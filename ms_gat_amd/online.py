@@ -195,7 +195,7 @@ class OnlineForecaster:
                                          dtype=torch.float64, device=dev),
                              torch.zeros((N, ops.SCORE_NODE_COLUMNS), dtype=torch.float64, device=dev))
         if dev.type == "cuda":
-            need = int(ops._lib.lib().msgat_forecast_score_partial_doubles(N, self.score_t_out, len(self.score_levels)))
+            need = int(ops._lib.checked().msgat_forecast_score_partial_doubles(N, self.score_t_out, len(self.score_levels)))
             self._score_partials = torch.empty(need, dtype=torch.float64, device=dev)
         if self.interval_levels:
             from . import intervals as _intervals

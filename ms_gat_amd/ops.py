@@ -47,7 +47,7 @@ class _GacnPlan:
     __slots__ = ("shape", "gstruct", "keep", "mode", "sizes", "offs", "total", "bwd_bytes", "z_channels", "nscratch", "ndense")
 
     def __init__(self, graph, dev, R, Bg, Cin, Co, N, T, need_bwd, own_q=True):
-        L = _lib.lib()
+        L = _lib.checked()
         G = R * Bg
         self.shape = _lib.Shape(R, Bg, Cin, Co, N, T)
         self.gstruct, self.keep = graph.on(dev)
@@ -150,26 +150,25 @@ class _AdjacencyGrad:
                  stream, dE: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`dE` [G,nnz]: the gradient at the returned attention weights (`need_weights`), or None; its share
         sum_g P_g dE_g is added at the edges (msgat_edge_softmax_grad, inside the library for a sparse adjacency)."""
-        L = _lib.lib()
+        L = _lib.checked()
         shape, dev = C.byref(plan.shape), dv.device
         gstruct = C.byref(plan.gstruct)
         if self.pattern is None:
             dadj = torch.empty((self.n_sets, plan.shape.N, plan.shape.N), device=dev, dtype=torch.float32)
             nbytes = int(L.msgat_adjacency_grad_workspace_bytes(shape, Cu, self.n_sets))
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-            _lib.check(L.msgat_adjacency_grad(shape, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, self.n_sets, _ptr(dadj), _ptr(ws),
-                                              nbytes, stream), "msgat_adjacency_grad")
+            L.msgat_adjacency_grad(shape, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, self.n_sets, _ptr(dadj), _ptr(ws),
+                                   nbytes, stream)
             if dE is not None:
-                _lib.check(L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), self.n_sets, _ptr(dadj), None,
-                                                     stream), "msgat_edge_softmax_grad")
+                L.msgat_edge_softmax_grad(shape, gstruct, q, kW, lse, _ptr(dE), self.n_sets, _ptr(dadj), None, stream)
             return dadj.view(self.shape)
         # dval [n_sets, nnz] on the structure (the union of the samples' patterns), gathered back to the stored entries
         nnz = self.pattern.structure.nnz
         dval = torch.empty((self.n_sets, max(nnz, 1)), device=dev, dtype=torch.float32)
         nbytes = int(L.msgat_edge_weight_grad_sets_workspace_bytes(shape, gstruct, Cu, self.n_sets))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-        _lib.check(L.msgat_edge_weight_grad_sets(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dE), self.n_sets,
-                                                 _ptr(dval), _ptr(ws), nbytes, stream), "msgat_edge_weight_grad_sets")
+        L.msgat_edge_weight_grad_sets(shape, gstruct, Cu, _ptr(dv), dv_gs, feat, q, kW, lse, _ptr(dE), self.n_sets,
+                                      _ptr(dval), _ptr(ws), nbytes, stream)
         dval = dval[:, :nnz]
         dval = self.pattern.to_input_order(dval if self.sets else dval.reshape(-1))
         if self.parts is None:                            # the weight [nnz] / [V,nnz] of an edge_adjacency
@@ -232,15 +231,15 @@ def _map_grad(plan: _GacnPlan, q: int, kW: int, lse: int, Wg: torch.Tensor, dP: 
               dWg_add: torch.Tensor, stream) -> None:
     """dq_add [G,N,T] += and dWg_add [R,T,T] += the share of the gradient dP [G,N,N] at the dense map
     (msgat_softmax_map_grad), enqueued on `stream`."""
-    L = _lib.lib()
+    L = _lib.checked()
     shape = C.byref(plan.shape)
     dP = dP.contiguous()
     if dP.data_ptr() % 16:                  # the row pass reads 16-byte pieces when N % 4 == 0
         dP = dP.clone()
     nbytes = int(L.msgat_softmax_map_grad_workspace_bytes(shape))
     ws = torch.empty(max(nbytes, 256), device=dP.device, dtype=torch.uint8)
-    _lib.check(L.msgat_softmax_map_grad(shape, q, kW, lse, _ptr(Wg), _ptr(dP), _ptr(dq_add), _ptr(dWg_add), _ptr(ws),
-                                        ws.numel(), stream), "msgat_softmax_map_grad")
+    L.msgat_softmax_map_grad(shape, q, kW, lse, _ptr(Wg), _ptr(dP), _ptr(dq_add), _ptr(dWg_add), _ptr(ws),
+                             ws.numel(), stream)
 
 
 def _refuse_softmax_grad(*inputs) -> None:
@@ -293,7 +292,7 @@ def _forward_weights(weights, plan: _GacnPlan, nnz: int, buf: torch.Tensor, q: i
     if weights == "masked":
         return buf.narrow(0, plan.offs[4], G * nnz).view(G, nnz).clone()
     out = torch.empty((G, N, N), device=buf.device, dtype=torch.float32)
-    _lib.check(_lib.lib().msgat_attention_map(C.byref(shape), q, kW, lse, _ptr(out), stream), "msgat_attention_map")
+    _lib.checked().msgat_attention_map(C.byref(shape), q, kW, lse, _ptr(out), stream)
     return out
 
 
@@ -305,7 +304,7 @@ class _GACNFunction(torch.autograd.Function):
     def forward(ctx, x, alpha, Wg, W, graph, recording: bool = True, adj_grad=None, adj=None, weights=None):
         # graph: see graph_for.  weights: None, or "masked" / "softmax" / "softmax_grad" -- then a second output (see
         # _forward_weights), whose gradient arrives in backward as `dE`: [G,nnz] at the edges, or [G,N,N] at the dense map
-        L = _lib.lib()
+        L = _lib.checked()
         dev = x.device
         G, Cin, N, T = x.shape
         R = alpha.shape[0] if alpha.dim() == 2 else 1     # alpha [C], Wg [T,T], W [Co,C]: ONE relation, no leading axis
@@ -338,8 +337,7 @@ class _GACNFunction(torch.autograd.Function):
         dense_t = torch.empty(plan.ndense, device=dev, dtype=torch.uint8) if plan.ndense else None
         io = _lib.Fwd(_ptr(x), _ptr(alpha), _ptr(Wg), _ptr(W), _ptr(z), q, kW, lse, pq, E, u, int(training_form), scratch, Ec,
                       _ptr(dense_t))
-        st = L.msgat_gacn_forward(C.byref(plan.shape), C.byref(plan.gstruct), C.byref(io), _stream_handle(dev))
-        _lib.check(st, "msgat_gacn_forward")
+        L.msgat_gacn_forward(C.byref(plan.shape), C.byref(plan.gstruct), C.byref(io), _stream_handle(dev))
 
         if need_bwd:
             ctx.plan, ctx.has_W, ctx.adj_grad, ctx.weights = plan, W is not None, adj_grad, weights
@@ -365,7 +363,7 @@ class _GACNFunction(torch.autograd.Function):
         # a LayerNorm output with learnable weights, msgat.py:122).  An adjacency that requires grad gets it from one more
         # launch after that backward (its `_AdjacencyGrad`), which re-creates the softmax from q, kW and lse:
         # dv / feat are dz / x (plain), dz / u = W x (project-first), W^T dz / x (aggregate-first, one more mix).
-        L = _lib.lib()
+        L = _lib.checked()
         saved = ctx.saved_tensors
         x, alpha, Wg, buf = saved[:4]
         W = saved[4] if ctx.has_W else None
@@ -400,21 +398,19 @@ class _GACNFunction(torch.autograd.Function):
             dq_map = torch.zeros((x.shape[0], shape.N, shape.T), device=dev, dtype=torch.float32)
             dWg_map = torch.zeros_like(Wg)
             _map_grad(plan, q, kW, lse, Wg, dP, dq_map, dWg_map, stream)
-            st = L.msgat_gacn_backward_map_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dq_map),
-                                                _ptr(dWg_map), stream)
+            L.msgat_gacn_backward_map_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dq_map),
+                                           _ptr(dWg_map), stream)
         elif dE is None:
-            st = L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
+            L.msgat_gacn_backward(C.byref(shape), C.byref(gstruct), C.byref(io), stream)
         else:
-            st = L.msgat_gacn_backward_edge_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dE), stream)
-        _lib.check(st, "msgat_gacn_backward")
+            L.msgat_gacn_backward_edge_grad(C.byref(shape), C.byref(gstruct), C.byref(io), _ptr(dE), stream)
         if ctx.adj_grad is None:
             return dx, dalpha, dWg, dW, None, None, None, None, None
         Cin = x.shape[1]
         if plan.mode == _lib.MODE_AGG_FIRST:
             dy = torch.empty_like(x)
             dzc = dz if dz_gs == 0 else dz.contiguous()
-            _lib.check(L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy), stream),
-                       "msgat_stage_mix")
+            L.msgat_stage_mix(C.byref(shape), shape.Co, Cin, _ptr(dzc), _ptr(W), 1, None, None, _ptr(dy), stream)
             Cu, dv, dv_gs, feat = Cin, dy, 0, _ptr(x)
         elif plan.mode == _lib.MODE_PROJ_FIRST:
             Cu, dv, dv_gs, feat = shape.Co, dz, dz_gs, u
@@ -553,7 +549,7 @@ class _LayerNormTFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float, relu_input: bool = False):
-        L = _lib.lib()
+        L = _lib.checked()
         x = x.contiguous()
         T = x.shape[-1]
         rows = x.numel() // T if T else 0
@@ -562,8 +558,7 @@ class _LayerNormTFunction(torch.autograd.Function):
         w = None if weight is None else weight.contiguous()
         b = None if bias is None else bias.contiguous()
         R, ctx.param_shape = _ln_sets(w, b, T)          # weight / bias [T] or [R,T]: R parameter sets, relation-major rows
-        st = L.msgat_layernorm_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, T, eps, R, _stream_handle(x.device))
-        _lib.check(st, "msgat_layernorm_forward")
+        L.msgat_layernorm_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, T, eps, R, _stream_handle(x.device))
         ctx.eps, ctx.has_w, ctx.has_b, ctx.R = eps, weight is not None, bias is not None, R
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(*([x] + ([w] if w is not None else [])))
@@ -571,7 +566,7 @@ class _LayerNormTFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
+        L = _lib.checked()
         saved = ctx.saved_tensors
         x, w = saved[0], (saved[1] if ctx.has_w else None)
         T = x.shape[-1]
@@ -581,11 +576,9 @@ class _LayerNormTFunction(torch.autograd.Function):
         R = ctx.R
         dw = torch.empty_like(w) if ctx.has_w else None
         db = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if ctx.has_b else None
-        part = torch.empty(max(int(L.msgat_layernorm_partial_floats(rows, T, R)), 1), device=x.device,
-                           dtype=torch.float32)
-        st = L.msgat_layernorm_backward(_ptr(x), _ptr(w), _ptr(dy), None, _ptr(dx), _ptr(dw), _ptr(db), _ptr(part),
-                                        rows, T, ctx.eps, R, int(ctx.relu_input), _stream_handle(x.device))
-        _lib.check(st, "msgat_layernorm_backward")
+        part = _scratch(x, L.msgat_layernorm_partial_floats(rows, T, R))
+        L.msgat_layernorm_backward(_ptr(x), _ptr(w), _ptr(dy), None, _ptr(dx), _ptr(dw), _ptr(db), _ptr(part),
+                                   rows, T, ctx.eps, R, int(ctx.relu_input), _stream_handle(x.device))
         return dx, dw, db, None, None
 
 
@@ -597,7 +590,7 @@ class _LnPoolTeeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float, relu_input: bool, pool_w):
-        L = _lib.lib()
+        L = _lib.checked()
         x = x.contiguous()
         B, Cc, N, T = x.shape
         rows = B * Cc * N
@@ -610,12 +603,12 @@ class _LnPoolTeeFunction(torch.autograd.Function):
         pooled = _new(x, B, Cc, T)
         Rp = pw.numel() // N
         if Rp == R and N >= 64:     # the pooling's sums come out of the LayerNorm pass itself (+ a small launch adding the shares)
-            part = _new(x, max(int(L.msgat_layernorm_pool_partial_floats(rows, T, R)), 1))
-            _lib.check(L.msgat_layernorm_forward_pooled(_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(pw), N, _ptr(pooled), _ptr(part),
-                                                        rows, T, eps, R, stream), "msgat_layernorm_forward_pooled")
+            part = _scratch(x, L.msgat_layernorm_pool_partial_floats(rows, T, R))
+            L.msgat_layernorm_forward_pooled(_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(pw), N, _ptr(pooled), _ptr(part),
+                                             rows, T, eps, R, stream)
         else:
-            _lib.check(L.msgat_layernorm_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, T, eps, R, stream), "msgat_layernorm_forward")
-            _lib.check(L.msgat_node_pool(_ptr(y), _ptr(pw), _ptr(pooled), B * Cc, N, T, Rp, 0, 0, stream), "msgat_node_pool")
+            L.msgat_layernorm_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(y), rows, T, eps, R, stream)
+            L.msgat_node_pool(_ptr(y), _ptr(pw), _ptr(pooled), B * Cc, N, T, Rp, 0, 0, stream)
         ctx.eps, ctx.relu_input, ctx.has_w, ctx.has_b, ctx.R, ctx.Rp = eps, bool(relu_input), w is not None, b is not None, R, Rp
         ctx.save_for_backward(*([x, y, pw] + ([w] if w is not None else []) + ([b] if b is not None else [])))
         ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None (backward handles each): no
@@ -623,7 +616,7 @@ class _LnPoolTeeFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dx_other, dpooled):
-        L = _lib.lib()
+        L = _lib.checked()
         saved = ctx.saved_tensors
         x, y, pw = saved[:3]
         w = saved[3] if ctx.has_w else None
@@ -637,9 +630,9 @@ class _LnPoolTeeFunction(torch.autograd.Function):
 
         def pool_weight_grad():     # its own pass over the stored y (msgat_node_pool_grad_weight)
             g = torch.empty_like(pw)
-            part = _new(x, max(int(L.msgat_node_pool_partial_floats(B, Cc, N)), 1))
-            _lib.check(L.msgat_node_pool_grad_weight(_ptr(y), _ptr(dpooled.contiguous()), _ptr(g), _ptr(part), B, Cc, N, T, ctx.Rp,
-                                                     stream), "msgat_node_pool_grad_weight")
+            part = _scratch(x, L.msgat_node_pool_partial_floats(B, Cc, N))
+            L.msgat_node_pool_grad_weight(_ptr(y), _ptr(dpooled.contiguous()), _ptr(g), _ptr(part), B, Cc, N, T, ctx.Rp,
+                                          stream)
             return g
         if dy is None and dpooled is None:
             if dx_other is not None and ctx.relu_input:
@@ -650,27 +643,25 @@ class _LnPoolTeeFunction(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.empty_like(w) if ctx.has_w else None
         db = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if ctx.has_b else None
-        part = _new(x, max(int(L.msgat_layernorm_partial_floats(rows, T, ctx.R)), 1))
+        part = _scratch(x, L.msgat_layernorm_partial_floats(rows, T, ctx.R))
         if fused:
             want_pw = bool(need[5])
             dpw = torch.empty_like(pw) if want_pw else None
             rows_scratch = _new(x, rows) if want_pw else None
-            st = L.msgat_layernorm_backward_pooled(_ptr(x), _ptr(w), _ptr(lnb), _ptr(dy), _ptr(other), _ptr(pw),
-                                                   _ptr(dpooled.contiguous()), N, _ptr(dx), _ptr(dw), _ptr(db), _ptr(dpw),
-                                                   _ptr(rows_scratch), _ptr(part), rows, T, ctx.eps, ctx.R,
-                                                   int(ctx.relu_input), stream)
-            _lib.check(st, "msgat_layernorm_backward_pooled")
+            L.msgat_layernorm_backward_pooled(_ptr(x), _ptr(w), _ptr(lnb), _ptr(dy), _ptr(other), _ptr(pw),
+                                              _ptr(dpooled.contiguous()), N, _ptr(dx), _ptr(dw), _ptr(db), _ptr(dpw),
+                                              _ptr(rows_scratch), _ptr(part), rows, T, ctx.eps, ctx.R,
+                                              int(ctx.relu_input), stream)
         else:
             if dpooled is not None:      # parameter-set counts differ: the pooling's gradients in their own passes, then the LayerNorm
                 if need[5]:
                     dpw = pool_weight_grad()
                 dyp = torch.empty_like(x)
-                _lib.check(L.msgat_node_pool_grad_signal(_ptr(pw), _ptr(dpooled.contiguous()), _ptr(dy), _ptr(dyp), B * Cc, N, T,
-                                                         ctx.Rp, stream), "msgat_node_pool_grad_signal")
+                L.msgat_node_pool_grad_signal(_ptr(pw), _ptr(dpooled.contiguous()), _ptr(dy), _ptr(dyp), B * Cc, N, T,
+                                              ctx.Rp, stream)
                 dy = dyp
-            st = L.msgat_layernorm_backward(_ptr(x), _ptr(w), _ptr(dy), _ptr(other), _ptr(dx), _ptr(dw), _ptr(db), _ptr(part),
-                                            rows, T, ctx.eps, ctx.R, int(ctx.relu_input), stream)
-            _lib.check(st, "msgat_layernorm_backward")
+            L.msgat_layernorm_backward(_ptr(x), _ptr(w), _ptr(dy), _ptr(other), _ptr(dx), _ptr(dw), _ptr(db), _ptr(part),
+                                       rows, T, ctx.eps, ctx.R, int(ctx.relu_input), stream)
         return dx, dw, db, None, None, dpw
 
 
@@ -742,6 +733,11 @@ def _new(like: torch.Tensor, *shape) -> torch.Tensor:
     return torch.empty(shape, device=like.device, dtype=torch.float32)
 
 
+def _scratch(like: torch.Tensor, n_floats: int) -> torch.Tensor:
+    """The float32 scratch a `msgat_*_partial_floats` query asked for, on `like`'s device; never empty."""
+    return _new(like, max(int(n_floats), 1))
+
+
 _ones_cache = {}
 
 
@@ -760,9 +756,8 @@ def _channel_sums(t: torch.Tensor, R: int = 0) -> torch.Tensor:
     G, Cc, N, T = t.shape
     pooled = _new(t, G, Cc, T)
     keep, seg = _as_segment(t)                    # a channel slice of a wider gradient tensor is read in place
-    st = _lib.lib().msgat_node_pool(seg.ptr, _ptr(_ones(t.device, N)), _ptr(pooled), G * Cc, N, T, 1, Cc if seg.group_stride else 0,
-                                    seg.group_stride, _stream_handle(t.device))
-    _lib.check(st, "msgat_node_pool")
+    _lib.checked().msgat_node_pool(seg.ptr, _ptr(_ones(t.device, N)), _ptr(pooled), G * Cc, N, T, 1, Cc if seg.group_stride else 0,
+                                   seg.group_stride, _stream_handle(t.device))
     if R > 0:
         return pooled.view(R, G // R, Cc, T).sum(dim=(1, 3))
     return pooled.sum(dim=(0, 2))
@@ -773,7 +768,7 @@ class _MixFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, M, bias, add, relu: bool):
-        L = _lib.lib()
+        L = _lib.checked()
         x, M = x.contiguous(), M.contiguous()
         G, Ci, N, T = x.shape
         R, Co = M.shape[0], M.shape[1]
@@ -781,16 +776,15 @@ class _MixFunction(torch.autograd.Function):
         out = _new(x, G, Co, N, T)
         b = None if bias is None else bias.contiguous()
         a = None if add is None else add.contiguous()
-        st = L.msgat_stage_mix_epilogue(C.byref(shape), Ci, Co, _ptr(x), _ptr(M), 0, _ptr(b), 0, _ptr(a), int(relu),
-                                        _ptr(out), _stream_handle(x.device))
-        _lib.check(st, "msgat_stage_mix_epilogue")
+        L.msgat_stage_mix_epilogue(C.byref(shape), Ci, Co, _ptr(x), _ptr(M), 0, _ptr(b), 0, _ptr(a), int(relu),
+                                   _ptr(out), _stream_handle(x.device))
         ctx.relu, ctx.has_bias, ctx.has_add = relu, bias is not None, add is not None
         ctx.save_for_backward(x, M, out if relu else None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         x, M, out = ctx.saved_tensors
         G, Ci, N, T = x.shape
         R, Co = M.shape[0], M.shape[1]
@@ -802,15 +796,13 @@ class _MixFunction(torch.autograd.Function):
         if need[0]:
             dx = torch.empty_like(x)
             shape = _lib.Shape(R, G // R, Co, Ci, N, T)
-            st = L.msgat_stage_mix(C.byref(shape), Co, Ci, _ptr(dpre), _ptr(M), 1, None, None, _ptr(dx), stream)
-            _lib.check(st, "msgat_stage_mix")
+            L.msgat_stage_mix(C.byref(shape), Co, Ci, _ptr(dpre), _ptr(M), 1, None, None, _ptr(dx), stream)
         if need[1]:
             dM = torch.empty_like(M)
             shape = _lib.Shape(R, G // R, Ci, Co, N, T)
-            part = _new(x, max(int(L.msgat_contract_partial_floats(C.byref(shape), Co, Ci)), 1))
-            st = L.msgat_stage_contract(C.byref(shape), Co, Ci, _ptr(dpre), None, _ptr(x), _ptr(part), _ptr(dM),
-                                        Co * Ci, None, 0, stream)
-            _lib.check(st, "msgat_stage_contract")
+            part = _scratch(x, L.msgat_contract_partial_floats(C.byref(shape), Co, Ci))
+            L.msgat_stage_contract(C.byref(shape), Co, Ci, _ptr(dpre), None, _ptr(x), _ptr(part), _ptr(dM),
+                                   Co * Ci, None, 0, stream)
         if ctx.has_bias and need[2]:
             dbias = _channel_sums(dpre)
         return dx, dM, dbias, (dpre if ctx.has_add and need[3] else None), None
@@ -836,7 +828,7 @@ class _TimeMixFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, A, bias):
-        L = _lib.lib()
+        L = _lib.checked()
         y, A = y.contiguous(), A.contiguous()
         G, KC, N, T = y.shape
         K = A.shape[1]
@@ -845,9 +837,8 @@ class _TimeMixFunction(torch.autograd.Function):
         out = _new(y, G, Co, N, T)
         b = None if bias is None else bias.contiguous()
         Rb = 1 if b is None or b.dim() == 1 else b.shape[0]     # bias [Co] or [R,Co]
-        st = L.msgat_time_mix(_ptr(y), _ptr(A), per_group, _ptr(b), _ptr(out), G, Co, K, N, T, 0, Rb, 0,
-                              _stream_handle(y.device))
-        _lib.check(st, "msgat_time_mix")
+        L.msgat_time_mix(_ptr(y), _ptr(A), per_group, _ptr(b), _ptr(out), G, Co, K, N, T, 0, Rb, 0,
+                         _stream_handle(y.device))
         ctx.dims, ctx.per_group, ctx.has_bias = (G, Co, K, N, T), per_group, bias is not None
         ctx.bias_R = 0 if b is None or b.dim() == 1 else b.shape[0]
         ctx.save_for_backward(y, A)
@@ -855,7 +846,7 @@ class _TimeMixFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         y, A = ctx.saved_tensors
         G, Co, K, N, T = ctx.dims
         dout, seg = _as_segment(dout)              # a channel slice of the block's concatenated gradient is read in place
@@ -864,15 +855,12 @@ class _TimeMixFunction(torch.autograd.Function):
         dy = dA = dbias = None
         if need[0]:
             dy = torch.empty_like(y)
-            st = L.msgat_time_mix(seg.ptr, _ptr(A), ctx.per_group, None, _ptr(dy), G, Co, K, N, T, 1, 1, seg.group_stride,
-                                  stream)
-            _lib.check(st, "msgat_time_mix (backward)")
+            L.msgat_time_mix(seg.ptr, _ptr(A), ctx.per_group, None, _ptr(dy), G, Co, K, N, T, 1, 1, seg.group_stride,
+                             stream)
         if need[1]:
             dAg = _new(y, G, K, T, T)
-            part = _new(y, max(int(L.msgat_time_mix_partial_floats(G, K, T)), 1))
-            st = L.msgat_time_mix_grad_matrix(seg.ptr, _ptr(y), _ptr(dAg), _ptr(part), G, Co, K, N, T, seg.group_stride,
-                                              stream)
-            _lib.check(st, "msgat_time_mix_grad_matrix")
+            part = _scratch(y, L.msgat_time_mix_partial_floats(G, K, T))
+            L.msgat_time_mix_grad_matrix(seg.ptr, _ptr(y), _ptr(dAg), _ptr(part), G, Co, K, N, T, seg.group_stride, stream)
             dA = dAg if A.shape[0] == G else dAg.sum(dim=0, keepdim=True)
         if ctx.has_bias and need[2]:
             dbias = _channel_sums(dout, ctx.bias_R)
@@ -898,22 +886,21 @@ class _CausalConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, taps, bias, dilation: int):
-        L = _lib.lib()
+        L = _lib.checked()
         h, taps = h.contiguous(), taps.contiguous()
         G, Ci, N, T = h.shape
         R, Co = taps.shape[0], taps.shape[1] // 2
         out = _new(h, G, Co, N, T)
         b = None if bias is None else bias.contiguous()
-        st = L.msgat_causal_conv(_ptr(h), _ptr(taps), _ptr(b), int(b is not None and b.dim() == 2), _ptr(out), R, G // R,
-                                 Ci, Co, N, T, int(dilation), 0, 0, _stream_handle(h.device))
-        _lib.check(st, "msgat_causal_conv")
+        L.msgat_causal_conv(_ptr(h), _ptr(taps), _ptr(b), int(b is not None and b.dim() == 2), _ptr(out), R, G // R,
+                            Ci, Co, N, T, int(dilation), 0, 0, _stream_handle(h.device))
         ctx.dilation, ctx.bias_R = int(dilation), (None if b is None else (b.shape[0] if b.dim() == 2 else 0))
         ctx.save_for_backward(h, taps)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         h, taps = ctx.saved_tensors
         G, Ci, N, T = h.shape
         R, Co = taps.shape[0], taps.shape[1] // 2
@@ -923,20 +910,18 @@ class _CausalConvFunction(torch.autograd.Function):
         dh = dtaps = dbias = None
         if need[0]:
             dh = torch.empty_like(h)
-            st = L.msgat_causal_conv(seg.ptr, _ptr(taps), None, 0, _ptr(dh), R, G // R, Ci, Co, N, T, ctx.dilation, 1,
-                                     seg.group_stride, stream)
-            _lib.check(st, "msgat_causal_conv (backward)")
+            L.msgat_causal_conv(seg.ptr, _ptr(taps), None, 0, _ptr(dh), R, G // R, Ci, Co, N, T, ctx.dilation, 1,
+                                seg.group_stride, stream)
         want_bias = ctx.bias_R is not None and need[2]
         if need[1] or want_bias:
             # d[W0; W1] = [dout[t+d]; dout] h^T with the 2 Co gradient rows read as time-shifted views of dout inside the
             # contraction (and a virtual channel of ones: the bias gradient is its tap-1 half)
             ones = int(bool(want_bias))
             buf = _new(h, R * 2 * Co * (Ci + ones))
-            part = _new(h, max(int(L.msgat_contract_segments_partial_floats(R, 2 * Co, Ci + ones)), 1))
+            part = _scratch(h, L.msgat_contract_segments_partial_floats(R, 2 * Co, Ci + ones))
             # with_ones = 2: the matrix [R,2Co,Ci] and, behind it, the ones column [R,2Co] (no slice copies)
-            st = L.msgat_causal_conv_grad_weight(seg.ptr, seg.group_stride, _ptr(h), _ptr(part), _ptr(buf), R, G // R, Ci, Co,
-                                                 N, T, ctx.dilation, 2 * ones, stream)
-            _lib.check(st, "msgat_causal_conv_grad_weight")
+            L.msgat_causal_conv_grad_weight(seg.ptr, seg.group_stride, _ptr(h), _ptr(part), _ptr(buf), R, G // R, Ci, Co,
+                                            N, T, ctx.dilation, 2 * ones, stream)
             dM = buf[: R * 2 * Co * Ci].view(R, 2 * Co, Ci)
             if ones:
                 colsum = buf[R * 2 * Co * Ci:].view(R, 2, Co)[:, 1]      # [R,Co]: sum of dout over the relation's groups and positions
@@ -947,7 +932,7 @@ class _CausalConvFunction(torch.autograd.Function):
 
 def causal_conv_fused(Ci: int, Co: int) -> bool:
     """Whether `causal_conv` has its one-pass kernels for these widths (else use mix_multi + time_mix)."""
-    return bool(_lib.lib().msgat_causal_conv_fused(int(Ci), int(Co)))
+    return bool(_lib.checked().msgat_causal_conv_fused(int(Ci), int(Co)))
 
 
 def causal_conv(h: torch.Tensor, taps: torch.Tensor, bias: Optional[torch.Tensor], dilation: int) -> torch.Tensor:
@@ -971,19 +956,18 @@ class _NodePoolFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        L = _lib.lib()
+        L = _lib.checked()
         x, w = x.contiguous(), w.contiguous()
         B, Cc, N, T = x.shape
         pooled = _new(x, B, Cc, T)
         R = w.numel() // N                                   # weights [N] or [R,N]
-        st = L.msgat_node_pool(_ptr(x), _ptr(w), _ptr(pooled), B * Cc, N, T, R, 0, 0, _stream_handle(x.device))
-        _lib.check(st, "msgat_node_pool")
+        L.msgat_node_pool(_ptr(x), _ptr(w), _ptr(pooled), B * Cc, N, T, R, 0, 0, _stream_handle(x.device))
         ctx.save_for_backward(x, w)
         return pooled
 
     @staticmethod
     def backward(ctx, dp):
-        L = _lib.lib()
+        L = _lib.checked()
         x, w = ctx.saved_tensors
         B, Cc, N, T = x.shape
         dp = dp.contiguous()
@@ -992,13 +976,11 @@ class _NodePoolFunction(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(L.msgat_node_pool_grad_signal(_ptr(w), _ptr(dp), None, _ptr(dx), B * Cc, N, T, R, stream),
-                       "msgat_node_pool_grad_signal")
+            L.msgat_node_pool_grad_signal(_ptr(w), _ptr(dp), None, _ptr(dx), B * Cc, N, T, R, stream)
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
-            part = _new(x, max(int(L.msgat_node_pool_partial_floats(B, Cc, N)), 1))
-            _lib.check(L.msgat_node_pool_grad_weight(_ptr(x), _ptr(dp), _ptr(dw), _ptr(part), B, Cc, N, T, R, stream),
-                       "msgat_node_pool_grad_weight")
+            part = _scratch(x, L.msgat_node_pool_partial_floats(B, Cc, N))
+            L.msgat_node_pool_grad_weight(_ptr(x), _ptr(dp), _ptr(dw), _ptr(part), B, Cc, N, T, R, stream)
         return dx, dw
 
 
@@ -1015,20 +997,19 @@ class _ChannelPoolFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, alpha):
-        L = _lib.lib()
+        L = _lib.checked()
         x, alpha = x.contiguous(), alpha.contiguous()
         B, Cc, N, T = x.shape
         R = alpha.numel() // Cc                              # alpha [C] or [R,C]
         shape = _lib.Shape(R, B // R, Cc, 0, N, T)
         q = _new(x, B, N, T)
-        st = L.msgat_stage_project(C.byref(shape), _ptr(x), _ptr(alpha), None, _ptr(q), None, _stream_handle(x.device))
-        _lib.check(st, "msgat_stage_project")
+        L.msgat_stage_project(C.byref(shape), _ptr(x), _ptr(alpha), None, _ptr(q), None, _stream_handle(x.device))
         ctx.save_for_backward(x, alpha)
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        L = _lib.lib()
+        L = _lib.checked()
         x, alpha = ctx.saved_tensors
         B, Cc, N, T = x.shape
         dq = dq.contiguous()
@@ -1038,15 +1019,13 @@ class _ChannelPoolFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             shape = _lib.Shape(R, B // R, 1, Cc, N, T)
-            st = L.msgat_stage_mix(C.byref(shape), 1, Cc, _ptr(dq), _ptr(alpha), 0, None, None, _ptr(dx), stream)
-            _lib.check(st, "msgat_stage_mix")
+            L.msgat_stage_mix(C.byref(shape), 1, Cc, _ptr(dq), _ptr(alpha), 0, None, None, _ptr(dx), stream)
         if ctx.needs_input_grad[1]:
             dalpha = torch.empty_like(alpha)
             shape = _lib.Shape(R, B // R, Cc, 0, N, T)
-            part = _new(x, max(int(L.msgat_contract_partial_floats(C.byref(shape), 1, Cc)), 1))
-            st = L.msgat_stage_contract(C.byref(shape), 1, Cc, None, _ptr(dq), _ptr(x), _ptr(part), _ptr(dalpha), Cc,
-                                        None, 0, stream)
-            _lib.check(st, "msgat_stage_contract")
+            part = _scratch(x, L.msgat_contract_partial_floats(C.byref(shape), 1, Cc))
+            L.msgat_stage_contract(C.byref(shape), 1, Cc, None, _ptr(dq), _ptr(x), _ptr(part), _ptr(dalpha), Cc,
+                                   None, 0, stream)
         return dx, dalpha
 
 
@@ -1061,11 +1040,10 @@ def channel_pool(x: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
 def _head_weight_grad(dout, x, W, B, Cc, N, T, To, R, stream) -> torch.Tensor:
     """The head's weight gradient, [R,To,T,1,C] (or [To,T,1,C] for a weight without the leading axis), from the
     incoming gradient dout[B,N,To] and the head's input x."""
-    L = _lib.lib()
+    L = _lib.checked()
     dWc = _new(x, R, Cc, To, T)
-    part = _new(x, max(int(L.msgat_head_grad_weight_partial_floats(Cc, T, To, R)), 1))
-    _lib.check(L.msgat_head_grad_weight(_ptr(dout), _ptr(x), _ptr(dWc), _ptr(part), B, Cc, N, T, To, R, stream),
-               "msgat_head_grad_weight")
+    part = _scratch(x, L.msgat_head_grad_weight_partial_floats(Cc, T, To, R))
+    L.msgat_head_grad_weight(_ptr(dout), _ptr(x), _ptr(dWc), _ptr(part), B, Cc, N, T, To, R, stream)
     # [R,To,T,1,C], made contiguous HERE, once for all R components: each component's parameter receives its row,
     # and a non-contiguous row would be copied per component when it is accumulated into .grad
     dW = dWc.permute(0, 2, 3, 1).contiguous().unsqueeze(3)
@@ -1076,8 +1054,7 @@ def _head_bias_grad(dout, W, B, N, To, R, stream) -> torch.Tensor:
     """The head's bias gradient, [R,To] (or [To] for a weight without the leading axis), from dout[B,N,To]."""
     if To in (4, 8, 12, 16):   # one streaming pass over dout (node pooling with unit weights), then a tiny sum
         pooled = _new(dout, B, To)
-        _lib.check(_lib.lib().msgat_node_pool(_ptr(dout), _ptr(_ones(dout.device, N)), _ptr(pooled), B, N, To, 1, 0, 0, stream),
-                   "msgat_node_pool")
+        _lib.checked().msgat_node_pool(_ptr(dout), _ptr(_ones(dout.device, N)), _ptr(pooled), B, N, To, 1, 0, 0, stream)
         return pooled.view(R, B // R, To).sum(dim=1) if W.dim() == 5 else pooled.sum(dim=0)
     return dout.view(R, B // R, N, To).sum(dim=(1, 2)) if W.dim() == 5 else dout.sum(dim=(0, 1))
 
@@ -1087,24 +1064,22 @@ class _HeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, bias):
-        L = _lib.lib()
+        L = _lib.checked()
         x, W = x.contiguous(), W.contiguous()
         B, Cc, N, T = x.shape
         To = W.shape[-4]
         R = 1 if W.dim() == 4 else W.shape[0]               # weight [To,T,1,C] or [R,To,T,1,C]
         out = _new(x, B, N, To)
-        part = _new(x, max(int(L.msgat_head_forward_partial_floats(B, Cc, N, To)), 1))
+        part = _scratch(x, L.msgat_head_forward_partial_floats(B, Cc, N, To))
         b = None if bias is None else bias.contiguous()
-        st = L.msgat_head_forward(_ptr(x), _ptr(W), _ptr(b), _ptr(out), _ptr(part), B, Cc, N, T, To, R,
-                                  _stream_handle(x.device))
-        _lib.check(st, "msgat_head_forward")
+        L.msgat_head_forward(_ptr(x), _ptr(W), _ptr(b), _ptr(out), _ptr(part), B, Cc, N, T, To, R, _stream_handle(x.device))
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x, W)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         x, W = ctx.saved_tensors
         B, Cc, N, T = x.shape
         To = W.shape[-4]
@@ -1114,8 +1089,7 @@ class _HeadFunction(torch.autograd.Function):
         dx = dW = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(L.msgat_head_grad_signal(_ptr(dout), _ptr(W), _ptr(dx), B, Cc, N, T, To, R, stream),
-                       "msgat_head_grad_signal")
+            L.msgat_head_grad_signal(_ptr(dout), _ptr(W), _ptr(dx), B, Cc, N, T, To, R, stream)
         if ctx.needs_input_grad[1]:
             dW = _head_weight_grad(dout, x, W, B, Cc, N, T, To, R, stream)
         if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -1131,7 +1105,7 @@ class _LnHeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, lnw, lnb, eps: float, W, bias, relu_input: bool):
-        L = _lib.lib()
+        L = _lib.checked()
         x, W = x.contiguous(), W.contiguous()
         B, Cc, N, T = x.shape
         To = W.shape[-4]
@@ -1140,14 +1114,13 @@ class _LnHeadFunction(torch.autograd.Function):
         w = None if lnw is None else lnw.contiguous()
         lb = None if lnb is None else lnb.contiguous()
         out = _new(x, B, N, To)
-        part = _new(x, max(int(L.msgat_head_forward_partial_floats(B, Cc, N, To)), 1))
+        part = _scratch(x, L.msgat_head_forward_partial_floats(B, Cc, N, To))
         b = None if bias is None else bias.contiguous()
         # the head normalises what it loads; LayerNorm(x) is written only when the weight gradient will read it
         keep = ctx.needs_input_grad[4]
         xn = torch.empty_like(x) if keep else None
-        st = L.msgat_head_forward_ln(_ptr(x), _ptr(w), _ptr(lb), eps, _ptr(W), _ptr(b), _ptr(out), _ptr(xn), _ptr(part), B, Cc, N, T,
-                                     To, R, stream)
-        _lib.check(st, "msgat_head_forward_ln")
+        L.msgat_head_forward_ln(_ptr(x), _ptr(w), _ptr(lb), eps, _ptr(W), _ptr(b), _ptr(out), _ptr(xn), _ptr(part), B, Cc, N, T,
+                                To, R, stream)
         ctx.eps, ctx.relu_input, ctx.has_lnw, ctx.has_lnb, ctx.has_bias = eps, bool(relu_input), w is not None, lb is not None, bias is not None
         ctx.has_xn = keep
         ctx.param_shape = _ln_sets(w, lb, T)[1]
@@ -1156,7 +1129,7 @@ class _LnHeadFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         saved = ctx.saved_tensors
         x, W = saved[:2]
         xn = saved[2] if ctx.has_xn else None
@@ -1172,10 +1145,9 @@ class _LnHeadFunction(torch.autograd.Function):
             dx = torch.empty_like(x)
             dlnw = torch.empty_like(w) if (ctx.has_lnw and need[1]) else None
             dlnb = torch.empty(ctx.param_shape, device=x.device, dtype=torch.float32) if (ctx.has_lnb and need[2]) else None
-            part = _new(x, max(int(L.msgat_layernorm_head_backward_partial_floats(B, Cc, N, T)), 1))
-            st = L.msgat_layernorm_head_backward(_ptr(dout), _ptr(W), _ptr(x), _ptr(w), _ptr(dx), _ptr(dlnw), _ptr(dlnb),
-                                                 _ptr(part), B, Cc, N, T, To, R, ctx.eps, int(ctx.relu_input), stream)
-            _lib.check(st, "msgat_layernorm_head_backward")
+            part = _scratch(x, L.msgat_layernorm_head_backward_partial_floats(B, Cc, N, T))
+            L.msgat_layernorm_head_backward(_ptr(dout), _ptr(W), _ptr(x), _ptr(w), _ptr(dx), _ptr(dlnw), _ptr(dlnb),
+                                            _ptr(part), B, Cc, N, T, To, R, ctx.eps, int(ctx.relu_input), stream)
         if need[4]:
             dW = _head_weight_grad(dout, xn, W, B, Cc, N, T, To, R, stream)
         if ctx.has_bias and need[5]:
@@ -1219,7 +1191,7 @@ class _GateSumFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, H, D, h_w, d_w):
-        L = _lib.lib()
+        L = _lib.checked()
         pred, h_w = pred.contiguous(), h_w.contiguous()
         d_w = None if d_w is None else d_w.contiguous()
         R, B = pred.shape[:2]
@@ -1227,9 +1199,8 @@ class _GateSumFunction(torch.autograd.Function):
         nh = h_w.shape[0] if H is not None else 1
         nd = d_w.shape[0] if d_w is not None else 0
         out = _new(pred, *pred.shape[1:])
-        st = L.msgat_gate_sum(_ptr(pred), _ptr(H), _ptr(D), _ptr(h_w), _ptr(d_w), _ptr(out), R, B, E, nh, nd,
-                              _stream_handle(pred.device))
-        _lib.check(st, "msgat_gate_sum")
+        L.msgat_gate_sum(_ptr(pred), _ptr(H), _ptr(D), _ptr(h_w), _ptr(d_w), _ptr(out), R, B, E, nh, nd,
+                         _stream_handle(pred.device))
         ctx.dims = (R, B, E, nh, nd)
         ctx.has_idx, ctx.has_day = H is not None, d_w is not None
         ctx.save_for_backward(*([pred, h_w] + ([H, D] if H is not None else []) + ([d_w] if d_w is not None else [])))
@@ -1237,7 +1208,7 @@ class _GateSumFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         saved = list(ctx.saved_tensors)
         pred, h_w = saved[:2]
         H, D = (saved[2], saved[3]) if ctx.has_idx else (None, None)
@@ -1248,9 +1219,8 @@ class _GateSumFunction(torch.autograd.Function):
         dpred = torch.empty_like(pred) if need[0] else None
         dh = torch.empty_like(h_w) if need[3] else None
         dd = torch.empty_like(d_w) if (d_w is not None and need[4]) else None
-        st = L.msgat_gate_sum_backward(_ptr(dout), _ptr(pred), _ptr(H), _ptr(D), _ptr(h_w), _ptr(d_w), _ptr(dpred), _ptr(dh),
-                                       _ptr(dd), R, B, E, nh, nd, _stream_handle(pred.device))
-        _lib.check(st, "msgat_gate_sum_backward")
+        L.msgat_gate_sum_backward(_ptr(dout), _ptr(pred), _ptr(H), _ptr(D), _ptr(h_w), _ptr(d_w), _ptr(dpred), _ptr(dh),
+                                  _ptr(dd), R, B, E, nh, nd, _stream_handle(pred.device))
         return dpred, None, None, dh, dd
 
 
@@ -1289,21 +1259,20 @@ class _EdgeTimeWeightsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, base, h_w, d_w, H, D):
-        L = _lib.lib()
+        L = _lib.checked()
         base, h_w, d_w = base.contiguous(), h_w.contiguous(), d_w.contiguous()
         B, nnz = H.shape[0], base.shape[0]
         nh, nd = h_w.shape[0], d_w.shape[0]
         out = _new(base, B, nnz)
-        st = L.msgat_edge_time_weights(_ptr(base), _ptr(h_w), _ptr(d_w), _ptr(H), _ptr(D), _ptr(out), B, nnz, nh, nd,
-                                       _stream_handle(base.device))
-        _lib.check(st, "msgat_edge_time_weights")
+        L.msgat_edge_time_weights(_ptr(base), _ptr(h_w), _ptr(d_w), _ptr(H), _ptr(D), _ptr(out), B, nnz, nh, nd,
+                                  _stream_handle(base.device))
         ctx.dims = (B, nnz, nh, nd)
         ctx.save_for_backward(H, D)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         H, D = ctx.saved_tensors
         B, nnz, nh, nd = ctx.dims
         need = ctx.needs_input_grad
@@ -1311,9 +1280,8 @@ class _EdgeTimeWeightsFunction(torch.autograd.Function):
         dbase = _new(dout, nnz) if need[0] else None
         dh = _new(dout, nh, nnz) if need[1] else None
         dd = _new(dout, nd, nnz) if need[2] else None
-        st = L.msgat_edge_time_weights_backward(_ptr(dout), _ptr(H), _ptr(D), _ptr(dbase), _ptr(dh), _ptr(dd), B, nnz, nh, nd,
-                                                _stream_handle(dout.device))
-        _lib.check(st, "msgat_edge_time_weights_backward")
+        L.msgat_edge_time_weights_backward(_ptr(dout), _ptr(H), _ptr(D), _ptr(dbase), _ptr(dh), _ptr(dd), B, nnz, nh, nd,
+                                           _stream_handle(dout.device))
         return dbase, dh, dd, None, None
 
 
@@ -1383,7 +1351,7 @@ class _EdgeSignalWeightsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, base, ab, pattern):
-        L = _lib.lib()
+        L = _lib.checked()
         ab = ab.contiguous()
         B, N, d = ab.shape[0], ab.shape[1], ab.shape[2] // 2
         nnz = pattern.structure.nnz
@@ -1391,24 +1359,22 @@ class _EdgeSignalWeightsFunction(torch.autograd.Function):
         order = _CallerOrder(pattern, ab.device)
         base = order.to_library(base)
         out = _new(ab, B, nnz)
-        st = L.msgat_edge_signal_weights(C.byref(gstruct), _ptr(base), _ptr(ab), B, d, _ptr(out), _stream_handle(ab.device))
-        _lib.check(st, "msgat_edge_signal_weights")
+        L.msgat_edge_signal_weights(C.byref(gstruct), _ptr(base), _ptr(ab), B, d, _ptr(out), _stream_handle(ab.device))
         ctx.call = (gstruct, keep, order, B, N, d, nnz)
         ctx.save_for_backward(ab)
         return order.to_caller(out)
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         ab, = ctx.saved_tensors
         gstruct, _, order, B, N, d, nnz = ctx.call
         need = ctx.needs_input_grad
         dout = order.to_library(dout)
         dbase = _new(dout, nnz) if need[0] else None
         dab = _new(dout, B, N, 2 * d) if need[1] else None
-        st = L.msgat_edge_signal_weights_backward(C.byref(gstruct), _ptr(dout), _ptr(ab), B, d, _ptr(dbase), _ptr(dab),
-                                                  _stream_handle(dout.device))
-        _lib.check(st, "msgat_edge_signal_weights_backward")
+        L.msgat_edge_signal_weights_backward(C.byref(gstruct), _ptr(dout), _ptr(ab), B, d, _ptr(dbase), _ptr(dab),
+                                             _stream_handle(dout.device))
         return order.to_caller(dbase), dab, None
 
 
@@ -1460,22 +1426,21 @@ class _EdgeDropoutFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w, exempt, state, V, sample_offset, thr, scale):
-        L = _lib.lib()
+        L = _lib.checked()
         w = w.contiguous()
         nnz = w.shape[-1]
         sets = int(w.dim() == 2)
         out = _new(w, V, nnz)
         used = torch.empty(1, device=w.device, dtype=torch.int64)
-        st = L.msgat_edge_dropout(_ptr(w), _ptr(exempt), _ptr(state), _ptr(used), _ptr(out), V, nnz, sets, sample_offset, thr,
-                                  scale, 1, _stream_handle(w.device))
-        _lib.check(st, "msgat_edge_dropout")
+        L.msgat_edge_dropout(_ptr(w), _ptr(exempt), _ptr(state), _ptr(used), _ptr(out), V, nnz, sets, sample_offset, thr,
+                             scale, 1, _stream_handle(w.device))
         ctx.call = (V, nnz, sets, sample_offset, thr, scale)
         ctx.operands = (exempt, state, used)               # integer tensors the launch reads by address: nothing to version
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         exempt, state, used = ctx.operands
         V, nnz, sets, sample_offset, thr, scale = ctx.call
         if not ctx.needs_input_grad[0]:
@@ -1483,9 +1448,8 @@ class _EdgeDropoutFunction(torch.autograd.Function):
         dout = dout.contiguous()
         dw = _shared_weight_grad(dout, V, nnz, sets)
         if V and nnz:                                      # else nothing was drawn
-            st = L.msgat_edge_dropout_backward(_ptr(dout), _ptr(exempt), _ptr(state), _ptr(used), _ptr(dw), V, nnz, sets,
-                                               sample_offset, thr, scale, _stream_handle(dout.device))
-            _lib.check(st, "msgat_edge_dropout_backward")
+            L.msgat_edge_dropout_backward(_ptr(dout), _ptr(exempt), _ptr(state), _ptr(used), _ptr(dw), V, nnz, sets,
+                                          sample_offset, thr, scale, _stream_handle(dout.device))
         return (dw,) + (None,) * 6
 
 
@@ -1604,7 +1568,7 @@ class _EdgeValidityFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w, validity, exempt, pattern, table):
-        L = _lib.lib()
+        L = _lib.checked()
         V, N, T = validity.shape
         if validity.stride(2) != 1 or validity.stride(1) != T or (V > 1 and validity.stride(0) < 0):
             validity = validity.contiguous()               # the kernel wants [N,T] rows contiguous; any sample stride is read
@@ -1616,9 +1580,8 @@ class _EdgeValidityFunction(torch.autograd.Function):
         stride = validity.stride(0) if V > 1 else N * T
         ctable = (C.c_float * (T + 1))(*table)
         out = _new(w, V, nnz)
-        st = L.msgat_edge_validity(C.byref(gstruct), _ptr(w), _ptr(exempt), _ptr(validity), stride, ctable, _ptr(out), V, T,
-                                   sets, _stream_handle(w.device))
-        _lib.check(st, "msgat_edge_validity")
+        L.msgat_edge_validity(C.byref(gstruct), _ptr(w), _ptr(exempt), _ptr(validity), stride, ctable, _ptr(out), V, T,
+                              sets, _stream_handle(w.device))
         ctx.call = (gstruct, keep, order, V, T, nnz, sets, stride, ctable)
         ctx.operands = (exempt,)                           # an integer tensor the launch reads by address: nothing to version
         ctx.save_for_backward(validity)
@@ -1626,7 +1589,7 @@ class _EdgeValidityFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
+        L = _lib.checked()
         validity, = ctx.saved_tensors
         exempt, = ctx.operands
         gstruct, _, order, V, T, nnz, sets, stride, ctable = ctx.call
@@ -1635,9 +1598,8 @@ class _EdgeValidityFunction(torch.autograd.Function):
         dout = order.to_library(dout)
         dw = _shared_weight_grad(dout, V, nnz, sets)
         if V and nnz:
-            st = L.msgat_edge_validity_backward(C.byref(gstruct), _ptr(dout), _ptr(exempt), _ptr(validity), stride, ctable,
-                                                _ptr(dw), V, T, sets, _stream_handle(dout.device))
-            _lib.check(st, "msgat_edge_validity_backward")
+            L.msgat_edge_validity_backward(C.byref(gstruct), _ptr(dout), _ptr(exempt), _ptr(validity), stride, ctable,
+                                           _ptr(dw), V, T, sets, _stream_handle(dout.device))
         return (order.to_caller(dw),) + (None,) * 4
 
 
@@ -1706,7 +1668,7 @@ class _MixMultiFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, M, bias, relu, n_in, n_add, out_channels, premasked, *tensors):
-        L = _lib.lib()
+        L = _lib.checked()
         ins, adds = tensors[:n_in], tensors[n_in:n_in + n_add]
         G, _, N, T = ins[0].shape
         M = M.contiguous()
@@ -1717,9 +1679,8 @@ class _MixMultiFunction(torch.autograd.Function):
         _, aout, _ = _seg_array(outs)
         b = None if bias is None else bias.contiguous()
         per_rel = int(b is not None and b.dim() == 2)         # bias [Co] or [R,Co] (one row per matrix)
-        st = L.msgat_mix_segments(R, G // R, N, T, ain, n_in, _ptr(M), 0, _ptr(b), per_rel, aad, n_add, int(relu), aout,
-                                  len(outs), _stream_handle(M.device))
-        _lib.check(st, "msgat_mix_segments")
+        L.msgat_mix_segments(R, G // R, N, T, ain, n_in, _ptr(M), 0, _ptr(b), per_rel, aad, n_add, int(relu), aout,
+                             len(outs), _stream_handle(M.device))
         relu_bwd = bool(relu and not premasked)   # premasked: the consumer of the output applies the ReLU's backward mask
         ctx.meta = (relu_bwd, n_in, tuple(out_channels), (0 if bias is None else (R if per_rel else -1)),
                     [t.shape[1] for t in ins], [t.shape[1] for t in adds])
@@ -1728,7 +1689,7 @@ class _MixMultiFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
-        L = _lib.lib()
+        L = _lib.checked()
         relu, n_in, out_channels, has_bias, in_channels, add_channels = ctx.meta
         saved = ctx.saved_tensors
         M, ins, outs = saved[0], saved[1:1 + n_in], saved[1 + n_in:]
@@ -1753,8 +1714,7 @@ class _MixMultiFunction(torch.autograd.Function):
             d_ins = [_new(like, G, c, N, T) for c in in_channels]
         if any(need[7:7 + n_in]) and not both:
             _, ai, _ = _seg_array(d_ins)
-            st = L.msgat_mix_segments(R, G // R, N, T, ad, nd, _ptr(M), 1, None, 0, None, 0, 0, ai, n_in, stream)
-            _lib.check(st, "msgat_mix_segments (backward)")
+            L.msgat_mix_segments(R, G // R, N, T, ad, nd, _ptr(M), 1, None, 0, None, 0, 0, ai, n_in, stream)
         want_bias = bool(has_bias and need[1])   # has_bias: 0 none, -1 shared [Co], R per matrix [R,Co]
         if need[0]:
             Co = sum(out_channels)
@@ -1763,18 +1723,15 @@ class _MixMultiFunction(torch.autograd.Function):
                 x = x.contiguous()
                 ones = int(want_bias and i == 0)   # the bias gradient = contraction with a virtual channel of ones
                 buf = _new(like, R * Co * (c + ones))
-                nfl = (L.msgat_contract_mix_partial_floats(R, G // R, N, T, Co, c + ones) if both
-                       else L.msgat_contract_segments_partial_floats(R, Co, c + ones))
-                part = _new(like, max(int(nfl), 1))
+                part = _scratch(like, L.msgat_contract_mix_partial_floats(R, G // R, N, T, Co, c + ones) if both
+                                else L.msgat_contract_segments_partial_floats(R, Co, c + ones))
                 # with_ones = 2: the matrix [R,Co,c] and, behind it, the ones column [R,Co] -- two contiguous tensors (a
                 # column slice handed down to the components' parameters would cost a copy per component in AccumulateGrad)
                 if both:
-                    st = L.msgat_contract_mix_segments(R, G // R, N, T, ad, nd, _ptr(x), c, 2 * ones, _ptr(M), _ptr(part),
-                                                       _ptr(buf), _ptr(d_ins[0]), stream)
-                    _lib.check(st, "msgat_contract_mix_segments")
+                    L.msgat_contract_mix_segments(R, G // R, N, T, ad, nd, _ptr(x), c, 2 * ones, _ptr(M), _ptr(part),
+                                                  _ptr(buf), _ptr(d_ins[0]), stream)
                 else:
-                    st = L.msgat_contract_segments(R, G // R, N, T, ad, nd, _ptr(x), c, 2 * ones, _ptr(part), _ptr(buf), stream)
-                    _lib.check(st, "msgat_contract_segments")
+                    L.msgat_contract_segments(R, G // R, N, T, ad, nd, _ptr(x), c, 2 * ones, _ptr(part), _ptr(buf), stream)
                 if ones:
                     colsum = buf[R * Co * c:].view(R, Co)                   # [R,Co]: sum over the relation's groups and positions
                     dbias = colsum if has_bias > 0 else colsum.sum(dim=0)
@@ -1827,7 +1784,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, q, Wg, graph, recording: bool = True, adj_grad=None, adj=None, weights=None):   # see _GACNFunction
-        L = _lib.lib()
+        L = _lib.checked()
         u, q, Wg = u.contiguous(), q.contiguous(), Wg.contiguous()
         G, Cu, N, T = u.shape
         R = Wg.shape[0]
@@ -1844,10 +1801,8 @@ class _AttentionCoreFunction(torch.autograd.Function):
         scratch = _new(u, plan.nscratch) if plan.nscratch else None
         stream = _stream_handle(dev)
         shape, gstruct = C.byref(plan.shape), C.byref(plan.gstruct)
-        _lib.check(L.msgat_stage_scores(shape, gstruct, _ptr(q), _ptr(Wg), kW, lse, pq, E, Ec, _ptr(dense_t), stream),
-                   "msgat_stage_scores")
-        _lib.check(L.msgat_stage_aggregate(shape, gstruct, Cu, _ptr(u), E, _ptr(z), _ptr(scratch), stream),
-                   "msgat_stage_aggregate")
+        L.msgat_stage_scores(shape, gstruct, _ptr(q), _ptr(Wg), kW, lse, pq, E, Ec, _ptr(dense_t), stream)
+        L.msgat_stage_aggregate(shape, gstruct, Cu, _ptr(u), E, _ptr(z), _ptr(scratch), stream)
         if need_bwd:
             ctx.plan, ctx.adj_grad, ctx.weights = plan, adj_grad, weights
             ctx.save_for_backward(u, q, Wg, buf)
@@ -1861,7 +1816,7 @@ class _AttentionCoreFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, dE=None):
-        L = _lib.lib()
+        L = _lib.checked()
         u, q, Wg, buf = ctx.saved_tensors
         plan = ctx.plan
         _, kW, lse, pq, E, Ec, _ = plan.pointers(buf)
@@ -1880,13 +1835,12 @@ class _AttentionCoreFunction(torch.autograd.Function):
         ws = torch.empty(plan.bwd_bytes, device=u.device, dtype=torch.uint8)
         stream = _stream_handle(u.device)
         if dE is None:
-            st = L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
-                                            _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
+            L.msgat_attention_backward(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec, _ptr(Wg),
+                                       _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(), stream)
         else:
-            st = L.msgat_attention_backward_edge_grad(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec,
-                                                      _ptr(Wg), _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(),
-                                                      _ptr(dE), stream)
-        _lib.check(st, "msgat_attention_backward")
+            L.msgat_attention_backward_edge_grad(shape, gstruct, _ptr(u), _ptr(dz), dz_gs, _ptr(q), kW, lse, pq, E, Ec,
+                                                 _ptr(Wg), _ptr(du), _ptr(dq), _ptr(dWg), _ptr(ws), ws.numel(),
+                                                 _ptr(dE), stream)
         if dP is not None:                    # dq and dWg are outputs here: the map's share is added to them
             _map_grad(plan, _ptr(q), kW, lse, Wg, dP, dq, dWg, stream)
         dadj = None if ctx.adj_grad is None else ctx.adj_grad(plan, u.shape[1], dz, dz_gs, _ptr(u), _ptr(q), kW, lse, stream,
@@ -1928,37 +1882,35 @@ class _ChannelAttentionMixFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pooled, Wc, conv):
-        L = _lib.lib()
+        L = _lib.checked()
         pooled, Wc, conv = pooled.contiguous(), Wc.contiguous(), conv.contiguous()
         G, Cc, T = pooled.shape
         R, cb = Wc.shape[0], conv.shape[1]
         att, Mc = _new(pooled, G, Cc, Cc), _new(pooled, G, cb, Cc)
-        st = L.msgat_channel_attention_forward(_ptr(pooled), _ptr(Wc), _ptr(conv), _ptr(att), _ptr(Mc), G, R, Cc, cb, T,
-                                               _stream_handle(pooled.device))
-        _lib.check(st, "msgat_channel_attention_forward")
+        L.msgat_channel_attention_forward(_ptr(pooled), _ptr(Wc), _ptr(conv), _ptr(att), _ptr(Mc), G, R, Cc, cb, T,
+                                          _stream_handle(pooled.device))
         ctx.save_for_backward(pooled, Wc, conv, att)
         return Mc
 
     @staticmethod
     def backward(ctx, dMc):
-        L = _lib.lib()
+        L = _lib.checked()
         pooled, Wc, conv, att = ctx.saved_tensors
         G, Cc, T = pooled.shape
         R, cb = Wc.shape[0], conv.shape[1]
         dMc = dMc.contiguous()
         dp, dWc, dconv = torch.empty_like(pooled), torch.empty_like(Wc), torch.empty_like(conv)
-        part = _new(pooled, max(int(L.msgat_channel_attention_partial_floats(G, Cc, cb, T)), 1))
-        st = L.msgat_channel_attention_backward(_ptr(dMc), _ptr(att), _ptr(pooled), _ptr(Wc), _ptr(conv), _ptr(dp),
-                                                _ptr(dWc), _ptr(dconv), _ptr(part), G, R, Cc, cb, T,
-                                                _stream_handle(pooled.device))
-        _lib.check(st, "msgat_channel_attention_backward")
+        part = _scratch(pooled, L.msgat_channel_attention_partial_floats(G, Cc, cb, T))
+        L.msgat_channel_attention_backward(_ptr(dMc), _ptr(att), _ptr(pooled), _ptr(Wc), _ptr(conv), _ptr(dp),
+                                           _ptr(dWc), _ptr(dconv), _ptr(part), G, R, Cc, cb, T,
+                                           _stream_handle(pooled.device))
         return dp, dWc, dconv
 
 
 def channel_attention_fused(C: int, cb: int, T: int) -> bool:
     """Whether `channel_attention_mix` has its one-launch kernels for these sizes in BOTH directions (the backward keeps
     more in LDS than the forward: include/msgat_hip.h, msgat_channel_attention_fused); else use `channel_matrix`."""
-    return bool(_lib.lib().msgat_channel_attention_fused(int(C), int(cb), int(T)))
+    return bool(_lib.checked().msgat_channel_attention_fused(int(C), int(cb), int(T)))
 
 
 def channel_attention_mix(pooled: torch.Tensor, Wc: torch.Tensor, conv: torch.Tensor) -> torch.Tensor:
@@ -2001,31 +1953,29 @@ class _TemporalAttentionTapsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pooled, Wt1, Wt2, dilation: int):
-        L = _lib.lib()
+        L = _lib.checked()
         pooled, Wt1, Wt2 = pooled.contiguous(), Wt1.contiguous(), Wt2.contiguous()
         G, N, T = pooled.shape
         R, K = Wt1.shape[0], Wt1.shape[1]
         lr, att, taps = _new(pooled, G, 2, T, K), _new(pooled, G, T, T), _new(pooled, G, 2, T, T)
-        st = L.msgat_temporal_attention_forward(_ptr(pooled), _ptr(Wt1), _ptr(Wt2), _ptr(lr), _ptr(att), _ptr(taps), G, R, N,
-                                                K, T, int(dilation), _stream_handle(pooled.device))
-        _lib.check(st, "msgat_temporal_attention_forward")
+        L.msgat_temporal_attention_forward(_ptr(pooled), _ptr(Wt1), _ptr(Wt2), _ptr(lr), _ptr(att), _ptr(taps), G, R, N,
+                                           K, T, int(dilation), _stream_handle(pooled.device))
         ctx.dilation = int(dilation)
         ctx.save_for_backward(pooled, Wt1, Wt2, lr, att)
         return taps
 
     @staticmethod
     def backward(ctx, dtaps):
-        L = _lib.lib()
+        L = _lib.checked()
         pooled, Wt1, Wt2, lr, att = ctx.saved_tensors
         G, N, T = pooled.shape
         R, K = Wt1.shape[0], Wt1.shape[1]
         dtaps = dtaps.contiguous()
         dp, dW1, dW2 = torch.empty_like(pooled), torch.empty_like(Wt1), torch.empty_like(Wt2)
-        part = _new(pooled, max(int(L.msgat_temporal_attention_partial_floats(G, K, N)), 1))
-        st = L.msgat_temporal_attention_backward(_ptr(dtaps), _ptr(att), _ptr(lr), _ptr(pooled), _ptr(Wt1), _ptr(Wt2), _ptr(dp),
-                                                 _ptr(dW1), _ptr(dW2), _ptr(part), G, R, N, K, T, ctx.dilation,
-                                                 _stream_handle(pooled.device))
-        _lib.check(st, "msgat_temporal_attention_backward")
+        part = _scratch(pooled, L.msgat_temporal_attention_partial_floats(G, K, N))
+        L.msgat_temporal_attention_backward(_ptr(dtaps), _ptr(att), _ptr(lr), _ptr(pooled), _ptr(Wt1), _ptr(Wt2), _ptr(dp),
+                                            _ptr(dW1), _ptr(dW2), _ptr(part), G, R, N, K, T, ctx.dilation,
+                                            _stream_handle(pooled.device))
         return dp, dW1, dW2, None
 
 
@@ -2173,16 +2123,15 @@ class _TailMetricsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, truth, call: _TailCall, mask_value: float, sums, valid):
-        L = _lib.lib()
+        L = _lib.checked()
         pred_c, truth_c = pred.contiguous(), truth.contiguous()
         n_part = int(getattr(L, call.partials)(*call.dims))
         part = torch.empty(max(n_part, 1), device=pred.device, dtype=torch.float64)
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         slot = () if valid is None else (_ptr(valid),)
         name = f"msgat_{call.stem}_metrics"
-        st = getattr(L, name)(_ptr(pred_c), _ptr(truth_c), *call.dims, *call.params, *call.null, float(mask_value),
-                              _ptr(part), _ptr(loss), *slot, _ptr(sums), *call.weight, _stream_handle(pred.device))
-        _lib.check(st, name)
+        getattr(L, name)(_ptr(pred_c), _ptr(truth_c), *call.dims, *call.params, *call.null, float(mask_value),
+                         _ptr(part), _ptr(loss), *slot, _ptr(sums), *call.weight, _stream_handle(pred.device))
         ctx.call = call
         ctx.save_for_backward(pred_c, truth_c, *(() if valid is None else (valid,)))
         return loss
@@ -2193,9 +2142,8 @@ class _TailMetricsFunction(torch.autograd.Function):
         call = ctx.call
         dpred = torch.empty_like(pred)
         name = f"msgat_{call.stem}_grad"
-        st = getattr(_lib.lib(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), *(_ptr(v) for v in valid),
-                                       *call.dims, *call.grad_params, *call.null, _ptr(dpred), _stream_handle(pred.device))
-        _lib.check(st, name)
+        getattr(_lib.checked(), name)(_ptr(pred), _ptr(truth), _ptr(dloss.contiguous()), *(_ptr(v) for v in valid),
+                                      *call.dims, *call.grad_params, *call.null, _ptr(dpred), _stream_handle(pred.device))
         return dpred, None, None, None, None, None
 
 
@@ -2435,13 +2383,12 @@ def _window_gather(what, inputs_dev, target_dev, origins, hours, tau, q, offsets
     outs, dims = (_ptr(X), _ptr(HD[0]), _ptr(HD[1]), _ptr(Y)), (B, R, C_, N, T_total, tau, q, history)
     with torch.cuda.device(dev):
         if climatology_dev is None:
-            st = _lib.lib().msgat_window_gather(_ptr(inputs_dev), _ptr(target_dev), _ptr(origins), _ptr(offsets), *outs,
-                                                *dims, _stream_handle(dev))
+            _lib.checked().msgat_window_gather(_ptr(inputs_dev), _ptr(target_dev), _ptr(origins), _ptr(offsets), *outs,
+                                               *dims, _stream_handle(dev))
         else:
-            st = _lib.lib().msgat_window_gather_imputed(_ptr(inputs_dev), _ptr(climatology_dev), _ptr(target_dev),
-                                                        _ptr(origins), _ptr(offsets), *outs, *dims,
-                                                        climatology_dev.shape[0], int(mask_channel), _stream_handle(dev))
-    _lib.check(st, f"msgat_{what}")
+            _lib.checked().msgat_window_gather_imputed(_ptr(inputs_dev), _ptr(climatology_dev), _ptr(target_dev),
+                                                       _ptr(origins), _ptr(offsets), *outs, *dims,
+                                                       climatology_dev.shape[0], int(mask_channel), _stream_handle(dev))
     return X, HD[0], HD[1], Y
 
 
@@ -2487,10 +2434,9 @@ def ring_push(raw: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, ring: to
         raise ValueError(f"ring_push: raw holds K = {K} steps, more than the ring's L = {L}")
     dev = ring.device
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_ring_push(_ptr(raw), _ptr(mean), _ptr(std), _ptr(ring), _ptr(clock), K, C_, N, L,
-                                        int(null_value is not None), 0.0 if null_value is None else float(null_value),
-                                        _stream_handle(dev))
-    _lib.check(st, "msgat_ring_push")
+        _lib.checked().msgat_ring_push(_ptr(raw), _ptr(mean), _ptr(std), _ptr(ring), _ptr(clock), K, C_, N, L,
+                                       int(null_value is not None), 0.0 if null_value is None else float(null_value),
+                                       _stream_handle(dev))
 
 
 def ring_windows(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int, climatology: Optional[torch.Tensor] = None,
@@ -2536,10 +2482,9 @@ def ring_windows(ring: torch.Tensor, clock: torch.Tensor, hours, tau: int, clima
             if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError(f"{what}: out's {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}")
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_ring_windows(_ptr(ring), _ptr(climatology), _ptr(clock), _ptr(offsets), _ptr(X), _ptr(H),
-                                           _ptr(D), R, C_, N, L, tau, 1 if climatology is None else climatology.shape[0],
-                                           int(bool(mask_channel)), _stream_handle(dev))
-    _lib.check(st, "msgat_ring_windows")
+        _lib.checked().msgat_ring_windows(_ptr(ring), _ptr(climatology), _ptr(clock), _ptr(offsets), _ptr(X), _ptr(H),
+                                          _ptr(D), R, C_, N, L, tau, 1 if climatology is None else climatology.shape[0],
+                                          int(bool(mask_channel)), _stream_handle(dev))
     return X, H, D
 
 
@@ -2582,9 +2527,8 @@ def forecast_store(pred: torch.Tensor, book: torch.Tensor, issued: torch.Tensor,
     P, N, out = _check_book("forecast_store", book, issued, clock, [("pred", pred, torch.float32, book.shape[1:])])
     dev = book.device
     with torch.cuda.device(dev):
-        st = _lib.lib().msgat_forecast_store(_ptr(pred), _ptr(book), _ptr(issued), _ptr(clock), N, out, P,
-                                             _stream_handle(dev))
-    _lib.check(st, "msgat_forecast_store")
+        _lib.checked().msgat_forecast_store(_ptr(pred), _ptr(book), _ptr(issued), _ptr(clock), N, out, P,
+                                            _stream_handle(dev))
 
 
 def forecast_score(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, clock: torch.Tensor, t_out: int,
@@ -2624,7 +2568,7 @@ def forecast_score(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, 
     if n_levels and not 0 <= point < n_levels:
         raise ValueError(f"{what}: point = {point} outside the {n_levels} levels")
     dev, K, C_ = book.device, raw.shape[0], raw.shape[1]
-    L = _lib.lib()
+    L = _lib.checked()
     need = int(L.msgat_forecast_score_partial_doubles(N, t_out, n_levels))
     if partials is None:
         partials = torch.empty(max(need, 1), device=dev, dtype=torch.float64)
@@ -2632,11 +2576,10 @@ def forecast_score(raw: torch.Tensor, book: torch.Tensor, issued: torch.Tensor, 
         raise ValueError(f"{what}: partials must be a contiguous float64 tensor of at least {need} elements on {dev}")
     host_levels = (C.c_float * n_levels)(*levels) if n_levels else None
     with torch.cuda.device(dev):
-        st = L.msgat_forecast_score(_ptr(raw), _ptr(book), _ptr(issued), _ptr(clock), K, C_, N, t_out, n_levels,
-                                    host_levels, point, P, int(null_value is not None),
-                                    0.0 if null_value is None else float(null_value), float(mask_value), _ptr(partials),
-                                    _ptr(sums), _ptr(node_sums), _stream_handle(dev))
-    _lib.check(st, "msgat_forecast_score")
+        L.msgat_forecast_score(_ptr(raw), _ptr(book), _ptr(issued), _ptr(clock), K, C_, N, t_out, n_levels,
+                               host_levels, point, P, int(null_value is not None),
+                               0.0 if null_value is None else float(null_value), float(mask_value), _ptr(partials),
+                               _ptr(sums), _ptr(node_sums), _stream_handle(dev))
 
 
 # ---- boundary hygiene for every autograd.Function above -----------------------------------------------------------

@@ -96,7 +96,7 @@ class _GatherTable:
 
     def __init__(self, sizes, offsets, dev):
         from . import _lib
-        chunk = int(_lib.lib().msgat_adam_chunk_elems())
+        chunk = int(_lib.checked().msgat_adam_chunk_elems())
         self.rel, offs, lens = [], [], []       # rel: (gradient index, byte offset) of every chunk
         for i, (n, o) in enumerate(zip(sizes, offsets)):
             for s in range(0, n, chunk):
@@ -163,19 +163,16 @@ def gather_scaled(flat: torch.Tensor, grads: Sequence[torch.Tensor], offsets: Se
     if table is None:
         table = cache[key] = _GatherTable(key[0], key[1], flat.device)
     table.point_at(tuple(g.data_ptr() for g in keep))
-    L = _lib.lib()
-    stream = torch.cuda.current_stream(flat.device).cuda_stream
+    L = _lib.checked()
+    stream = _lib.stream_handle(flat.device)
     if torch.is_tensor(weight):
-        launch, what = ((L.msgat_gather_accumulate_dev, "msgat_gather_accumulate_dev") if accumulate else
-                        (L.msgat_gather_scaled_dev, "msgat_gather_scaled_dev"))
-        st = launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
-                    _device_weight(weight, flat.device).data_ptr(), flat.data_ptr(), int(weight_index), stream)
+        launch = L.msgat_gather_accumulate_dev if accumulate else L.msgat_gather_scaled_dev
+        launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n,
+               _device_weight(weight, flat.device).data_ptr(), flat.data_ptr(), int(weight_index), stream)
     else:
-        launch, what = ((L.msgat_gather_accumulate, "msgat_gather_accumulate") if accumulate else
-                        (L.msgat_gather_scaled, "msgat_gather_scaled"))
-        st = launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n, float(weight),
-                    flat.data_ptr(), int(weight_index), stream)
-    _lib.check(st, what)
+        launch = L.msgat_gather_accumulate if accumulate else L.msgat_gather_scaled
+        launch(table.ptrs.data_ptr(), table.offs.data_ptr(), table.lens.data_ptr(), table.n, float(weight),
+               flat.data_ptr(), int(weight_index), stream)
 
 
 class FlatGradAllReduce:

@@ -94,6 +94,98 @@ def test_bad_arguments_come_back_as_status_codes():
         _lib.check(-4, "x")
 
 
+_MINI_HEADER = """
+/* a header in the style of include/msgat_hip.h */
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define MSGAT_ABI_VERSION 3
+enum { MSGAT_OK = 0, MSGAT_ERR_NULL = -1 };
+typedef struct msgat_seg { float* ptr; int32_t channels; } msgat_seg_t;
+int msgat_first(const msgat_seg_t* seg, const float* levels, int32_t* n_out, float* const* chunks, void* stream);
+%s
+size_t msgat_second(int64_t rows, %s eps);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_the_binding_is_parsed_from_the_header_and_a_header_it_cannot_read_is_an_error():
+    from ms_gat_amd import _lib
+    consts, structs, protos = _lib.parse_header(_MINI_HEADER % ("", "float"), {("msgat_first", "levels"): _lib.c_float_p,
+                                                                              ("msgat_first", "n_out"): _lib.c_int_p})
+    assert consts == {"MSGAT_ABI_VERSION": 3, "MSGAT_OK": 0, "MSGAT_ERR_NULL": -1}
+    assert structs == {"msgat_seg_t": [("ptr", C.c_void_p), ("channels", C.c_int32)]}
+    assert protos == {"msgat_first": (C.c_int, [C.POINTER(_lib.Seg), _lib.c_float_p, _lib.c_int_p, C.c_void_p, C.c_void_p]),
+                      "msgat_second": (C.c_size_t, [C.c_int64, C.c_float])}
+    assert _lib.parse_header(_MINI_HEADER % ("", "float"), {})[2]["msgat_first"][1][1:3] == [C.c_void_p, C.c_void_p]
+    with pytest.raises(_lib.MsgatError, match="msgat_second"):           # an unknown parameter type names its declaration
+        _lib.parse_header(_MINI_HEADER % ("", "half"), {})
+    with pytest.raises(_lib.MsgatError, match="stray"):                  # a token between two declarations
+        _lib.parse_header(_MINI_HEADER % ("stray", "float"), {})
+    for damaged in ("int msgat_third(int32_t);", "int msgat_third(int32_t n)", "short msgat_third(void);",
+                    "typedef struct { msgat_seg_t* next; half h; } msgat_list_t;", "int32_t msgat_global;"):
+        with pytest.raises(_lib.MsgatError):
+            _lib.parse_header(_MINI_HEADER % (damaged, "float"), {})
+    # the typed-pointer table: a key that names no parameter of the header, or one of another C type, is an error
+    for key, typ in ((("msgat_first", "quantiles"), _lib.c_float_p), (("msgat_zeroth", "levels"), _lib.c_float_p),
+                     (("msgat_first", "levels"), _lib.c_int_p), (("msgat_second", "rows"), _lib.c_int_p)):
+        with pytest.raises(_lib.MsgatError, match=key[1]):
+            _lib.parse_header(_MINI_HEADER % ("", "float"), {key: typ})
+    with open(os.path.join(ROOT, "include", "msgat_hip.h")) as f:
+        text = f.read()
+    with pytest.raises(_lib.MsgatError, match="levels_of"):
+        _lib.parse_header(text, {**_lib._TYPED_POINTERS, ("msgat_quantile_grad", "levels_of"): _lib.c_float_p})
+    consts, structs, protos = _lib.parse_header(text)
+    assert protos == _lib._PROTOTYPES and len(protos) == len(_declared_functions())
+    assert [structs[c] for c in _lib._STRUCTS] == [cls._fields_ for cls in _lib._STRUCTS.values()]
+    assert (_lib.ABI_VERSION, _lib.SELL_SLACK, _lib.GUARD_FLOATS, _lib.MSGAT_OK) == tuple(
+        consts["MSGAT_" + n] for n in ("ABI_VERSION", "SELL_SLACK", "GUARD_FLOATS", "OK"))
+    assert (_lib.MODE_PLAIN, _lib.MODE_AGG_FIRST, _lib.MODE_PROJ_FIRST) == (0, 1, 2)
+    for (fn, param), typ in _lib._TYPED_POINTERS.items():
+        assert _lib._PROTOTYPES[fn][1].count(typ) >= 1, (fn, param)
+
+
+def test_the_checked_handle_raises_under_the_entry_points_own_name_and_the_raw_handle_returns_codes():
+    from ms_gat_amd import _lib
+    raw, checked = _lib.lib(), _lib.checked()
+    assert raw is not checked and raw.msgat_gacn_forward is not checked.msgat_gacn_forward
+    shape = _lib.Shape(1, 2, 3, 24, 16, 12)
+    assert raw.msgat_gacn_forward(C.byref(shape), None, None, None) == -1
+    with pytest.raises(_lib.MsgatError) as err:
+        checked.msgat_gacn_forward(C.byref(shape), None, None, None)
+    text = raw.msgat_status_string(-1).decode()
+    assert str(err.value) == f"msgat_gacn_forward failed: {text} (status -1)"
+    with pytest.raises(_lib.MsgatError, match=re.escape(f"x failed: {text} (status -1)")):
+        _lib.check(-1, "x")
+    # sizes, modes and yes/no answers pass through
+    assert raw.msgat_gacn_mode(72, 24) == checked.msgat_gacn_mode(72, 24) == _lib.MODE_PROJ_FIRST
+    assert checked.msgat_bwd_workspace_bytes(C.byref(shape), None) == 0
+    assert checked.msgat_abi_version() == _lib.ABI_VERSION and checked.msgat_adam_chunk_elems() == raw.msgat_adam_chunk_elems() > 0
+    assert checked.msgat_causal_conv_fused(24, 24) == raw.msgat_causal_conv_fused(24, 24)
+    for name, (res, _) in _lib._PROTOTYPES.items():
+        assert getattr(raw, name).errcheck is None
+        assert (getattr(checked, name).errcheck is _lib._raise_on_error) == (res is C.c_int), name
+
+
+def test_no_call_site_of_the_package_checks_a_status_by_hand():
+    """Every call goes through `_lib.checked()`: `check(` is left as `_lib.check`'s own definition and as the unrelated
+    `check` methods and helpers of graph.py and intervals.py."""
+    pkg = os.path.join(ROOT, "ms_gat_amd")
+    found = []
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            with open(os.path.join(pkg, f)) as src:
+                found += [(f, line.strip()) for line in src if "check(" in line]
+    assert ("_lib.py", "def check(status: int, what: str) -> None:") in found
+    for f, line in found:
+        assert (f, line) == ("_lib.py", "def check(status: int, what: str) -> None:") or \
+            (f == "graph.py" and ("def check(self)" in line or "`check()`" in line)) or \
+            (f == "intervals.py" and "_check(" in line), (f, line)
+        assert "_lib.check(" not in line
+
+
 def _numpy_csr(adj):
     rows, cols = np.nonzero(adj)
     return rows, cols, adj[rows, cols]
