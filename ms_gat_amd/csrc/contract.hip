@@ -750,7 +750,8 @@ static int launch_chanpair_glds_t(const CpArgs& a, ChanMix mix = ChanMix()) {
 //                       GACN projection backward     merged channel mixing          residual convolution
 //                       [Co + 1 x C]                 [4 Co + 2 x C + 1]             [C x C + 1]
 //   msgat48             17 x 48   <2,3,128> mix 1    66 x 49   <5,4,64> mix 2       48 x 49   <3,4,128> mix 1
-//   msgat72             25 x 72   <2,5,128> mix 1    98 x 73   <7,5,64> mix 2       72 x 73   <5,5,64>  mix 2
+//   msgat72             25 x 72   <2,3,128> mix 1    98 x 73   <7,5,64> mix 2       72 x 73   <5,5,64>  mix 2
+//                       two z-blocks over B, 36 columns each (launch_glds_mix; the plain contraction: <2,5,128>)
 //   msgat96             33 x 96   <3,6,64>  mix 2    130 x 97  <9,4,64> mix 2       96 x 97   <6,4,64>  mix 2
 //                                                    two z-blocks over B, 49 + 48 columns each with ALL rows of A
 //                                                    (a [96 x 112] accumulator block spills; A is read twice, B once)
@@ -807,11 +808,19 @@ static int launch_glds_mix(const CpArgs& a, const float* Mw, const float* Mlast,
   ChanMix mix;
   mix.Mw = Mw; mix.Mlast = Mlast; mix.out = mixout;
   mix.dump = a.part + (((size_t)a.R * a.nblk_max * Ca * Cb + 3) & ~(size_t)3);   // chanpair_partial_floats() leaves 260 floats behind the partials
-  int nzb_lo = 1, nzb_hi = 2;
+  // z-blocks over B, each staging all of A, in the order they are tried: one block where a form covers it, else two.
+  // The [25 x 72] block (the GACN projection backward of msgat72: 24 rows of du and dq against 72 channels) takes two
+  // z-blocks of 36 columns first, k_chanpair_glds<2,3,128,3,1> instead of <2,5,128,3,1>: parent against tree on one box
+  // the pass runs 180 -> 164-170 us in the hot-path step, k_aggfirst_bwd behind it 35 -> 32, the step 0.6794 -> 0.6524 ms,
+  // HBM-side traffic 749 -> 698 MB although both z-blocks stage A (profiles/project_wide_tiles/).  The rule is one of the two channel counts alone -- never of the batch, the row
+  // length or the device -- and covers nothing but that measured block; the wider blocks lose as z-blocks (round 5).
+  int order[2] = {1, 2}, n_order = 2;
+  if (Ca == 25 && Cb == 72) { order[0] = 2; order[1] = 1; }
 #ifdef MSGAT_LAB
-  if (lab_env("MSGAT_LAB_NZB", 0) > 0) nzb_lo = nzb_hi = lab_env("MSGAT_LAB_NZB", 0);
+  if (lab_env("MSGAT_LAB_NZB", 0) > 0) { order[0] = lab_env("MSGAT_LAB_NZB", 0); n_order = 1; }   // overrides the rule above
 #endif
-  for (int nzb = nzb_lo; nzb <= nzb_hi; ++nzb) {           // z-blocks over B: each stages all of A
+  for (int t = 0; t < n_order; ++t) {
+    const int nzb = order[t];
     // the narrowest block that covers the z-block's columns, or one tile wider (columns past the operand read the zero
     // row): the list is written for the widths WITH a bias column (49 / 73 / 97), and the same mixing without one
     // (48 / 72 / 96 columns: the merged channel mixing of the stacked schedule) must not fall back to two passes
